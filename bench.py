@@ -14,9 +14,12 @@ Workloads (BASELINE.json configs; SURVEY §8(d) sizes):
   other_configs (N = 1, after the headline): configs[2] (modmap: 3 Gbp reference modset, 90 Gbp of reads queried in
           10 Gbp batches) and configs[4] (depth histogram of 50x 150 b reads, k=31 d=4), each with its own roofline.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   --gpus N > 1 without WORLD_SIZE in the environment: this process starts N ranks (torch.distributed.run, one per GPU)
   BEFORE anything touches the GPU and passes their output through; under torch.distributed.run it is a rank itself.
+  A plain run is the headline alone: set-up, warm-up, exactly K timed steps, the result line.  --full adds everything
+  else: the per-kernel table and roofline, the CPU baseline, the other configs, the N > 1 checks and bench_extra.py's legs.
+  --dump-outputs DIR writes what the last timed step computed (rank 0's modset: a fixed, seeded sample) as DIR/*.npy.
 Environment overrides (for quick runs): MODGPU_BENCH_GBP, MODGPU_BENCH_BITS, MODGPU_CPU_SAMPLE_MBP,
 MODGPU_BENCH_FORCE_DIST=1 (run the N>1 code path at whatever world size, even 1); MODGPU_BENCH_ONE_GPU=1 (all ranks on cuda:0,
 gloo: the world > 1 code path on a one-GPU box, rates meaningless).
@@ -46,10 +49,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-other", action="store_true", help="skip configs 3 and 5 (other_configs)")
-    ap.add_argument("--full", action="store_true", help="also the legs of bench_extra.py (host bytes, files, result mirror, .mod writing, the reference's "
-                    "unmodified programs on the library, minimizers, repeat-rich genomes): minutes, not for the driver's run")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the per-kernel table and roofline, the CPU baseline, the other configs, "
+                    "the N > 1 checks, and the legs of bench_extra.py (host bytes, files, result mirror, .mod writing, the reference's unmodified "
+                    "programs on the library, minimizers, repeat-rich genomes): minutes")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip the other configs (other_configs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs of bench_extra.py")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, a fixed seeded sample, < 64 MB)")
     ap.add_argument("--only", default="", help="run ONE of the other configs (c3, c5, c4_block, ref_default, realistic) without the headline workload and print its JSON: for profiler passes")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch path only: gloo ranks, a tiny host-side modset each, the histogram all-reduce (no GPU)")
@@ -210,23 +217,27 @@ def bound_actual(kernel, avg_ms, units, alu=None):
     return None
 
 
-def time_steps(cx, step, steps, warmup, multi):
+def time_steps(cx, step, steps, warmup, multi, profile=True, after_timed=None):
     """W untimed warm-up steps (every launch bracketed: the per-kernel table and the dominant kernel), then exactly
     K steps between barrier + synchronize on both sides with only the dominant kernel bracketed (an event pair costs
-    a few microseconds of stream time per launch).  Returns (seconds, events of the dominant kernel, per-kernel table)."""
+    a few microseconds of stream time per launch).  Returns (seconds, events of the dominant kernel, per-kernel table).
+    profile=False: no event anywhere and no extra step; returns (seconds, None, None).  after_timed() runs right after the
+    timed region, before anything else touches what its last step left."""
     torch, dist, L, mg = cx.torch, cx.dist, cx.L, cx.mg
-    L.mgProfileOnly(-1); L.mgProfileEnable(1); L.mgProfileReset()
+    if profile:
+        L.mgProfileOnly(-1); L.mgProfileEnable(1); L.mgProfileReset()
     # the dominant kernel is taken from the LAST warm-up step alone (one more untimed step when W < 2), not from the first ones: those hold
     # what happens once (first allocations, the transfer team's streams being made on their own thread: a launch that waits behind one of
     # these looks like a 40 ms kernel)
     for i in range(max(warmup, 2)):
-        if i == max(warmup, 2) - 1:
+        if profile and i == max(warmup, 2) - 1:
             torch.cuda.synchronize(); L.mgProfileReset()
         step()
     torch.cuda.synchronize()
-    warm = read_profile(L, mg)
-    dom_id = max(warm.values(), key=lambda v: v[0])[2] if warm else -1
-    L.mgProfileReset(); L.mgProfileOnly(dom_id)
+    if profile:
+        warm = read_profile(L, mg)
+        dom_id = max(warm.values(), key=lambda v: v[0])[2] if warm else -1
+        L.mgProfileReset(); L.mgProfileOnly(dom_id)
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
@@ -241,9 +252,14 @@ def time_steps(cx, step, steps, warmup, multi):
         tmax = torch.tensor([dt], dtype=torch.float64, device=cx.dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    kern = read_profile(L, mg)
+    kern = read_profile(L, mg) if profile else None
+    if after_timed is not None:
+        L.mgProfileEnable(0)
+        after_timed()
+    if not profile:
+        return dt, None, None
     # one more step, outside the timed region, with every launch bracketed: the per-kernel table
-    L.mgProfileOnly(-1); L.mgProfileReset()
+    L.mgProfileOnly(-1); L.mgProfileEnable(1); L.mgProfileReset()
     step()
     torch.cuda.synchronize()
     table = read_profile(L, mg)
@@ -415,29 +431,14 @@ def gpu_rank(args):
             mg.check(L.modsetDepthHistogramDevice(ms, hist.data_ptr(), stream))
             dist.all_reduce(hist)
 
-    dt, kern, table = time_steps(cx, step, args.steps, args.warmup, multi)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda: dump_outputs(cx, ms, n_hash.value, args.dump_outputs, hist if multi else None)
+    # a plain run times the steps and nothing else: no HIP event in the step, no extra step after it (--full: both, as they feed the roofline)
+    dt, kern, table = time_steps(cx, step, args.steps, args.warmup, multi, profile=args.full, after_timed=dump)
     S = n_hash.value
     entries = ms.contents.max
-    slots = float(L.mgModsetDeviceSlots(ms))
-    alg = alg_bytes_table(total, S, entries, d, slots)
-
-    # the scan's two bounds (SURVEY §8(d) asks for both): HBM bytes and integer issue
-    scan_ms = table.get("mgScanKernel", (0, 1))[0] / max(table.get("mgScanKernel", (0, 1))[1], 1)
-    starts = float(total)
-    alu = scan_alu(starts, scan_ms)
-    extra = {"alu": alu,
-             "scan_bytes": {"this_path_8B_per_modimizer": alg["mgScanKernel"],
-                            "survey_12B_per_modimizer": (0.25 + 12.0 / d) * total,
-                            "read_only_0.25B_per_base": 0.25 * total,
-                            "scan_GBps_this_path": round(alg["mgScanKernel"] / (scan_ms * 1e-3) / 1e9, 1) if scan_ms else None,
-                            "scan_read_only_frac": round(0.25 * total / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if scan_ms else None},
-             "whole_step": {"bytes_per_base": 0.25 + 28.0 / d, "algorithmic_bytes_per_step": (0.25 + 28.0 / d) * total,
-                            "GBps": round((0.25 + 28.0 / d) * total * args.steps / dt / 1e9, 1),
-                            "frac": round((0.25 + 28.0 / d) * total * args.steps / dt / 1e9 / HBM_PEAK_GBS, 4)}}
-    roofline = roofline_of(kern, table, alg, "%g" % gbp, extra, units={"mgScanKernel": starts, "mgRankLookupKernel": float(entries)})
-
     value = world * total * args.steps / dt / 1e9
-    scan_step_ms = sum(v[0] for kname, v in table.items() if kname in ("mgScanKernel", "mgSegScanKernel", "mgSegCompactKernel", "mgTileInfoKernel"))
     out = {
         "metric": "Gbp/s hashed+sketched (k=21,d=64)", "value": round(value, 3), "unit": "Gbp/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "untimed_steps_before_the_timed_region": max(args.warmup, 2),
@@ -452,14 +453,32 @@ def gpu_rank(args):
                    "reads_per_gpu": n_reads, "bases_per_gpu": total, "modimizers_per_gpu": S,
                    "modset_entries": entries, "k": k, "d": d, "table_bits": bits,
                    "parallelism": "reads sharded x%d, modset per GPU" % world},
-        "roofline": roofline,
-        "scan_only": {"ms": round(scan_step_ms, 4), "Gbp_per_s": round(total / (scan_step_ms * 1e-3) / 1e9, 1) if scan_step_ms else None,
-                      "what": "tile info + scan (which also counts the first partition digit) + segment scan, by HIP events; the modimizers stay in the "
-                              "per-worker segments, where the build reads them (a dense (read,pos)-ordered copy, as the query path makes, is mgSegCompactKernel: +0.6 ms)"},
         "setup_s": round(t_gen, 2),
     }
 
-    if multi:
+    if args.full:
+        slots = float(L.mgModsetDeviceSlots(ms))
+        alg = alg_bytes_table(total, S, entries, d, slots)
+        # the scan's two bounds (SURVEY §8(d) asks for both): HBM bytes and integer issue
+        scan_ms = table.get("mgScanKernel", (0, 1))[0] / max(table.get("mgScanKernel", (0, 1))[1], 1)
+        starts = float(total)
+        alu = scan_alu(starts, scan_ms)
+        extra = {"alu": alu,
+                 "scan_bytes": {"this_path_8B_per_modimizer": alg["mgScanKernel"],
+                                "survey_12B_per_modimizer": (0.25 + 12.0 / d) * total,
+                                "read_only_0.25B_per_base": 0.25 * total,
+                                "scan_GBps_this_path": round(alg["mgScanKernel"] / (scan_ms * 1e-3) / 1e9, 1) if scan_ms else None,
+                                "scan_read_only_frac": round(0.25 * total / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if scan_ms else None},
+                 "whole_step": {"bytes_per_base": 0.25 + 28.0 / d, "algorithmic_bytes_per_step": (0.25 + 28.0 / d) * total,
+                                "GBps": round((0.25 + 28.0 / d) * total * args.steps / dt / 1e9, 1),
+                                "frac": round((0.25 + 28.0 / d) * total * args.steps / dt / 1e9 / HBM_PEAK_GBS, 4)}}
+        out["roofline"] = roofline_of(kern, table, alg, "%g" % gbp, extra, units={"mgScanKernel": starts, "mgRankLookupKernel": float(entries)})
+        scan_step_ms = sum(v[0] for kname, v in table.items() if kname in ("mgScanKernel", "mgSegScanKernel", "mgSegCompactKernel", "mgTileInfoKernel"))
+        out["scan_only"] = {"ms": round(scan_step_ms, 4), "Gbp_per_s": round(total / (scan_step_ms * 1e-3) / 1e9, 1) if scan_step_ms else None,
+                            "what": "tile info + scan (which also counts the first partition digit) + segment scan, by HIP events; the modimizers stay in the "
+                                    "per-worker segments, where the build reads them (a dense (read,pos)-ordered copy, as the query path makes, is mgSegCompactKernel: +0.6 ms)"}
+
+    if multi and args.full:
         # the collective by itself, and a check of what it produced
         local_hist.zero_()
         mg.check(L.modsetDepthHistogramDevice(ms, local_hist.data_ptr(), stream))
@@ -507,12 +526,12 @@ def gpu_rank(args):
         dist.barrier()
 
     # ---- CPU baseline (rank 0, N=1 only): the compiled reference on a bounded sample ---------
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(cx, reads, offsets, k, d, seed)
 
-    full = args.full and rank == 0 and world == 1 and not multi
+    full = args.full and not args.no_extra and rank == 0 and world == 1 and not multi
     n4 = None
-    if full:                                          # what a caller waits for around the kernels (bench_extra.py): never the driver's run
+    if full:                                          # what a caller waits for around the kernels (bench_extra.py)
         import bench_extra as X
         try:
             out["end_to_end"] = X.end_to_end(cx, reads, offsets, k, d, seed)
@@ -536,7 +555,7 @@ def gpu_rank(args):
         except Exception as e:
             out["end_to_end"]["modmap_query_file_long"] = {"error": str(e)[:300]}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not multi and not args.no_other:
+    if args.full and rank == 0 and world == 1 and not multi and not args.no_other:
         other = {}
         legs = [("c4_block", bench_c4_block), ("c5", bench_c5), ("c3", bench_c3), ("ref_default", bench_ref_default)]
         if full:
@@ -553,7 +572,7 @@ def gpu_rank(args):
             other["n4_minimizers"] = n4
         out["other_configs"] = other
 
-    if multi and not args.no_other:
+    if multi and args.full and not args.no_other:
         # north_star's other sharding (query reads over replicated modsets), every rank taking part
         try:
             c3s = bench_c3(cx, args, shard=(rank, world))
@@ -628,7 +647,8 @@ def compact_line(out, detail_path=None):
     nothing that grows with the number of legs.  tests/test_bench_line.py feeds recorded results through this."""
     c = _pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config")
-    c["roofline"] = compact_roofline(out.get("roofline"))
+    if "roofline" in out:                               # --full only: a plain run brackets no kernel
+        c["roofline"] = compact_roofline(out["roofline"])
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         c["cpu_baseline"] = _pick(cb, "value", "unit", "cores", "kind", "sample", "scan_only_gbps")
@@ -677,6 +697,37 @@ def emit(out):
             pass
     print("BENCH_DETAIL " + json.dumps(out), flush=True)
     print(compact_line(out, detail), flush=True)
+
+
+DUMP_SEED = 20261016
+DUMP_SAMPLE = 1 << 21          # entries sampled: 2M x (8 + 8 + 4) bytes = 40 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(cx, ms, n_hash, path, hist=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the modset (value[1..max], depth[1..max]) and
+    the modimizer count -- mirrored to the host (modsetSyncToHost) and written as float .npy files.  The modset holds ~1e8 entries, so
+    value and depth go out at one fixed, seeded sample of entry indices (the same for the same max), and the depth of EVERY entry goes
+    out as its histogram.  value[] holds 2k = 42-bit k-mers, exact in float64.  hist: the all-reduced depth histogram (N > 1)."""
+    import numpy as np
+    L, mg = cx.L, cx.mg
+    mg.check(L.modsetSyncToHost(ms, 0))
+    u = int(ms.contents.max)
+    value = np.ctypeslib.as_array(ms.contents.value, (u + 1,))
+    depth = np.ctypeslib.as_array(ms.contents.depth, (u + 1,))
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(1, u + 1, size=min(DUMP_SAMPLE, u))) if u else np.zeros(0, np.int64)
+    vs = value[idx]
+    if vs.size and int(vs.max()) >= 1 << 53:
+        raise RuntimeError("modset values above 2^53 cannot be written as float64 exactly")
+    arrays = {"modset_counts": np.array([n_hash, u], np.float64),                    # modimizers of the step, entries of the set
+              "modset_sample_index": idx.astype(np.float64),
+              "modset_value_sample": vs.astype(np.float64),
+              "modset_depth_sample": depth[idx].astype(np.float32),
+              "modset_depth_histogram": np.bincount(depth[1:], minlength=65536).astype(np.float64)}
+    if hist is not None:
+        arrays["allreduced_depth_histogram"] = hist.cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def rank_parity(cx, ms, reads, d_offsets, offsets, n_reads, S, k, d, seed):
@@ -889,7 +940,7 @@ def bench_c3(cx, args, shard=None):
     del s_idx, s_pos, s_rd
     torch.cuda.empty_cache()
     ref_read = None
-    if not shard and getattr(args, "full", False) and os.environ.get("MODGPU_BENCH_C3_REFREAD", "1") == "1":    # the whole mgReferenceRead call from host bytes: --full
+    if not shard and getattr(args, "full", False) and not getattr(args, "no_extra", False) and os.environ.get("MODGPU_BENCH_C3_REFREAD", "1") == "1":    # the whole mgReferenceRead call from host bytes: --full
         try:
             import bench_extra as X
             ref_read = X.reference_read_whole(cx, genome, genome_bases, n_seq, seq_len, k, d, bits, ref_occ, ref_entries)

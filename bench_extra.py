@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench_extra.py -- the legs of the benchmark that are NOT the driver's line: what a caller waits for around the kernels
 (host bytes, files, result mirrors, .mod writing, the reference's unmodified programs on the library) and the secondary
-paths (minimizers, repeat-rich genomes).  `python bench.py --full` runs them after the headline and writes them, with
-everything else, to profiles/bench_detail_last.json; the driver's command does not set the flag, so its run is the
-headline workload, the CPU baseline and one {value, ms, frac} triple per other BASELINE config.
+paths (minimizers, repeat-rich genomes).  `python bench.py --full` runs them after the headline, the CPU baseline and the
+other BASELINE configs, and writes them, with everything else, to profiles/bench_detail_last.json (`--no-extra` leaves them
+out); a plain run is the headline workload alone.
 
 Every function takes the bench's context `cx` (torch, library handle, device, stream; `cx.B` is bench.py's module: its
 generators and timers)."""

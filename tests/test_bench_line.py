@@ -5,9 +5,11 @@ import copy
 import io
 import json
 import os
+import subprocess
 import sys
 from contextlib import redirect_stdout
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,3 +81,36 @@ def test_emit_prints_the_compact_line_last(tmp_path, monkeypatch):
     assert json.loads(lines[0][len("BENCH_DETAIL "):]) == full
     assert json.loads(lines[1])["detail"] == "profiles/bench_detail_last.json" and len(lines[1]) < 8192
     assert json.load(open(tmp_path / "profiles" / "bench_detail_last.json")) == full
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_what_it_computed(tmp_path):
+    """a plain run (no --full): exactly --steps timed steps and the contract's keys, nothing measured beside the headline; --dump-outputs
+    writes float32 / float64 arrays, under 64 MB in all, that agree with the line's counts -- the same arrays whatever the number of steps"""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["MODGPU_BENCH_GBP"] = "0.2"
+    dumps = []
+    for steps in (3, 4):
+        out = tmp_path / ("out%d" % steps)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.rstrip().splitlines()[-1])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in j, k
+        assert j["steps"] == steps and j["value"] > 0 and j["ms_per_step"] > 0 and j["higher_is_better"] is True
+        for k in ("roofline", "scan_only", "cpu_baseline", "other_configs", "end_to_end"):
+            assert k not in j, k
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        a = {f[:-len(".npy")]: np.load(out / f) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        n_hash, entries = a["modset_counts"]
+        assert n_hash == j["config"]["modimizers_per_gpu"] and entries == j["config"]["modset_entries"] > 0
+        h = a["modset_depth_histogram"]                  # every entry's depth: one per entry, one depth count per modimizer
+        assert h[0] == 0 and h.sum() == entries and (h * np.arange(65536)).sum() == n_hash
+        idx = a["modset_sample_index"]
+        assert 0 < len(idx) == len(a["modset_value_sample"]) == len(a["modset_depth_sample"]) and 1 <= idx.min() and idx.max() <= entries
+        assert (a["modset_depth_sample"] >= 1).all() and len(np.unique(a["modset_value_sample"])) == len(idx)
+        dumps.append(a)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])

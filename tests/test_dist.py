@@ -248,7 +248,7 @@ def test_bench_multi_rank_path_on_one_gpu():
                MODGPU_BENCH_C3_SCALE="0.02", MODGPU_BENCH_C3_BATCHES="2")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j, full, compact = bench_lines(r.stdout)
@@ -357,7 +357,7 @@ def test_bench_world2_code_path_on_one_gpu():
     reads split into two shares over replicated modsets.  The rates of such a run mean nothing and are not looked at."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MODGPU_BENCH_ONE_GPU="1", MODGPU_BENCH_GBP="0.3", MODGPU_BENCH_C3_SCALE="0.02", MODGPU_BENCH_C3_BATCHES="3")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j, full, lines = bench_lines(r.stdout)
@@ -383,7 +383,7 @@ def test_bench_forced_dist_agrees_with_plain_single_gpu():
     the barriers must not cost more than 3 % of a step."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MODGPU_BENCH_GBP="6", MASTER_PORT=str(_free_port()))
-    a = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu", "--no-other"],
+    a = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full", "--no-cpu", "--no-other"],
                        capture_output=True, text=True, timeout=900, env=dict(env, MODGPU_BENCH_FORCE_DIST="1"), cwd=ROOT)
     assert a.returncode == 0, a.stderr[-2000:]
     ja, _, _ = bench_lines(a.stdout)
@@ -413,7 +413,7 @@ def test_bench_on_every_gpu_of_the_box(n):
     if _gpu_count() < n:
         pytest.skip("needs %d GPUs, this box has %d" % (n, _gpu_count()))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=2400, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j, full, lines = bench_lines(r.stdout)

@@ -6,5 +6,5 @@
 for cfg in "$@"; do
   name=${cfg%%:*}; envs=${cfg#*:}
   [ -n "$ABL" ] && envs="$envs MODGPU_LIB=$PWD/tools/variants_abl/libmodgpu.so"
-  env $envs python bench.py --steps 10 --warmup 2 --no-cpu --no-other 2>/dev/null | grep "^{" | python tools/kern_ms.py "$name" | sed "s/'PartChunks+Scan'[^']*//; s/'RankScan'.*//; s/'SegScan'.*//"
+  env $envs python bench.py --full --no-extra --steps 10 --warmup 2 --no-cpu --no-other 2>/dev/null | grep "^{" | python tools/kern_ms.py "$name" | sed "s/'PartChunks+Scan'[^']*//; s/'RankScan'.*//; s/'SegScan'.*//"
 done
