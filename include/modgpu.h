@@ -355,6 +355,27 @@ int  mgTextParseFileDevice (const char *filename, char **bases, int64_t **offset
 int  mgAddSequenceFile (Modset *ms, const char *filename, FILE *out) ;                        /* modutils.c:33-51 */
 int  mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FILE *out) ;   /* modmap.c:93-134 */
 int  mgQueryFile (MgReference *ref, const char *filename, FILE *out) ;                        /* modmap.c:188-281 */
+/* modutils' two commands that read a set already built (the set itself is not changed: not its max, entries or depths; a lookup may
+ * bring a device table to the lookup load, as modsetFindBatchDevice does).  The lookups, the depth gathers and the formatting of the
+ * text run on the device (mg_report.hip); the host copies the text out and a writer thread puts it to the FILE * in order.  Depths
+ * are those after every pending add, counts not yet synced to the host included (the host depth[] receives them as modsetSyncToHost
+ * would bring them).  0 = done, -1 = error (mgLastError); without a HIP device both fail (there is no CPU fallback).
+ *
+ * mgReportDepths: modutils.c:65-77 ("-d"): for i = 1 .. ms->max one line "MH	%llx	%d	%u" (value[i], msCopy (ms, i), depth[i]), then
+ * "	%u" per other set, the depth of value[i] there (0 if absent), and "
+".  The other sets may come straight from modsetRead: their
+ * device tables are made on first use and LEFT RESIDENT (release them with mgModsetDeviceRelease, or modsetDestroy).  A value wider than
+ * an other set's 2k bits is answered 0 without a lookup in that set (it holds only values below 4^k). */
+int  mgReportDepths (Modset *ms, Modset **others, int nOthers, FILE *f) ;
+/* modutils.c:260-273 ("-P") on records already in memory (bases 0..3, offsets[n+1], names[n]): "painting %s length %d\n" per record,
+ * then "  %d\t%d\n" (pos, depth) for every modimizer of the record found in ms, in modRCnext order -- also for a record shorter than k
+ * or empty (its header alone).  N is base 0 here as everywhere in the library: the reference's -P reads its file through dna2indexConv,
+ * which maps N to 0 only after an earlier -a (modutils.c:39; without one its iterator reads past patternRC[]), so compare with
+ * `-a ... -P`.  The reference prints to stdout; these write to `out`. */
+int  mgRefPaint (Modset *ms, const char *bases, const int64_t *offsets, int nSeq, const char **names, FILE *out) ;
+/* the same from a FASTA / FASTQ file: plain text through the device parser, gzip, an unterminated last line or FASTQ that breaks a
+ * rule through the host parser, as mgQueryFile.  An unreadable file: -1 with "failed to open ref seq file <name>" (modutils.c:262). */
+int  mgRefPaintFile (Modset *ms, const char *filename, FILE *out) ;
 int  mgFormatF2 (char *buf64, double x) ;	/* test hook: the "%.2f" of the Q / M lines as the library's parallel formatter writes it (glibc's rounding of the double's exact value, in integer arithmetic; snprintf itself for nan / inf / negative); returns the length */
 
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):

@@ -77,6 +77,7 @@ EXPORTS = [
     "mgCommInitAll", "mgCommGetUniqueId", "mgCommInitRank", "mgCommRank", "mgCommSize", "mgCommDestroy", "mgHistogramAllReduce", "mgDepthAllReduce", "mgModsetMergeRankOrder",
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
+    "mgReportDepths", "mgRefPaint", "mgRefPaintFile",
     "mgIterScanHost", "mgIterHostBelow", "mgReloadKnobs", "mgFormatF2", "mgModsetMergeArrays", "mgModsetMergeDeviceArrays", "mgModsetClear", "mgModsetDeviceSlots", "mgSetVerbose", "mgProfileEnable", "mgProfileOnly", "mgProfileReset", "mgProfileKernels", "mgProfileGet",
 ]
 
@@ -227,6 +228,8 @@ def lib():
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
     sig("mgAddSequenceFile", i32, MS, C.c_char_p, vp); sig("mgReferenceFastaRead", i32, vp, C.c_char_p, C.c_bool, vp)
     sig("mgQueryFile", i32, vp, C.c_char_p, vp)
+    sig("mgReportDepths", i32, MS, C.POINTER(MS), i32, vp)
+    sig("mgRefPaint", i32, MS, vp, vp, i32, C.POINTER(C.c_char_p), vp); sig("mgRefPaintFile", i32, MS, C.c_char_p, vp)
     sig("mgReferenceWrite", None, vp, C.c_char_p); sig("mgGzipOpenWrite", vp, C.c_char_p); sig("mgGzipOpenRead", vp, C.c_char_p); sig("mgFzOpen", vp, C.c_char_p, C.c_char_p);
     sig("mgCommInitAll", i32, C.POINTER(vp), i32, C.POINTER(i32)); sig("mgCommGetUniqueId", i32, vp); sig("mgCommInitRank", i32, C.POINTER(vp), i32, i32, vp, i32)
     sig("mgCommRank", i32, vp); sig("mgCommSize", i32, vp); sig("mgCommDestroy", None, vp)
@@ -413,3 +416,33 @@ def add_sequence_batch(ms, bases, offsets):
     if n < 0:
         raise ModgpuError("mgAddSequenceBatch failed: " + lib().mgLastError().decode())
     return n
+
+
+def report_depths(ms, others, path):
+    """mgReportDepths: modutils -d (modutils.c:65-77) into the file `path`; others: a list of Modset*.  Their device tables stay resident
+    (mgModsetDeviceRelease releases one)."""
+    arr = (C.POINTER(Modset) * max(len(others), 1))(*others)
+    with CFile(path, "w") as f:
+        rc = lib().mgReportDepths(ms, arr, len(others), f)
+    if rc:
+        raise ModgpuError("mgReportDepths failed: " + lib().mgLastError().decode())
+
+
+def refpaint_file(ms, path, out_path):
+    """mgRefPaintFile: modutils -P (modutils.c:260-273) on the FASTA / FASTQ file `path`, its lines into the file `out_path`."""
+    with CFile(out_path, "w") as f:
+        rc = lib().mgRefPaintFile(ms, path.encode(), f)
+    if rc:
+        raise ModgpuError("mgRefPaintFile failed: " + lib().mgLastError().decode())
+
+
+def refpaint(ms, bases, offsets, names, out_path):
+    """mgRefPaint: modutils -P on records already in memory (bases 0..3, offsets[n+1], names: list of str) into `out_path`."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    nm = (C.c_char_p * max(n, 1))(*[x.encode() for x in names])
+    with CFile(out_path, "w") as f:
+        rc = lib().mgRefPaint(ms, bases.ctypes.data, offsets.ctypes.data, n, nm, f)
+    if rc:
+        raise ModgpuError("mgRefPaint failed: " + lib().mgLastError().decode())

@@ -16,6 +16,7 @@ int  mgHookHasDevice (Modset *ms);
 int  mgHookMergeDevice (Modset *ms1, Modset *ms2);   /* modsetMerge with ms1 on the device; 0 = done */
 int  mgHookDeviceView (Modset *ms, const U64 **dValue1, const U16 **dDepth1, U32 *max);      /* entries 1 .. max on the device, counts folded; -1: no device table */
 int  mgHookMergeDeviceArrays (Modset *ms1, const U64 *dValue2, const U16 *dDepth2, const U8 *dInfo2, U32 n2);   /* the second set as device arrays */
+int  mgHookDeviceViewMake (Modset *ms, const U64 **dValue1, const U16 **dDepth1, U32 *max);  /* the same, the device table made from the host arrays if there is none */
 int  mgHookPruneDevice (Modset *ms, int lo, int hi);  /* modsetDepthPrune on the device; 0 = done */
 /* one GPU scan of one read for the iterator facade: *blk = malloc()ed replay block {U64 n; U64 kmer[n]; U32 posF[n]} */
 int  mgIterScan (Seqhash *sh, const char *s, int len, U64 **blk);
@@ -75,6 +76,15 @@ MG_HIDDEN MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax,
 MG_HIDDEN void mgReadsetDevForget (const void *rs);
 MG_HIDDEN void mgReadsetDevAppendHits (const void *rs, const U32 *dHit, U64 n);      /* a batch's hit list kept on the device for the end of the file */
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
+/* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
+typedef struct MgTextOut MgTextOut;
+MG_HIDDEN MgTextOut *mgTextOutOpen (FILE *out);
+MG_HIDDEN int  mgTextOutFromDevice (MgTextOut *w, const void *dSrc, size_t bytes);   /* copied into page-locked blocks now, written behind the caller, in order */
+MG_HIDDEN int  mgTextOutClose (MgTextOut *w);                /* returns when every byte is written; -1 if a write failed */
+MG_HIDDEN int  mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
+                                      const char *idBytes, const U64 *idOff, MgTextOut *w, void **scratch);   /* modutils.c:262-270 over a device batch; 0 / -1 */
+MG_HIDDEN void mgRefPaintScratchFree (void *scratch);
+MG_HIDDEN void mgSetErrorText (const char *msg);
 /* element count of the reference's Array after appending elements 0..n-1 (array.c:144-170,180-183) */
 MG_HIDDEN int mgRefArrayDim (int first, int size, int n);
 #ifdef __cplusplus

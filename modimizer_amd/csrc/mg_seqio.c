@@ -1120,3 +1120,47 @@ int mgQueryFile (MgReference *ref, const char *filename, FILE *out)            /
   if (rc == -1 && access (filename, R_OK)) { fprintf (stderr, "FATAL ERROR: failed to read query sequence file %s\n", filename); exit (-1); }   /* modmap.c:196 */
   return rc;
 }
+
+/* modutils.c:260-273 ("-P"): plain FASTA / FASTQ text is parsed on the device and each batch painted there (mg_report.hip), its text
+   written behind the next batch by the writer thread; gzip, a last line without its newline, FASTQ that breaks a rule: the host parser
+   (from the first record the device parser has not handed on), each of its batches uploaded and painted the same way */
+typedef struct { Modset *ms; MgTextOut *w; void *scratch; } PaintCtx;
+static int paintDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *idBytes, const U64 *idOff, void *stream)
+{ PaintCtx *c = (PaintCtx *) v; (void) stream; return mgRefPaintBatchDevice (c->ms, dPacked, total, dOff, nReads, idBytes, idOff, c->w, &c->scratch); }
+static int paintHostBatch (MgSeqBatch *b, void *v)
+{
+  PaintCtx *c = (PaintCtx *) v;
+  if (b->nSeq <= 0) return 0;
+  U64 *idOff = (U64 *) malloc ((size_t) b->nSeq * 8);
+  if (!idOff) return -1;
+  for (int r = 0 ; r < b->nSeq ; ++r) idOff[r] = (U64) (b->names[r] - b->names[0]);      /* the ids share one block (mgSeqBatchFree) */
+  MgDevBatch d; mgBatchUpload (&d, b->bases, b->offsets, b->nSeq);
+  const int rc = mgRefPaintBatchDevice (c->ms, (const U32 *) d.dPacked, d.total, (const U64 *) d.dOff, (U32) b->nSeq, b->names[0], idOff, c->w, &c->scratch);
+  mgBatchFree (&d);
+  free (idOff);
+  return rc;
+}
+#define MG_PAINT_FILE_BATCH 128000000ull
+
+int mgRefPaintFile (Modset *ms, const char *filename, FILE *out)
+{
+  char msg[600];
+  if (!ms || !filename || !out) { mgSetErrorText ("mgRefPaintFile: invalid arguments"); return -1; }
+  { FILE *f = fopen (filename, "r");
+    if (!f) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); return -1; }    /* modutils.c:262 */
+    fclose (f);
+  }
+  if (mgIterRequireDevice ()) return -1;
+  PaintCtx c; c.ms = ms; c.w = mgTextOutOpen (out); c.scratch = 0;
+  U64 nSeq = 0, totLen = 0, resumeOff = 0, resumeLine = 1;
+  int rc = mgTextForEachBatchDevice (filename, paintDeviceBatch, &c, MG_PAINT_FILE_BATCH, 1, &nSeq, &totLen, &resumeOff, &resumeLine);
+  if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, nSeq, paintHostBatch, &c);
+  else if (rc == -2)
+    { MgSeqReader *r = mgSeqOpen (filename);                /* (what the host parser cannot take either: the reference's seqIOopenRead fails) */
+      if (!r) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); rc = -1; }
+      else { mgSeqClose (r); rc = forEachBatch (filename, paintHostBatch, &c); }
+    }
+  if (mgTextOutClose (c.w) && !rc) { mgSetErrorText ("mgRefPaintFile: write failed"); rc = -1; }
+  mgRefPaintScratchFree (c.scratch);
+  return rc ? -1 : 0;
+}
