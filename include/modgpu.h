@@ -179,6 +179,12 @@ MgStatus mgModsetClear (Modset *ms, void *stream) ;
 /* Slots of the device table behind ms (0 when there is none): what bench.py prices the bucket image with. */
 U64 mgModsetDeviceSlots (Modset *ms) ;
 
+/* A check of the device table's layout that does not use the lookups (tests, diagnostics).  out6 (host): [0] keys whose path from
+ * their home slot to their own crosses an empty slot, [1] keys in a bucket other than the one they imply, [2] keys held twice in a
+ * bucket -- all 0 in a sound table -- [3] keys in the table; and, since the device table was made, [4] buckets the build laid out by
+ * prefix scan, [5] those of them whose entries ran over the bucket's end and came in again at its first slot. */
+MgStatus mgTableCheckLayout (Modset *ms, U64 *out6) ;
+
 /* modutils.c:53-63 on the device: dHist[65536] (U64) += histogram of depth[1..max], where depth is
  * the host depth at last sync plus pending device counts, saturated at 65535. */
 MgStatus modsetDepthHistogramDevice (Modset *ms, U64 *dHist65536, void *stream) ;

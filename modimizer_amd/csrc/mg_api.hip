@@ -951,6 +951,17 @@ extern "C" int mgHookDeviceViewMake (Modset *ms, const U64 **dValue1, const U16 
 
 extern "C" U64 mgModsetDeviceSlots (Modset *ms) { MgDev *d = mgDevLookup (ms); return d && d->built ? d->t.nSlots : 0; }
 
+extern "C" MgStatus mgTableCheckLayout (Modset *ms, U64 *out6)
+{
+  MgDev *d; MgStatus s = mgDevGet (ms, &d, 0); if (s) return s;
+  U64 *dOut = 0;
+  MG_HIP (hipMalloc ((void **) &dOut, 32));
+  s = mgTableLayoutCheck (&d->t, dOut, 0);
+  if (!s && (hipMemcpy (out6, dOut, 32, hipMemcpyDeviceToHost) || hipMemcpy (out6 + 4, d->t.counters + 4, 16, hipMemcpyDeviceToHost))) s = MG_ERR_HIP;
+  (void) hipFree (dOut);
+  return s;
+}
+
 extern "C" MgStatus modsetDepthHistogramDevice (Modset *ms, U64 *dHist, void *stream)
 {
   hipStream_t st = (hipStream_t) stream;

@@ -233,7 +233,8 @@ struct MgTable {
   U32 size;            /* capacity in entries (ms->size) */
   U32 max;             /* entries known to the device table */
   U32 syncedMax;       /* entries whose value[] the host already has */
-  U64 *counters;       /* device U64[8]: 0 = new entries of the last add, 1 = bucket overflow */
+  U64 *counters;       /* device U64[8]: 0 = new entries of the last add, 1 = bucket overflow, 2-3 = the tightening's entry counts; since the table was
+                          made: 4 = buckets the merge kernel laid out by prefix scan, 5 = those of them that ran over their end */
   bool pendingDepth;   /* an add with depth counting ran since the counts were last folded into baseDepth / the host's depth[] */
   bool dirty;          /* buckets with occ == 0 hold undefined bytes (never zeroed): see mgTableClean */
   U64 *find8;          /* the partitioned lookups' copy of the table, 8 bytes a slot: (key's bits below the bucket id + 1) << 31 | index, 0 = empty (mg_table.hip
@@ -264,6 +265,7 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
 bool     mgTableAddTakesSegments (const MgTable *t, U64 n, const MgHistReq *counted);
 MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st);
 MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipStream_t st);
+MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut4, hipStream_t st);      /* see mgTableCheckLayoutKernel */
 size_t   mgTableFindPartScratchBytes (U64 n);
 int      mgTableFindDigitBits (const MgTable *t);       /* bits of the partitioned lookup's digit: pieces of the table that fit an XCD's L2 */
 bool     mgTableFindTakesPartition (const MgTable *t, U64 n, const MgHistReq *counted);

@@ -29,6 +29,8 @@ typedef struct {
   long rankSliceShift;     /* MODGPU_RANK_SLICE_SHIFT */
   long flagPolarity;       /* MODGPU_FLAG_POLARITY: 0 / 1 force which way round the first-occurrence flags are written */
   long mergeSlots;         /* MODGPU_MERGE_SLOTS: 0 / 1: the merge kernel probes / takes the dedup kernel's slots */
+  long mergePlace;         /* MODGPU_MERGE_PLACE: 0 = the merge kernel claims the slots of a bucket that was empty one by one, 1 = it lays them out by prefix scan,
+                              unset = by prefix scan where the expected lists fit the kernel's spill-free instance (mgTableAdd) */
   long bucketR, bucketT;   /* MODGPU_BUCKET_R / MODGPU_BUCKET_T: slots per bucket / threads of the bucket kernels */
   long hotSplit, hotChunk; /* MODGPU_HOT_SPLIT="split[,chunk]": occurrences above which a bucket is reduced chunk-wise first */
   long noAvx2;             /* MODGPU_NO_AVX2: 1 = portable packer / parser loops */

@@ -887,6 +887,7 @@ struct MgBucketArgs {
   int slotShift;                   /* != 0 (2k <= 48): a list entry carries, above bit slotShift of its mixed k-mer, the slot the k-mer holds in
                                       the dedup kernel's LDS image of the bucket -- a valid place in the bucket (the image starts from the
                                       table's own), so the merge kernel puts it there without probing */
+  int place;                       /* != 0: the merge kernel lays a bucket that was empty (occ = 0) out by prefix scan (mgPlaceFresh), without a probe */
   int markDup;                     /* which way round the flags are written: 0 = cleared by a memset, the dedup kernel sets the first occurrence
                                       of every new k-mer (one store per unique); 1 = preset to 1, it clears every occurrence that is NOT one (one
                                       store per duplicate: fewer when most of a batch's modimizers are new k-mers) */
@@ -900,7 +901,7 @@ struct MgBucketArgs {
   U64 *hotItems; unsigned long long *hotCount;     /* the chunks to reduce: (bucket << 32 | chunk), and how many ([0]; [1]: oversize buckets) */
   U32 *hotBuckets;                                 /* the oversize buckets, for the dedup kernel's HOT instance */
 #ifdef MG_ABLATE
-  int debug;                       /* ablation builds only (MODGPU_BUCKET_DEBUG): dedup: 1 no flag stores, 2 plain stores for max/add, 4 no claim loop, 8 no list stores; merge: 32 no claim loop, 64 no image stores; lookup: 16 no rank gathers, 128 no index stores, 256 no ordinal loads; results are wrong */
+  int debug;                       /* ablation builds only (MODGPU_BUCKET_DEBUG): dedup: 1 no flag stores, 2 plain stores for max/add, 4 no claim loop, 8 no list stores; merge: 32 no claim loop, 64 no image stores; lookup: 16 no rank gathers, 128 no index stores, 256 no ordinal loads; the merge kernel's scan placement: 512 no home counts, 1024 no scans, 2048 no placement stores; results are wrong */
 #endif
   unsigned long long *liveHist;    /* != 0: the merge kernel also counts the final depths of the entries it writes */
 };
@@ -938,6 +939,7 @@ __device__ __forceinline__ U32 mgLdsClaim (unsigned long long *sKey, U32 R, U32 
 #ifndef MG_HOT_DEPTH
 #define MG_HOT_DEPTH 4                /* occurrences per thread and turn of the dedup kernel's loop over what was not fetched ahead */
 #endif
+#define MG_PLACE_KEEP 4              /* uniques per thread the merge kernel's scan placement takes: R <= 4 x threads, so every list of a bucket of up to 4096 slots */
 #define MG_RANK_GROUPS 64            /* most groups a bucket's list is cut into: slices of the ordinal range + 1 */
 #define MG_SLOT_SHIFT 48             /* a list entry's slot sits above this bit of its mixed k-mer (when 2k <= 48) */
 #define MG_DEDUP_PER 4               /* slots of the LDS image per thread of the dedup kernel: R <= 4 x threads ... */
@@ -1314,8 +1316,81 @@ void mgBucketDedupKernel (const MgBucketArgs a, U32 bucketsPerBlock)
   }
 }
 
+/* ---- placement by prefix scan (the merge kernel, a bucket that was empty before the add) ----
+ * All of the bucket's keys are known at once and distinct, so the linear-probing layout follows without a probe:
+ *     cnt[h]   = keys whose home slot is h (a key's rank r among them: what its LDS add returns)
+ *     C[h]     = exclusive prefix sum of cnt
+ *     start[h] = max (h, start[h-1] + cnt[h-1]) = C[h] + max (carry, max over j <= h of (j - C[j]))
+ *     slot     = (start[home] + r) mod R
+ * carry is what runs over the bucket's end and comes in again at slot 0: max (0, max over all j of (j - C[j]) + N - R) for N < R
+ * keys -- it never exceeds that maximum, so one pass with carry = 0 gives it and it enters as a plain max.  Keys end up ordered by
+ * home slot with no empty slot between a key's home and its place: an ordinary linear-probing bucket to every reader.
+ * A block of consecutive slots is summed up as (S, M) = (its keys, max of j - C[j] with C counted from the block's start); two
+ * neighbours combine to (SA + SB, max (MA, MB - SA)). */
+/* inclusive prefix max over the 64 lanes of a wave (DPP, the steps of mgWaveInclusiveSum; lanes without a source take 0) */
+__device__ __forceinline__ U32 mgWavePrefixMax (U32 v)
+{
+#define MG_MAX_DPP(ctrl, rows) do { const U32 o_ = (U32) __builtin_amdgcn_update_dpp (0, (int) v, ctrl, rows, 0xf, false); v = o_ > v ? o_ : v; } while (0)
+  MG_MAX_DPP (0x111, 0xf); MG_MAX_DPP (0x112, 0xf); MG_MAX_DPP (0x114, 0xf); MG_MAX_DPP (0x118, 0xf); MG_MAX_DPP (0x142, 0xa); MG_MAX_DPP (0x143, 0xc);
+#undef MG_MAX_DPP
+  return v;
+}
+/* start[] of the bucket whose home counts stand in cnt[0..R) (every thread of the workgroup calls this after the barrier behind the
+ * counting): left in sStart as 16-bit words (start < 2R <= 16384), cnt[] zeroed again; returns the carry.  n: the keys counted
+ * (< R).  A thread owns `per` consecutive slots (a multiple of four: 16-byte LDS accesses), sWave: 2 x 16 words.  Ends WITHOUT a
+ * barrier: the caller puts one before sStart is read. */
+__device__ __forceinline__ U32 mgPlaceStarts (U32 *cnt, unsigned short *sStart, int *sWave, U32 R, U32 T, U32 tid, U32 n)
+{
+  const U32 per = (R + 4 * T - 1) / (4 * T) * 4;
+  const U32 j0 = tid * per, j1 = j0 + per < R ? j0 + per : R;      /* (R is a multiple of MG_R_QUANTUM, so of four) */
+  /* M never falls below 0 where it counts (slot 0 gives 0 - 0), so every max below is taken with 0 and the scans are the wave's
+     plain sum and max: first the sums, then the maxima moved to the common origin, inside the wave and then over the waves */
+  U32 vS = 0; int vM = 0;
+  for (U32 j = j0 ; j < j1 ; j += 4)
+    { const uint4 c = *reinterpret_cast<const uint4 *> (&cnt[j]);
+      int m = (int) j - (int) vS;               vM = m > vM ? m : vM; vS += c.x;
+      m = (int) (j + 1) - (int) vS;             vM = m > vM ? m : vM; vS += c.y;
+      m = (int) (j + 2) - (int) vS;             vM = m > vM ? m : vM; vS += c.z;
+      m = (int) (j + 3) - (int) vS;             vM = m > vM ? m : vM; vS += c.w;
+    }
+  const int lane = (int) (tid & 63);
+  const U32 wave = (U32) __builtin_amdgcn_readfirstlane ((int) (tid >> 6));
+  const U32 inS = mgWaveInclusiveSum (vS), exS = inS - vS;               /* keys before this thread inside its wave */
+  const U32 inM = mgWavePrefixMax (vM > (int) exS ? (U32) vM - exS : 0u);  /* counted from the wave's first slot */
+  if (lane == 63) { sWave[2 * wave] = (int) inS; sWave[2 * wave + 1] = (int) inM; }
+  U32 exM = (U32) __shfl_up ((int) inM, 1);
+  if (lane == 0) exM = 0;
+  __syncthreads ();
+  /* the waves' sums: every wave scans the (at most 16) pairs for itself, one per lane */
+  U32 wS = 0, wM = 0;
+  if ((U32) lane < (T + 63) / 64) { wS = (U32) sWave[2 * lane]; wM = (U32) sWave[2 * lane + 1]; }
+  const U32 wInS = mgWaveInclusiveSum (wS), wExS = wInS - wS;
+  const U32 wInM = mgWavePrefixMax (wM > wExS ? wM - wExS : 0u);
+  const int mAll = __builtin_amdgcn_readlane ((int) wInM, 63);
+  U32 beforeS = 0, beforeM = 0;
+  if (wave) { beforeS = (U32) __builtin_amdgcn_readlane ((int) wInS, (int) wave - 1); beforeM = (U32) __builtin_amdgcn_readlane ((int) wInM, (int) wave - 1); }
+  { const U32 m = exM > beforeS ? exM - beforeS : 0u; beforeM = beforeM > m ? beforeM : m; beforeS += exS; }
+  const int over = mAll + (int) n - (int) R;
+  const U32 carry = over > 0 ? (U32) over : 0u;
+  U32 c = beforeS; int e = beforeM > carry ? (int) beforeM : (int) carry;
+  for (U32 j = j0 ; j < j1 ; j += 4)
+    { const uint4 k = *reinterpret_cast<const uint4 *> (&cnt[j]);
+      *reinterpret_cast<uint4 *> (&cnt[j]) = make_uint4 (0, 0, 0, 0);
+      U32 s0, s1, s2, s3; int m;
+      m = (int) j - (int) c;       e = m > e ? m : e; s0 = c + (U32) e; c += k.x;
+      m = (int) (j + 1) - (int) c; e = m > e ? m : e; s1 = c + (U32) e; c += k.y;
+      m = (int) (j + 2) - (int) c; e = m > e ? m : e; s2 = c + (U32) e; c += k.z;
+      m = (int) (j + 3) - (int) c; e = m > e ? m : e; s3 = c + (U32) e; c += k.w;
+      *reinterpret_cast<uint2 *> (&sStart[j]) = make_uint2 (s0 | (s1 << 16), s2 | (s3 << 16));
+    }
+  return carry;
+}
+/* LDS of the merge kernel: the image (16 bytes a slot), 16 bytes, the live-depth bins, the scan's 2 x 16 words, start[] */
+static inline size_t mgMergeLdsBytes (U32 R) { return (size_t) R * 16 + 16 + MG_LIVE_BINS * 4 + 128 + (size_t) R * 2; }
+
 /* step 4: merge the bucket's uniques into the table bucket and stream it back */
-__global__ __launch_bounds__ (1024)
+template <int KEEP>          /* uniques per thread the scan placement takes (2: the ones fetched ahead, no more registers; MG_PLACE_KEEP: every list of a bucket of up to 4 x T slots) */
+__global__ __launch_bounds__ (1024) __attribute__ ((amdgpu_waves_per_eu (8)))      /* 64 registers: two workgroups per CU */
 void mgBucketMergeKernel (const MgBucketArgs a, U32 bucketsPerBlock)
 {
   MG_BUILD_PRIO ();
@@ -1329,6 +1404,10 @@ void mgBucketMergeKernel (const MgBucketArgs a, U32 bucketsPerBlock)
   for (U32 i = tid ; i < R ; i += T) { sKey[i] = 0; sOrd[i] = 0; sCnt[i] = 0; }
   U32 *sLive = sCnt + R + 4;                       /* MG_LIVE_BINS small-depth bins */
   for (U32 i = tid ; i < MG_LIVE_BINS ; i += T) sLive[i] = 0;
+  int *sWave = reinterpret_cast<int *> (sLive + MG_LIVE_BINS);                            /* mgPlaceStarts: 2 x 16 words */
+  unsigned short *sStart = reinterpret_cast<unsigned short *> (sWave + 32);              /* [R] */
+  U32 *sPlaced = sCnt + R;                         /* [2] (thread 0's) buckets laid out by scan, and those of them that ran over their end */
+  if (tid < 2) sPlaced[tid] = 0;
   U32 n1 = 0, n2 = 0;                              /* depth 1 and 2, the commonest, counted per wave */
   U32 nu = a.uniqCount[b];
   U32 nNew = a.sliceOff[(U64) b * (a.nSlices + 2) + a.nSlices];   /* the list's first nNew uniques are new to the table, the others are in it */
@@ -1363,6 +1442,57 @@ void mgBucketMergeKernel (const MgBucketArgs a, U32 bucketsPerBlock)
                 }
               __syncthreads ();
             }
+          if (!occNow && a.place && !a.slotShift)   /* (uniform) the bucket was empty: every unique is new, and all of them are here.  (With carried slots a
+                                                       list entry holds its slot above the k-mer and goes where it says, below, empty bucket or not.) */
+            { /* KEEP x T uniques are laid out by scan, their home and rank kept in a register each between the counting and
+                 the stores (those beyond the ones fetched ahead are read again for the stores); a longer list's others -- the launcher picks KEEP so that only a
+                 bucket of more than 4 x T slots, the 8192-slot table, has any -- are then claimed into the image the scan left (a valid
+                 linear-probing bucket) as in the parent. */
+              const U32 nScan = nu < (U32) KEEP * T ? nu : (U32) KEEP * T;
+              if (nu >= R) { a.counters[1] = 1; }             /* (uniform) no room: as mgLdsClaim returning R; the bucket stays empty */
+              else
+                { U32 hr[KEEP];                             /* home << 16 | rank (both < R <= 8192) */
+#pragma unroll
+                  for (int j = 0 ; j < KEEP ; ++j)
+                    { const U32 i = (U32) j * T + tid;
+                      hr[j] = 0;
+                      if (i < nScan MG_ABLATE_AND (!(a.debug & 512)))
+                        { const U64 km = j < MG_MERGE_PREFETCH ? ck[j < MG_MERGE_PREFETCH ? j : 0] : __builtin_nontemporal_load (&a.pK[lo + i]);
+                          const U32 home = mgHomeOfM (km, a.g); hr[j] = (home << 16) | atomicAdd (&sOrd[home], 1u);
+                        }
+                    }
+                  __syncthreads ();
+                  U32 carry = 0;
+#ifdef MG_ABLATE
+                  if (a.debug & 1024) { for (U32 i = tid ; i < R ; i += T) { sStart[i] = (unsigned short) i; sOrd[i] = 0; } } else
+#endif
+                  carry = mgPlaceStarts (sOrd, sStart, sWave, R, T, tid, nScan);
+                  if (tid == 0) { ++sPlaced[0]; if (carry) ++sPlaced[1]; }
+                  __syncthreads ();
+#pragma unroll
+                  for (int j = 0 ; j < KEEP ; ++j)
+                    { const U32 i = (U32) j * T + tid;
+                      if (i < nScan MG_ABLATE_AND (!(a.debug & 2048)))
+                        { U64 km; U32 ord, c;
+                          if (j < MG_MERGE_PREFETCH) { km = ck[j < MG_MERGE_PREFETCH ? j : 0]; ord = co[j < MG_MERGE_PREFETCH ? j : 0]; c = cc[j < MG_MERGE_PREFETCH ? j : 0]; }
+                          else { km = __builtin_nontemporal_load (&a.pK[lo + i]); ord = __builtin_nontemporal_load (&a.pT[lo + i]); c = __builtin_nontemporal_load (&a.pC[lo + i]); }
+                          U32 at = (U32) sStart[hr[j] >> 16] + (hr[j] & 0xffffu);
+                          if (at >= R) at -= R;
+                          sKey[at] = km + 1; sOrd[at] = ord; sCnt[at] = a.withDepth ? c : 0;
+                        }
+                    }
+                  if (nu > nScan)                                /* (uniform) */
+                    { __syncthreads ();
+                      for (U32 i = nScan + tid ; i < nu ; i += T)
+                        { const U64 km = __builtin_nontemporal_load (&a.pK[lo + i]);
+                          const U32 at = mgLdsClaim (sKey, R, mgHomeOfM (km, a.g), km + 1);
+                          if (at == R) { a.counters[1] = 1; continue; }
+                          sOrd[at] = __builtin_nontemporal_load (&a.pT[lo + i]); sCnt[at] = a.withDepth ? __builtin_nontemporal_load (&a.pC[lo + i]) : 0;
+                        }
+                    }
+                }
+            }
+          else
           /* the rank lookup kernel has turned the new uniques' ordinals into indices: place and count */
           for (U32 i = tid, jj = 0 ; i < nu ; i += T, ++jj)
             { U64 km; U32 ord, c;
@@ -1417,6 +1547,7 @@ void mgBucketMergeKernel (const MgBucketArgs a, U32 bucketsPerBlock)
 #pragma unroll
       for (int j = 0 ; j < MG_MERGE_PREFETCH ; ++j) { ck[j] = nk[j]; co[j] = no[j]; cc[j] = ncc[j]; }
     }
+  if (tid == 0 && sPlaced[0]) { atomicAdd ((unsigned long long *) &a.counters[4], (unsigned long long) sPlaced[0]); if (sPlaced[1]) atomicAdd ((unsigned long long *) &a.counters[5], (unsigned long long) sPlaced[1]); }
   if (a.liveHist)
     { __syncthreads ();
       if ((tid & 63) == 0) { if (n1) atomicAdd (&sLive[1], n1); if (n2) atomicAdd (&sLive[2], n2); }
@@ -1852,7 +1983,9 @@ void mgUniqStatsKernel (const U32 *__restrict__ uniqCount, U32 nBuckets, unsigne
   if ((threadIdx.x & 63) == 0) { if (sum) atomicAdd (&out[0], sum); if (mx) atomicMax (&out[1], (unsigned long long) mx); }
 }
 
-#define MG_TIGHT_PCT_DEFAULT 50      /* see MgTable.tightPct */
+#define MG_TIGHT_PCT_DEFAULT 70      /* see MgTable.tightPct.  80 is 0.06 ms a step faster still on config 2 (DESIGN_EXPERIMENTS.md section L); 70 is what the full-size
+                                        parity cases (tests/fullsize_whole.py) force as their other geometry, and they expect the default to be no tighter */
+#define MG_TIGHT_PCT_CLAIMS 50       /* the same with MODGPU_MERGE_PLACE=0: the merge kernel's claims pay for the load */
 #define MG_TIGHT_MIN_R 1024u         /* a bucket keeps room for the spread of a later add's share around its mean (mgTableEnsure sizes by the mean) */
 
 /* insert a batch (ordinal order = array order); counters[0] = number of new entries afterwards */
@@ -1963,13 +2096,39 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
      per cent on config 2, against 0.65 ms with carried slots at load 0.77).  So the table is only tightened where that pays: when the share
      of new k-mers the previous add saw (newPct; unknown: all new) says the entries will leave a quarter of the slots and more unused even at
      the tight load -- reads of deep coverage with few errors (config 5: a sixth of the modimizers are new; 4.3 -> 1.07 GB of bucket images). */
-  int tightPct = t->tightPct ? t->tightPct : MG_TIGHT_PCT_DEFAULT;
+  int tightPct = t->tightPct ? t->tightPct : MG_TIGHT_PCT_CLAIMS;      /* (MG_TIGHT_PCT_DEFAULT below, where the merge kernel places by scan) */
   { const long tk = mgKnobs ()->tightLoad; if (tk != MG_KNOB_UNSET && tk >= 0 && tk <= 95) tightPct = (int) tk; }
   bool tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
   if (tighten && mgKnobs ()->tightLoad == MG_KNOB_UNSET)          /* (the knob forces it: tests, sweeps) */
     { const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
       tighten = expectNew * 100 / (U64) tightPct < t->nSlots - t->nSlots / 4;
     }
+  /* a bucket that is empty before the add is laid out by prefix scan in the merge kernel (mgPlaceStarts): no probe whatever the load,
+     so an add into an empty table has no use for the dedup kernel's slots, and the tightening costs the merge kernel nothing: it is
+     done whenever the table was empty and the scan is on (DESIGN_EXPERIMENTS.md section L).  Only lists without carried slots go
+     through the scan (the kernel checks a.slotShift): a later add that carries slots puts an empty bucket's entries where they say. */
+  { const long pk = mgKnobs ()->mergePlace;                        /* MODGPU_MERGE_PLACE: 0 = claims everywhere, 1 = the scan for every fresh bucket, unset = the rule below */
+    a.place = pk == MG_KNOB_UNSET ? 1 : (pk != 0);
+    /* Left to itself the placement is for lists the kernel's spill-free instance takes whole (the uniques fetched ahead: MG_MERGE_PREFETCH
+       per thread).  Where the buckets' lists will be longer -- a config-4 block: 2500 uniques per bucket and 1024 threads -- the add goes
+       as before (carried slots; 11.06 ms a step against 11.16-11.44 with the scan's larger instance and the table at load 0.8).
+       The lists' length is estimated from the share of new k-mers the previous add saw; the FIRST add a table ever sees has none to go by,
+       is taken as all new (n / NB = 0.75 R uniques per bucket: over the limit at every default geometry) and so goes as before too: the
+       scan and the tightening start with the second set a process builds from empty, which is every timed step of the benchmarks but not
+       the first file of a run.  Which instance fits is known exactly only after the dedup kernel -- too late for the choice between
+       the scan and carried slots, which the dedup kernel's own instance depends on. */
+    if (pk == MG_KNOB_UNSET)
+      { const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
+        unsigned thr = t->R >= 4096 ? 1024u : (t->R >= 2048 ? 512u : 256u);
+        while (thr < 1024 && (U64) thr * MG_DEDUP_PER < t->R) thr *= 2;
+        if (expectNew / NB * 115 / 100 > (U64) MG_MERGE_PREFETCH * thr) a.place = 0;
+      }
+    if (a.place && wasEmpty) a.slotShift = 0;
+    if (a.place && mgKnobs ()->tightLoad == MG_KNOB_UNSET)
+      { if (!t->tightPct) tightPct = MG_TIGHT_PCT_DEFAULT;
+        tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
+      }
+  }
   if (tighten) a.slotShift = 0;
   a.slots = t->slots; a.g = g; a.nBuckets = (U32) NB; a.bucketStart = bucketStart;
   a.pK = kB; a.pT = tB; a.pC = cB; a.uniqCount = uniqCount; a.occ = t->occ; a.flags = flags;
@@ -1999,7 +2158,7 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
       a.liveHist = (unsigned long long *) t->liveHist;
     }
   t->liveHistValid = track;
-  size_t lds = (size_t) t->R * 16 + 16 + MG_LIVE_BINS * 4;
+  size_t lds = mgMergeLdsBytes (t->R);
   { const size_t ldsDedup = (size_t) t->R * 16 + MG_RANK_GROUPS * 4; if (ldsDedup > lds) lds = ldsDedup; }
   const bool bigR = t->R > MG_DEDUP_PER * 1024u;       /* R = 8192: the dedup kernel's threads take eight slots each */
   if (t->R > MG_DEDUP_PER_BIG * 1024u) { mgSetError ("internal: bucket of %u slots", t->R); return MG_ERR_ARG; }
@@ -2010,7 +2169,8 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
       if (bigR) { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER_BIG); }
       else      { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER); }
 #undef MG_DEDUP_ATTR
-      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_MERGE_PREFETCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_PLACE_KEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     }
   const int bThreadsEnv = mgKnobs ()->bucketT == MG_KNOB_UNSET ? 0 : (int) mgKnobs ()->bucketT;
   unsigned bThreads = bThreadsEnv ? (unsigned) bThreadsEnv : (t->R >= 4096 ? 1024u : (t->R >= 2048 ? 512u : 256u));
@@ -2039,6 +2199,7 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
   if (bigR) MG_DEDUP_PICK (MG_DEDUP_PER_BIG); else MG_DEDUP_PICK (MG_DEDUP_PER);
 #undef MG_DEDUP_PICK
 #undef MG_DEDUP_LAUNCH
+  U64 fullest = t->R;                                  /* the longest list a bucket may have: not known unless the tightening counts it */
   if (tighten)
     { unsigned long long *st2 = (unsigned long long *) (t->counters + 2);
       MG_HIP (hipMemsetAsync (st2, 0, 16, st));
@@ -2047,13 +2208,14 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
       MG_HIP (hipStreamSynchronize (st));
       const U64 over = t->pin[0], U = t->pin[1], M = t->pin[2];
       if (!over)
-        { U64 Rn = (U * 100 / ((U64) NB * (U64) tightPct) + 1 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
+        { fullest = M;
+          U64 Rn = (U * 100 / ((U64) NB * (U64) tightPct) + 1 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
           const U64 Rfit = (M + M / 8 + 16 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;      /* the fullest bucket at load 0.89 at most */
           if (Rn < Rfit) Rn = Rfit;
           if (Rn < MG_TIGHT_MIN_R) Rn = MG_TIGHT_MIN_R;
           if (Rn < t->R)
             { t->R = (U32) Rn; t->nSlots = (U64) NB * Rn; a.g = mgGeomOf (t);
-              lds = (size_t) t->R * 16 + 16 + MG_LIVE_BINS * 4;
+              lds = mgMergeLdsBytes (t->R);
             }
         }
     }
@@ -2069,7 +2231,12 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
     const U32 blocksPerSlice = (groupsPerSlice + 3) / 4, rounds = (a.nSlices + 7) / 8;
     MG_LAUNCH (MG_K_RANK_LOOKUP, st, mgRankLookupKernel, dim3 (8 * rounds * blocksPerSlice), dim3 (256), 0, st, a, groupsPerSlice);
   }
-  MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
+  /* the scan placement keeps a register per unique: the instance that takes only the uniques fetched ahead where no list is longer (the
+     tightening has counted the fullest bucket's; otherwise by the bucket's size), the one with MG_PLACE_KEEP otherwise (it spills a little) */
+  if (fullest <= (U64) MG_MERGE_PREFETCH * bThreads)
+    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_MERGE_PREFETCH>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
+  else
+    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_PLACE_KEEP>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }
@@ -2098,6 +2265,46 @@ MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipSt
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
   const unsigned fgrid = mgGrid ((n + MG_FIND_PER - 1) / MG_FIND_PER);
   MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableFindKernel<false>, dim3 (fgrid), dim3 (256), 0, st, t->slots, t->occ, mgGeomOf (t), dKmer, n, dIndexOut);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* A check of the table's layout that does not go through the lookups: a thread per slot walks from its key's home to the slot.
+   out[0] += keys whose walk crosses an empty slot (a lookup would stop there), out[1] += keys in a bucket other than the one they
+   imply, out[2] += keys met a second time on that walk (a duplicate inside the bucket), out[3] += keys */
+__global__ __launch_bounds__ (256)
+void mgTableCheckLayoutKernel (const MgSlot *__restrict__ slots, MgGeom g, U64 nSlots, unsigned long long *__restrict__ out)
+{
+  const U64 stride = (U64) gridDim.x * blockDim.x;
+  U32 broken = 0, stray = 0, dup = 0, keys = 0;
+  for (U64 o = (U64) blockIdx.x * blockDim.x + threadIdx.x ; o < nSlots ; o += stride)
+    { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[o]);
+      const U64 key = ((U64) v.y << 32) | v.x;
+      if (!key) continue;
+      ++keys;
+      const U32 bkt = (U32) (o / g.R), me = (U32) (o - (U64) bkt * g.R);
+      const U64 m = key - 1;
+      if (mgBucketOfM (m, g) != bkt) { ++stray; continue; }
+      const U64 base = (U64) bkt * g.R;
+      for (U32 at = mgHomeOfM (m, g) ; at != me ; at = mgNextSlot (at, g.R))
+        { const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base + at]);
+          const U64 k2 = ((U64) w.y << 32) | w.x;
+          if (!k2) { ++broken; break; }
+          if (k2 == key) { ++dup; break; }
+        }
+    }
+  if (broken) atomicAdd (&out[0], (unsigned long long) broken);
+  if (stray) atomicAdd (&out[1], (unsigned long long) stray);
+  if (dup) atomicAdd (&out[2], (unsigned long long) dup);
+  if (keys) atomicAdd (&out[3], (unsigned long long) keys);
+}
+
+/* dOut: four device words (see the kernel), zeroed here */
+MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut, hipStream_t st)
+{
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  MG_HIP (hipMemsetAsync (dOut, 0, 32, st));
+  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableCheckLayoutKernel, dim3 (mgGrid (t->nSlots)), dim3 (256), 0, st, t->slots, mgGeomOf (t), t->nSlots, (unsigned long long *) dOut);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }

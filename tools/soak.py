@@ -85,12 +85,21 @@ BUILD_KNOBS = [{}, {}, {"TABLE_PATH": "bucket"}, {"TABLE_PATH": "direct"}, {"TAB
                {"TABLE_PATH": "bucket", "MERGE_SLOTS": 1}, {"ADD_CHUNK": 100000}, {"SCAN_GENERIC": 1}, {"SCAN_GRID": 64},
                # round 6: the table brought to a tight load after the dedup kernel's count (forced, with the slack a bucket keeps cut to nothing at 95), or never
                {"TABLE_PATH": "bucket", "TIGHT_LOAD": 70}, {"TABLE_PATH": "bucket", "TIGHT_LOAD": 95, "FLAG_POLARITY": 1}, {"TABLE_PATH": "bucket", "TIGHT_LOAD": 0},
-               {"TABLE_PATH": "bucket", "TIGHT_LOAD": 50, "BUCKET_R": 2048, "BUCKET_T": 512}, {"TABLE_LOAD": 95}, {"TABLE_PATH": "bucket", "TABLE_LOAD": 30}]
+               {"TABLE_PATH": "bucket", "TIGHT_LOAD": 50, "BUCKET_R": 2048, "BUCKET_T": 512}, {"TABLE_LOAD": 95}, {"TABLE_PATH": "bucket", "TABLE_LOAD": 30},
+               # the merge kernel's placement by prefix scan (the default) off, and forced on at loads and bucket sizes where buckets run over their end
+               {"TABLE_PATH": "bucket", "MERGE_PLACE": 0}, {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "TIGHT_LOAD": 85},
+               {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "BUCKET_R": 256, "BUCKET_T": 256, "TABLE_LOAD": 85, "TIGHT_LOAD": 0},
+               {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "MERGE_SLOTS": 0, "FLAG_POLARITY": 1}]
 
 
 def trial_build(rng, k, w, sd):
-    with mg.knobs(**BUILD_KNOBS[int(rng.integers(0, len(BUILD_KNOBS)))]):
-        _trial_build(rng, k, w, sd)
+    kn = BUILD_KNOBS[int(rng.integers(0, len(BUILD_KNOBS)))]
+    with mg.knobs(**kn):
+        try:
+            _trial_build(rng, k, w, sd)
+        except Exception:
+            print("build trial's knobs:", kn, flush=True)      # (a failing trial is rerun with: soak.py <budget> <its seed - 1>: the second trial of a run is a build)
+            raise
 
 
 def _trial_build(rng, k, w, sd):

@@ -42,3 +42,10 @@ for kn in "MODGPU_TIGHT_LOAD=70" "MODGPU_TIGHT_LOAD=95" "MODGPU_TIGHT_LOAD=0" "M
   env $kn MODGPU_TABLE_PATH=bucket python -m pytest tests/test_gpu_modset.py tests/test_readset.py tests/test_dropin.py -q -x -m gpu 2>&1 | tail -2
   env $kn MODGPU_TABLE_PATH=bucket python tests/fuzz_gpu.py 23 150 2>&1 | tail -2
 done
+echo "== MODGPU_MERGE_PLACE=0 (the merge kernel claims a fresh bucket's slots one by one, as before the placement by prefix scan) and =1 at tight loads"
+for kn in "MODGPU_MERGE_PLACE=0" "MODGPU_MERGE_PLACE=1 MODGPU_TIGHT_LOAD=85" "MODGPU_MERGE_PLACE=1 MODGPU_BUCKET_R=256 MODGPU_BUCKET_T=256 MODGPU_TABLE_LOAD=85"; do
+  echo "-- $kn"
+  env $kn python -m pytest tests -q -m gpu -x --deselect tests/test_gpu_fullsize.py 2>&1 | tail -3
+  env $kn MODGPU_TABLE_PATH=bucket python tests/fuzz_gpu.py 31 150 2>&1 | tail -2
+  env $kn python tests/fullsize_whole.py c2 2>&1 | tail -3
+done
