@@ -382,6 +382,31 @@ int  mgRefPaint (Modset *ms, const char *bases, const int64_t *offsets, int nSeq
 /* the same from a FASTA / FASTQ file: plain text through the device parser, gzip, an unterminated last line or FASTQ that breaks a
  * rule through the host parser, as mgQueryFile.  An unreadable file: -1 with "failed to open ref seq file <name>" (modutils.c:262). */
 int  mgRefPaintFile (Modset *ms, const char *filename, FILE *out) ;
+/* modutils' text form of a set (modutils.c:169-199): the header line "modset bits B size S k K w W seed SEED", then one line
+ * "index<TAB>k-mer letters<TAB>depth<TAB>info" per entry.  Without a HIP device both fail (there is no CPU fallback; mgModsetWriteText
+ * above is the host loop, and works on a host-only set).
+ *
+ * mgModsetWriteTextDevice: modutils.c:191-199 ("-wt") with the lines formatted on the device (mg_report.hip).  Depths are those after
+ * every pending add (as mgReportDepths), info[] is the host's.  The set is not changed (a set without a device table gets one, as
+ * with mgReportDepths; one that holds a value of 4^k or more -- mgModsetReadText's path 2 -- is refused: write it with
+ * mgModsetWriteText).  0 = done, -1 = error (mgLastError). */
+int     mgModsetWriteTextDevice (Modset *ms, FILE *f) ;
+/* mgModsetReadText: modutils.c:169-190 ("-rt"): creates the Seqhash and the Modset the header names and fills it from the size - 1
+ * lines that follow (lines after those are ignored).  0 = error: mgLastError holds the text the reference die()s with ("failed to open
+ * text file %s", "failed to read first line of text file %s\n", "bad line %d", and what seqhashCreate / modsetCreate would die() on,
+ * checked before they are called).  The caller destroys the set and its hasher.
+ *   The file's bytes go to the device as they are and are parsed there (mg_settext.hip) against the grammar -wt writes:
+ * "-?[0-9]{1,9}" TAB, a token of 1..32 bytes without white space, TAB, "[0-9]{1,9}" TAB, "[0-9]{1,9}" "\n", the token exactly k bytes
+ * long.  c C g G t T are 1 2 3, every other byte 0 (modutils.c:178-184); a k-mer that occurs on several lines keeps its LAST line's
+ * depth and info and its FIRST line's place, as the reference's loop leaves it.  A file with any other line is parsed on the host by
+ * the reference's own fscanf format (blanks for tabs, empty lines, "+6", several records on a line) and inserted on the device; if a
+ * token longer than k gives a value of 4^k or more -- which no device table may hold -- the set is built by the host algorithm and has
+ * no device table.  A token longer than 32 bytes overruns a static buffer in the reference (undefined behaviour): here it is
+ * "bad line N".
+ *   On return ms->max, depth[] and info[] are current on the host; value[] and index[] of a set built on the device reach the host
+ * arrays with modsetSyncToHost, as for any set built there (the call has NOT synced them). */
+Modset *mgModsetReadText (const char *filename) ;
+int     mgModsetReadTextPath (void) ;   /* test hook: what the calling thread's last mgModsetReadText did: 0 = parsed on the device, 1 = parsed on the host and inserted on the device, 2 = built on the host, -1 = it failed before it chose */
 int  mgFormatF2 (char *buf64, double x) ;	/* test hook: the "%.2f" of the Q / M lines as the library's parallel formatter writes it (glibc's rounding of the double's exact value, in integer arithmetic; snprintf itself for nan / inf / negative); returns the length */
 
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):

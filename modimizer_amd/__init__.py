@@ -77,7 +77,7 @@ EXPORTS = [
     "mgCommInitAll", "mgCommGetUniqueId", "mgCommInitRank", "mgCommRank", "mgCommSize", "mgCommDestroy", "mgHistogramAllReduce", "mgDepthAllReduce", "mgModsetMergeRankOrder",
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
-    "mgReportDepths", "mgRefPaint", "mgRefPaintFile",
+    "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgIterScanHost", "mgIterHostBelow", "mgReloadKnobs", "mgFormatF2", "mgModsetMergeArrays", "mgModsetMergeDeviceArrays", "mgModsetClear", "mgModsetDeviceSlots", "mgSetVerbose", "mgProfileEnable", "mgProfileOnly", "mgProfileReset", "mgProfileKernels", "mgProfileGet",
 ]
 
@@ -230,6 +230,7 @@ def lib():
     sig("mgQueryFile", i32, vp, C.c_char_p, vp)
     sig("mgReportDepths", i32, MS, C.POINTER(MS), i32, vp)
     sig("mgRefPaint", i32, MS, vp, vp, i32, C.POINTER(C.c_char_p), vp); sig("mgRefPaintFile", i32, MS, C.c_char_p, vp)
+    sig("mgModsetWriteTextDevice", i32, MS, vp); sig("mgModsetReadText", MS, C.c_char_p); sig("mgModsetReadTextPath", i32)
     sig("mgReferenceWrite", None, vp, C.c_char_p); sig("mgGzipOpenWrite", vp, C.c_char_p); sig("mgGzipOpenRead", vp, C.c_char_p); sig("mgFzOpen", vp, C.c_char_p, C.c_char_p);
     sig("mgCommInitAll", i32, C.POINTER(vp), i32, C.POINTER(i32)); sig("mgCommGetUniqueId", i32, vp); sig("mgCommInitRank", i32, C.POINTER(vp), i32, i32, vp, i32)
     sig("mgCommRank", i32, vp); sig("mgCommSize", i32, vp); sig("mgCommDestroy", None, vp)
@@ -446,3 +447,25 @@ def refpaint(ms, bases, offsets, names, out_path):
         rc = lib().mgRefPaint(ms, bases.ctypes.data, offsets.ctypes.data, n, nm, f)
     if rc:
         raise ModgpuError("mgRefPaint failed: " + lib().mgLastError().decode())
+
+
+def write_text_device(ms, path):
+    """mgModsetWriteTextDevice: modutils -wt (modutils.c:191-199) into the file `path`, the lines formatted on the device."""
+    with CFile(path, "w") as f:
+        rc = lib().mgModsetWriteTextDevice(ms, f)
+    if rc:
+        raise ModgpuError("mgModsetWriteTextDevice failed: " + lib().mgLastError().decode())
+
+
+def read_text(path):
+    """mgModsetReadText: modutils -rt (modutils.c:169-190): the Modset* the text table `path` describes (the caller destroys it and its
+    hasher).  read_text_path() tells which way it was read: 0 parsed on the device, 1 parsed on the host and inserted on the device,
+    2 built on the host."""
+    ms = lib().mgModsetReadText(path.encode())
+    if not ms:
+        raise ModgpuError("mgModsetReadText failed: " + lib().mgLastError().decode())
+    return ms
+
+
+def read_text_path():
+    return lib().mgModsetReadTextPath()

@@ -88,7 +88,8 @@ static const char *gKernelNames[MG_K_COUNT] = {
   "mgSynthGenomeKernel", "mgSynthReadsKernel", "memset", "mgSegScanKernel", "mgSegCompactKernel",
   "mgPartChunks+ScanKernel", "mgPartHistKernel", "mgPartScatterKernel", "mgRankCountKernel", "mgRankScanKernel", "mgBucketDedupKernel",
   "mgBucketMergeKernel", "mgRankLookupKernel", "mgTableFindSegKernel", "mgHotPlan+ReduceKernel", "mgBucketFindKernel", "mgUnpartKernel", "mgChainKernel", "mgChainResolveKernel",
-  "mgPaintItemsKernel", "mgDepthGuardKernel", "mgDepthGatherKernel", "mgTextLenKernel", "mgTextScanKernel", "mgTextWriteKernel" };
+  "mgPaintItemsKernel", "mgDepthGuardKernel", "mgDepthGatherKernel", "mgTextLenKernel", "mgTextScanKernel", "mgTextWriteKernel",
+  "mgSetTextLinesKernel", "mgSetTextScanKernel", "mgSetTextParseKernel", "mgSetTextLastKernel" };
 #define MG_PROF_POOL 8192
 struct MgProfRec { int id; hipEvent_t a, b; };
 static struct {

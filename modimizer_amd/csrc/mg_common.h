@@ -43,7 +43,8 @@ enum MgKernelId {
   MG_K_INDEX_REPLAY, MG_K_INDEX_FINISH, MG_K_SYNTH_GENOME, MG_K_SYNTH_READS, MG_K_MEMSET,
   MG_K_SEG_SCAN, MG_K_SEG_COMPACT, MG_K_PART, MG_K_PART_HIST, MG_K_PART_SCATTER, MG_K_RANK_COUNT, MG_K_RANK_SCAN, MG_K_BUCKET_DEDUP,
   MG_K_BUCKET_MERGE, MG_K_RANK_LOOKUP, MG_K_TABLE_FIND_SEG, MG_K_HOT_REDUCE, MG_K_BUCKET_FIND, MG_K_UNPART, MG_K_CHAIN, MG_K_CHAIN_RESOLVE,
-  MG_K_PAINT_ITEMS, MG_K_DEPTH_GUARD, MG_K_DEPTH_GATHER, MG_K_TEXT_LEN, MG_K_TEXT_SCAN, MG_K_TEXT_WRITE, MG_K_COUNT
+  MG_K_PAINT_ITEMS, MG_K_DEPTH_GUARD, MG_K_DEPTH_GATHER, MG_K_TEXT_LEN, MG_K_TEXT_SCAN, MG_K_TEXT_WRITE,
+  MG_K_SETTEXT_LINES, MG_K_SETTEXT_SCAN, MG_K_SETTEXT_PARSE, MG_K_SETTEXT_LAST, MG_K_COUNT
 };
 void mgProfBegin (int id, hipStream_t st);
 void mgProfEnd (int id, hipStream_t st);
@@ -100,6 +101,21 @@ __device__ __forceinline__ U32 mgWaveInclusiveSum (U32 v)
   v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x142, 0xa, 0xf, false);
   v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x143, 0xc, 0xf, false);
   return v;
+}
+/* inclusive sum over a workgroup of 256 lanes (lds: 4 words, free again on return); *total = the workgroup's sum (mg_settext.hip; the
+   reports' formatter, mg_report.hip, has the same under its own name) */
+__device__ __forceinline__ U32 mgBlockInclusive256 (U32 v, U32 *lds, U32 *total)
+{
+  const U32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const U32 inc = mgWaveInclusiveSum (v);
+  if (lane == 63u) lds[wv] = inc;
+  __syncthreads ();
+  U32 before = 0, tot = 0;
+  #pragma unroll
+  for (U32 i = 0 ; i < 4 ; ++i) { const U32 s = lds[i]; before += i < wv ? s : 0u; tot += s; }
+  __syncthreads ();
+  *total = tot;
+  return before + inc;
 }
 /* The modset table's hash of a k-mer: a BIJECTION of the 2k-bit k-mer onto 2k-bit values (odd multipliers and
  * xor-shifts, all invertible modulo 2^(2k)), murmur-style.  Bucket = its top log2NB bits, home slot = its low bits, and

@@ -85,6 +85,17 @@ MG_HIDDEN int  mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
                                       const char *idBytes, const U64 *idOff, MgTextOut *w, void **scratch);   /* modutils.c:262-270 over a device batch; 0 / -1 */
 MG_HIDDEN void mgRefPaintScratchFree (void *scratch);
 MG_HIDDEN void mgSetErrorText (const char *msg);
+/* the file mover of the device text parser (mg_textgpu.hip), for the other reader of plain text (mg_settext.hip) */
+MG_HIDDEN int mgTextReadParallel (int fd, unsigned char *dst, size_t n, int64_t off);      /* [off, off + n) of the file into dst by the parser's team of threads; 0 = read */
+MG_HIDDEN size_t mgTextWindowBytes (size_t fileSize);      /* text per window: MODGPU_TEXT_WINDOW_KB, or the parser's default for a file of that size; whole tiles of 4 KiB */
+/* modutils -rt (mg_settext.hip): the `want` lines that follow byte bodyOff of the file parsed on the device against the strict grammar
+   (modgpu.h), tokens of k bytes; 0 = all of them passed, the three device arrays (hipMalloc: mgDeviceFree) hold them; 1 = some line
+   does not pass, or there are fewer (nothing is returned); -1 = error */
+MG_HIDDEN int mgSetTextParseDevice (const char *filename, U64 bodyOff, U64 want, int k, U64 **dKey, U16 **dDepth, U8 **dInfo);
+/* the lines' values into the (fresh) set: inserted in order, every k-mer's last line gives its depth and info; ms->max, depth[], info[]
+   current on return.  0 / -1.  ...HostArrays: the same from host arrays (the lines the host parsed) */
+MG_HIDDEN int mgSetTextFillDevice (Modset *ms, const U64 *dKey, const U16 *dDepth, const U8 *dInfo, U64 n);
+MG_HIDDEN int mgSetTextFillHostArrays (Modset *ms, const U64 *key, const U16 *depth, const U8 *info, U64 n);
 /* element count of the reference's Array after appending elements 0..n-1 (array.c:144-170,180-183) */
 MG_HIDDEN int mgRefArrayDim (int first, int size, int n);
 #ifdef __cplusplus

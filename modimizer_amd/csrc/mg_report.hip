@@ -1,9 +1,11 @@
-/* mg_report.hip — modutils' two reports on a set that is already built, on the device:
+/* mg_report.hip — modutils' two reports on a set that is already built, and its text dump, on the device:
  *
  *   -d  reportDepths (modutils.c:65-77): per entry i of the set "MH\t%llx\t%d\t%u" (value, copy, depth), then the entry's depth in
  *       each of N other sets ("\t%u", 0 if absent), "\n";
  *   -P  refpaint (modutils.c:260-273): per record "painting %s length %d\n", then "  %d\t%d\n" (pos, depth) for every modimizer of the
  *       record that is in the set, in modRCnext order.
+ * and, with the same formatter, the text form of the set itself:
+ *   -wt (modutils.c:191-199): per entry i "%d\t%s\t%d\t%d\n" (i, the k letters of value[i], depth, info) behind the host's header line.
  *
  * The lookups are the library's batch finds (mgQueryReadsDevice: scan + find with positions; modsetFindBatchDevice), the depths are
  * gathered from the folded view of each set (host depth plus pending device counts, saturated: mgHookDeviceView), and the text itself
@@ -114,6 +116,25 @@ struct MgDepthLines {
     p = mgPutDec (p, d, mgDecLen (d));
     for (int o = 0 ; o < nOth ; ++o)
       { const U32 e = oth[(U64) o * m + j]; *p++ = '\t'; p = mgPutDec (p, e, mgDecLen (e)); }
+    *p = '\n';
+  }
+};
+
+/* -wt (modutils.c:196-198): entry j + 1 of the set, "%d\t%s\t%d\t%d\n" = index, the k letters of the value (seqhash.c:198-206: the low 2k
+   bits, first base in the high ones), depth, info */
+struct MgSetLines {
+  const U64 *value; const U16 *depth; const U8 *info; int k;
+  __device__ U32 len (U64 j) const { return mgDecLen ((U32) j + 1u) + 1u + (U32) k + 1u + mgDecLen (depth[j]) + 1u + mgDecLen (info[j]) + 1u; }
+  __device__ void put (U64 j, char *p) const
+  {
+    const U64 v = value[j]; const U32 i = (U32) j + 1u, d = depth[j], f = info[j];
+    p = mgPutDec (p, i, mgDecLen (i));
+    *p++ = '\t';
+    for (int b = k - 1 ; b >= 0 ; --b) *p++ = "acgt"[(v >> (2 * b)) & 3u];
+    *p++ = '\t';
+    p = mgPutDec (p, d, mgDecLen (d));
+    *p++ = '\t';
+    p = mgPutDec (p, f, mgDecLen (f));
     *p = '\n';
   }
 };
@@ -371,5 +392,37 @@ extern "C" int mgReportDepths (Modset *ms, Modset **others, int nOthers, FILE *f
   } while (0);
   if (mgTextOutClose (w) && !rc) { mgSetError ("mgReportDepths: write failed"); rc = -1; }
   (void) hipFree (dInfo); (void) hipFree (dKey); (void) hipFree (dIdx); (void) hipFree (dOth);
+  return rc;
+}
+
+/* modutils.c:191-199.  The header line is the host's, written before the writer thread exists, so the bytes are in order. */
+extern "C" int mgModsetWriteTextDevice (Modset *ms, FILE *f)
+{
+  if (!ms || !ms->hasher || !f) { mgSetError ("mgModsetWriteTextDevice: invalid arguments"); return -1; }
+  if (mgEnsureDevice ()) return -1;
+  const Seqhash *sh = ms->hasher;
+  if (!mgHookHasDevice (ms) && sh->k < 32)               /* a set from the host: no value of 4^k or more may enter a device table (mgDepthGuardKernel) */
+    for (U32 i = 1 ; i <= ms->max ; ++i)
+      if (ms->value[i] >> (2 * sh->k)) { mgSetError ("mgModsetWriteTextDevice: entry %u holds a value of 4^k or more (mgModsetWriteText writes such a set)", i); return -1; }
+  const U64 *dValue1; const U16 *dDepth1; U32 max;
+  if (mgHookDeviceViewMake (ms, &dValue1, &dDepth1, &max)) { if (!mgLastError ()[0]) mgSetError ("mgModsetWriteTextDevice: no device view of the set"); return -1; }
+  if (fprintf (f, "modset bits %d size %d k %d w %d seed %d\n", ms->tableBits, max + 1, sh->k, sh->w, sh->seed) < 0)
+    { mgSetError ("mgModsetWriteTextDevice: write failed"); return -1; }
+  if (!max) return 0;
+  hipStream_t st = 0;
+  MgReportBufs b;
+  U8 *dInfo = 0;
+  int rc = -1;
+  MgTextOut *w = mgTextOutOpen (f);
+  do {
+    if (hipMalloc ((void **) &dInfo, max) != hipSuccess) { mgHipFail (hipGetLastError (), "mgModsetWriteTextDevice: hipMalloc"); break; }
+    if (mgCopyH2DBig (dInfo, ms->info + 1, max)) break;                  /* the host info[] is the authority */
+    MgSetLines L;
+    L.value = dValue1; L.depth = dDepth1; L.info = dInfo; L.k = sh->k;
+    if (mgTextFormat (L, (U64) max, &b, w, st)) break;
+    rc = 0;
+  } while (0);
+  if (mgTextOutClose (w) && !rc) { mgSetError ("mgModsetWriteTextDevice: write failed"); rc = -1; }
+  (void) hipFree (dInfo);
   return rc;
 }

@@ -661,6 +661,9 @@ static int txHostThreads (void)
   if (v > 32) v = 32;
   return (int) v;
 }
+/* the two for mg_settext.hip (mg_internal.h) */
+extern "C" int mgTextReadParallel (int fd, unsigned char *dst, size_t n, int64_t off) { return txReadParallel (fd, dst, n, (off_t) off, txHostThreads ()) ? 0 : -1; }
+extern "C" size_t mgTextWindowBytes (size_t fileSize) { return txWindowBytes (fileSize); }
 
 struct TxSink {                                            /* what is done with a batch of complete records */
   int (*fn) (void *ctx, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads, const char *idBytes, const U64 *idOff, hipStream_t st);
