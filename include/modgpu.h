@@ -184,6 +184,13 @@ U64 mgModsetDeviceSlots (Modset *ms) ;
  * bucket -- all 0 in a sound table -- [3] keys in the table; and, since the device table was made, [4] buckets the build laid out by
  * prefix scan, [5] those of them whose entries ran over the bucket's end and came in again at its first slot. */
 MgStatus mgTableCheckLayout (Modset *ms, U64 *out6) ;
+/* Which geometry the device table behind ms has and which kernels have run on it (tests, diagnostics).  out9 (host): [0] log2 of the
+ * number of buckets, [1] slots per bucket; and, counted since the device table was made: lookup batches answered [2] by direct probes,
+ * [3] by one partition level, [4] by two levels over the 16-byte slots, [5] by two levels over the 8-byte copy, [6] times that copy was
+ * made, [7] changes of geometry done bucket by bucket, [8] those done with global atomics.  [2] also counts every chunk of an add that
+ * returns indices (modsetAddBatchDevice with dIndexOut, mgInsertReadsDevice): it finds them by the same direct probes.  All 0 when ms
+ * has no device table (this call makes none). */
+MgStatus mgTableDiag (Modset *ms, U64 *out9) ;
 
 /* modutils.c:53-63 on the device: dHist[65536] (U64) += histogram of depth[1..max], where depth is
  * the host depth at last sync plus pending device counts, saturated at 65535. */

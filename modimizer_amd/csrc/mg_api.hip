@@ -581,6 +581,10 @@ static MgStatus mgDevGet (Modset *ms, MgDev **out, hipStream_t st)
       MG_HIP (hipMemcpyAsync (d->t.value + first, ms->value + first, (size_t) (last - first + 1) * sizeof (U64), hipMemcpyHostToDevice, st));
       MG_HIP (hipMemcpyAsync (d->t.baseDepth + first, ms->depth + first, (size_t) (last - first + 1) * sizeof (U16), hipMemcpyHostToDevice, st));
       d->t.baseZero = false;
+      /* room for them, as for a batch of as many -- unless a query batch is in flight, whose scan has counted its digits for the geometry
+         the table has.  (The loader may still have to refit the geometry where a bucket overflows, mgTableLoadHost; the waiting batch's
+         counts are then for another geometry, mgTableFindTakesPartition sees that and its lookups go by direct probes: correct, slower.) */
+      if (!d->ticketsOut && (s = mgTableEnsure (&d->t, last - first + 1, st))) return s;
       if ((s = mgTableLoadHost (&d->t, d->t.value, first, last, st))) return s;
       MG_HIP (hipStreamSynchronize (st));
       d->t.max = d->t.syncedMax = last;
@@ -819,6 +823,8 @@ static MgStatus mgAddChunk (Modset *ms, MgDev *d, const U64 *dKmer, U64 n, U32 *
   U64 newMax = (U64) t.max + c[0];
   if (c[1] || newMax >= t.size)
     { /* modset.c:58 */
+      /* what the add had written by then goes out of the table again: the set answers as before the call, whichever lookup path is asked */
+      if ((s = mgTableRollback (&t, st))) return s;
       mgSetError ("hashTableSize %u is too small for %llu", t.size, (unsigned long long) newMax);
       return MG_ERR_CAPACITY;
     }
@@ -961,6 +967,16 @@ extern "C" MgStatus mgTableCheckLayout (Modset *ms, U64 *out6)
   if (!s && (hipMemcpy (out6, dOut, 32, hipMemcpyDeviceToHost) || hipMemcpy (out6 + 4, d->t.counters + 4, 16, hipMemcpyDeviceToHost))) s = MG_ERR_HIP;
   (void) hipFree (dOut);
   return s;
+}
+
+extern "C" MgStatus mgTableDiag (Modset *ms, U64 *out9)
+{
+  memset (out9, 0, 9 * sizeof (U64));
+  MgDev *d = mgDevLookup (ms);
+  if (!d || !d->built) return MG_OK;
+  out9[0] = (U64) d->t.log2NB; out9[1] = d->t.R;
+  for (int i = 0 ; i < 7 ; ++i) out9[2 + i] = d->t.diag[i];
+  return MG_OK;
 }
 
 extern "C" MgStatus modsetDepthHistogramDevice (Modset *ms, U64 *dHist, void *stream)

@@ -249,7 +249,7 @@ struct MgTable {
   U32 size;            /* capacity in entries (ms->size) */
   U32 max;             /* entries known to the device table */
   U32 syncedMax;       /* entries whose value[] the host already has */
-  U64 *counters;       /* device U64[8]: 0 = new entries of the last add, 1 = bucket overflow, 2-3 = the tightening's entry counts; since the table was
+  U64 *counters;       /* device U64[8]: 0 = new entries of the last add, 1 = bucket overflow (of an add, a load or a change of geometry: each zeroes it, and reads it when it is done), 2-3 = the tightening's entry counts; since the table was
                           made: 4 = buckets the merge kernel laid out by prefix scan, 5 = those of them that ran over their end */
   bool pendingDepth;   /* an add with depth counting ran since the counts were last folded into baseDepth / the host's depth[] */
   bool dirty;          /* buckets with occ == 0 hold undefined bytes (never zeroed): see mgTableClean */
@@ -258,7 +258,7 @@ struct MgTable {
   U64 find8Cap;        /* slots allocated for it */
   U64 find8Version, version;      /* version: bumped by whatever changes a slot's key or index (add, load, rehash, clear); find8 is the copy of find8Version */
   bool empty;          /* nothing has been put into the table since it was made or forgotten (every occ[] is zero): its geometry is free to change */
-  U64 *pin;            /* four page-locked host words for small read-backs in the middle of an add (mgDevBuild) */
+  U64 *pin;            /* four page-locked host words for small read-backs in the middle of an add (mgDevBuild): 0-2 the tightening's, 3 the overflow flag of a load or a change of geometry */
   int newPct;          /* new entries per 100 modimizers in the last bucketed add (a hint for the next one: mg_table.hip, markDup) */
   int loadPct;         /* slots are provided for entries * 100 / loadPct (0: 60).  A set that is only being built and counted
                           (mgAddReadsDevice) takes 75: its size is set from the OCCURRENCES of a batch, an upper bound of
@@ -266,11 +266,14 @@ struct MgTable {
                           table is brought back to 60 (a probe that misses walks to the next empty slot) */
   int  maxLog2Slots;   /* tableBits - 1: the size at which load <= 0.5 for the largest legal set */
   U32  wantR;          /* most slots per bucket (4096: 64 KiB of LDS); a table's R lies between half of it and it */
+  U64  diag[7];        /* launches since the table was made (mgTableDiag): lookup batches by direct probes, by one partition level, by two levels over the
+                          16-byte slots, by two levels over the 8-byte copy; mgTablePack8Kernel runs; rehashes bucket by bucket, rehashes by global atomics */
   int  tightPct;       /* a set built by ONE bucketed add into an empty table is brought to this load once the dedup kernel has counted its
                           entries (mgTableAdd; 0: MG_TIGHT_PCT_DEFAULT): the bucket images the merge kernel streams back hold entries, not air */
 };
 MgStatus mgTableAlloc (MgTable *t, U64 slotsWanted, hipStream_t st);     /* geometry for that many slots (or a few more), empty table; allocates only when the capacity is short */
 MgStatus mgTableEnsure (MgTable *t, U64 nIncoming, hipStream_t st);      /* grow (rehash) so that max+nIncoming fits at load <= 0.6 */
+MgStatus mgTableRollback (MgTable *t, hipStream_t st);                   /* after a refused add: only the entries 1 .. max stay in the table */
 MgStatus mgTableClean (MgTable *t, hipStream_t st);                      /* zero the never-written buckets; dirty = false */
 void     mgTableForget (MgTable *t, hipStream_t st);                     /* all buckets empty again (no memset of the slots) */
 size_t   mgTableAddScratchBytes (const MgTable *t, U64 n);
@@ -282,6 +285,7 @@ bool     mgTableAddTakesSegments (const MgTable *t, U64 n, const MgHistReq *coun
 MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st);
 MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipStream_t st);
 MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut4, hipStream_t st);      /* see mgTableCheckLayoutKernel */
+enum { MG_DIAG_FIND_DIRECT = 0, MG_DIAG_FIND_PART1, MG_DIAG_FIND_PART2_16, MG_DIAG_FIND_PART2_8, MG_DIAG_PACK8, MG_DIAG_REHASH_BUCKET, MG_DIAG_REHASH_ATOMIC };
 size_t   mgTableFindPartScratchBytes (U64 n);
 int      mgTableFindDigitBits (const MgTable *t);       /* bits of the partitioned lookup's digit: pieces of the table that fit an XCD's L2 */
 bool     mgTableFindTakesPartition (const MgTable *t, U64 n, const MgHistReq *counted);

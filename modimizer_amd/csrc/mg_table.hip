@@ -1723,7 +1723,7 @@ void mgBucketFindKernel (const MgSlot *__restrict__ slots, const U32 *__restrict
 
 /* The same out of an 8-byte-per-slot copy of the table (round 6).  The two-level lookups STREAM the table once per batch -- 16 bytes a slot of which
  * a lookup needs the key and the index; a bucket implies the key's leading bits, so where 2k - log2 NB <= 32 both fit one word:
- * (key's bits below the bucket id + 1) << 31 | index, 0 = empty.  The copy (MgTable.find8) is made by mgTablePack8Kernel when a lookup batch finds
+ * (key's bits below the bucket id + 1) << 31 | index (0: the key has none), 0 = empty.  The copy (MgTable.find8) is made by mgTablePack8Kernel when a lookup batch finds
  * it missing or older than the table (one streaming pass), and a batch then reads half the bytes: config 3's table 1.9 -> 0.95 GB per batch. */
 __global__ __launch_bounds__ (256)
 void mgTablePack8Kernel (const MgSlot *__restrict__ slots, const U32 *__restrict__ occ, U32 nBuckets, U32 R, int remB, U64 *__restrict__ out)
@@ -1734,8 +1734,8 @@ void mgTablePack8Kernel (const MgSlot *__restrict__ slots, const U32 *__restrict
       for (U32 i = threadIdx.x ; i < R ; i += blockDim.x)
         { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) b * R + i]);
           const U64 key = ((U64) v.y << 32) | v.x;
-          U64 w = 0;
-          if (key && mgIsAssigned (v.z)) w = ((((key - 1) & remMask) + 1) << 31) | (U64) (v.z & ~MG_ASSIGNED);
+          U64 w = 0;            /* a keyed slot without an index (an add that was refused left it) keeps its key and answers 0: the chain goes on, as in the 16-byte table */
+          if (key) w = ((((key - 1) & remMask) + 1) << 31) | (U64) (mgIsAssigned (v.z) ? (v.z & ~MG_ASSIGNED) : 0u);
           __builtin_nontemporal_store (w, &out[(U64) b * R + i]);
         }
     }
@@ -2264,6 +2264,7 @@ MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipSt
   /* with the never-written buckets zeroed once, a probe needs no look at occ[] first */
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
   const unsigned fgrid = mgGrid ((n + MG_FIND_PER - 1) / MG_FIND_PER);
+  ++t->diag[MG_DIAG_FIND_DIRECT];
   MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableFindKernel<false>, dim3 (fgrid), dim3 (256), 0, st, t->slots, t->occ, mgGeomOf (t), dKmer, n, dIndexOut);
   MG_HIP (hipGetLastError ());
   return MG_OK;
@@ -2318,6 +2319,7 @@ MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dInde
   if (waves > nRows) waves = nRows;
   const U64 rowsPerWave = (nRows + waves - 1) / waves;
   waves = (nRows + rowsPerWave - 1) / rowsPerWave;
+  ++t->diag[MG_DIAG_FIND_DIRECT];
   MG_LAUNCH (MG_K_TABLE_FIND_SEG, st, mgTableFindSegKernel, dim3 ((unsigned) ((waves + 3) / 4)), dim3 (256), 0, st, t->slots, mgGeomOf (t), src, n, rowsPerWave, dIndexOut);
   MG_HIP (hipGetLastError ());
   return MG_OK;
@@ -2422,16 +2424,19 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
                   MG_HIP (hipMalloc ((void **) &t->find8, t->nSlots * sizeof (U64)));
                   t->find8Cap = t->nSlots;
                 }
+              ++t->diag[MG_DIAG_PACK8];
               MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTablePack8Kernel, dim3 ((unsigned) (NB < 8192 ? NB : 8192)), dim3 (256), 0, st, t->slots, t->occ, (U32) NB, t->R, remB, t->find8);
               t->find8Version = t->version;
             }
           const size_t lds8 = (size_t) t->R * 8 + 16;
           if (lds8 > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFind8Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds8));
+          ++t->diag[MG_DIAG_FIND_PART2_8];
           MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFind8Kernel, dim3 (bGrid), dim3 (1024), lds8, st, t->find8, t->occ, mgGeomOf (t), f, (U32) NB, remB, fineStart, el2, perBlock);
         }
       else
         { const size_t lds = (size_t) t->R * 12 + 16;
           if (lds > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFindKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+          ++t->diag[MG_DIAG_FIND_PART2_16];
           MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFindKernel, dim3 (bGrid), dim3 (1024), lds, st, t->slots, t->occ, mgGeomOf (t), f, (U32) NB, fineStart, el2, perBlock);
         }
       const unsigned g2 = 2 * maxChunks2 < 2048 ? 2 * maxChunks2 : 2048;
@@ -2445,6 +2450,7 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
       return MG_OK;
     }
   const U32 wgPerXcd = 256;                                  /* 2048 workgroups of 256: eight waves per SIMD */
+  ++t->diag[MG_DIAG_FIND_PART1];
   MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBinFindKernel, dim3 (8 * wgPerXcd), dim3 (256), 0, st, t->slots, mgGeomOf (t), f, el, binStart, nBins, wgPerXcd);
   const U64 nSub = (n + subElems - 1) / subElems;
   const unsigned ug = (unsigned) (nSub < 2048 ? nSub : 2048);
@@ -2454,14 +2460,61 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
   return MG_OK;
 }
 
+static U64 mgSlotsFor (const MgTable *t, U64 entries);
+static MgStatus mgFitGeometry (const MgTable *t, const U32 *dFine, U64 want, int *lgOut, U32 *ROut, hipStream_t st);
+static MgStatus mgTableRehashExact (MgTable *t, int log2NB, U32 R, hipStream_t st);
+#define MG_FINE_LOG2 18            /* the most buckets a table has (mgSetGeometry): counts per finest bucket give every coarser geometry's by addition */
+__global__ void mgFineCountValuesKernel (const U64 *__restrict__ value, U32 first, U32 last, int kbits, U32 *__restrict__ fine);
+
+/* the overflow flag (counters[1]) comes back through the table's page-locked words, or by a plain copy where it has none */
+static MgStatus mgReadOverflow (MgTable *t, hipStream_t st, U64 *over)
+{
+  if (t->pin)
+    { MG_HIP (hipMemcpyAsync (t->pin + 3, t->counters + 1, 8, hipMemcpyDeviceToHost, st));
+      MG_HIP (hipStreamSynchronize (st));
+      *over = t->pin[3];
+    }
+  else
+    { MG_HIP (hipStreamSynchronize (st));
+      MG_HIP (hipMemcpy (over, t->counters + 1, 8, hipMemcpyDeviceToHost));
+    }
+  return MG_OK;
+}
+
+/* the loader, waited for; *over != 0: a bucket had no room for one of the values (the others are in) */
+static MgStatus mgLoadLaunch (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st, U64 *over)
+{
+  MG_HIP (hipMemsetAsync (t->counters + 1, 0, 8, st));
+  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGrid ((U64) last - first + 1)), dim3 (256), 0, st,
+             t->slots, mgGeomOf (t), dValue, first, last, t->occ, t->counters);
+  MG_HIP (hipGetLastError ());
+  return mgReadOverflow (t, st, over);
+}
+
 MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st)
 {
   if (last < first) return MG_OK;
   t->liveHistValid = false; t->empty = false; ++t->version;
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGrid ((U64) last - first + 1)), dim3 (256), 0, st,
-             t->slots, mgGeomOf (t), dValue, first, last, t->occ, t->counters);
-  MG_HIP (hipGetLastError ());
+  U64 over = 0;
+  MgStatus s = mgLoadLaunch (t, dValue, first, last, st, &over);
+  if (s || !over) return s;
+  /* A bucket had no room: the table was sized by the mean (mgTableEnsure) and these values crowd one bucket.  The entries that found
+     a slot stay where they are; the table goes into a geometry that holds the fullest bucket of ALL the values (value[1 .. last]:
+     what is in the table and what was left out), and the values are loaded again -- those already there are met as duplicates. */
+  int lg = 0; U32 R = 0;
+  U32 *dFine = 0;
+  if (hipMalloc ((void **) &dFine, sizeof (U32) << MG_FINE_LOG2) != hipSuccess) return mgHipFail (hipGetLastError (), "hipMalloc");
+  if (hipMemsetAsync (dFine, 0, sizeof (U32) << MG_FINE_LOG2, st) != hipSuccess) s = mgHipFail (hipGetLastError (), "hipMemsetAsync");
+  else
+    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountValuesKernel, dim3 (mgGrid (last)), dim3 (256), 0, st, dValue, 1u, last, t->kbits, dFine);
+      s = mgFitGeometry (t, dFine, mgSlotsFor (t, last), &lg, &R, st);
+    }
+  (void) hipFree (dFine);
+  if (!s) s = mgTableRehashExact (t, lg, R, st);
+  if (s) return s;
+  if ((s = mgLoadLaunch (t, dValue, first, last, st, &over))) return s;
+  if (over) { mgSetError ("internal: the device table's fitted geometry (2^%d x %u) does not hold the host's entries", lg, R); return MG_ERR_CAPACITY; }
   return MG_OK;
 }
 
@@ -2530,14 +2583,14 @@ void mgCleanEmptyBucketsKernel (MgSlot *__restrict__ slots, MgGeom g, const U32 
 
 /* old table -> new table (another geometry): every assigned entry is re-inserted with its index and count */
 __global__ void mgRehashKernel (const MgSlot *__restrict__ oldSlots, U32 oldNB, const U32 *__restrict__ oldOcc, U32 oldR,
-                                MgSlot *__restrict__ slots, MgGeom g, U32 *__restrict__ occ, U64 *counters)
+                                MgSlot *__restrict__ slots, MgGeom g, U32 *__restrict__ occ, U64 *counters, U32 keepMax)
 {
   for (U32 bk = blockIdx.x ; bk < oldNB ; bk += gridDim.x)
     { if (!oldOcc[bk]) continue;
       const MgSlot *from = oldSlots + (U64) bk * oldR;
       for (U32 i = threadIdx.x ; i < oldR ; i += blockDim.x)
         { uint4 v = *reinterpret_cast<const uint4 *> (&from[i]);
-          if (!(v.x | v.y) || !mgIsAssigned (v.z)) continue;
+          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;      /* (keepMax: what a refused add left behind is dropped, mgTableRollback) */
           const unsigned long long key = ((unsigned long long) v.y << 32) | v.x;
           const U64 m = key - 1;                                  /* the key IS the mixed k-mer: no re-hash needed to re-place it */
           const U32 b = mgBucketOfM (m, g);
@@ -2561,7 +2614,7 @@ __global__ void mgRehashKernel (const MgSlot *__restrict__ oldSlots, U32 oldNB, 
    (tools/incremental_probe.py: 4.4 -> 1.3 ms for 9.3e7 entries). */
 __global__ __launch_bounds__ (1024)
 void mgRehashBucketKernel (const MgSlot *__restrict__ oldSlots, int oldLog2NB, const U32 *__restrict__ oldOcc, U32 oldR,
-                           MgSlot *__restrict__ slots, MgGeom g, U32 *__restrict__ occ, U64 *counters)
+                           MgSlot *__restrict__ slots, MgGeom g, U32 *__restrict__ occ, U64 *counters, U32 keepMax)
 {
   unsigned long long *sKey = reinterpret_cast<unsigned long long *> (mgDynLds);
   U32 *sOrd = reinterpret_cast<U32 *> (mgDynLds + (size_t) g.R * 8);
@@ -2579,7 +2632,7 @@ void mgRehashBucketKernel (const MgSlot *__restrict__ oldSlots, int oldLog2NB, c
       U32 mine = 0;
       for (U32 i = tid ; i < oldR ; i += T)
         { const uint4 v = *reinterpret_cast<const uint4 *> (&from[i]);
-          if (!(v.x | v.y) || !mgIsAssigned (v.z)) continue;
+          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;
           const unsigned long long key = ((unsigned long long) v.y << 32) | v.x;
           const U64 m = key - 1;
           if (mgBucketOfM (m, g) != b) continue;
@@ -2603,6 +2656,77 @@ void mgRehashBucketKernel (const MgSlot *__restrict__ oldSlots, int oldLog2NB, c
     }
 }
 
+/* How many entries every bucket of the finest geometry (2^MG_FINE_LOG2 buckets) would hold: a bucket id is a prefix of the key, so the
+   counts of any coarser geometry are sums of these.  From the table's assigned entries, or from value[first .. last]. */
+__global__ void mgFineCountSlotsKernel (const MgSlot *__restrict__ slots, U32 NB, const U32 *__restrict__ occ, U32 R, int kbits, U32 keepMax, U32 *__restrict__ fine)
+{
+  MgGeom g; g.R = R; g.log2NB = MG_FINE_LOG2 < kbits ? MG_FINE_LOG2 : kbits; g.kbits = kbits;
+  for (U32 bk = blockIdx.x ; bk < NB ; bk += gridDim.x)
+    { if (!occ[bk]) continue;                                      /* (never written: its bytes are undefined) */
+      for (U32 i = threadIdx.x ; i < R ; i += blockDim.x)
+        { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) bk * R + i]);
+          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;
+          const U64 m = ((((U64) v.y << 32) | v.x) - 1) & (kbits >= 64 ? ~0ull : (((U64) 1 << kbits) - 1));
+          atomicAdd (&fine[mgBucketOfM (m, g)], 1u);               /* (m < 2^kbits: the id is below 2^log2NB) */
+        }
+    }
+}
+__global__ void mgFineCountValuesKernel (const U64 *__restrict__ value, U32 first, U32 last, int kbits, U32 *__restrict__ fine)
+{
+  MgGeom g; g.R = MG_R_QUANTUM; g.log2NB = MG_FINE_LOG2 < kbits ? MG_FINE_LOG2 : kbits; g.kbits = kbits;
+  const U64 mask = kbits >= 64 ? ~0ull : (((U64) 1 << kbits) - 1);
+  const U64 stride = (U64) gridDim.x * blockDim.x;
+  for (U64 i = (U64) first + (U64) blockIdx.x * blockDim.x + threadIdx.x ; i <= last ; i += stride)
+    atomicAdd (&fine[mgBucketOfM (mgMixK (value[i] & mask, kbits) & mask, g)], 1u);
+}
+
+/* The smallest legal geometry of at least `want` slots whose fullest bucket holds its entries with one slot to spare (a bucket that is
+   offered as many keys as it has slots refuses them: mgBucketMergeKernel), from the fine counts.  Legal: NB a power of two up to 2^18,
+   R a multiple of 64 up to the table's own limit (wantR) -- or, where nothing else fits, up to 8192 -- and no more slots than the set's
+   table bits allow (maxLog2Slots).  MG_ERR_CAPACITY when there is none. */
+static void mgSetGeometry (MgTable *t, U64 want);
+static MgStatus mgFitGeometry (const MgTable *t, const U32 *dFine, U64 want, int *lgOut, U32 *ROut, hipStream_t st)
+{
+  const size_t nFine = (size_t) 1 << MG_FINE_LOG2;
+  U32 *h = (U32 *) malloc (nFine * sizeof (U32));
+  if (!h) { mgSetError ("out of host memory"); return MG_ERR_NOMEM; }
+  if (hipMemcpyAsync (h, dFine, nFine * sizeof (U32), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess)
+    { free (h); return mgHipFail (hipGetLastError (), "mgFitGeometry"); }
+  const int fineLg = MG_FINE_LOG2 < t->kbits ? MG_FINE_LOG2 : t->kbits;
+  U64 fullest[MG_FINE_LOG2 + 1];
+  for (int lg = fineLg ; lg >= 0 ; --lg)
+    { U32 m = 0;
+      for (size_t i = 0 ; i < ((size_t) 1 << lg) ; ++i) if (h[i] > m) m = h[i];
+      fullest[lg] = m;
+      if (lg) for (size_t i = 0 ; i < ((size_t) 1 << (lg - 1)) ; ++i) h[i] = h[2 * i] + h[2 * i + 1];
+    }
+  free (h);
+  U32 Rown = t->wantR ? t->wantR : 4096;
+  if (Rown > 8192) Rown = 8192;
+  if (Rown < MG_R_QUANTUM) Rown = MG_R_QUANTUM;
+  if (want < MG_R_QUANTUM) want = MG_R_QUANTUM;
+  const U32 limits[2] = { Rown, 8192 };
+  /* the most slots a geometry may have: what the table bits allow -- or what mgSetGeometry makes of `want` itself, which rounds R up */
+  U64 maxSlots = (U64) 1 << t->maxLog2Slots;
+  { MgTable byMean = *t; mgSetGeometry (&byMean, want); if (byMean.nSlots > maxSlots) maxSlots = byMean.nSlots; }
+  for (int pass = 0 ; pass < 2 ; ++pass)
+    { U64 best = 0;
+      for (int lg = 0 ; lg <= fineLg ; ++lg)
+        { U64 R = (want + ((U64) 1 << lg) - 1) >> lg;
+          if (R < fullest[lg] + 1) R = fullest[lg] + 1;
+          R = (R + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
+          if (R > limits[pass]) continue;
+          const U64 slots = R << lg;
+          if (slots > maxSlots) continue;
+          if (!best || slots < best) { best = slots; *lgOut = lg; *ROut = (U32) R; }
+        }
+      if (best) return MG_OK;
+    }
+  mgSetError ("no geometry of the device table holds the set: its fullest bucket has %llu entries in 2^%d buckets (at most 8192 slots a bucket, 2^%d slots)",
+              (unsigned long long) fullest[fineLg], fineLg, t->maxLog2Slots);
+  return MG_ERR_CAPACITY;
+}
+
 /* Geometry for `want` slots: NB a power of two, R = want / NB rounded up to a multiple of 64, between half of wantR and wantR where the size
    allows (R = 4096: a bucket's image is 64 KiB of LDS); at most 2^18 buckets (two 9-bit partition passes), R up to 8192 beyond that. */
 static void mgSetGeometry (MgTable *t, U64 want)
@@ -2620,9 +2744,15 @@ static void mgSetGeometry (MgTable *t, U64 want)
 }
 
 /* an empty table of (at least) `want` slots; memory is only allocated when the capacity is short */
+static MgStatus mgTableAllocGeom (MgTable *t, hipStream_t st);
 MgStatus mgTableAlloc (MgTable *t, U64 want, hipStream_t st)
 {
   mgSetGeometry (t, want);
+  return mgTableAllocGeom (t, st);
+}
+/* the same for the geometry t already names (R, log2NB, nSlots) */
+static MgStatus mgTableAllocGeom (MgTable *t, hipStream_t st)
+{
   const U32 NB = (U32) 1 << t->log2NB;
   if (!t->slots || t->nSlots > t->capSlots)
     { if (t->slots) { MG_HIP (hipStreamSynchronize (st)); MG_HIP (hipFree (t->slots)); t->slots = 0; t->capSlots = 0; }
@@ -2668,32 +2798,97 @@ static U64 mgSlotsFor (const MgTable *t, U64 entries)
   return need;
 }
 
-/* the table in another geometry: the assigned entries re-placed (their keys are their hashes) */
-static MgStatus mgTableRehashTo (MgTable *t, U64 want, hipStream_t st)
+/* The table in another geometry: the assigned entries re-placed (their keys are their hashes).  The new geometry is sized by the MEAN
+   bucket (mgSetGeometry), and a set whose keys crowd one bucket may not fit it: the kernels raise the overflow flag, which is read here,
+   before anything zeroes it.  Then the old table -- kept until the new one is complete -- is counted by finest bucket, the smallest legal
+   geometry that holds its fullest bucket is taken (mgFitGeometry), and the entries are placed again.  MG_ERR_CAPACITY only when no legal
+   geometry holds them; the old table is then still in place and still answers.
+   exact: that geometry (log2NB, R) instead of one for `want` slots.  keepMax: entries with a larger index are dropped (mgTableRollback). */
+struct MgOldTable { MgSlot *slots; U32 *occ; U64 nSlots, capSlots; U32 capNB, R; int log2NB; bool dirty; };
+static void mgTableTakeOld (MgTable *t, MgOldTable *o)
+{ o->slots = t->slots; o->occ = t->occ; o->nSlots = t->nSlots; o->capSlots = t->capSlots; o->capNB = t->capNB; o->R = t->R; o->log2NB = t->log2NB; o->dirty = t->dirty;
+  t->slots = 0; t->occ = 0; t->capSlots = 0; t->capNB = 0; }
+static void mgTablePutOld (MgTable *t, const MgOldTable &o, hipStream_t st)
+{ (void) hipStreamSynchronize (st);
+  if (t->slots) (void) hipFree (t->slots);
+  if (t->occ) (void) hipFree (t->occ);
+  t->slots = o.slots; t->occ = o.occ; t->nSlots = o.nSlots; t->capSlots = o.capSlots; t->capNB = o.capNB; t->R = o.R; t->log2NB = o.log2NB; t->dirty = o.dirty;
+  t->empty = false; ++t->version; }
+
+/* one pass old -> t (allocated, every occ[] zero), waited for; *over != 0: a new bucket had no room */
+static MgStatus mgRehashPass (MgTable *t, const MgOldTable &o, U32 keepMax, hipStream_t st, U64 *over)
 {
-  MgSlot *oldSlots = t->slots; U32 *oldOcc = t->occ; const U32 oldNB = (U32) 1 << t->log2NB, oldR = t->R;
-  t->slots = 0; t->occ = 0; t->capSlots = 0; t->capNB = 0;
-  MgStatus s = mgTableAlloc (t, want, st); if (s) return s;
-  int oldLog2NB = 0; while (((U32) 1 << oldLog2NB) < oldNB) ++oldLog2NB;
-  if (t->log2NB >= oldLog2NB && mgKnobs ()->tablePath != 'd')             /* bucket by bucket, out of LDS (the new buckets nothing goes into stay unwritten: dirty again) */
+  MgStatus s;
+  const U32 oldNB = (U32) 1 << o.log2NB;
+  MG_HIP (hipMemsetAsync (t->counters + 1, 0, 8, st));
+  if (t->log2NB >= o.log2NB && mgKnobs ()->tablePath != 'd')             /* bucket by bucket, out of LDS (the new buckets nothing goes into stay unwritten: dirty again) */
     { const U32 NB = (U32) 1 << t->log2NB;
       const size_t lds = (size_t) t->R * 16 + 16;
       if (lds > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgRehashBucketKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
       MG_HIP (hipMemsetAsync (t->occ, 0, (size_t) NB * sizeof (U32), st));
+      ++t->diag[MG_DIAG_REHASH_BUCKET];
       MG_LAUNCH (MG_K_TABLE_LOAD, st, mgRehashBucketKernel, dim3 (NB < 2048 ? NB : 2048), dim3 (1024), lds, st,
-                 oldSlots, oldLog2NB, oldOcc, oldR, t->slots, mgGeomOf (t), t->occ, t->counters);
+                 o.slots, o.log2NB, o.occ, o.R, t->slots, mgGeomOf (t), t->occ, t->counters, keepMax);
       t->dirty = true;
     }
   else
     { if ((s = mgTableClean (t, st))) return s;                          /* (the atomic path claims slots in a zeroed table) */
+      ++t->diag[MG_DIAG_REHASH_ATOMIC];
       MG_LAUNCH (MG_K_TABLE_LOAD, st, mgRehashKernel, dim3 (oldNB < 8192 ? oldNB : 8192), dim3 (256), 0, st,
-                 oldSlots, oldNB, oldOcc, oldR, t->slots, mgGeomOf (t), t->occ, t->counters);
+                 o.slots, oldNB, o.occ, o.R, t->slots, mgGeomOf (t), t->occ, t->counters, keepMax);
     }
   MG_HIP (hipGetLastError ());
-  MG_HIP (hipStreamSynchronize (st));
-  MG_HIP (hipFree (oldSlots)); MG_HIP (hipFree (oldOcc));
-  t->empty = false; ++t->version;
-  return MG_OK;
+  return mgReadOverflow (t, st, over);
+}
+
+static MgStatus mgTableRehash (MgTable *t, U64 want, bool exact, int exactLg, U32 exactR, U32 keepMax, hipStream_t st)
+{
+  MgOldTable o; mgTableTakeOld (t, &o);
+  MgStatus s = MG_OK;
+  for (int attempt = 0 ; attempt < 2 ; ++attempt)
+    { if (attempt == 0 && exact) { t->log2NB = exactLg; t->R = exactR; t->nSlots = (U64) exactR << exactLg; }
+      else if (attempt == 0) mgSetGeometry (t, want);
+      else
+        { int lg = 0; U32 R = 0;
+          U32 *dFine = 0;
+          if (hipMalloc ((void **) &dFine, sizeof (U32) << MG_FINE_LOG2) != hipSuccess) { s = mgHipFail (hipGetLastError (), "hipMalloc"); break; }
+          if (hipMemsetAsync (dFine, 0, sizeof (U32) << MG_FINE_LOG2, st) != hipSuccess) { s = mgHipFail (hipGetLastError (), "hipMemsetAsync"); (void) hipFree (dFine); break; }
+          const U32 oldNB = (U32) 1 << o.log2NB;
+          MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountSlotsKernel, dim3 (oldNB < 8192 ? oldNB : 8192), dim3 (256), 0, st, o.slots, oldNB, o.occ, o.R, t->kbits, keepMax, dFine);
+          s = mgFitGeometry (t, dFine, want, &lg, &R, st);
+          (void) hipFree (dFine);
+          if (s) break;
+          t->log2NB = lg; t->R = R; t->nSlots = (U64) R << lg;
+        }
+      if ((s = mgTableAllocGeom (t, st))) break;
+      U64 over = 0;
+      if ((s = mgRehashPass (t, o, keepMax, st, &over))) break;
+      if (!over)
+        { MG_HIP (hipFree (o.slots)); MG_HIP (hipFree (o.occ));
+          t->empty = false; ++t->version;
+          return MG_OK;
+        }
+      (void) hipFree (t->slots); (void) hipFree (t->occ);
+      t->slots = 0; t->occ = 0; t->capSlots = 0; t->capNB = 0;
+      if (attempt) { mgSetError ("internal: the device table's fitted geometry (2^%d x %u) does not hold its entries", t->log2NB, t->R); s = MG_ERR_CAPACITY; }
+    }
+  mgTablePutOld (t, o, st);
+  return s;
+}
+static MgStatus mgTableRehashTo (MgTable *t, U64 want, hipStream_t st) { return mgTableRehash (t, want, false, 0, 0, 0x7fffffffu, st); }
+static MgStatus mgTableRehashExact (MgTable *t, int log2NB, U32 R, hipStream_t st) { return mgTableRehash (t, (U64) R << log2NB, true, log2NB, R, 0x7fffffffu, st); }
+
+/* After an add that was refused (MG_ERR_CAPACITY: the set's size reached, or a bucket without room) the table holds what the add had
+   written by then: keys without an index, and entries whose index lies beyond max.  They go, by a pass over the table that keeps the
+   entries 1 .. max: the set then answers as before the add, on every lookup path.  The pass is a whole rehash into a second allocation of
+   the table's size: the price of an error the reference program exits on.  Where that allocation fails the caller gets MG_ERR_HIP in the
+   place of MG_ERR_CAPACITY, and the table keeps what the add wrote (the old table is put back as it was).  Depth counts the refused batch
+   had added to earlier entries stay: they are not the table's to take back. */
+MgStatus mgTableRollback (MgTable *t, hipStream_t st)
+{
+  t->liveHistValid = false;
+  if (!t->slots) return MG_OK;
+  return mgTableRehash (t, t->nSlots, true, t->log2NB, t->R, t->max, st);
 }
 
 MgStatus mgTableEnsure (MgTable *t, U64 nIncoming, hipStream_t st)

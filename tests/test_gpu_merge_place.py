@@ -151,44 +151,50 @@ def test_empty_buckets_of_a_filled_table(slots):
         mg.lib().modsetDestroy(ms)
 
 
+DIAG, diag = util.DIAG, util.table_diag          # mgTableDiag: the table's geometry and the launches by kernel since it was made
+
+
 @pytest.mark.parametrize("find8", [0, 1])
 @pytest.mark.parametrize("path", ["direct", "part", "2"])
 def test_lookups_on_a_placed_table(path, find8):
-    """direct probes, the partitioned lookups and the two-level ones over the 8-byte copy, on a table the scan laid out"""
+    """direct probes, the partitioned lookups and the two-level ones over the 16-byte slots and over the 8-byte copy, on a table the
+    scan laid out.  Only the scan-fed query (mgQueryReadsDevice) takes the partitioned paths, and two levels need more than 512
+    buckets: 1024 x 192 slots here (MODGPU_BUCKET_R=256), 2k - log2 NB = 32.  mgTableDiag says which kernel ran."""
     sh = mg.seqhashCreate(K, W, 17); oh = po.Hasher(K, W, 17)
     L = mg.lib()
-    b = synth_batch(2_400_000, 700_000, 47)
-    q = synth_batch(600_000, 700_000, 47, err=0.08)
+    b = synth_batch(3_000_000, 900_000, 47)
+    q = synth_batch(600_000, 900_000, 47, err=0.08)
     qk = util.oracle_scan_batch(oh, *q)[0]
     oms = oracle_build(oh, BITS, [b])
     want = np.array([oms.find(x) for x in qk], np.uint32)
     # a lookup batch first brings the table to its own load (0.4, by a rehash that places with claims) unless the table is sparse enough
-    # already: TABLE_LOAD=85 holds for the lookups too, the table is past the 2^16-slot floor, and the slot count and the counter of
+    # already: TABLE_LOAD=100 holds for the lookups too, the table is past the 2^16-slot floor, and the slot count and the counter of
     # scan-placed buckets must be what the build left -- the lookups then run on the layout the scan made
-    with mg.knobs(MERGE_PLACE=1, TABLE_PATH="bucket", TIGHT_LOAD=80, TABLE_LOAD=85):
+    with mg.knobs(MERGE_PLACE=1, TABLE_PATH="bucket", TIGHT_LOAD=80, TABLE_LOAD=100, BUCKET_R=256, BUCKET_T=256):
         ms = mg.modsetCreate(sh, BITS)
         mg.add_sequence_batch(ms, *b)
         slots = L.mgModsetDeviceSlots(ms)
         lay = layout(ms)
         assert lay[:3] == [0, 0, 0] and lay[4] > 0 and slots > 1 << 16 and lay[3] * 100 > slots * 60, (lay, slots)
+        d0 = diag(ms)
+        assert d0["log2NB"] == 10 and 2 * K - d0["log2NB"] == 32, d0
+        d_p = mg.DeviceBuffer.from_numpy(mg.pack_host(q[0])); d_o = mg.DeviceBuffer.from_numpy(q[1].astype(np.uint64))
+        d_ix = mg.DeviceBuffer((len(qk) + 8) * 4)
+        n = C.c_uint64()
         with mg.knobs(FIND_PATH=path, FIND8=find8):
-            got = device_find(ms, qk)
+            mg.check(L.mgQueryReadsDevice(ms, d_p.ptr, int(q[1][-1]), d_o.ptr, len(q[1]) - 1, d_ix.ptr, None, None, len(qk) + 8, C.byref(n), None))
+            assert n.value == len(qk)
+            got = d_ix.to_numpy(np.uint32, len(qk))
+            d1 = diag(ms)
+            also = device_find(ms, qk)                    # (modsetFindBatchDevice: direct probes whatever the knobs say)
+        ran = {c for c in DIAG[2:6] if d1[c] != d0[c]}
+        assert ran == {{"direct": "direct", "part": "part1", "2": "part2_8" if find8 else "part2_16"}[path]}, (path, find8, d0, d1)
+        assert d1["pack8"] - d0["pack8"] == (1 if (path, find8) == ("2", 1) else 0)
         assert L.mgModsetDeviceSlots(ms) == slots, "the lookups rehashed the table: they did not see the scan's layout"
         assert layout(ms) == lay
         assert np.array_equal(got, want) and (got == 0).any() and (got != 0).any()
+        assert np.array_equal(also, want)
         mg.lib().modsetDestroy(ms)
-
-
-def _kmers_in_bucket0(rng, n, other=False):
-    """n distinct 21-mers whose table hash (mg_common.h mgMixK, 2k = 42 >= 24) starts with ten zero bits -- bucket 0 of any table
-    of up to 1024 buckets -- or, other = True, with a one bit (a bucket of the upper half).  mix = (A ^ g (L)) : mixBits (L) with A
-    the k-mer's top 10 bits, L its low 32 and g (L) = (L * 0x9E3779B1 mod 2^32) >> 22."""
-    low = np.unique(rng.integers(0, 1 << 32, n + n // 8 + 8).astype(np.uint64))[:n]
-    assert len(low) == n
-    rng.shuffle(low)
-    g = ((low * np.uint64(0x9E3779B1)) & np.uint64(0xffffffff)) >> np.uint64(22)
-    top = rng.integers(512, 1024, n).astype(np.uint64) if other else np.zeros(n, np.uint64)
-    return ((top ^ g) << np.uint64(32)) | low
 
 
 @pytest.mark.parametrize("extra", [-1, 0])
@@ -199,8 +205,8 @@ def test_full_bucket(extra):
     R = 256
     rng = np.random.default_rng(9)
     sh = mg.seqhashCreate(21, 64, 17)
-    base = _kmers_in_bucket0(rng, 20_000, other=True)
-    hot = _kmers_in_bucket0(rng, R + extra)
+    base = util.kmers_with_mix_prefix(rng, 20_000, 1, 1, 21)           # the table hash starts with a one bit: a bucket of the upper half
+    hot = util.kmers_with_mix_prefix(rng, R + extra, 0, 10, 21)          # ... with ten zero bits: bucket 0 of any table of up to 1024 buckets
     with mg.knobs(MERGE_PLACE=1, TABLE_PATH="bucket", BUCKET_R=R, BUCKET_T=256, TIGHT_LOAD=0, MERGE_SLOTS=0):
         ms = mg.modsetCreate(sh, 20)
         d_b = mg.DeviceBuffer.from_numpy(base)

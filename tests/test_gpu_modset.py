@@ -244,7 +244,9 @@ def test_golden_modmap_flow(tag, golden_dir, tmp_path):
 @pytest.mark.parametrize("k,w,bits,path", [(21, 32, 22, "direct"), (21, 32, 22, "part"), (19, 31, 23, "part"), (15, 8, 24, "part"),
                                             (27, 4, 22, "part"), (31, 4, 22, "part"),
                                             (21, 32, 22, "2 levels"), (19, 31, 23, "2 levels"), (15, 8, 24, "2 levels"), (27, 4, 22, "2 levels"), (21, 64, 28, "2 levels"),
-                                            # round 6: the two-level lookups read an 8-byte copy of the table where 2k - log2 NB <= 32 (16 buckets here: k <= 18): the widest key that fits, and one more bit
+                                            # round 6: the two-level lookups read an 8-byte copy of the table where 2k - log2 NB <= 32.  Two levels need more than 512 buckets
+                                            # (see TWO_LEVELS below): 2048 here, so every k <= 21 of this list reads the copy (narrow keys: k = 16 .. 18) and k = 27 the 16-byte
+                                            # slots; the widest key that fits and one more bit are tests/test_gpu_table_skew.py's (k = 21 in 1024 buckets, k = 22 in 2048)
                                             (18, 8, 22, "2 levels"), (17, 4, 22, "2 levels"), (16, 8, 22, "2 levels")])
 def test_seed_lists_vs_oracle(k, w, bits, path):
     """mgQueryReadsDevice: Seed{index,pos} per read incl. misses (modmap.c:197-206) -- by direct probes in ordinal order and by
@@ -252,13 +254,40 @@ def test_seed_lists_vs_oracle(k, w, bits, path):
     bin against one piece of the table, results pulled back into ordinal order through the scatter's run table); k = 31 has no
     one-word element and must fall back to the direct probes by itself"""
     L = mg.lib()
-    with mg.knobs(FIND_PATH=path):
-        _seed_lists_vs_oracle(L, k, w, bits)
+    if path == "2 levels":
+        with mg.knobs(FIND_PATH=path, **TWO_LEVELS):
+            ms = _seed_lists_vs_oracle(L, k, w, bits, TWO_LEVEL_ENTRIES * w)
+        # three query batches.  k = 27: an element fits one word up to 2^16 seeds (2k - 6 + log2 n <= 64), which only the first batch is
+        assert_two_levels_ran(ms, k, batches=1 if k == 27 else 3, direct=2 if k == 27 else 0)
+    else:
+        with mg.knobs(FIND_PATH=path):
+            _seed_lists_vs_oracle(L, k, w, bits)
 
 
-def _seed_lists_vs_oracle(L, k, w, bits):
+# The two-level lookups need a fine digit of the bucket id, which a table has beyond 512 buckets (mg_common.h mgPartSplit): with the
+# default 4096 slots a bucket that is more than 2^21 slots.  The "2 levels" cases run with 256 slots a bucket and a reference of about
+# 125 000 entries (a genome of 200 000 modimizers, of which reads of its own length cover five eighths): 2048 buckets at the lookups'
+# load -- which k = 27 needs besides: its elements fit one word only with a coarse digit of 6 bits and batches of 2^16 seeds at most.
+# mgTableDiag counts the launches: the cases assert that two levels ran, and over which table (the 8-byte copy where 2k - log2 NB <= 32).
+TWO_LEVELS = dict(BUCKET_R=256, BUCKET_T=256)
+TWO_LEVEL_ENTRIES = 200_000
+
+
+def assert_two_levels_ran(ms, k, batches=None, direct=None):
+    """batches, direct: how many lookup batches went by two levels and by direct probes, where the test knows"""
+    d = util.table_diag(ms)
+    print("k", k, "launch census", d)
+    assert d["log2NB"] > 9, "a table of %d buckets has no fine digit: two levels cannot run (%s)" % (1 << d["log2NB"], d)
+    took, other = ("part2_8", "part2_16") if 2 * k - d["log2NB"] <= 32 else ("part2_16", "part2_8")
+    assert d[took] >= 1 and d[other] == 0 and d["part1"] == 0 and (d["pack8"] >= 1) == (took == "part2_8"), d
+    assert batches is None or d[took] == batches, d
+    assert direct is None or d["direct"] == direct, d
+    return d
+
+
+def _seed_lists_vs_oracle(L, k, w, bits, genome=300_000):
     sh = mg.seqhashCreate(k, w, 17); oh = po.Hasher(k, w, 17)
-    refb = synth_batch(300_000, 300_000, 41, err=0.0, n50=50_000)
+    refb = synth_batch(genome, genome, 41, err=0.0, n50=50_000)
     ms = mg.modsetCreate(sh, bits); oms = po.Modset(oh, bits)
     for r in range(len(refb[1]) - 1):
         for x in oh.scan(refb[0][refb[1][r]:refb[1][r + 1]])[0]:
@@ -266,7 +295,7 @@ def _seed_lists_vs_oracle(L, k, w, bits):
     km_ref = util.oracle_scan_batch(oh, *refb)[0]
     d_k = mg.DeviceBuffer.from_numpy(km_ref)
     mg.check(L.modsetAddBatchDevice(ms, d_k.ptr, len(km_ref), None, 0, None))
-    q = synth_batch(200_000, 300_000, 41, err=0.04, n50=6000)       # reads of the same genome, with errors
+    q = synth_batch(200_000, genome, 41, err=0.04, n50=6000)       # reads of the same genome, with errors
     qk, qp, _, qst = util.oracle_scan_batch(oh, *q)
     want = np.array([oms.find(x) for x in qk], np.uint32)
     total = int(q[1][-1])
@@ -282,7 +311,7 @@ def _seed_lists_vs_oracle(L, k, w, bits):
     assert np.array_equal(np.searchsorted(rid, np.arange(len(q[1]))), qst)
     assert (want == 0).any() and (want != 0).any()
     # a second, larger query batch against the same table (other sub-chunk counts, a last partial sub-chunk), twice
-    q = synth_batch(1_500_000, 300_000, 41, err=0.02, n50=3000)
+    q = synth_batch(1_500_000, genome, 41, err=0.02, n50=3000)
     qk = util.oracle_scan_batch(oh, *q)[0]
     order = np.argsort(oms.values()[1:], kind="stable"); vs = oms.values()[1:][order]
     at = np.minimum(np.searchsorted(vs, qk), len(vs) - 1)
@@ -294,6 +323,7 @@ def _seed_lists_vs_oracle(L, k, w, bits):
     for rep in range(2):
         mg.check(L.mgQueryReadsDevice(ms, d_p.ptr, total, d_o.ptr, len(q[1]) - 1, d_ix.ptr, None, None, cap, C.byref(n), None))
         assert n.value == len(qk) and np.array_equal(d_ix.to_numpy(np.uint32, n.value), want), rep
+    return ms
 
 
 @pytest.mark.parametrize("path", ["direct", "2 levels", None])
@@ -306,15 +336,18 @@ def test_query_batches_pipelined_equal_synchronous(path):
     k, w, bits = 21, 32, 22
     sh = mg.seqhashCreate(k, w, 17)
     ms = mg.modsetCreate(sh, bits)
-    refb = synth_batch(300_000, 300_000, 41, err=0.0, n50=50_000)
+    two = path == "2 levels"
+    genome = TWO_LEVEL_ENTRIES * w if two else 300_000        # (two levels: a table of more than 512 buckets, see TWO_LEVELS)
+    refb = synth_batch(genome, genome, 41, err=0.0, n50=50_000)
     d_rp = mg.DeviceBuffer.from_numpy(mg.pack_host(refb[0])); d_ro = mg.DeviceBuffer.from_numpy(refb[1].astype(np.uint64))
     nh = C.c_uint64()
-    mg.check(L.mgAddReadsDevice(ms, d_rp.ptr, int(refb[1][-1]), d_ro.ptr, len(refb[1]) - 1, C.byref(nh), None))
-    with mg.knobs(FIND_PATH=path):
+    with mg.knobs(**(TWO_LEVELS if two else {})):
+        mg.check(L.mgAddReadsDevice(ms, d_rp.ptr, int(refb[1][-1]), d_ro.ptr, len(refb[1]) - 1, C.byref(nh), None))
+    with mg.knobs(FIND_PATH=path, **(TWO_LEVELS if two else {})):
         batches = []
         for i, (nb, n50, err) in enumerate([(400_000, 6000, 0.03), (1_200_000, 3000, 0.02), (0, 1, 0), (150_000, 800, 0.05), (900_000, 20_000, 0.01)]):
             if nb:
-                q = synth_batch(nb, 300_000, 41, err=err, n50=n50)
+                q = synth_batch(nb, genome, 41, err=err, n50=n50)
                 d_p = mg.DeviceBuffer.from_numpy(mg.pack_host(q[0])); d_o = mg.DeviceBuffer.from_numpy(q[1].astype(np.uint64))
                 total, nr = int(q[1][-1]), len(q[1]) - 1
             else:
@@ -358,6 +391,9 @@ def test_query_batches_pipelined_equal_synchronous(path):
         o3 = [mg.DeviceBuffer(cap * 4) for _ in range(3)]
         mg.check(L.mgQueryReadsDevice(ms, d_p.ptr, total, d_o.ptr, nr, o3[0].ptr, o3[1].ptr, o3[2].ptr, cap, C.byref(n), None))
         assert np.array_equal(o3[0].to_numpy(np.uint32, n.value), want[0])
+    if two:
+        d = assert_two_levels_ran(ms, k)
+        assert d["part2_8"] >= 8 and d["direct"] == 0, "four non-empty batches, synchronous and pipelined, by two levels: %s" % d
     L.modsetDestroy(ms)
 
 
@@ -835,11 +871,18 @@ def test_modmap_randomized_vs_oracle(k, w, seed, path, tmp_path):
     6 parameter sets x 6 references x 7-9 reads = about 290 reads; the reference build's own report lines and arrays
     (index / offset / id / depth / loc / rev, modmap.c:74-134) are compared on the way."""
     L = mg.lib()
-    with mg.knobs(FIND_PATH=path):                      # the seeds' lookups by direct probes / through the partitioned path
-        _modmap_randomized(L, k, w, seed, tmp_path)
+    if path == "2 levels":
+        # references of 30 - 270 kbp sit at the table's floor of 2^16 slots: 256 buckets at most, no fine digit, one level.  So these
+        # cases pad the reference with one more sequence of random bases (130 000 modimizers: 2048 buckets of 256 slots at the lookups'
+        # load, see TWO_LEVELS), which the oracle gets too, and every trial asserts that its seeds' lookups went by two levels
+        with mg.knobs(FIND_PATH=path, **TWO_LEVELS):
+            _modmap_randomized(L, k, w, seed, tmp_path, pad=130_000 * w)
+    else:
+        with mg.knobs(FIND_PATH=path):                  # the seeds' lookups by direct probes / through the partitioned path
+            _modmap_randomized(L, k, w, seed, tmp_path)
 
 
-def _modmap_randomized(L, k, w, seed, tmp_path):
+def _modmap_randomized(L, k, w, seed, tmp_path, pad=0):
     rng = np.random.default_rng(1000 * k + w)
     n_reads_total = n_m_lines = n_overflow = 0
     for trial in range(6):
@@ -858,7 +901,6 @@ def _modmap_randomized(L, k, w, seed, tmp_path):
                 b = int(rng.integers(0, len(dst) - ln))
                 dst[b:b + ln] = _mutate(rng, piece, 0.002 * rng.random())
         names = ["s%d_%d" % (trial, i) for i in range(n_seq)]
-        g = np.concatenate(seqs)
         # ---- reads --------------------------------------------------------------------------------------------------
         def cut(ln):
             s = seqs[int(rng.integers(0, n_seq))]
@@ -877,6 +919,11 @@ def _modmap_randomized(L, k, w, seed, tmp_path):
             reads.append(_mutate(rng, np.concatenate([cut(900) for _ in range(25)]), 0.01))
             reads.append(np.zeros(3000, np.uint8))                                             # poly-A
         rnames = ["q%d_%d" % (trial, i) for i in range(len(reads))]
+        if pad:                                             # (after the reads are cut: they come from the sequences above, with the same draws as without it)
+            seqs = seqs + [np.random.default_rng(trial).integers(0, 4, pad).astype(np.uint8)]
+            names = names + ["pad%d" % trial]
+            n_seq += 1
+        g = np.concatenate(seqs)
         # ---- oracle -------------------------------------------------------------------------------------------------
         oh = po.Hasher(k, w, seed); oms = po.Modset(oh, 20); oref = po.Reference(oms)
         for nm, s in zip(names, seqs):
@@ -909,6 +956,8 @@ def _modmap_randomized(L, k, w, seed, tmp_path):
         n_reads_total += len(reads)
         n_m_lines += sum(l.startswith("M\t") for l in want.splitlines())
         n_overflow += sum(sum(l.startswith("M\t%s\t" % nm) for l in want.splitlines()) > 16 for nm in rnames)
+        if pad:
+            assert_two_levels_ran(ms, k)                      # (the reference's inserts find their indices by direct probes: those count too)
         L.mgReferenceDestroy(ref); L.modsetDestroy(ms)
         oref.close()
     assert n_reads_total >= 42 and n_m_lines > 20

@@ -86,3 +86,118 @@ def bench_lines(stdout):
     compact = [l for l in lines if l.startswith("{")]
     detail = [l for l in lines if l.startswith("BENCH_DETAIL ")]
     return (json.loads(compact[-1]) if compact else None, json.loads(detail[-1][len("BENCH_DETAIL "):]) if detail else None, compact)
+
+
+# ------------------------------------------------------------------------------------------------
+# Where a k-mer belongs in the device table: a numpy restatement of csrc/mg_common.h (mgMixBits, mgMixK, mgBucketOfM) and of the geometry
+# choice in csrc/mg_table.hip (mgSetGeometry, mgSlotsFor), written from their comments and formulas.  The tests use it to craft
+# k-mers that crowd one bucket and to say beforehand which geometry a table will take.
+
+MIX_TOP = 10                    # the top bits of the mix that cost one multiply: (A ^ g (L)) : mixBits (L)
+MIX_MUL = 0x9E3779B1
+_M1, _M2 = 0xff51afd7ed558ccd, 0xc4ceb9fe1a85ec53
+U = np.uint64
+
+
+def mix_bits(x, b):
+    """murmur-style bijection of b-bit values (x: uint64 array)"""
+    x = np.asarray(x, np.uint64)
+    mask = U((1 << b) - 1)
+    h = U((b + 1) >> 1)
+    # modulo 2^b only the multipliers' low b bits count, so one formula serves the 32-bit form (b <= 32: 0xed558ccd, 0x1a85ec53) too
+    with np.errstate(over="ignore"):
+        x = x ^ (x >> h); x = (x * U(_M1)) & mask
+        x = x ^ (x >> h); x = (x * U(_M2)) & mask
+        x = x ^ (x >> h)
+    return x
+
+
+def mix_k(x, b):
+    """the table's hash of a k-mer of b = 2k bits: a bijection onto b-bit values"""
+    x = np.asarray(x, np.uint64)
+    if b < 24:
+        return mix_bits(x, b)
+    lb = b - MIX_TOP
+    L = x & U((1 << lb) - 1); A = x >> U(lb)
+    return ((A ^ _mix_g(L, lb)) << U(lb)) | mix_bits(L, lb)
+
+
+def _mix_g(L, lb):
+    low = L & U((1 << min(lb, 32)) - 1)
+    return ((low * U(MIX_MUL)) & U(0xffffffff)) >> U(32 - MIX_TOP)
+
+
+def bucket_of(kmers, k, log2nb):
+    """bucket of each k-mer in a table of 2^log2nb buckets: the top bits of its mix"""
+    m = mix_k(kmers, 2 * k)
+    if not log2nb:
+        return np.zeros(len(m), np.uint64)
+    s = 2 * k - log2nb
+    return m >> U(s) if s >= 0 else (m << U(-s)) & U(0xffffffff)
+
+
+def kmers_with_mix_prefix(rng, n, prefix, prefix_bits, k):
+    """n distinct k-mers (2k >= 24) whose table hash starts with the prefix_bits <= 10 bits of `prefix`: they share a bucket in every
+    table of up to 2^prefix_bits buckets, and spread evenly over the buckets below it in a larger one"""
+    b = 2 * k
+    assert b >= 24 and 0 <= prefix_bits <= MIX_TOP and 0 <= prefix < (1 << prefix_bits)
+    lb = b - MIX_TOP
+    assert n <= (1 << lb) // 2, "not that many distinct low parts"
+    low = np.unique(rng.integers(0, 1 << lb, n + n // 8 + 8, dtype=np.uint64))
+    assert len(low) >= n
+    low = rng.permutation(low)[:n]
+    free = MIX_TOP - prefix_bits
+    top = (U(prefix) << U(free)) | rng.integers(0, 1 << free, n, dtype=np.uint64)
+    return ((top ^ _mix_g(low, lb)) << U(lb)) | low
+
+
+R_QUANTUM = 64
+
+
+def table_geometry(want_slots, want_r=4096):
+    """(log2 NB, R) for a table of want_slots slots: NB a power of two, at most 2^18, R the slots of a bucket, a multiple of 64 and at
+    most want_r where the size allows (8192 beyond that)"""
+    rmax = max(min(want_r, 8192), R_QUANTUM)
+    want = max(want_slots, R_QUANTUM)
+    lg = 0
+    while lg < 18 and (want + (1 << lg) - 1) // (1 << lg) > rmax:
+        lg += 1
+    r = (want + (1 << lg) - 1) >> lg
+    r = (r + R_QUANTUM - 1) // R_QUANTUM * R_QUANTUM
+    return lg, min(r, 8192)
+
+
+def slots_for(entries, load_pct, table_bits):
+    """slots wanted for `entries` at that load: 2^16 at least, 2^(table_bits - 1) at most"""
+    return min(max(entries * 100 // load_pct + 1, 1 << 16), 1 << (table_bits - 1))
+
+
+LOOKUP_LOAD, BUILD_LOAD = 40, 60
+
+
+def kmer_reads(hasher, kmers, k):
+    """every candidate k-mer as a read of k bases (first base in the top bits), scanned with the oracle: a set built with w = 1 takes
+    every k-mer start as a modimizer, and the scan emits the canonical one of a k-mer and its reverse complement.  Returns (kept,
+    bases, offs): the candidates the oracle emits unchanged, in order, and their reads.  A mistake here shows as a smaller kept set
+    (callers assert its size), never as an agreement of the device with itself: the device is compared with the oracle on the reads."""
+    kmers = np.asarray(kmers, np.uint64)
+    shifts = (2 * (k - 1 - np.arange(k))).astype(np.uint64)
+    bases = ((kmers[:, None] >> shifts[None, :]) & U(3)).astype(np.uint8)
+    offs = np.arange(len(kmers) + 1, dtype=np.int64) * k
+    got, _, _, st = oracle_scan_batch(hasher, bases.reshape(-1), offs)
+    assert np.array_equal(st, np.arange(len(kmers) + 1)), "a read of k bases has one k-mer"
+    keep = got == kmers
+    return kmers[keep], bases[keep].reshape(-1), np.arange(int(keep.sum()) + 1, dtype=np.int64) * k
+
+
+DIAG = ("log2NB", "R", "direct", "part1", "part2_16", "part2_8", "pack8", "rehash_bucket", "rehash_atomic")
+
+
+def table_diag(ms):
+    """mgTableDiag: the device table's geometry and, since it was made, its lookup batches by direct probes, by one partition level,
+    by two levels over the 16-byte slots and over the 8-byte copy, the copies made, the changes of geometry by either kernel"""
+    import ctypes
+    import modimizer_amd as mg
+    out = (ctypes.c_uint64 * 9)()
+    mg.check(mg.lib().mgTableDiag(ms, out))
+    return dict(zip(DIAG, (int(x) for x in out)))

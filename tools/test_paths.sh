@@ -29,6 +29,10 @@ MODGPU_FIND_PATH=part python tests/fuzz_gpu.py 19 150 2>&1 | tail -2
 echo "== MODGPU_FIND_PATH=2 (two-level partitioned lookups)"
 MODGPU_FIND_PATH=2 python -m pytest tests/test_gpu_modset.py tests/test_dropin.py tests/test_ref_files.py tests/test_readset.py tests/test_seqio.py -q -x -m gpu 2>&1 | tail -2
 MODGPU_FIND_PATH=2 python tests/fuzz_gpu.py 20 150 2>&1 | tail -2
+echo "== MODGPU_BUCKET_R=256 MODGPU_BUCKET_T=256 MODGPU_FIND_PATH=2 (a small table has more than 512 buckets only at 256 slots a bucket: with the default 4096 the leg above has no fine digit and runs one level -- tests/test_gpu_table_skew.py asserts which kernel ran, mgTableDiag)"
+MODGPU_BUCKET_R=256 MODGPU_BUCKET_T=256 MODGPU_FIND_PATH=2 python -m pytest tests/test_gpu_modset.py tests/test_gpu_table_skew.py tests/test_dropin.py tests/test_ref_files.py tests/test_readset.py -q -x -m gpu 2>&1 | tail -2
+MODGPU_BUCKET_R=256 MODGPU_BUCKET_T=256 MODGPU_FIND_PATH=2 MODGPU_FIND8=0 python -m pytest tests/test_gpu_modset.py tests/test_dropin.py -q -x -m gpu 2>&1 | tail -2
+MODGPU_BUCKET_R=256 MODGPU_BUCKET_T=256 MODGPU_FIND_PATH=2 python tests/fuzz_gpu.py 21 150 2>&1 | tail -2
 echo "== MODGPU_RANK_SLICE_SHIFT=16 (the smallest rank-lookup slices, as many as the list groups allow)"
 MODGPU_RANK_SLICE_SHIFT=16 MODGPU_TABLE_PATH=bucket python -m pytest tests/test_gpu_modset.py -q -x 2>&1 | tail -2
 MODGPU_RANK_SLICE_SHIFT=16 MODGPU_TABLE_PATH=bucket python tests/fuzz_gpu.py 23 150 2>&1 | tail -2
