@@ -58,6 +58,11 @@
 #endif
 __device__ __forceinline__ U32 mgToken (U64 o) { return 0x7fffffffu - (U32) o; }     /* 1..0x7fffffff */
 __device__ __forceinline__ bool mgIsAssigned (U32 v) { return (v & MG_ASSIGNED) != 0; }
+/* a 16-byte slot read as one uint4 {key lo, key hi, ord, cnt}: its key, the index its ordinal word holds (0: none yet), and
+   "an entry with an index up to keepMax" -- what a rehash keeps */
+__device__ __forceinline__ U64 mgKeyOf (const uint4 &v) { return ((U64) v.y << 32) | v.x; }
+__device__ __forceinline__ U32 mgIndexOf (U32 ordWord) { return mgIsAssigned (ordWord) ? (ordWord & ~MG_ASSIGNED) : 0; }
+__device__ __forceinline__ bool mgLiveEntry (const uint4 &v, U32 keepMax) { return (v.x | v.y) && mgIsAssigned (v.z) && (v.z & ~MG_ASSIGNED) <= keepMax; }
 
 /* bucket geometry: MgGeom, mgMixK, mgBucketOfM, mgHomeOfM in mg_common.h */
 
@@ -302,6 +307,45 @@ void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__r
     }
 }
 
+/* ---- the read-only probe walk: every lookup kernel's ----
+ * A view of one bucket's slots says how slot i is read (read), what it is compared by (tag: the key, or what stands for it;
+ * 0 = empty) and which index it answers on a hit (index). */
+struct MgTableSlots            /* the table's own 16-byte slots, in global memory */
+{ const MgSlot *s;
+  typedef uint4 Word;
+  __device__ __forceinline__ Word read (U32 i) const { return *reinterpret_cast<const uint4 *> (&s[i]); }
+  __device__ __forceinline__ U64 tag (const Word &w) const { return mgKeyOf (w); }
+  __device__ __forceinline__ U32 index (U32, const Word &w) const { return mgIndexOf (w.z); }
+};
+struct MgImageSlots            /* a bucket's image in LDS: keys and indices apart */
+{ const unsigned long long *sKey; const U32 *sIdx;
+  typedef unsigned long long Word;
+  __device__ __forceinline__ Word read (U32 i) const { return sKey[i]; }
+  __device__ __forceinline__ U64 tag (Word w) const { return w; }
+  __device__ __forceinline__ U32 index (U32 i, Word) const { return sIdx[i]; }
+};
+struct MgImageWords8           /* the same from the 8-byte copy (mgTablePack8Kernel): (key's low bits + 1) << 31 | index */
+{ const unsigned long long *sW;
+  typedef unsigned long long Word;
+  __device__ __forceinline__ Word read (U32 i) const { return sW[i]; }
+  __device__ __forceinline__ U64 tag (Word w) const { return w >> 31; }
+  __device__ __forceinline__ U32 index (U32, Word w) const { return (U32) w & 0x7fffffffu; }
+};
+/* Linear probing, wrapping inside the bucket: from slot `at` on until the slot that holds `want` (its index is the answer) or an empty
+ * one, over at most R slots in all (then, as at an empty slot, 0).  probes: slots of the walk the caller has looked at itself. */
+template <class Slots>
+__device__ __forceinline__ U32 mgProbeFind (const Slots &sl, U32 at, U32 R, U64 want, U32 probes = 0)
+{
+  for ( ; probes < R ; ++probes)
+    { const typename Slots::Word w = sl.read (at);
+      const U64 cur = sl.tag (w);
+      if (cur == want) return sl.index (at, w);
+      if (cur == 0) break;
+      at = mgNextSlot (at, R);
+    }
+  return 0;
+}
+
 /* The query's lookups.  MG_FIND_PER k-mers per thread and step: all the k-mer loads, then all the first probes (one
  * 16-byte load each: key and index together), land before anything is stored -- a loop of "load, probe, store" made
  * every store wait for the one before it; only the probes that hit another k-mer's slot walk on.  CHECK_OCC = false
@@ -335,15 +379,9 @@ void mgTableFindKernel (const MgSlot *__restrict__ slots, const U32 *__restrict_
       for (int j = 0 ; j < MG_FIND_PER ; ++j) asm volatile ("" : "+v" (v[j].x), "+v" (v[j].y), "+v" (v[j].z));
 #pragma unroll
       for (int j = 0 ; j < MG_FIND_PER ; ++j)
-        { res[j] = 0;
-          U64 cur = ((U64) v[j].y << 32) | v[j].x; U32 ord = v[j].z;
-          for (U32 probes = 1 ; live[j] && cur != 0 ; ++probes)
-            { if (cur == key[j]) { res[j] = mgIsAssigned (ord) ? (ord & ~MG_ASSIGNED) : 0; break; }
-              if (probes >= g.R) break;
-              at[j] = mgNextSlot (at[j], g.R);
-              const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base[j] + at[j]]);
-              cur = ((U64) w.y << 32) | w.x; ord = w.z;
-            }
+        { const U64 cur = mgKeyOf (v[j]);
+          res[j] = cur == key[j] ? mgIndexOf (v[j].z) : 0;
+          if (live[j] && cur != 0 && cur != key[j]) res[j] = mgProbeFind (MgTableSlots { slots + base[j] }, mgNextSlot (at[j], g.R), g.R, key[j], 1);   /* met another k-mer's slot: walk on */
         }
 #pragma unroll
       for (int j = 0 ; j < MG_FIND_PER ; ++j) { const U64 o = o0 + (U64) j * stride; if (o < n) __builtin_nontemporal_store (res[j], &out[o]); }
@@ -371,15 +409,7 @@ void mgTableFindSegKernel (const MgSlot *__restrict__ slots, MgGeom g, const MgS
       if (o >= n) continue;
       const U64 m = mgMixK (__builtin_nontemporal_load (at), g.kbits), key = m + 1;
       const U64 base = (U64) mgBucketOfM (m, g) * g.R;
-      U32 slot = mgHomeOfM (m, g), res = 0;
-      for (U32 probes = 0 ; probes < g.R ; ++probes)
-        { const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base + slot]);
-          const U64 cur64 = ((U64) w.y << 32) | w.x;
-          if (cur64 == key) { res = mgIsAssigned (w.z) ? (w.z & ~MG_ASSIGNED) : 0; break; }
-          if (cur64 == 0) break;
-          slot = mgNextSlot (slot, g.R);
-        }
-      __builtin_nontemporal_store (res, &out[o]);
+      __builtin_nontemporal_store (mgProbeFind (MgTableSlots { slots + base }, mgHomeOfM (m, g), g.R, key), &out[o]);
     }
 }
 
@@ -972,14 +1002,16 @@ __device__ __forceinline__ void mgDedupCount (const MgBucketArgs &a, U32 *sOrd, 
   else atomicMax (&sOrd[at], tok);
   atomicAdd (&sCnt[at], 1u);
 }
-/* the largest value over the 64 lanes of a wave (DPP, as mgWaveInclusiveSum; every lane must be active) */
-__device__ __forceinline__ U32 mgWaveMax (U32 v)
+/* inclusive prefix max over the 64 lanes of a wave (DPP, the steps of mgWaveInclusiveSum; lanes without a source take 0; every lane
+   must be active), and the largest value of them all */
+__device__ __forceinline__ U32 mgWavePrefixMax (U32 v)
 {
 #define MG_MAX_DPP(ctrl, rows) do { const U32 o_ = (U32) __builtin_amdgcn_update_dpp (0, (int) v, ctrl, rows, 0xf, false); v = o_ > v ? o_ : v; } while (0)
   MG_MAX_DPP (0x111, 0xf); MG_MAX_DPP (0x112, 0xf); MG_MAX_DPP (0x114, 0xf); MG_MAX_DPP (0x118, 0xf); MG_MAX_DPP (0x142, 0xa); MG_MAX_DPP (0x143, 0xc);
 #undef MG_MAX_DPP
-  return (U32) __builtin_amdgcn_readlane ((int) v, 63);
+  return v;
 }
+__device__ __forceinline__ U32 mgWaveMax (U32 v) { return (U32) __builtin_amdgcn_readlane ((int) mgWavePrefixMax (v), 63); }
 /* A bucket's occurrences beyond the ones fetched ahead -- only a bucket with a k-mer of very many copies has any (a poly-A
  * 21-mer is a modimizer at k = 21, d = 64, seed 17, and a human read set holds millions of them): a wave takes 64 of them at a
  * time, and the lanes that landed in the same slot as its first lane are counted as ONE occurrence with their number -- the
@@ -1236,7 +1268,7 @@ void mgBucketDedupKernel (const MgBucketArgs a, U32 bucketsPerBlock)
         { if (occNow)
             { for (U32 i = tid ; i < R ; i += T)
                 { uint4 v = *reinterpret_cast<const uint4 *> (&a.slots[(U64) b * R + i]);
-                  sKey[i] = ((unsigned long long) v.y << 32) | v.x; sOrd[i] = v.z;
+                  sKey[i] = mgKeyOf (v); sOrd[i] = v.z;
                 }
               __syncthreads ();
             }
@@ -1327,14 +1359,6 @@ void mgBucketDedupKernel (const MgBucketArgs a, U32 bucketsPerBlock)
  * home slot with no empty slot between a key's home and its place: an ordinary linear-probing bucket to every reader.
  * A block of consecutive slots is summed up as (S, M) = (its keys, max of j - C[j] with C counted from the block's start); two
  * neighbours combine to (SA + SB, max (MA, MB - SA)). */
-/* inclusive prefix max over the 64 lanes of a wave (DPP, the steps of mgWaveInclusiveSum; lanes without a source take 0) */
-__device__ __forceinline__ U32 mgWavePrefixMax (U32 v)
-{
-#define MG_MAX_DPP(ctrl, rows) do { const U32 o_ = (U32) __builtin_amdgcn_update_dpp (0, (int) v, ctrl, rows, 0xf, false); v = o_ > v ? o_ : v; } while (0)
-  MG_MAX_DPP (0x111, 0xf); MG_MAX_DPP (0x112, 0xf); MG_MAX_DPP (0x114, 0xf); MG_MAX_DPP (0x118, 0xf); MG_MAX_DPP (0x142, 0xa); MG_MAX_DPP (0x143, 0xc);
-#undef MG_MAX_DPP
-  return v;
-}
 /* start[] of the bucket whose home counts stand in cnt[0..R) (every thread of the workgroup calls this after the barrier behind the
  * counting): left in sStart as 16-bit words (start < 2R <= 16384), cnt[] zeroed again; returns the carry.  n: the keys counted
  * (< R).  A thread owns `per` consecutive slots (a multiple of four: 16-byte LDS accesses), sWave: 2 x 16 words.  Ends WITHOUT a
@@ -1438,7 +1462,7 @@ void mgBucketMergeKernel (const MgBucketArgs a, U32 bucketsPerBlock)
           if (occNow)
             { for (U32 i = tid ; i < R ; i += T)
                 { uint4 v = *reinterpret_cast<const uint4 *> (&a.slots[(U64) b * R + i]);
-                  sKey[i] = ((unsigned long long) v.y << 32) | v.x; sOrd[i] = v.z; sCnt[i] = v.w;
+                  sKey[i] = mgKeyOf (v); sOrd[i] = v.z; sCnt[i] = v.w;
                 }
               __syncthreads ();
             }
@@ -1637,43 +1661,44 @@ void mgBinFindKernel (const MgSlot *__restrict__ slots, MgGeom g, MgPartFmt f, U
         { const U64 x = __builtin_nontemporal_load (&el[i]);
           const U64 m = ((U64) b << f.remBits) | (x >> f.ordBits), key = m + 1;
           const U64 base = (U64) mgBucketOfM (m, g) * g.R;
-          U32 slot = mgHomeOfM (m, g), res = 0;
-          for (U32 probes = 0 ; probes < g.R ; ++probes)
-            { const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base + slot]);
-              const U64 cur64 = ((U64) w.y << 32) | w.x;
-              if (cur64 == key) { res = mgIsAssigned (w.z) ? (w.z & ~MG_ASSIGNED) : 0; break; }
-              if (cur64 == 0) break;
-              slot = mgNextSlot (slot, g.R);
-            }
+          const U32 res = mgProbeFind (MgTableSlots { slots + base }, mgHomeOfM (m, g), g.R, key);
           __builtin_nontemporal_store (((x & ordMask) << 32) | res, &el[i]);
         }
     }
 }
 
-template <int SUB>
-__global__ __launch_bounds__ (1024)
-void mgUnpartKernel (const U64 *__restrict__ el, const unsigned long long *__restrict__ runTab, U32 nBins, U64 n, U32 *__restrict__ out)
+/* One tile of a pull-back, the whole workgroup (1024 threads): runRow[b] = where the tile's run of bin b went and its length (what the
+ * scatter kernel noted); 16 waves take the runs in turn, 64 elements at a time, and dec (place in the partitioned array, &pos, &val)
+ * says which place of the tile an element's result belongs to and what it is; then the tile's cnt results leave in order
+ * (NT: non-temporal stores). */
+template <int SUB, bool NT, class Decode>
+__device__ __forceinline__ void mgPullTile (const unsigned long long *__restrict__ runRow, U32 nBins, const Decode &dec, U32 cnt, U32 *__restrict__ out)
 {
   __shared__ U32 sTile[SUB];
   __shared__ unsigned long long sRun[MG_PART_MAXBINS];
   const U32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (U32 b = tid ; b < nBins ; b += 1024) sRun[b] = runRow[b];
+  __syncthreads ();
+  for (U32 b = wave ; b < nBins ; b += 16)
+    { const unsigned long long r = sRun[b];
+      const U64 base = r & (((U64) 1 << 40) - 1); const U32 len = (U32) (r >> 40);
+      for (U32 i = lane ; i < len ; i += 64) { U32 pos, val; dec (base + i, &pos, &val); sTile[pos] = val; }
+    }
+  __syncthreads ();
+  for (U32 i = tid ; i < cnt ; i += 1024) { if (NT) __builtin_nontemporal_store (sTile[i], &out[i]); else out[i] = sTile[i]; }
+  __syncthreads ();
+}
+
+/* one level: every element is (ordinal << 32 | index) by now; a workgroup per sub-chunk of ordinals */
+template <int SUB>
+__global__ __launch_bounds__ (1024)
+void mgUnpartKernel (const U64 *__restrict__ el, const unsigned long long *__restrict__ runTab, U32 nBins, U64 n, U32 *__restrict__ out)
+{
   const U64 nSub = (n + SUB - 1) / SUB;
   for (U64 s = blockIdx.x ; s < nSub ; s += gridDim.x)
     { const U64 o0 = s * SUB;
-      const U32 cnt = (U32) (o0 + SUB < n ? SUB : n - o0);
-      for (U32 b = tid ; b < nBins ; b += 1024) sRun[b] = runTab[s * nBins + b];
-      __syncthreads ();
-      for (U32 b = wave ; b < nBins ; b += 16)
-        { const unsigned long long r = sRun[b];
-          const U64 base = r & (((U64) 1 << 40) - 1); const U32 len = (U32) (r >> 40);
-          for (U32 i = lane ; i < len ; i += 64)
-            { const U64 v = __builtin_nontemporal_load (&el[base + i]);
-              sTile[(U32) ((v >> 32) - o0)] = (U32) v;
-            }
-        }
-      __syncthreads ();
-      for (U32 i = tid ; i < cnt ; i += 1024) __builtin_nontemporal_store (sTile[i], &out[o0 + i]);
-      __syncthreads ();
+      const auto dec = [=] (U64 at, U32 *pos, U32 *val) { const U64 v = __builtin_nontemporal_load (&el[at]); *pos = (U32) ((v >> 32) - o0); *val = (U32) v; };
+      mgPullTile<SUB, true> (runTab + s * nBins, nBins, dec, (U32) (o0 + SUB < n ? SUB : n - o0), out + o0);
     }
 }
 
@@ -1681,14 +1706,16 @@ void mgUnpartKernel (const U64 *__restrict__ el, const unsigned long long *__res
  * and the bucket (64 KiB) sits in LDS while they run.  The second pass replaces every element's ordinal by its position in the
  * first pass's output, where the element itself (with its ordinal) stays; results come back in two pulls: (chunk, half) tiles of
  * the first pass's output from the second pass's runs, then sub-chunks of ordinals from the first pass's runs. ---- */
+/* WORD8: out of the 8-byte-per-slot copy of the table (find8, made by mgTablePack8Kernel below) instead of the table's own slots */
+template <bool WORD8>
 __global__ __launch_bounds__ (1024)
-void mgBucketFindKernel (const MgSlot *__restrict__ slots, const U32 *__restrict__ occ, MgGeom g, MgPartFmt f, U32 nBuckets,
+void mgBucketFindKernel (const MgSlot *__restrict__ slots, const U64 *__restrict__ find8, const U32 *__restrict__ occ, MgGeom g, MgPartFmt f, U32 nBuckets, int remB,
                          const U64 *__restrict__ bucketStart, U64 *__restrict__ el, U32 bucketsPerBlock)
 {
   const U32 R = g.R, T = blockDim.x, tid = threadIdx.x;
-  unsigned long long *sKey = reinterpret_cast<unsigned long long *> (mgDynLds);
+  unsigned long long *sKey = reinterpret_cast<unsigned long long *> (mgDynLds);      /* WORD8: the copy's words, and no sIdx */
   U32 *sIdx = reinterpret_cast<U32 *> (mgDynLds + (size_t) R * 8);
-  const U64 posMask = ((U64) 1 << f.ordBits) - 1;
+  const U64 posMask = ((U64) 1 << f.ordBits) - 1, remMask = ((U64) 1 << remB) - 1;
   U32 b = blockIdx.x * bucketsPerBlock, bEnd = b + bucketsPerBlock;
   if (bEnd > nBuckets) bEnd = nBuckets;
   for ( ; b < bEnd ; ++b)
@@ -1697,23 +1724,20 @@ void mgBucketFindKernel (const MgSlot *__restrict__ slots, const U32 *__restrict
       const bool any = occ[b] != 0;
       if (any)
         { for (U32 i = tid ; i < R ; i += T)
-            { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) b * R + i]);
-              sKey[i] = ((unsigned long long) v.y << 32) | v.x; sIdx[i] = mgIsAssigned (v.z) ? (v.z & ~MG_ASSIGNED) : 0;
-            }
+            if (WORD8) sKey[i] = __builtin_nontemporal_load (&find8[(U64) b * R + i]);
+            else
+              { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) b * R + i]);
+                sKey[i] = mgKeyOf (v); sIdx[i] = mgIndexOf (v.z);
+              }
           __syncthreads ();
         }
       for (U64 i = lo + tid ; i < hi ; i += T)
         { const U64 x = __builtin_nontemporal_load (&el[i]);
           U32 res = 0;
           if (any)
-            { const U64 m = ((U64) (b >> f.loB) << f.remBits) | (x >> f.ordBits), key = m + 1;
-              U32 slot = mgHomeOfM (m, g);
-              for (U32 probes = 0 ; probes < R ; ++probes)
-                { const unsigned long long cur = sKey[slot];
-                  if (cur == key) { res = sIdx[slot]; break; }
-                  if (cur == 0) break;
-                  slot = mgNextSlot (slot, g.R);
-                }
+            { const U64 m = ((U64) (b >> f.loB) << f.remBits) | (x >> f.ordBits);
+              res = WORD8 ? mgProbeFind (MgImageWords8 { sKey }, mgHomeOfM (m, g), R, (m & remMask) + 1)
+                          : mgProbeFind (MgImageSlots { sKey, sIdx }, mgHomeOfM (m, g), R, m + 1);
             }
           __builtin_nontemporal_store (((x & posMask) << 32) | res, &el[i]);
         }
@@ -1721,7 +1745,7 @@ void mgBucketFindKernel (const MgSlot *__restrict__ slots, const U32 *__restrict
     }
 }
 
-/* The same out of an 8-byte-per-slot copy of the table (round 6).  The two-level lookups STREAM the table once per batch -- 16 bytes a slot of which
+/* The 8-byte-per-slot copy of the table (round 6).  The two-level lookups STREAM the table once per batch -- 16 bytes a slot of which
  * a lookup needs the key and the index; a bucket implies the key's leading bits, so where 2k - log2 NB <= 32 both fit one word:
  * (key's bits below the bucket id + 1) << 31 | index (0: the key has none), 0 = empty.  The copy (MgTable.find8) is made by mgTablePack8Kernel when a lookup batch finds
  * it missing or older than the table (one streaming pass), and a batch then reads half the bytes: config 3's table 1.9 -> 0.95 GB per batch. */
@@ -1733,47 +1757,11 @@ void mgTablePack8Kernel (const MgSlot *__restrict__ slots, const U32 *__restrict
     { if (!occ[b]) continue;                                /* (never read: the lookups ask occ[] first) */
       for (U32 i = threadIdx.x ; i < R ; i += blockDim.x)
         { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) b * R + i]);
-          const U64 key = ((U64) v.y << 32) | v.x;
+          const U64 key = mgKeyOf (v);
           U64 w = 0;            /* a keyed slot without an index (an add that was refused left it) keeps its key and answers 0: the chain goes on, as in the 16-byte table */
-          if (key) w = ((((key - 1) & remMask) + 1) << 31) | (U64) (mgIsAssigned (v.z) ? (v.z & ~MG_ASSIGNED) : 0u);
+          if (key) w = ((((key - 1) & remMask) + 1) << 31) | (U64) mgIndexOf (v.z);
           __builtin_nontemporal_store (w, &out[(U64) b * R + i]);
         }
-    }
-}
-
-__global__ __launch_bounds__ (1024)
-void mgBucketFind8Kernel (const U64 *__restrict__ find8, const U32 *__restrict__ occ, MgGeom g, MgPartFmt f, U32 nBuckets, int remB,
-                          const U64 *__restrict__ bucketStart, U64 *__restrict__ el, U32 bucketsPerBlock)
-{
-  const U32 R = g.R, T = blockDim.x, tid = threadIdx.x;
-  unsigned long long *sW = reinterpret_cast<unsigned long long *> (mgDynLds);
-  const U64 posMask = ((U64) 1 << f.ordBits) - 1, remMask = ((U64) 1 << remB) - 1;
-  U32 b = blockIdx.x * bucketsPerBlock, bEnd = b + bucketsPerBlock;
-  if (bEnd > nBuckets) bEnd = nBuckets;
-  for ( ; b < bEnd ; ++b)
-    { const U64 lo = bucketStart[b], hi = bucketStart[b + 1];
-      if (hi == lo) continue;                                /* (uniform) */
-      const bool any = occ[b] != 0;
-      if (any)
-        { for (U32 i = tid ; i < R ; i += T) sW[i] = __builtin_nontemporal_load (&find8[(U64) b * R + i]);
-          __syncthreads ();
-        }
-      for (U64 i = lo + tid ; i < hi ; i += T)
-        { const U64 x = __builtin_nontemporal_load (&el[i]);
-          U32 res = 0;
-          if (any)
-            { const U64 m = ((U64) (b >> f.loB) << f.remBits) | (x >> f.ordBits), want = (m & remMask) + 1;
-              U32 slot = mgHomeOfM (m, g);
-              for (U32 probes = 0 ; probes < R ; ++probes)
-                { const unsigned long long cur = sW[slot];
-                  if ((cur >> 31) == want) { res = (U32) cur & 0x7fffffffu; break; }
-                  if (cur == 0) break;
-                  slot = mgNextSlot (slot, g.R);
-                }
-            }
-          __builtin_nontemporal_store (((x & posMask) << 32) | res, &el[i]);
-        }
-      __syncthreads ();                                      /* the image is loaded again for the next bucket */
     }
 }
 
@@ -1783,9 +1771,6 @@ __global__ __launch_bounds__ (1024)
 void mgUnpartPosKernel (const U64 *__restrict__ el, const unsigned long long *__restrict__ runTab, U32 nBins,
                         const U64 *__restrict__ segStart, const U32 *__restrict__ chunkBase, U32 nSeg, U32 chunkElems, U32 *__restrict__ idxOut)
 {
-  __shared__ U32 sTile[SUB];
-  __shared__ unsigned long long sRun[MG_PART_MAXBINS];
-  const U32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const U32 nChunks = chunkBase[nSeg];
   for (U32 w = blockIdx.x ; w < 2 * nChunks ; w += gridDim.x)
     { const U32 c = w >> 1, h = w & 1;
@@ -1793,20 +1778,8 @@ void mgUnpartPosKernel (const U64 *__restrict__ el, const unsigned long long *__
       if (!mgChunkRange (segStart, chunkBase, nSeg, chunkElems, c, &seg, &lo, &hi)) continue;
       const U64 sub = lo + (U64) h * SUB;
       if (sub >= hi) continue;                               /* (uniform) */
-      const U32 cnt = (U32) (sub + SUB < hi ? SUB : hi - sub);
-      for (U32 b = tid ; b < nBins ; b += 1024) sRun[b] = runTab[(U64) w * nBins + b];
-      __syncthreads ();
-      for (U32 b = wave ; b < nBins ; b += 16)
-        { const unsigned long long r = sRun[b];
-          const U64 base = r & (((U64) 1 << 40) - 1); const U32 len = (U32) (r >> 40);
-          for (U32 i = lane ; i < len ; i += 64)
-            { const U64 v = __builtin_nontemporal_load (&el[base + i]);
-              sTile[(U32) ((v >> 32) - sub)] = (U32) v;
-            }
-        }
-      __syncthreads ();
-      for (U32 i = tid ; i < cnt ; i += 1024) idxOut[sub + i] = sTile[i];
-      __syncthreads ();
+      const auto dec = [=] (U64 at, U32 *pos, U32 *val) { const U64 v = __builtin_nontemporal_load (&el[at]); *pos = (U32) ((v >> 32) - sub); *val = (U32) v; };
+      mgPullTile<SUB, false> (runTab + (U64) w * nBins, nBins, dec, (U32) (sub + SUB < hi ? SUB : hi - sub), idxOut + sub);
     }
 }
 
@@ -1816,24 +1789,11 @@ __global__ __launch_bounds__ (1024)
 void mgUnpartOrdKernel (const U64 *__restrict__ el, const U32 *__restrict__ idx, int ordBits, const unsigned long long *__restrict__ runTab, U32 nBins, U64 n,
                         U32 *__restrict__ out)
 {
-  __shared__ U32 sTile[SUB];
-  __shared__ unsigned long long sRun[MG_PART_MAXBINS];
-  const U32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const U64 nSub = (n + SUB - 1) / SUB, ordMask = ((U64) 1 << ordBits) - 1;
   for (U64 s = blockIdx.x ; s < nSub ; s += gridDim.x)
     { const U64 o0 = s * SUB;
-      const U32 cnt = (U32) (o0 + SUB < n ? SUB : n - o0);
-      for (U32 b = tid ; b < nBins ; b += 1024) sRun[b] = runTab[s * nBins + b];
-      __syncthreads ();
-      for (U32 b = wave ; b < nBins ; b += 16)
-        { const unsigned long long r = sRun[b];
-          const U64 base = r & (((U64) 1 << 40) - 1); const U32 len = (U32) (r >> 40);
-          for (U32 i = lane ; i < len ; i += 64)
-            sTile[(U32) ((__builtin_nontemporal_load (&el[base + i]) & ordMask) - o0)] = __builtin_nontemporal_load (&idx[base + i]);
-        }
-      __syncthreads ();
-      for (U32 i = tid ; i < cnt ; i += 1024) __builtin_nontemporal_store (sTile[i], &out[o0 + i]);
-      __syncthreads ();
+      const auto dec = [=] (U64 at, U32 *pos, U32 *val) { *pos = (U32) ((__builtin_nontemporal_load (&el[at]) & ordMask) - o0); *val = __builtin_nontemporal_load (&idx[at]); };
+      mgPullTile<SUB, true> (runTab + s * nBins, nBins, dec, (U32) (o0 + SUB < n ? SUB : n - o0), out + o0);
     }
 }
 
@@ -1846,625 +1806,32 @@ static inline size_t mgAl (size_t n) { return (n + 255) & ~(size_t) 255; }
 static inline int mgLog2 (U64 x) { int l = 0; while (((U64) 1 << l) < x) ++l; return l; }
 static inline MgGeom mgGeomOf (const MgTable *t) { MgGeom g; g.R = t->R; g.log2NB = t->log2NB; g.kbits = t->kbits; return g; }
 
-#define MG_RANK_UNITS 8192           /* waves that share the ordered flag count */
-static inline U64 mgRankRowsPerUnit (U64 n, U32 *nBlocks)
+/* the element format of the partition passes for a batch of n whose first pass sorts by the top hiB bits of the bucket id, and whether
+   an element then fits one packed 8-byte word: the mixed k-mer without its coarse digit and the ordinal in 64 bits */
+static inline MgPartFmt mgPartFmtOf (const MgTable *t, U64 n, int hiB)
+{ MgPartFmt f; f.ordBits = mgLog2 (n) > 1 ? mgLog2 (n) : 1; f.remBits = t->kbits - hiB; f.loB = t->log2NB - hiB; return f; }
+static inline bool mgPartFmtFits (const MgTable *t, const MgPartFmt &f) { return t->kbits >= t->log2NB + 4 && f.remBits + f.ordBits <= 64; }
+/* threads of a workgroup of the bucket kernels: by the bucket's size (knobOrZero != 0: MODGPU_BUCKET_T instead), and enough of them for
+   the dedup kernel's closing sweep, MG_DEDUP_PER slots a thread */
+static inline unsigned mgBucketThreads (U32 R, int knobOrZero)
 {
-  U64 nRows = (n + 63) / 64;
-  U64 per = (nRows + MG_RANK_UNITS - 1) / MG_RANK_UNITS; if (!per) per = 1;
-  U64 units = (nRows + per - 1) / per; if (!units) units = 1;
-  *nBlocks = (U32) ((units + 3) / 4);
-  return per;
+  unsigned thr = knobOrZero ? (unsigned) knobOrZero : (R >= 4096 ? 1024u : (R >= 2048 ? 512u : 256u));
+  while (thr < 1024 && (U64) thr * MG_DEDUP_PER < R) thr *= 2;
+  return thr;
 }
-
-/* the split of oversize buckets: occurrences above which a bucket is split, occurrences of a chunk at least */
-static void mgHotKnobs (U32 *split, U32 *chunk)
+/* the grid of a kernel whose workgroups take *perBlock consecutive buckets each: 4096 workgroups at most */
+static inline unsigned mgBucketGrid (U64 NB, U32 *perBlock)
 {
-  const MgKnobs *k = mgKnobs ();                             /* test knob "split,chunk": small values send ordinary buckets through the split path */
-  U32 a = MG_HOT_SPLIT_DEFAULT, b = MG_HOT_CHUNK_DEFAULT;
-  if (k->hotSplit != MG_KNOB_UNSET && k->hotSplit > 0)
-    { a = (U32) k->hotSplit; b = k->hotChunk != MG_KNOB_UNSET && k->hotChunk > 0 ? (U32) k->hotChunk : a / 4; }
-  if (b < 64) b = 64;
-  if (a < b) a = b;
-  *split = a; *chunk = b;
+  const unsigned grid = (unsigned) (NB < 4096 ? NB : 4096);
+  *perBlock = (U32) ((NB + grid - 1) / grid);
+  return (unsigned) ((NB + *perBlock - 1) / *perBlock);
 }
-static U64 mgHotItemsCap (U64 n) { U32 sp, ch; mgHotKnobs (&sp, &ch); return n / ch + n / sp + 16; }
+/* f (SUB as a std::integral_constant) for the sub-chunk size `sub` a partition pass ran with: its kernels and the pulls take it as a template parameter */
+template <class F> static inline void mgForSub (U32 sub, F f)
+{ if (sub == MG_PART_SUB_BIG) f (std::integral_constant<int, MG_PART_SUB_BIG> ()); else f (std::integral_constant<int, MG_PART_SUB> ()); }
 
-/* scratch needed by mgTableAdd for a batch of n */
-size_t mgTableAddScratchBytes (const MgTable *t, U64 n)
-{
-  (void) t;
-  U64 NB = (U64) 1 << 18;               /* the largest bucket count: the table may grow between passes of one call */
-  size_t rank = mgAl (n) /*flags*/ + 2 * mgAl ((MG_RANK_UNITS + 8) * 8) + mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
-  size_t direct = mgAl (n * 4);
-  size_t part = 2 * (mgAl (n * 8) + mgAl (n * 4)) + mgAl (n * 4)
-              + mgAl ((NB + 2) * 8) * 3 + mgAl ((NB + 2) * 4) * 2 + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 3 + 2 * mgAl ((U64) MG_PART_MAXBINS * 16 * 8 + 4096)
-              + mgAl ((MG_PART_MAXBINS + 2) * 4) + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4)
-              + mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short)) + mgAl ((n / MG_PART_SUB + 2) * 24)
-              + mgAl (mgHotItemsCap (n) * 8) + mgAl (mgHotItemsCap (n) * 4) + 256;
-  return rank + (direct > part ? direct : part) + 4096;
-}
-
-static int mgPathOverride (void)
-{
-  const long c = mgKnobs ()->tablePath;                       /* test knob: the first letter of "direct" / "bucket" */
-  return c == 'd' ? 1 : (c == 'b' ? 2 : 0);
-}
-
-bool mgTableUseBuckets (const MgTable *t, U64 n);
-/* can mgTableAdd read this batch from the scan's segments?  Only the bucketed path does, and its first pass then
-   needs the digit counts the scan made for exactly this table geometry */
-bool mgTableAddTakesSegments (const MgTable *t, U64 n, const MgHistReq *counted)
-{
-  const int off = mgKnobs ()->noSegmentInput == 1;   /* test knob: always compact first */
-  return !off && n && mgTableUseBuckets (t, n) && counted && counted->binCount && counted->log2NB == t->log2NB && counted->kbits == t->kbits && !counted->hiB;
-}
-
-bool mgTableUseBuckets (const MgTable *t, U64 n)
-{
-  int ov = mgPathOverride ();
-  if (ov == 1) return false;
-  if (ov == 2) return true;
-  /* a batch of a million or so: the bucketed path's dozen launches and its per-bucket lists cost 0.43 ms whatever the size, the atomics
-     0.1 ms + 0.19 ms per million (tools/size_sweep_probe.py: 0.78 M modimizers 0.30 against 0.43 ms, 3.1 M 0.68 against 0.45) */
-  if (n < 1500000) return false;
-  return n >= t->nSlots / 16;           /* streaming every touched bucket twice beats ~100 ps/modimizer of atomics */
-}
-
-/* one partition pass: nSeg segments of kIn -> nBins bins each.  inMode: what kIn holds (MG_EL_*); packed: the format
- * of the output (and, after the first pass, of the input) */
-static MgStatus mgPartPass (const MgTable *t, int inMode, bool packed, const MgPartFmt &f, const U64 *kIn, const U32 *tIn, U64 n,
-                            const U64 *segStart, U32 nSeg, int shift, U32 nBins,
-                            U64 *kOut, U32 *tOut, U64 *binStart, unsigned long long *cursor, U32 *binCount, U32 *chunkBase,
-                            hipStream_t st, const U32 *counted = 0, const MgSegSrc *segSrc = 0, MgSubSeg *subSeg = 0,
-                            unsigned long long *runTab = 0, U32 *subElems = 0, int runMode = 0, U32 *maxChunksOut = 0,
-                            unsigned char *digitOut = 0, int nextShift = 0, U32 nextBins = 0, const unsigned char *digitIn = 0)
-{
-  /* digitOut: this pass also writes the NEXT pass's digit (bits [nextShift, ..) of the bucket id, nextBins <= 256 of them) of every element
-     beside it; digitIn: this pass counts its digits from such bytes */
-  MgGeom g = mgGeomOf (t);
-  MgSegSrc src; src.segKmer = 0; src.segCount = 0; src.segStart = 0; src.segCap = 0; src.nSegs = 0;
-  if (inMode == MG_EL_SEG)
-    { if (!segSrc || !subSeg || !counted) { mgSetError ("internal: segment input needs its counts"); return MG_ERR_ARG; }
-      src = *segSrc;
-      const U64 nSub = (n + MG_PART_SUB - 1) / MG_PART_SUB;
-      MG_LAUNCH (MG_K_PART, st, mgSubSegKernel, dim3 ((unsigned) ((nSub + 255) / 256)), dim3 (256), 0, st, src, n, (U32) MG_PART_SUB, subSeg);
-    }
-  if (counted) MG_HIP (hipMemcpy2DAsync (binCount, sizeof (U32), counted, MG_HIST_STRIDE * sizeof (U32), sizeof (U32), nBins, hipMemcpyDeviceToDevice, st));   /* the scan counted them */
-  else MG_HIP (hipMemsetAsync (binCount, 0, (size_t) nSeg * nBins * sizeof (U32), st));
-  /* large sub-chunks where the kernel has them: packed elements, at most 256 bins */
-  const int bigEnv = mgKnobs ()->partBig == MG_KNOB_UNSET ? 1 : (int) mgKnobs ()->partBig;      /* test knob: 0 = sub-chunks of MG_PART_SUB everywhere */
-  const bool big = bigEnv && packed && nBins <= MG_PART_BIG_BINS && MG_PART_THREADS == 1024;
-  const U32 chunkElems = 2u * (U32) (big ? MG_PART_SUB_BIG : MG_PART_SUB);
-  if (subElems) *subElems = (U32) (big ? MG_PART_SUB_BIG : MG_PART_SUB);
-  MG_LAUNCH (MG_K_PART, st, mgPartChunksKernel, dim3 (1), dim3 (MG_PART_MAXBINS), 0, st, segStart, nSeg, chunkElems, chunkBase);
-  unsigned maxChunks = (unsigned) (n / chunkElems + nSeg + 1);
-  if (maxChunksOut) *maxChunksOut = maxChunks;
-  const int sgEnv = mgKnobs ()->scatterGrid == MG_KNOB_UNSET ? 0 : (int) mgKnobs ()->scatterGrid;   /* dev knob */
-  unsigned scatterGrid = maxChunks < (unsigned) (sgEnv > 0 ? sgEnv : 1024) ? maxChunks : (unsigned) (sgEnv > 0 ? sgEnv : 1024);
-  const dim3 hg (maxChunks < 4096 ? maxChunks : 4096), sg (scatterGrid);
-  if (!counted && digitIn)
-    MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistBytesKernel, hg, dim3 (256), 0, st, digitIn, nBins, segStart, chunkBase, nSeg, chunkElems, binCount);
-  else if (!counted)
-    { if (inMode == MG_EL_DENSE)
-        MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistKernel<MG_EL_DENSE>, hg, dim3 (256), 0, st, kIn, g, f, shift, nBins, segStart, chunkBase, nSeg, chunkElems, binCount);
-      else if (inMode == MG_EL_WIDE)
-        MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistKernel<MG_EL_WIDE>, hg, dim3 (256), 0, st, kIn, g, f, shift, nBins, segStart, chunkBase, nSeg, chunkElems, binCount);
-      else
-        MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistKernel<MG_EL_PACKED>, hg, dim3 (256), 0, st, kIn, g, f, shift, nBins, segStart, chunkBase, nSeg, chunkElems, binCount);
-    }
-  /* one segment (the first pass): every workgroup reserves in the same few hundred cursors -- one cache line each
-     (scatter 0.88 -> 0.73 ms: returning atomics on cursors that share a line queue behind each other) */
-  const U32 cstride = nSeg == 1 ? 16u : 1u;                  /* (the second pass's 65536 cursors: no gain from padding) */
-  MG_LAUNCH (MG_K_PART, st, mgPartScanKernel, dim3 (nSeg), dim3 (MG_PART_MAXBINS), 0, st, binCount, nBins, segStart, binStart, cursor, cstride, nSeg, n);
-#define MG_SCATTER(IN, PK, SUB) MG_LAUNCH (MG_K_PART_SCATTER, st, (mgPartScatterKernel<IN, PK, SUB>), sg, dim3 (MG_PART_THREADS), 0, st, \
-                                           kIn, tIn, src, subSeg, g, f, shift, nBins, segStart, chunkBase, nSeg, chunkElems, cursor, cstride, kOut, tOut, runTab, runMode, \
-                                           digitOut, nextShift, nextBins ? nextBins - 1 : 0u)
-#define MG_SCATTER_P(IN) do { if (big) MG_SCATTER (IN, true, MG_PART_SUB_BIG); else MG_SCATTER (IN, true, MG_PART_SUB); } while (0)
-  if (inMode == MG_EL_DENSE) { if (packed) MG_SCATTER_P (MG_EL_DENSE); else MG_SCATTER (MG_EL_DENSE, false, MG_PART_SUB); }
-  else if (inMode == MG_EL_SEG) { if (packed) MG_SCATTER_P (MG_EL_SEG); else MG_SCATTER (MG_EL_SEG, false, MG_PART_SUB); }
-  else if (inMode == MG_EL_WIDE) MG_SCATTER (MG_EL_WIDE, false, MG_PART_SUB);
-  else MG_SCATTER_P (MG_EL_PACKED);
-#undef MG_SCATTER_P
-#undef MG_SCATTER
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-/* the dedup kernel's per-bucket counts of distinct k-mers: out[0] = their sum, out[1] = the largest (out[] zeroed by the launcher) */
-__global__ __launch_bounds__ (256)
-void mgUniqStatsKernel (const U32 *__restrict__ uniqCount, U32 nBuckets, unsigned long long *__restrict__ out)
-{
-  unsigned long long sum = 0; U32 mx = 0;
-  for (U32 b = blockIdx.x * 256 + threadIdx.x ; b < nBuckets ; b += gridDim.x * 256) { const U32 c = uniqCount[b]; sum += c; mx = c > mx ? c : mx; }
-  for (int off = 32 ; off ; off >>= 1)
-    { sum += ((unsigned long long) (U32) __shfl_xor ((int) (U32) (sum >> 32), off) << 32) | (U32) __shfl_xor ((int) (U32) sum, off);
-      const U32 o = (U32) __shfl_xor ((int) mx, off); mx = o > mx ? o : mx;
-    }
-  if ((threadIdx.x & 63) == 0) { if (sum) atomicAdd (&out[0], sum); if (mx) atomicMax (&out[1], (unsigned long long) mx); }
-}
-
-#define MG_TIGHT_PCT_DEFAULT 70      /* see MgTable.tightPct.  80 is 0.06 ms a step faster still on config 2 (DESIGN_EXPERIMENTS.md section L); 70 is what the full-size
-                                        parity cases (tests/fullsize_whole.py) force as their other geometry, and they expect the default to be no tighter */
-#define MG_TIGHT_PCT_CLAIMS 50       /* the same with MODGPU_MERGE_PLACE=0: the merge kernel's claims pay for the load */
-#define MG_TIGHT_MIN_R 1024u         /* a bucket keeps room for the spread of a later add's share around its mean (mgTableEnsure sizes by the mean) */
-
-/* insert a batch (ordinal order = array order); counters[0] = number of new entries afterwards */
-MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *scratch, hipStream_t st,
-                     const MgHistReq *counted, const MgSegSrc *segSrc)
-{
-  if (!n) return MG_OK;
-  if (segSrc && !mgTableAddTakesSegments (t, n, counted)) { mgSetError ("internal: this insert needs the dense k-mers"); return MG_ERR_ARG; }
-  MgSegSrc noSrc; noSrc.segKmer = 0; noSrc.segCount = 0; noSrc.segStart = 0; noSrc.segCap = 0; noSrc.nSegs = 0;
-  t->liveHistValid = false;                          /* set again below if this add is the set's only one */
-  if (withDepth) t->pendingDepth = true;
-  const bool wasEmpty = t->empty && t->max == 0;
-  t->empty = false; ++t->version;
-  MgGeom g = mgGeomOf (t);
-  char *wb = (char *) scratch;
-  unsigned char *flags = (unsigned char *) wb;       wb += mgAl (n);
-  U64 *blockCount = (U64 *) wb;                      wb += mgAl ((MG_RANK_UNITS + 8) * 8);
-  U64 *blockBase = (U64 *) wb;                       wb += mgAl ((MG_RANK_UNITS + 8) * 8);
-  MgRankGrp *grp = (MgRankGrp *) wb;                 wb += mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
-  U32 nRankBlocks; U64 rankTiles = mgRankRowsPerUnit (n, &nRankBlocks);
-  MG_HIP (hipMemsetAsync (blockCount, 0, (MG_RANK_UNITS + 8) * 8, st));
-
-  if (!mgTableUseBuckets (t, n))
-    { U32 *slotId = (U32 *) wb;
-      { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-      MG_LAUNCH (MG_K_TABLE_INSERT, st, mgTableInsertKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, g, dKmer, n, slotId, withDepth, t->counters);
-      MG_LAUNCH (MG_K_TABLE_FLAG, st, mgDirectFlagKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, slotId, n, flags);
-      MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
-      MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
-      MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<true, false>), dim3 (nRankBlocks), dim3 (256), 0, st,
-                 flags, dKmer, noSrc, (const MgSubSeg *) 0, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, slotId, grp);
-      MG_HIP (hipGetLastError ());
-      /* occ[] is kept exact only by the bucketed path and the loader; the direct path marks buckets non-empty */
-      return mgTableMarkOccupied (t, dKmer, n, st);
-    }
-
-  /* ---- bucketed ---- */
-  const U64 NB = (U64) 1 << t->log2NB;
-  U64 *kA = (U64 *) wb;  wb += mgAl (n * 8);
-  U32 *tA = (U32 *) wb;  wb += mgAl (n * 4);
-  U64 *kB = (U64 *) wb;  wb += mgAl (n * 8);
-  U32 *tB = (U32 *) wb;  wb += mgAl (n * 4);
-  U32 *cB = (U32 *) wb;  wb += mgAl (n * 4);
-  U64 *fineStart = (U64 *) wb;                wb += mgAl ((NB + 2) * 8);
-  unsigned long long *fineCursor = (unsigned long long *) wb; wb += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
-  U64 *spare64 = (U64 *) wb;                  wb += mgAl ((NB + 2) * 8);
-  U32 *fineCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
-  U32 *uniqCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
-  U64 *coarseStart = (U64 *) wb;              wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  unsigned long long *coarseCursor = (unsigned long long *) wb; wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
-  U64 *whole = (U64 *) wb;                    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  U32 *coarseCount = (U32 *) wb;              wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
-  U32 *chunkBase = (U32 *) wb;                wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);   /* + the segment of every chunk */
-  unsigned short *sliceOff = (unsigned short *) wb;   wb += mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short));
-  MgSubSeg *subSeg = (MgSubSeg *) wb;         wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
-  U64 *hotItems = (U64 *) wb;                 wb += mgAl (mgHotItemsCap (n) * 8);
-  U32 *hotBuckets = (U32 *) wb;               wb += mgAl (mgHotItemsCap (n) * 4);
-  unsigned long long *hotCount = (unsigned long long *) wb; wb += 256;
-  (void) spare64;
-
-  /* split the bucket-id bits into a coarse digit (high) and a fine digit (low), each <= 9 bits */
-  const int j = t->log2NB;
-  int hiB, loB;
-  mgPartSplit (j, &hiB, &loB);
-  const U32 *pre = (counted && counted->binCount && counted->log2NB == j && counted->kbits == t->kbits && !counted->hiB) ? counted->binCount : 0;
-  U64 segInit[2] = { 0, n };
-  MG_HIP (hipMemcpyAsync (whole, segInit, 16, hipMemcpyHostToDevice, st));
-  /* element format: one packed 8-byte word when the mixed k-mer without its coarse digit and the ordinal fit in 64 bits */
-  MgPartFmt f;
-  f.ordBits = mgLog2 (n) > 1 ? mgLog2 (n) : 1; f.remBits = t->kbits - hiB; f.loB = loB;
-  const int packEnv = mgKnobs ()->partPacked == MG_KNOB_UNSET ? 1 : (int) mgKnobs ()->partPacked;   /* test knob: 0 forces the wide format */
-  const bool packed = packEnv && t->kbits >= j + 4 && f.remBits + f.ordBits <= 64;
-  MgStatus s;
-  const U64 *bucketStart = fineStart;
-  const int firstMode = segSrc ? MG_EL_SEG : MG_EL_DENSE;
-  if (!loB)
-    { if ((s = mgPartPass (t, firstMode, packed, f, dKmer, 0, n, whole, 1, 0, (U32) 1 << hiB, kB, tB, fineStart, fineCursor, fineCount, chunkBase, st, pre, segSrc, subSeg))) return s; }
-  else
-    { /* the first pass leaves every element's fine digit in a byte beside it (in cB, which the dedup kernel only writes later): the second
-         pass counts 156 MB of bytes instead of reading 1.25 GB of elements twice */
-      unsigned char *digits = (loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> (cB) : 0;
-      if ((s = mgPartPass (t, firstMode, packed, f, dKmer, 0, n, whole, 1, loB, (U32) 1 << hiB, kA, tA, coarseStart, coarseCursor, coarseCount, chunkBase, st, pre, segSrc, subSeg,
-                           0, 0, 0, 0, digits, 0, (U32) 1 << loB))) return s;
-      if ((s = mgPartPass (t, packed ? MG_EL_PACKED : MG_EL_WIDE, packed, f, kA, tA, n, coarseStart, (U32) 1 << hiB, 0, (U32) 1 << loB, kB, tB, fineStart, fineCursor, fineCount, chunkBase, st,
-                           0, 0, 0, 0, 0, 0, 0, 0, 0, 0, digits))) return s;
-    }
-
-  MgBucketArgs a;
-  /* flag polarity from what the previous bucketed add saw (MgTable.newPct: new entries per 100 modimizers) */
-  { const int polEnv = mgKnobs ()->flagPolarity == MG_KNOB_UNSET ? -1 : (int) mgKnobs ()->flagPolarity;   /* test knob: 0 / 1 force it */
-    a.markDup = polEnv >= 0 ? (polEnv ? 1 : 0) : (t->newPct > 50 ? 1 : 0);
-  }
-  MG_HIP (hipMemsetAsync (flags, a.markDup ? 1 : 0, n, st));
-  /* the merge kernel takes the slots from the dedup kernel when the buckets will be more than half full (there its
-     probing costs more than the dedup kernel's extra work: a 12.5 Gbp block at load 0.62 gains 0.4 ms, config 2 at 0.38
-     nothing); the load is estimated from the share of new k-mers the previous add saw */
-  { const int slotEnv = mgKnobs ()->mergeSlots == MG_KNOB_UNSET ? -1 : (int) mgKnobs ()->mergeSlots;   /* test knob: 0 / 1 force it */
-    const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
-    const bool dense = ((U64) t->max + expectNew) * 2 > t->nSlots;
-    a.slotShift = (t->kbits <= MG_SLOT_SHIFT && (slotEnv >= 0 ? slotEnv != 0 : dense)) ? MG_SLOT_SHIFT : 0;
-  }
-  /* An add into an EMPTY table (a set built from one batch: every step of the benchmarks, the first file of a run) does not know its
-     entries until the dedup kernel has counted them -- the table was sized from the batch's occurrences, an upper bound -- and nothing is
-     in the table yet, so its geometry is still free: after the dedup kernel R can be brought down to what the entries need at the tight
-     load, and the merge kernel streams back that much less.  The price: the dedup kernel's image is then not the merge kernel's, so no
-     slots are carried over and the merge kernel claims its own -- and a workgroup waits for its LONGEST probe chain (8 links at load 0.38,
-     30 at 0.6, 80 at 0.75; profiles/r06_ab_table_geometry.txt: the merge kernel 1.07 / 1.20 / 1.44 / 2.5 ms at tight loads 50 / 60 / 70 / 80
-     per cent on config 2, against 0.65 ms with carried slots at load 0.77).  So the table is only tightened where that pays: when the share
-     of new k-mers the previous add saw (newPct; unknown: all new) says the entries will leave a quarter of the slots and more unused even at
-     the tight load -- reads of deep coverage with few errors (config 5: a sixth of the modimizers are new; 4.3 -> 1.07 GB of bucket images). */
-  int tightPct = t->tightPct ? t->tightPct : MG_TIGHT_PCT_CLAIMS;      /* (MG_TIGHT_PCT_DEFAULT below, where the merge kernel places by scan) */
-  { const long tk = mgKnobs ()->tightLoad; if (tk != MG_KNOB_UNSET && tk >= 0 && tk <= 95) tightPct = (int) tk; }
-  bool tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
-  if (tighten && mgKnobs ()->tightLoad == MG_KNOB_UNSET)          /* (the knob forces it: tests, sweeps) */
-    { const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
-      tighten = expectNew * 100 / (U64) tightPct < t->nSlots - t->nSlots / 4;
-    }
-  /* a bucket that is empty before the add is laid out by prefix scan in the merge kernel (mgPlaceStarts): no probe whatever the load,
-     so an add into an empty table has no use for the dedup kernel's slots, and the tightening costs the merge kernel nothing: it is
-     done whenever the table was empty and the scan is on (DESIGN_EXPERIMENTS.md section L).  Only lists without carried slots go
-     through the scan (the kernel checks a.slotShift): a later add that carries slots puts an empty bucket's entries where they say. */
-  { const long pk = mgKnobs ()->mergePlace;                        /* MODGPU_MERGE_PLACE: 0 = claims everywhere, 1 = the scan for every fresh bucket, unset = the rule below */
-    a.place = pk == MG_KNOB_UNSET ? 1 : (pk != 0);
-    /* Left to itself the placement is for lists the kernel's spill-free instance takes whole (the uniques fetched ahead: MG_MERGE_PREFETCH
-       per thread).  Where the buckets' lists will be longer -- a config-4 block: 2500 uniques per bucket and 1024 threads -- the add goes
-       as before (carried slots; 11.06 ms a step against 11.16-11.44 with the scan's larger instance and the table at load 0.8).
-       The lists' length is estimated from the share of new k-mers the previous add saw; the FIRST add a table ever sees has none to go by,
-       is taken as all new (n / NB = 0.75 R uniques per bucket: over the limit at every default geometry) and so goes as before too: the
-       scan and the tightening start with the second set a process builds from empty, which is every timed step of the benchmarks but not
-       the first file of a run.  Which instance fits is known exactly only after the dedup kernel -- too late for the choice between
-       the scan and carried slots, which the dedup kernel's own instance depends on. */
-    if (pk == MG_KNOB_UNSET)
-      { const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
-        unsigned thr = t->R >= 4096 ? 1024u : (t->R >= 2048 ? 512u : 256u);
-        while (thr < 1024 && (U64) thr * MG_DEDUP_PER < t->R) thr *= 2;
-        if (expectNew / NB * 115 / 100 > (U64) MG_MERGE_PREFETCH * thr) a.place = 0;
-      }
-    if (a.place && wasEmpty) a.slotShift = 0;
-    if (a.place && mgKnobs ()->tightLoad == MG_KNOB_UNSET)
-      { if (!t->tightPct) tightPct = MG_TIGHT_PCT_DEFAULT;
-        tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
-      }
-  }
-  if (tighten) a.slotShift = 0;
-  a.slots = t->slots; a.g = g; a.nBuckets = (U32) NB; a.bucketStart = bucketStart;
-  a.pK = kB; a.pT = tB; a.pC = cB; a.uniqCount = uniqCount; a.occ = t->occ; a.flags = flags;
-  a.grp = grp; a.baseMax = t->max; a.size = t->size; a.withDepth = withDepth;
-  /* slices of the ordinal range for the rank lookups: 2^sliceShift ordinals each (2^22: 1 MiB of rank records, and a
-     bucket's share of a slice is usually shorter than a wave), at most MG_RANK_GROUPS - 1 of them */
-  { a.sliceShift = 22;
-    /* a batch much smaller than the headline's would be three or four slices -- and the lookup kernel gives a slice to an XCD, so half
-       the chip would idle (1 Gbp batches, as the file entry points make them: the rank lookups 0.31 ms of 1.39, with 2^18-ordinal slices
-       0.11 of 1.11): smaller slices until there are 32 of them */
-    while (a.sliceShift > 16 && ((n - 1) >> a.sliceShift) + 1 < 32) --a.sliceShift;
-    if (mgKnobs ()->rankSliceShift != MG_KNOB_UNSET) a.sliceShift = (int) mgKnobs ()->rankSliceShift;   /* dev knob */
-    while (((n - 1) >> a.sliceShift) + 1 > (U64) (MG_RANK_GROUPS - 1)) ++a.sliceShift;
-    a.nSlices = (U32) (((n - 1) >> a.sliceShift) + 1);
-    a.sliceOff = sliceOff;
-  }
-  a.counters = t->counters; a.f = f;
-#ifdef MG_ABLATE
-  { const long dbg = mgKnobs ()->bucketDebug; a.debug = dbg != MG_KNOB_UNSET ? (int) dbg : 0; }
-#endif
-  /* depth histogram on the fly: possible when this add builds the whole set (empty before, no host depths) */
-  const bool track = t->max == 0 && t->baseZero;
-  a.liveHist = 0;
-  if (track)
-    { if (!t->liveHist) MG_HIP (hipMalloc ((void **) &t->liveHist, 65536 * sizeof (U64)));
-      MG_HIP (hipMemsetAsync (t->liveHist, 0, 65536 * sizeof (U64), st));
-      a.liveHist = (unsigned long long *) t->liveHist;
-    }
-  t->liveHistValid = track;
-  size_t lds = mgMergeLdsBytes (t->R);
-  { const size_t ldsDedup = (size_t) t->R * 16 + MG_RANK_GROUPS * 4; if (ldsDedup > lds) lds = ldsDedup; }
-  const bool bigR = t->R > MG_DEDUP_PER * 1024u;       /* R = 8192: the dedup kernel's threads take eight slots each */
-  if (t->R > MG_DEDUP_PER_BIG * 1024u) { mgSetError ("internal: bucket of %u slots", t->R); return MG_ERR_ARG; }
-  if (lds > 48 * 1024)
-    {
-#define MG_DEDUP_ATTR(PK, SL, PER) do { MG_HIP (hipFuncSetAttribute ((const void *) mgBucketDedupKernel<PK, SL, PER, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-                                        MG_HIP (hipFuncSetAttribute ((const void *) mgBucketDedupKernel<PK, SL, PER, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); } while (0)
-      if (bigR) { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER_BIG); }
-      else      { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER); }
-#undef MG_DEDUP_ATTR
-      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_MERGE_PREFETCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_PLACE_KEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-  const int bThreadsEnv = mgKnobs ()->bucketT == MG_KNOB_UNSET ? 0 : (int) mgKnobs ()->bucketT;
-  unsigned bThreads = bThreadsEnv ? (unsigned) bThreadsEnv : (t->R >= 4096 ? 1024u : (t->R >= 2048 ? 512u : 256u));
-  while (bThreads < 1024 && (U64) bThreads * MG_DEDUP_PER < t->R) bThreads *= 2;
-  unsigned bGrid = (unsigned) (NB < 4096 ? NB : 4096);
-  U32 perBlock = (U32) ((NB + bGrid - 1) / bGrid);
-  bGrid = (unsigned) ((NB + perBlock - 1) / perBlock);
-  if ((U64) bThreads * (bigR ? MG_DEDUP_PER_BIG : MG_DEDUP_PER) < t->R)      /* every slot of the image must belong to a thread of the closing sweep */
-    { mgSetError ("internal: %u threads for a bucket of %u slots", bThreads, t->R); return MG_ERR_ARG; }
-  /* oversize buckets first: their chunks reduced to weighted entries by a workgroup each (nothing to do on ordinary data:
-     the plan finds no bucket and the reduce kernel's workgroups leave at once) */
-  mgHotKnobs (&a.hotSplit, &a.hotChunk);
-  a.hotItems = hotItems; a.hotCount = hotCount; a.hotBuckets = hotBuckets;
-  MG_HIP (hipMemsetAsync (hotCount, 0, 16, st));
-  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotPlanKernel, dim3 ((unsigned) ((NB + 255) / 256)), dim3 (256), 0, st, a);
-  { const size_t ldsHot = (size_t) t->R * 16 + 16;
-    if (packed) { if (ldsHot > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgHotReduceKernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsHot));
-                  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotReduceKernel<true>, dim3 (1024), dim3 (bThreads), ldsHot, st, a); }
-    else        { if (ldsHot > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgHotReduceKernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsHot));
-                  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotReduceKernel<false>, dim3 (1024), dim3 (bThreads), ldsHot, st, a); }
-  }
-#define MG_DEDUP_LAUNCH(PK, SL, PER) do { MG_LAUNCH (MG_K_BUCKET_DEDUP, st, (mgBucketDedupKernel<PK, SL, PER, false>), dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock); \
-                                          MG_LAUNCH (MG_K_HOT_REDUCE, st, (mgBucketDedupKernel<PK, SL, PER, true>), dim3 (64), dim3 (bThreads), lds, st, a, perBlock); } while (0)
-#define MG_DEDUP_PICK(PER) do { if (packed) { if (a.slotShift) MG_DEDUP_LAUNCH (true, true, PER); else MG_DEDUP_LAUNCH (true, false, PER); } \
-                                else        { if (a.slotShift) MG_DEDUP_LAUNCH (false, true, PER); else MG_DEDUP_LAUNCH (false, false, PER); } } while (0)
-  if (bigR) MG_DEDUP_PICK (MG_DEDUP_PER_BIG); else MG_DEDUP_PICK (MG_DEDUP_PER);
-#undef MG_DEDUP_PICK
-#undef MG_DEDUP_LAUNCH
-  U64 fullest = t->R;                                  /* the longest list a bucket may have: not known unless the tightening counts it */
-  if (tighten)
-    { unsigned long long *st2 = (unsigned long long *) (t->counters + 2);
-      MG_HIP (hipMemsetAsync (st2, 0, 16, st));
-      MG_LAUNCH (MG_K_RANK_SCAN, st, mgUniqStatsKernel, dim3 ((unsigned) (NB / 256 < 256 ? (NB + 255) / 256 : 256)), dim3 (256), 0, st, uniqCount, (U32) NB, st2);
-      MG_HIP (hipMemcpyAsync (t->pin, t->counters + 1, 24, hipMemcpyDeviceToHost, st));      /* overflow flag, entries, the fullest bucket's */
-      MG_HIP (hipStreamSynchronize (st));
-      const U64 over = t->pin[0], U = t->pin[1], M = t->pin[2];
-      if (!over)
-        { fullest = M;
-          U64 Rn = (U * 100 / ((U64) NB * (U64) tightPct) + 1 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
-          const U64 Rfit = (M + M / 8 + 16 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;      /* the fullest bucket at load 0.89 at most */
-          if (Rn < Rfit) Rn = Rfit;
-          if (Rn < MG_TIGHT_MIN_R) Rn = MG_TIGHT_MIN_R;
-          if (Rn < t->R)
-            { t->R = (U32) Rn; t->nSlots = (U64) NB * Rn; a.g = mgGeomOf (t);
-              lds = mgMergeLdsBytes (t->R);
-            }
-        }
-    }
-  MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
-  MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
-  if (segSrc)
-    MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, true>), dim3 (nRankBlocks), dim3 (256), 0, st,
-               flags, (const U64 *) 0, *segSrc, subSeg, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, (const U32 *) 0, grp);
-  else
-    MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, false>), dim3 (nRankBlocks), dim3 (256), 0, st,
-               flags, dKmer, noSrc, (const MgSubSeg *) 0, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, (const U32 *) 0, grp);
-  { const U32 groupsPerSlice = (U32) ((NB + 63) / 64);
-    const U32 blocksPerSlice = (groupsPerSlice + 3) / 4, rounds = (a.nSlices + 7) / 8;
-    MG_LAUNCH (MG_K_RANK_LOOKUP, st, mgRankLookupKernel, dim3 (8 * rounds * blocksPerSlice), dim3 (256), 0, st, a, groupsPerSlice);
-  }
-  /* the scan placement keeps a register per unique: the instance that takes only the uniques fetched ahead where no list is longer (the
-     tightening has counted the fullest bucket's; otherwise by the bucket's size), the one with MG_PLACE_KEEP otherwise (it spills a little) */
-  if (fullest <= (U64) MG_MERGE_PREFETCH * bThreads)
-    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_MERGE_PREFETCH>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
-  else
-    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_PLACE_KEEP>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-__global__ void mgMarkOccKernel (MgGeom g, const U64 *__restrict__ kmer, U64 n, U32 *__restrict__ occ)
-{
-  U64 o = (U64) blockIdx.x * blockDim.x + threadIdx.x;
-  const U64 stride = (U64) gridDim.x * blockDim.x;
-  for ( ; o < n ; o += stride)
-    { U32 b = mgBucketOfM (mgMixK (kmer[o], g.kbits), g);
-      if (!occ[b]) occ[b] = 1;
-    }
-}
-
-MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st)
-{
-  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgMarkOccKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, mgGeomOf (t), dKmer, n, t->occ);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipStream_t st)
-{
-  if (!n) return MG_OK;
-  /* with the never-written buckets zeroed once, a probe needs no look at occ[] first */
-  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  const unsigned fgrid = mgGrid ((n + MG_FIND_PER - 1) / MG_FIND_PER);
-  ++t->diag[MG_DIAG_FIND_DIRECT];
-  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableFindKernel<false>, dim3 (fgrid), dim3 (256), 0, st, t->slots, t->occ, mgGeomOf (t), dKmer, n, dIndexOut);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-/* A check of the table's layout that does not go through the lookups: a thread per slot walks from its key's home to the slot.
-   out[0] += keys whose walk crosses an empty slot (a lookup would stop there), out[1] += keys in a bucket other than the one they
-   imply, out[2] += keys met a second time on that walk (a duplicate inside the bucket), out[3] += keys */
-__global__ __launch_bounds__ (256)
-void mgTableCheckLayoutKernel (const MgSlot *__restrict__ slots, MgGeom g, U64 nSlots, unsigned long long *__restrict__ out)
-{
-  const U64 stride = (U64) gridDim.x * blockDim.x;
-  U32 broken = 0, stray = 0, dup = 0, keys = 0;
-  for (U64 o = (U64) blockIdx.x * blockDim.x + threadIdx.x ; o < nSlots ; o += stride)
-    { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[o]);
-      const U64 key = ((U64) v.y << 32) | v.x;
-      if (!key) continue;
-      ++keys;
-      const U32 bkt = (U32) (o / g.R), me = (U32) (o - (U64) bkt * g.R);
-      const U64 m = key - 1;
-      if (mgBucketOfM (m, g) != bkt) { ++stray; continue; }
-      const U64 base = (U64) bkt * g.R;
-      for (U32 at = mgHomeOfM (m, g) ; at != me ; at = mgNextSlot (at, g.R))
-        { const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base + at]);
-          const U64 k2 = ((U64) w.y << 32) | w.x;
-          if (!k2) { ++broken; break; }
-          if (k2 == key) { ++dup; break; }
-        }
-    }
-  if (broken) atomicAdd (&out[0], (unsigned long long) broken);
-  if (stray) atomicAdd (&out[1], (unsigned long long) stray);
-  if (dup) atomicAdd (&out[2], (unsigned long long) dup);
-  if (keys) atomicAdd (&out[3], (unsigned long long) keys);
-}
-
-/* dOut: four device words (see the kernel), zeroed here */
-MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut, hipStream_t st)
-{
-  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  MG_HIP (hipMemsetAsync (dOut, 0, 32, st));
-  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableCheckLayoutKernel, dim3 (mgGrid (t->nSlots)), dim3 (256), 0, st, t->slots, mgGeomOf (t), t->nSlots, (unsigned long long *) dOut);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dIndexOut, hipStream_t st)
-{
-  if (!n) return MG_OK;
-  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  const U64 nRows = (n + 63) / 64;
-  U64 waves = 256ull * 4 * 8;                           /* eight waves per SIMD */
-  if (waves > nRows) waves = nRows;
-  const U64 rowsPerWave = (nRows + waves - 1) / waves;
-  waves = (nRows + rowsPerWave - 1) / rowsPerWave;
-  ++t->diag[MG_DIAG_FIND_DIRECT];
-  MG_LAUNCH (MG_K_TABLE_FIND_SEG, st, mgTableFindSegKernel, dim3 ((unsigned) ((waves + 3) / 4)), dim3 (256), 0, st, t->slots, mgGeomOf (t), src, n, rowsPerWave, dIndexOut);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-/* scratch of the partitioned lookup for a batch of n: the run table and the partition's small arrays (the packed elements,
-   8 bytes each, go where the caller says: the scan's unused dense k-mer array) */
-size_t mgTableFindPartScratchBytes (U64 n)
-{
-  return mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8) + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 2
-       + mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16) + mgAl ((MG_PART_MAXBINS + 2) * 4)
-       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg)) + 4096;
-}
-
-/* the two-level path's extra scratch: the second pass's output (8 bytes an element), the results beside the first pass's output
-   (4), the second run table, the fine starts / cursors / counts and its chunk table */
-size_t mgTableFindPart2ScratchBytes (U64 n)
-{
-  const U64 NB = (U64) 1 << 18;
-  return mgAl (n * 8) + mgAl (n * 4) + mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8)
-       + mgAl ((NB + 2) * 8) + mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8) + mgAl ((NB + 2) * 4)
-       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + 4096;
-}
-
-/* does a lookup batch take the partitioned path?  It needs the scan's digit counts for this table geometry, elements that
-   fit one word, and a table the direct probes would have to fetch from HBM */
-/* The digit of the partitioned lookup: the top bits of the bucket id one pass sorts by; a bin's piece of the table is
-   nSlots * 16 bytes >> bits (MODGPU_FIND_BITS: dev, 3..9) */
-int mgTableFindDigitBits (const MgTable *t)
-{
-  const long kb = mgKnobs ()->findBits;
-  int hiB, loB; mgPartSplit (t->log2NB, &hiB, &loB);          /* the build's own first digit: 256 bins of 8 MB at config 3 (512 bins of 4 MB: scatter and pull-back cost 0.7 ms more, the lookups gain nothing) */
-  int bits = kb != MG_KNOB_UNSET && kb >= 3 && kb <= 9 ? (int) kb : hiB;
-  if (bits > t->log2NB) bits = t->log2NB;
-  return bits;
-}
-
-bool mgTableFindTakesPartition (const MgTable *t, U64 n, const MgHistReq *counted)
-{
-  const long kp = mgKnobs ()->findPath;                      /* test knob: 'p' / 'd' force it */
-  if (kp == 'd') return false;
-  if (!n || !counted || !counted->binCount || counted->log2NB != t->log2NB || counted->kbits != t->kbits) return false;
-  const int hiB = counted->hiB;
-  if (hiB != mgTableFindDigitBits (t)) return false;
-  const int ordBits = mgLog2 (n) > 1 ? mgLog2 (n) : 1;
-  if (!(t->kbits >= t->log2NB + 4 && t->kbits - hiB + ordBits <= 64) || hiB < 3) return false;
-  if (t->kbits < 24 || mgKnobs ()->scanHist == 0) return false;          /* (the counts must be the scan's own: mgLaunchScanRange) */
-  if (kp == 'p' || kp == '2') return true;
-  /* by itself: the two-level path where the direct probes would fetch a line from HBM per lookup -- a table of 256 MB and more,
-     a batch that fills the chip (config 3: 3.5 against 4.2-4.6 ms per 1.56e8 lookups; one level ties with the direct probes) */
-  return n >= ((U64) 1 << 24) && t->nSlots >= ((U64) 1 << 24) && t->log2NB > 9;
-}
-
-MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, const MgHistReq *counted, U32 *dIndexOut, U64 *el, void *scratch, hipStream_t st,
-                                 void *scratch2)
-{
-  if (!n) return MG_OK;
-  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  char *wb = (char *) scratch;
-  unsigned long long *runTab = (unsigned long long *) wb;    wb += mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8);
-  U64 *binStart = (U64 *) wb;                                wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  U64 *whole = (U64 *) wb;                                   wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  unsigned long long *cursor = (unsigned long long *) wb;    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
-  U32 *binCount = (U32 *) wb;                                wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
-  U32 *chunkBase = (U32 *) wb;                               wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
-  MgSubSeg *subSeg = (MgSubSeg *) wb;                        wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
-  const int hiB = counted->hiB, loB = t->log2NB - hiB;
-  MgPartFmt f; f.ordBits = mgLog2 (n) > 1 ? mgLog2 (n) : 1; f.remBits = t->kbits - hiB; f.loB = loB;
-  const U32 nBins = (U32) 1 << hiB;
-  U64 segInit[2] = { 0, n };
-  MG_HIP (hipMemcpyAsync (whole, segInit, 16, hipMemcpyHostToDevice, st));
-  U32 subElems = 0;
-  const bool twoLevels = scratch2 && loB > 0 && ((U32) 1 << loB) <= MG_PART_MAXBINS;
-  /* (two levels) the fine digits as bytes beside the first pass's output, for the second pass's counts: in idxA, which is only written by the first pull */
-  unsigned char *digits = (twoLevels && loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> ((char *) scratch2 + mgAl (n * 8)) : 0;
-  MgStatus s = mgPartPass (t, MG_EL_SEG, true, f, (const U64 *) 0, 0, n, whole, 1, loB, nBins, el, (U32 *) 0, binStart, cursor, binCount, chunkBase, st,
-                           counted->binCount, &segSrc, subSeg, runTab, &subElems, 0, 0, digits, 0, (U32) 1 << loB);
-  if (s) return s;
-  if (twoLevels)      /* ---- two levels: the lookups bucket by bucket out of LDS (a table of few buckets has no fine digit: one level) ---- */
-    { char *w2 = (char *) scratch2;
-      const U64 NB = (U64) 1 << t->log2NB;
-      U64 *el2 = (U64 *) w2;                                   w2 += mgAl (n * 8);
-      U32 *idxA = (U32 *) w2;                                  w2 += mgAl (n * 4);
-      unsigned long long *runTab2 = (unsigned long long *) w2; w2 += mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8);
-      U64 *fineStart = (U64 *) w2;                             w2 += mgAl ((NB + 2) * 8);
-      unsigned long long *fineCursor = (unsigned long long *) w2; w2 += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
-      U32 *fineCount = (U32 *) w2;                             w2 += mgAl ((NB + 2) * 4);
-      U32 *chunkBase2 = (U32 *) w2;                            w2 += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
-      U32 sub2 = 0, maxChunks2 = 0;
-      const U32 nBins2 = (U32) 1 << loB;
-      s = mgPartPass (t, MG_EL_PACKED, true, f, el, (const U32 *) 0, n, binStart, nBins, 0, nBins2, el2, (U32 *) 0, fineStart, fineCursor, fineCount, chunkBase2, st,
-                      (const U32 *) 0, (const MgSegSrc *) 0, (MgSubSeg *) 0, runTab2, &sub2, 1, &maxChunks2, 0, 0, 0, digits);
-      if (s) return s;
-      unsigned bGrid = (unsigned) (NB < 4096 ? NB : 4096);
-      const U32 perBlock = (U32) ((NB + bGrid - 1) / bGrid);
-      bGrid = (unsigned) ((NB + perBlock - 1) / perBlock);
-      const int remB = t->kbits - t->log2NB;
-      if (remB >= 1 && remB <= 32 && mgKnobs ()->find8 != 0)          /* (rem + 1 <= 2^32 above a 31-bit index: one word) */       /* (test knob MODGPU_FIND8=0: the 16-byte table itself) */
-        { if (!t->find8 || t->find8Version != t->version || t->find8Cap < t->nSlots)
-            { if (t->find8Cap < t->nSlots)
-                { if (t->find8) { MG_HIP (hipStreamSynchronize (st)); MG_HIP (hipFree (t->find8)); t->find8 = 0; t->find8Cap = 0; }
-                  MG_HIP (hipMalloc ((void **) &t->find8, t->nSlots * sizeof (U64)));
-                  t->find8Cap = t->nSlots;
-                }
-              ++t->diag[MG_DIAG_PACK8];
-              MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTablePack8Kernel, dim3 ((unsigned) (NB < 8192 ? NB : 8192)), dim3 (256), 0, st, t->slots, t->occ, (U32) NB, t->R, remB, t->find8);
-              t->find8Version = t->version;
-            }
-          const size_t lds8 = (size_t) t->R * 8 + 16;
-          if (lds8 > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFind8Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds8));
-          ++t->diag[MG_DIAG_FIND_PART2_8];
-          MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFind8Kernel, dim3 (bGrid), dim3 (1024), lds8, st, t->find8, t->occ, mgGeomOf (t), f, (U32) NB, remB, fineStart, el2, perBlock);
-        }
-      else
-        { const size_t lds = (size_t) t->R * 12 + 16;
-          if (lds > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFindKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-          ++t->diag[MG_DIAG_FIND_PART2_16];
-          MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFindKernel, dim3 (bGrid), dim3 (1024), lds, st, t->slots, t->occ, mgGeomOf (t), f, (U32) NB, fineStart, el2, perBlock);
-        }
-      const unsigned g2 = 2 * maxChunks2 < 2048 ? 2 * maxChunks2 : 2048;
-      if (sub2 == MG_PART_SUB_BIG) MG_LAUNCH (MG_K_UNPART, st, mgUnpartPosKernel<MG_PART_SUB_BIG>, dim3 (g2), dim3 (1024), 0, st, el2, runTab2, nBins2, binStart, chunkBase2, nBins, 2 * sub2, idxA);
-      else                         MG_LAUNCH (MG_K_UNPART, st, mgUnpartPosKernel<MG_PART_SUB>, dim3 (g2), dim3 (1024), 0, st, el2, runTab2, nBins2, binStart, chunkBase2, nBins, 2 * sub2, idxA);
-      const U64 nSub1 = (n + subElems - 1) / subElems;
-      const unsigned g1 = (unsigned) (nSub1 < 2048 ? nSub1 : 2048);
-      if (subElems == MG_PART_SUB_BIG) MG_LAUNCH (MG_K_UNPART, st, mgUnpartOrdKernel<MG_PART_SUB_BIG>, dim3 (g1), dim3 (1024), 0, st, el, idxA, f.ordBits, runTab, nBins, n, dIndexOut);
-      else                             MG_LAUNCH (MG_K_UNPART, st, mgUnpartOrdKernel<MG_PART_SUB>, dim3 (g1), dim3 (1024), 0, st, el, idxA, f.ordBits, runTab, nBins, n, dIndexOut);
-      MG_HIP (hipGetLastError ());
-      return MG_OK;
-    }
-  const U32 wgPerXcd = 256;                                  /* 2048 workgroups of 256: eight waves per SIMD */
-  ++t->diag[MG_DIAG_FIND_PART1];
-  MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBinFindKernel, dim3 (8 * wgPerXcd), dim3 (256), 0, st, t->slots, mgGeomOf (t), f, el, binStart, nBins, wgPerXcd);
-  const U64 nSub = (n + subElems - 1) / subElems;
-  const unsigned ug = (unsigned) (nSub < 2048 ? nSub : 2048);
-  if (subElems == MG_PART_SUB_BIG) MG_LAUNCH (MG_K_UNPART, st, mgUnpartKernel<MG_PART_SUB_BIG>, dim3 (ug), dim3 (1024), 0, st, el, runTab, nBins, n, dIndexOut);
-  else                             MG_LAUNCH (MG_K_UNPART, st, mgUnpartKernel<MG_PART_SUB>, dim3 (ug), dim3 (1024), 0, st, el, runTab, nBins, n, dIndexOut);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-static U64 mgSlotsFor (const MgTable *t, U64 entries);
-static MgStatus mgFitGeometry (const MgTable *t, const U32 *dFine, U64 want, int *lgOut, U32 *ROut, hipStream_t st);
-static MgStatus mgTableRehashExact (MgTable *t, int log2NB, U32 R, hipStream_t st);
-#define MG_FINE_LOG2 18            /* the most buckets a table has (mgSetGeometry): counts per finest bucket give every coarser geometry's by addition */
-__global__ void mgFineCountValuesKernel (const U64 *__restrict__ value, U32 first, U32 last, int kbits, U32 *__restrict__ fine);
+/* ======================================================================================== */
+/* table life cycle: allocation, lazy zeroing, growth                                         */
 
 /* the overflow flag (counters[1]) comes back through the table's page-locked words, or by a plain copy where it has none */
 static MgStatus mgReadOverflow (MgTable *t, hipStream_t st, U64 *over)
@@ -2480,95 +1847,6 @@ static MgStatus mgReadOverflow (MgTable *t, hipStream_t st, U64 *over)
     }
   return MG_OK;
 }
-
-/* the loader, waited for; *over != 0: a bucket had no room for one of the values (the others are in) */
-static MgStatus mgLoadLaunch (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st, U64 *over)
-{
-  MG_HIP (hipMemsetAsync (t->counters + 1, 0, 8, st));
-  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGrid ((U64) last - first + 1)), dim3 (256), 0, st,
-             t->slots, mgGeomOf (t), dValue, first, last, t->occ, t->counters);
-  MG_HIP (hipGetLastError ());
-  return mgReadOverflow (t, st, over);
-}
-
-MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st)
-{
-  if (last < first) return MG_OK;
-  t->liveHistValid = false; t->empty = false; ++t->version;
-  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  U64 over = 0;
-  MgStatus s = mgLoadLaunch (t, dValue, first, last, st, &over);
-  if (s || !over) return s;
-  /* A bucket had no room: the table was sized by the mean (mgTableEnsure) and these values crowd one bucket.  The entries that found
-     a slot stay where they are; the table goes into a geometry that holds the fullest bucket of ALL the values (value[1 .. last]:
-     what is in the table and what was left out), and the values are loaded again -- those already there are met as duplicates. */
-  int lg = 0; U32 R = 0;
-  U32 *dFine = 0;
-  if (hipMalloc ((void **) &dFine, sizeof (U32) << MG_FINE_LOG2) != hipSuccess) return mgHipFail (hipGetLastError (), "hipMalloc");
-  if (hipMemsetAsync (dFine, 0, sizeof (U32) << MG_FINE_LOG2, st) != hipSuccess) s = mgHipFail (hipGetLastError (), "hipMemsetAsync");
-  else
-    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountValuesKernel, dim3 (mgGrid (last)), dim3 (256), 0, st, dValue, 1u, last, t->kbits, dFine);
-      s = mgFitGeometry (t, dFine, mgSlotsFor (t, last), &lg, &R, st);
-    }
-  (void) hipFree (dFine);
-  if (!s) s = mgTableRehashExact (t, lg, R, st);
-  if (s) return s;
-  if ((s = mgLoadLaunch (t, dValue, first, last, st, &over))) return s;
-  if (over) { mgSetError ("internal: the device table's fitted geometry (2^%d x %u) does not hold the host's entries", lg, R); return MG_ERR_CAPACITY; }
-  return MG_OK;
-}
-
-MgStatus mgTableExportDepth (MgTable *t, U16 *dDelta, hipStream_t st)
-{
-  if (!t->max) return MG_OK;
-  MG_HIP (hipMemsetAsync (dDelta, 0, (size_t) t->max * sizeof (U16), st));
-  t->baseZero = false;                                   /* the fold below writes baseDepth */
-  t->pendingDepth = false;
-  t->liveHistValid = false;
-  { const U32 NB = (U32) 1 << t->log2NB;
-    MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgTableExportDepthKernel, dim3 (NB < 8192 ? NB : 8192), dim3 (256), 0, st,
-               t->slots, NB, t->occ, t->R, t->baseDepth, dDelta, t->max);
-  }
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-/* dHist[i] += live[i] */
-__global__ void mgHistAddKernel (const U64 *__restrict__ live, unsigned long long *__restrict__ hist)
-{ U32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i < 65536 && live[i]) atomicAdd (&hist[i], (unsigned long long) live[i]); }
-
-MgStatus mgTableHistogram (MgTable *t, U64 *dHist, hipStream_t st)
-{
-  if (!t->max) return MG_OK;
-  if (t->liveHistValid && t->liveHist)                 /* the merge kernel kept it while it built the set */
-    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgHistAddKernel, dim3 (256), dim3 (256), 0, st, t->liveHist, (unsigned long long *) dHist);
-      MG_HIP (hipGetLastError ());
-      return MG_OK;
-    }
-  { const U32 NB = (U32) 1 << t->log2NB;
-    MG_LAUNCH (MG_K_TABLE_HIST, st, mgTableHistKernel, dim3 (NB < 2048 ? NB : 2048), dim3 (256), 0, st,
-               t->slots, NB, t->occ, t->R, t->baseZero ? (const U16 *) 0 : t->baseDepth, (unsigned long long *) dHist);
-  }
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-MgStatus mgTableReplayIndex (MgTable *t, const MgHashParams &p, int tableBits, U32 *dIndex, hipStream_t st)
-{
-  U64 n = (U64) 1 << tableBits;
-  MG_HIP (hipMemsetAsync (dIndex, 0xff, n * sizeof (U32), st));
-  if (t->max)
-    { MG_LAUNCH (MG_K_INDEX_REPLAY, st, mgReplayIndexKernel, dim3 (mgGrid (t->max)), dim3 (256), 0, st,
-                          t->value, t->max, p.factor1, p.shift1, tableBits, dIndex);
-      MG_HIP (hipGetLastError ());
-    }
-  MG_LAUNCH (MG_K_INDEX_FINISH, st, mgIndexFinishKernel, dim3 (mgGrid (n, 256, 8192)), dim3 (256), 0, st, dIndex, n);
-  MG_HIP (hipGetLastError ());
-  return MG_OK;
-}
-
-/* ======================================================================================== */
-/* table life cycle: allocation, lazy zeroing, growth                                         */
 
 /* zero the buckets nothing has been written to (occ == 0); everything else is left alone */
 __global__ __launch_bounds__ (256)
@@ -2590,8 +1868,8 @@ __global__ void mgRehashKernel (const MgSlot *__restrict__ oldSlots, U32 oldNB, 
       const MgSlot *from = oldSlots + (U64) bk * oldR;
       for (U32 i = threadIdx.x ; i < oldR ; i += blockDim.x)
         { uint4 v = *reinterpret_cast<const uint4 *> (&from[i]);
-          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;      /* (keepMax: what a refused add left behind is dropped, mgTableRollback) */
-          const unsigned long long key = ((unsigned long long) v.y << 32) | v.x;
+          if (!mgLiveEntry (v, keepMax)) continue;      /* (keepMax: what a refused add left behind is dropped, mgTableRollback) */
+          const unsigned long long key = mgKeyOf (v);
           const U64 m = key - 1;                                  /* the key IS the mixed k-mer: no re-hash needed to re-place it */
           const U32 b = mgBucketOfM (m, g);
           const U64 base = (U64) b * g.R;
@@ -2632,8 +1910,8 @@ void mgRehashBucketKernel (const MgSlot *__restrict__ oldSlots, int oldLog2NB, c
       U32 mine = 0;
       for (U32 i = tid ; i < oldR ; i += T)
         { const uint4 v = *reinterpret_cast<const uint4 *> (&from[i]);
-          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;
-          const unsigned long long key = ((unsigned long long) v.y << 32) | v.x;
+          if (!mgLiveEntry (v, keepMax)) continue;
+          const unsigned long long key = mgKeyOf (v);
           const U64 m = key - 1;
           if (mgBucketOfM (m, g) != b) continue;
           const U32 at = mgLdsClaim (sKey, g.R, mgHomeOfM (m, g), key);
@@ -2656,6 +1934,7 @@ void mgRehashBucketKernel (const MgSlot *__restrict__ oldSlots, int oldLog2NB, c
     }
 }
 
+#define MG_FINE_LOG2 18            /* the most buckets a table has (mgSetGeometry): counts per finest bucket give every coarser geometry's by addition */
 /* How many entries every bucket of the finest geometry (2^MG_FINE_LOG2 buckets) would hold: a bucket id is a prefix of the key, so the
    counts of any coarser geometry are sums of these.  From the table's assigned entries, or from value[first .. last]. */
 __global__ void mgFineCountSlotsKernel (const MgSlot *__restrict__ slots, U32 NB, const U32 *__restrict__ occ, U32 R, int kbits, U32 keepMax, U32 *__restrict__ fine)
@@ -2665,8 +1944,8 @@ __global__ void mgFineCountSlotsKernel (const MgSlot *__restrict__ slots, U32 NB
     { if (!occ[bk]) continue;                                      /* (never written: its bytes are undefined) */
       for (U32 i = threadIdx.x ; i < R ; i += blockDim.x)
         { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[(U64) bk * R + i]);
-          if (!(v.x | v.y) || !mgIsAssigned (v.z) || (v.z & ~MG_ASSIGNED) > keepMax) continue;
-          const U64 m = ((((U64) v.y << 32) | v.x) - 1) & (kbits >= 64 ? ~0ull : (((U64) 1 << kbits) - 1));
+          if (!mgLiveEntry (v, keepMax)) continue;
+          const U64 m = (mgKeyOf (v) - 1) & (kbits >= 64 ? ~0ull : (((U64) 1 << kbits) - 1));
           atomicAdd (&fine[mgBucketOfM (m, g)], 1u);               /* (m < 2^kbits: the id is below 2^log2NB) */
         }
     }
@@ -2680,11 +1959,26 @@ __global__ void mgFineCountValuesKernel (const U64 *__restrict__ value, U32 firs
     atomicAdd (&fine[mgBucketOfM (mgMixK (value[i] & mask, kbits) & mask, g)], 1u);
 }
 
+/* Geometry for `want` slots: NB a power of two, R = want / NB rounded up to a multiple of 64, between half of wantR and wantR where the size
+   allows (R = 4096: a bucket's image is 64 KiB of LDS); at most 2^18 buckets (two 9-bit partition passes), R up to 8192 beyond that. */
+static void mgSetGeometry (MgTable *t, U64 want)
+{
+  U32 Rmax = t->wantR ? t->wantR : 4096;
+  if (Rmax > 8192) Rmax = 8192;                   /* the dedup kernel's threads hold MG_DEDUP_PER (R <= 4096) or MG_DEDUP_PER_BIG slots each */
+  if (Rmax < MG_R_QUANTUM) Rmax = MG_R_QUANTUM;
+  if (want < MG_R_QUANTUM) want = MG_R_QUANTUM;
+  int lgNB = 0;
+  while (lgNB < 18 && (want + ((U64) 1 << lgNB) - 1) / ((U64) 1 << lgNB) > Rmax) ++lgNB;
+  U64 R = (want + ((U64) 1 << lgNB) - 1) >> lgNB;
+  R = (R + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
+  if (R > 8192) R = 8192;
+  t->R = (U32) R; t->log2NB = lgNB; t->nSlots = R << lgNB;
+}
+
 /* The smallest legal geometry of at least `want` slots whose fullest bucket holds its entries with one slot to spare (a bucket that is
    offered as many keys as it has slots refuses them: mgBucketMergeKernel), from the fine counts.  Legal: NB a power of two up to 2^18,
    R a multiple of 64 up to the table's own limit (wantR) -- or, where nothing else fits, up to 8192 -- and no more slots than the set's
    table bits allow (maxLog2Slots).  MG_ERR_CAPACITY when there is none. */
-static void mgSetGeometry (MgTable *t, U64 want);
 static MgStatus mgFitGeometry (const MgTable *t, const U32 *dFine, U64 want, int *lgOut, U32 *ROut, hipStream_t st)
 {
   const size_t nFine = (size_t) 1 << MG_FINE_LOG2;
@@ -2727,30 +2021,7 @@ static MgStatus mgFitGeometry (const MgTable *t, const U32 *dFine, U64 want, int
   return MG_ERR_CAPACITY;
 }
 
-/* Geometry for `want` slots: NB a power of two, R = want / NB rounded up to a multiple of 64, between half of wantR and wantR where the size
-   allows (R = 4096: a bucket's image is 64 KiB of LDS); at most 2^18 buckets (two 9-bit partition passes), R up to 8192 beyond that. */
-static void mgSetGeometry (MgTable *t, U64 want)
-{
-  U32 Rmax = t->wantR ? t->wantR : 4096;
-  if (Rmax > 8192) Rmax = 8192;                   /* the dedup kernel's threads hold MG_DEDUP_PER (R <= 4096) or MG_DEDUP_PER_BIG slots each */
-  if (Rmax < MG_R_QUANTUM) Rmax = MG_R_QUANTUM;
-  if (want < MG_R_QUANTUM) want = MG_R_QUANTUM;
-  int lgNB = 0;
-  while (lgNB < 18 && (want + ((U64) 1 << lgNB) - 1) / ((U64) 1 << lgNB) > Rmax) ++lgNB;
-  U64 R = (want + ((U64) 1 << lgNB) - 1) >> lgNB;
-  R = (R + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
-  if (R > 8192) R = 8192;
-  t->R = (U32) R; t->log2NB = lgNB; t->nSlots = R << lgNB;
-}
-
-/* an empty table of (at least) `want` slots; memory is only allocated when the capacity is short */
-static MgStatus mgTableAllocGeom (MgTable *t, hipStream_t st);
-MgStatus mgTableAlloc (MgTable *t, U64 want, hipStream_t st)
-{
-  mgSetGeometry (t, want);
-  return mgTableAllocGeom (t, st);
-}
-/* the same for the geometry t already names (R, log2NB, nSlots) */
+/* an empty table of the geometry t names (R, log2NB, nSlots); memory is only allocated when the capacity is short */
 static MgStatus mgTableAllocGeom (MgTable *t, hipStream_t st)
 {
   const U32 NB = (U32) 1 << t->log2NB;
@@ -2766,6 +2037,13 @@ static MgStatus mgTableAllocGeom (MgTable *t, hipStream_t st)
     }
   mgTableForget (t, st);
   return MG_OK;
+}
+
+/* the same of (at least) `want` slots */
+MgStatus mgTableAlloc (MgTable *t, U64 want, hipStream_t st)
+{
+  mgSetGeometry (t, want);
+  return mgTableAllocGeom (t, st);
 }
 
 void mgTableForget (MgTable *t, hipStream_t st)
@@ -2905,6 +2183,709 @@ MgStatus mgTableEnsure (MgTable *t, U64 nIncoming, hipStream_t st)
 }
 
 /* ======================================================================================== */
+/* the launchers: add, lookups, whole-table passes                                            */
+
+#define MG_RANK_UNITS 8192           /* waves that share the ordered flag count */
+static inline U64 mgRankRowsPerUnit (U64 n, U32 *nBlocks)
+{
+  U64 nRows = (n + 63) / 64;
+  U64 per = (nRows + MG_RANK_UNITS - 1) / MG_RANK_UNITS; if (!per) per = 1;
+  U64 units = (nRows + per - 1) / per; if (!units) units = 1;
+  *nBlocks = (U32) ((units + 3) / 4);
+  return per;
+}
+
+/* the split of oversize buckets: occurrences above which a bucket is split, occurrences of a chunk at least */
+static void mgHotKnobs (U32 *split, U32 *chunk)
+{
+  const MgKnobs *k = mgKnobs ();                             /* test knob "split,chunk": small values send ordinary buckets through the split path */
+  U32 a = MG_HOT_SPLIT_DEFAULT, b = MG_HOT_CHUNK_DEFAULT;
+  if (k->hotSplit != MG_KNOB_UNSET && k->hotSplit > 0)
+    { a = (U32) k->hotSplit; b = k->hotChunk != MG_KNOB_UNSET && k->hotChunk > 0 ? (U32) k->hotChunk : a / 4; }
+  if (b < 64) b = 64;
+  if (a < b) a = b;
+  *split = a; *chunk = b;
+}
+static U64 mgHotItemsCap (U64 n) { U32 sp, ch; mgHotKnobs (&sp, &ch); return n / ch + n / sp + 16; }
+
+/* scratch needed by mgTableAdd for a batch of n */
+size_t mgTableAddScratchBytes (const MgTable *t, U64 n)
+{
+  (void) t;
+  U64 NB = (U64) 1 << 18;               /* the largest bucket count: the table may grow between passes of one call */
+  size_t rank = mgAl (n) /*flags*/ + 2 * mgAl ((MG_RANK_UNITS + 8) * 8) + mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
+  size_t direct = mgAl (n * 4);
+  size_t part = 2 * (mgAl (n * 8) + mgAl (n * 4)) + mgAl (n * 4)
+              + mgAl ((NB + 2) * 8) * 3 + mgAl ((NB + 2) * 4) * 2 + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 3 + 2 * mgAl ((U64) MG_PART_MAXBINS * 16 * 8 + 4096)
+              + mgAl ((MG_PART_MAXBINS + 2) * 4) + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4)
+              + mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short)) + mgAl ((n / MG_PART_SUB + 2) * 24)
+              + mgAl (mgHotItemsCap (n) * 8) + mgAl (mgHotItemsCap (n) * 4) + 256;
+  return rank + (direct > part ? direct : part) + 4096;
+}
+
+static int mgPathOverride (void)
+{
+  const long c = mgKnobs ()->tablePath;                       /* test knob: the first letter of "direct" / "bucket" */
+  return c == 'd' ? 1 : (c == 'b' ? 2 : 0);
+}
+
+bool mgTableUseBuckets (const MgTable *t, U64 n)
+{
+  int ov = mgPathOverride ();
+  if (ov == 1) return false;
+  if (ov == 2) return true;
+  /* a batch of a million or so: the bucketed path's dozen launches and its per-bucket lists cost 0.43 ms whatever the size, the atomics
+     0.1 ms + 0.19 ms per million (tools/size_sweep_probe.py: 0.78 M modimizers 0.30 against 0.43 ms, 3.1 M 0.68 against 0.45) */
+  if (n < 1500000) return false;
+  return n >= t->nSlots / 16;           /* streaming every touched bucket twice beats ~100 ps/modimizer of atomics */
+}
+
+/* can mgTableAdd read this batch from the scan's segments?  Only the bucketed path does, and its first pass then
+   needs the digit counts the scan made for exactly this table geometry */
+bool mgTableAddTakesSegments (const MgTable *t, U64 n, const MgHistReq *counted)
+{
+  const int off = mgKnobs ()->noSegmentInput == 1;   /* test knob: always compact first */
+  return !off && n && mgTableUseBuckets (t, n) && counted && counted->binCount && counted->log2NB == t->log2NB && counted->kbits == t->kbits && !counted->hiB;
+}
+
+/* One partition pass: nSeg segments of kIn -> nBins bins each.  What is not set stays 0: not there, not wanted. */
+struct MgPartPassArgs {
+  int inMode; bool packed; MgPartFmt f;            /* inMode: what kIn holds (MG_EL_*); packed: the format of the output (and, after the first pass, of the input) */
+  const U64 *kIn; const U32 *tIn; U64 n;           /* the elements (tIn: the ordinals of wide ones) */
+  const U64 *segStart; U32 nSeg;                   /* [nSeg + 1] the segments of kIn */
+  int shift; U32 nBins;                            /* the digit: bits [shift, shift + log2 nBins) of the bucket id */
+  U64 *kOut; U32 *tOut; U64 *binStart;             /* out: the elements by (segment, bin), and [nSeg x nBins + 1] where every bin starts */
+  unsigned long long *cursor; U32 *binCount, *chunkBase;   /* work space */
+  const U32 *counted;                              /* the digit counts the scan made (one segment), instead of a counting pass */
+  const MgSegSrc *segSrc; MgSubSeg *subSeg;        /* MG_EL_SEG: the scan's segments the k-mers sit in (with counted), and work space */
+  unsigned long long *runTab; int runMode;         /* the partitioned lookup: out, where every sub-chunk's run of every bin went (mgPartScatterKernel) */
+  unsigned char *digitOut; int nextShift; U32 nextBins;    /* out: the NEXT pass's digit (bits [nextShift, ..) of the bucket id, nextBins <= 256 of them) of every element, beside it */
+  const unsigned char *digitIn;                    /* such bytes of the pass before: the digits are counted from them */
+  U32 subElems, maxChunks;                         /* out: elements of a sub-chunk (a chunk is two), and a bound on the chunks */
+};
+static MgStatus mgPartPass (const MgTable *t, MgPartPassArgs &p, hipStream_t st)
+{
+  MgGeom g = mgGeomOf (t);
+  MgSegSrc src = {};
+  if (p.inMode == MG_EL_SEG)
+    { if (!p.segSrc || !p.subSeg || !p.counted) { mgSetError ("internal: segment input needs its counts"); return MG_ERR_ARG; }
+      src = *p.segSrc;
+      const U64 nSub = (p.n + MG_PART_SUB - 1) / MG_PART_SUB;
+      MG_LAUNCH (MG_K_PART, st, mgSubSegKernel, dim3 ((unsigned) ((nSub + 255) / 256)), dim3 (256), 0, st, src, p.n, (U32) MG_PART_SUB, p.subSeg);
+    }
+  if (p.counted) MG_HIP (hipMemcpy2DAsync (p.binCount, sizeof (U32), p.counted, MG_HIST_STRIDE * sizeof (U32), sizeof (U32), p.nBins, hipMemcpyDeviceToDevice, st));   /* the scan counted them */
+  else MG_HIP (hipMemsetAsync (p.binCount, 0, (size_t) p.nSeg * p.nBins * sizeof (U32), st));
+  /* large sub-chunks where the kernel has them: packed elements, at most 256 bins */
+  const int bigEnv = mgKnobs ()->partBig == MG_KNOB_UNSET ? 1 : (int) mgKnobs ()->partBig;      /* test knob: 0 = sub-chunks of MG_PART_SUB everywhere */
+  const bool big = bigEnv && p.packed && p.nBins <= MG_PART_BIG_BINS && MG_PART_THREADS == 1024;
+  p.subElems = (U32) (big ? MG_PART_SUB_BIG : MG_PART_SUB);
+  const U32 chunkElems = 2u * p.subElems;
+  MG_LAUNCH (MG_K_PART, st, mgPartChunksKernel, dim3 (1), dim3 (MG_PART_MAXBINS), 0, st, p.segStart, p.nSeg, chunkElems, p.chunkBase);
+  const unsigned maxChunks = p.maxChunks = (unsigned) (p.n / chunkElems + p.nSeg + 1);
+  const int sgEnv = mgKnobs ()->scatterGrid == MG_KNOB_UNSET ? 0 : (int) mgKnobs ()->scatterGrid;   /* dev knob */
+  unsigned scatterGrid = maxChunks < (unsigned) (sgEnv > 0 ? sgEnv : 1024) ? maxChunks : (unsigned) (sgEnv > 0 ? sgEnv : 1024);
+  const dim3 hg (maxChunks < 4096 ? maxChunks : 4096), sg (scatterGrid);
+  if (!p.counted && p.digitIn)
+    MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistBytesKernel, hg, dim3 (256), 0, st, p.digitIn, p.nBins, p.segStart, p.chunkBase, p.nSeg, chunkElems, p.binCount);
+  else if (!p.counted)
+    {
+#define MG_HIST(IN) MG_LAUNCH (MG_K_PART_HIST, st, mgPartHistKernel<IN>, hg, dim3 (256), 0, st, p.kIn, g, p.f, p.shift, p.nBins, p.segStart, p.chunkBase, p.nSeg, chunkElems, p.binCount)
+      if (p.inMode == MG_EL_DENSE) MG_HIST (MG_EL_DENSE); else if (p.inMode == MG_EL_WIDE) MG_HIST (MG_EL_WIDE); else MG_HIST (MG_EL_PACKED);
+#undef MG_HIST
+    }
+  /* one segment (the first pass): every workgroup reserves in the same few hundred cursors -- one cache line each
+     (scatter 0.88 -> 0.73 ms: returning atomics on cursors that share a line queue behind each other) */
+  const U32 cstride = p.nSeg == 1 ? 16u : 1u;                  /* (the second pass's 65536 cursors: no gain from padding) */
+  MG_LAUNCH (MG_K_PART, st, mgPartScanKernel, dim3 (p.nSeg), dim3 (MG_PART_MAXBINS), 0, st, p.binCount, p.nBins, p.segStart, p.binStart, p.cursor, cstride, p.nSeg, p.n);
+#define MG_SCATTER(IN, PK, SUB) MG_LAUNCH (MG_K_PART_SCATTER, st, (mgPartScatterKernel<IN, PK, SUB>), sg, dim3 (MG_PART_THREADS), 0, st, \
+                                           p.kIn, p.tIn, src, p.subSeg, g, p.f, p.shift, p.nBins, p.segStart, p.chunkBase, p.nSeg, chunkElems, p.cursor, cstride, p.kOut, p.tOut, p.runTab, p.runMode, \
+                                           p.digitOut, p.nextShift, p.nextBins ? p.nextBins - 1 : 0u)
+#define MG_SCATTER_P(IN) mgForSub (p.subElems, [&] (auto S) { MG_SCATTER (IN, true, decltype (S)::value); })
+  if (p.inMode == MG_EL_DENSE) { if (p.packed) MG_SCATTER_P (MG_EL_DENSE); else MG_SCATTER (MG_EL_DENSE, false, MG_PART_SUB); }
+  else if (p.inMode == MG_EL_SEG) { if (p.packed) MG_SCATTER_P (MG_EL_SEG); else MG_SCATTER (MG_EL_SEG, false, MG_PART_SUB); }
+  else if (p.inMode == MG_EL_WIDE) MG_SCATTER (MG_EL_WIDE, false, MG_PART_SUB);
+  else MG_SCATTER_P (MG_EL_PACKED);
+#undef MG_SCATTER_P
+#undef MG_SCATTER
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* the dedup kernel's per-bucket counts of distinct k-mers: out[0] = their sum, out[1] = the largest (out[] zeroed by the launcher) */
+__global__ __launch_bounds__ (256)
+void mgUniqStatsKernel (const U32 *__restrict__ uniqCount, U32 nBuckets, unsigned long long *__restrict__ out)
+{
+  unsigned long long sum = 0; U32 mx = 0;
+  for (U32 b = blockIdx.x * 256 + threadIdx.x ; b < nBuckets ; b += gridDim.x * 256) { const U32 c = uniqCount[b]; sum += c; mx = c > mx ? c : mx; }
+  for (int off = 32 ; off ; off >>= 1)
+    { sum += ((unsigned long long) (U32) __shfl_xor ((int) (U32) (sum >> 32), off) << 32) | (U32) __shfl_xor ((int) (U32) sum, off);
+      const U32 o = (U32) __shfl_xor ((int) mx, off); mx = o > mx ? o : mx;
+    }
+  if ((threadIdx.x & 63) == 0) { if (sum) atomicAdd (&out[0], sum); if (mx) atomicMax (&out[1], (unsigned long long) mx); }
+}
+
+#define MG_TIGHT_PCT_DEFAULT 70      /* see MgTable.tightPct.  80 is 0.06 ms a step faster still on config 2 (DESIGN_EXPERIMENTS.md section L); 70 is what the full-size
+                                        parity cases (tests/fullsize_whole.py) force as their other geometry, and they expect the default to be no tighter */
+#define MG_TIGHT_PCT_CLAIMS 50       /* the same with MODGPU_MERGE_PLACE=0: the merge kernel's claims pay for the load */
+#define MG_TIGHT_MIN_R 1024u         /* a bucket keeps room for the spread of a later add's share around its mean (mgTableEnsure sizes by the mean) */
+
+/* insert a batch (ordinal order = array order); counters[0] = number of new entries afterwards */
+MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *scratch, hipStream_t st,
+                     const MgHistReq *counted, const MgSegSrc *segSrc)
+{
+  if (!n) return MG_OK;
+  if (segSrc && !mgTableAddTakesSegments (t, n, counted)) { mgSetError ("internal: this insert needs the dense k-mers"); return MG_ERR_ARG; }
+  const MgSegSrc noSrc = {};
+  t->liveHistValid = false;                          /* set again below if this add is the set's only one */
+  if (withDepth) t->pendingDepth = true;
+  const bool wasEmpty = t->empty && t->max == 0;
+  t->empty = false; ++t->version;
+  MgGeom g = mgGeomOf (t);
+  char *wb = (char *) scratch;
+  unsigned char *flags = (unsigned char *) wb;       wb += mgAl (n);
+  U64 *blockCount = (U64 *) wb;                      wb += mgAl ((MG_RANK_UNITS + 8) * 8);
+  U64 *blockBase = (U64 *) wb;                       wb += mgAl ((MG_RANK_UNITS + 8) * 8);
+  MgRankGrp *grp = (MgRankGrp *) wb;                 wb += mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
+  U32 nRankBlocks; U64 rankTiles = mgRankRowsPerUnit (n, &nRankBlocks);
+  MG_HIP (hipMemsetAsync (blockCount, 0, (MG_RANK_UNITS + 8) * 8, st));
+
+  if (!mgTableUseBuckets (t, n))
+    { U32 *slotId = (U32 *) wb;
+      { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+      MG_LAUNCH (MG_K_TABLE_INSERT, st, mgTableInsertKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, g, dKmer, n, slotId, withDepth, t->counters);
+      MG_LAUNCH (MG_K_TABLE_FLAG, st, mgDirectFlagKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, slotId, n, flags);
+      MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
+      MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
+      MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<true, false>), dim3 (nRankBlocks), dim3 (256), 0, st,
+                 flags, dKmer, noSrc, (const MgSubSeg *) 0, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, slotId, grp);
+      MG_HIP (hipGetLastError ());
+      /* occ[] is kept exact only by the bucketed path and the loader; the direct path marks buckets non-empty */
+      return mgTableMarkOccupied (t, dKmer, n, st);
+    }
+
+  /* ---- bucketed ---- */
+  const U64 NB = (U64) 1 << t->log2NB;
+  U64 *kA = (U64 *) wb;  wb += mgAl (n * 8);
+  U32 *tA = (U32 *) wb;  wb += mgAl (n * 4);
+  U64 *kB = (U64 *) wb;  wb += mgAl (n * 8);
+  U32 *tB = (U32 *) wb;  wb += mgAl (n * 4);
+  U32 *cB = (U32 *) wb;  wb += mgAl (n * 4);
+  U64 *fineStart = (U64 *) wb;                wb += mgAl ((NB + 2) * 8);
+  unsigned long long *fineCursor = (unsigned long long *) wb; wb += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
+  U64 *spare64 = (U64 *) wb;                  wb += mgAl ((NB + 2) * 8);
+  U32 *fineCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
+  U32 *uniqCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
+  U64 *coarseStart = (U64 *) wb;              wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
+  unsigned long long *coarseCursor = (unsigned long long *) wb; wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
+  U64 *whole = (U64 *) wb;                    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
+  U32 *coarseCount = (U32 *) wb;              wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
+  U32 *chunkBase = (U32 *) wb;                wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);   /* + the segment of every chunk */
+  unsigned short *sliceOff = (unsigned short *) wb;   wb += mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short));
+  MgSubSeg *subSeg = (MgSubSeg *) wb;         wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
+  U64 *hotItems = (U64 *) wb;                 wb += mgAl (mgHotItemsCap (n) * 8);
+  U32 *hotBuckets = (U32 *) wb;               wb += mgAl (mgHotItemsCap (n) * 4);
+  unsigned long long *hotCount = (unsigned long long *) wb; wb += 256;
+  (void) spare64;
+
+  /* split the bucket-id bits into a coarse digit (high) and a fine digit (low), each <= 9 bits */
+  const int j = t->log2NB;
+  int hiB, loB;
+  mgPartSplit (j, &hiB, &loB);
+  const U32 *pre = (counted && counted->binCount && counted->log2NB == j && counted->kbits == t->kbits && !counted->hiB) ? counted->binCount : 0;
+  U64 segInit[2] = { 0, n };
+  MG_HIP (hipMemcpyAsync (whole, segInit, 16, hipMemcpyHostToDevice, st));
+  /* element format: one packed 8-byte word when the mixed k-mer without its coarse digit and the ordinal fit in 64 bits */
+  const MgPartFmt f = mgPartFmtOf (t, n, hiB);
+  const int packEnv = mgKnobs ()->partPacked == MG_KNOB_UNSET ? 1 : (int) mgKnobs ()->partPacked;   /* test knob: 0 forces the wide format */
+  const bool packed = packEnv && mgPartFmtFits (t, f);
+  MgStatus s;
+  const U64 *bucketStart = fineStart;
+  MgPartPassArgs p1 = {};                /* the first pass: the batch, dense or in the scan's segments, by the coarse digit -- the only digit of a table of few buckets */
+  p1.inMode = segSrc ? MG_EL_SEG : MG_EL_DENSE; p1.packed = packed; p1.f = f; p1.kIn = dKmer; p1.n = n; p1.segStart = whole; p1.nSeg = 1;
+  p1.nBins = (U32) 1 << hiB; p1.chunkBase = chunkBase; p1.counted = pre; p1.segSrc = segSrc; p1.subSeg = subSeg;
+  if (!loB)
+    { p1.kOut = kB; p1.tOut = tB; p1.binStart = fineStart; p1.cursor = fineCursor; p1.binCount = fineCount;
+      if ((s = mgPartPass (t, p1, st))) return s;
+    }
+  else
+    { /* the first pass leaves every element's fine digit in a byte beside it (in cB, which the dedup kernel only writes later): the second
+         pass counts 156 MB of bytes instead of reading 1.25 GB of elements twice */
+      unsigned char *digits = (loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> (cB) : 0;
+      p1.shift = loB; p1.kOut = kA; p1.tOut = tA; p1.binStart = coarseStart; p1.cursor = coarseCursor; p1.binCount = coarseCount;
+      p1.digitOut = digits; p1.nextBins = (U32) 1 << loB;
+      if ((s = mgPartPass (t, p1, st))) return s;
+      MgPartPassArgs p2 = {};            /* the second pass: every coarse bin by the fine digit, into the buckets */
+      p2.inMode = packed ? MG_EL_PACKED : MG_EL_WIDE; p2.packed = packed; p2.f = f; p2.kIn = kA; p2.tIn = tA; p2.n = n; p2.segStart = coarseStart; p2.nSeg = (U32) 1 << hiB;
+      p2.nBins = (U32) 1 << loB; p2.kOut = kB; p2.tOut = tB; p2.binStart = fineStart; p2.cursor = fineCursor; p2.binCount = fineCount; p2.chunkBase = chunkBase;
+      p2.digitIn = digits;
+      if ((s = mgPartPass (t, p2, st))) return s;
+    }
+
+  MgBucketArgs a;
+  /* flag polarity from what the previous bucketed add saw (MgTable.newPct: new entries per 100 modimizers) */
+  { const int polEnv = mgKnobs ()->flagPolarity == MG_KNOB_UNSET ? -1 : (int) mgKnobs ()->flagPolarity;   /* test knob: 0 / 1 force it */
+    a.markDup = polEnv >= 0 ? (polEnv ? 1 : 0) : (t->newPct > 50 ? 1 : 0);
+  }
+  MG_HIP (hipMemsetAsync (flags, a.markDup ? 1 : 0, n, st));
+  /* the merge kernel takes the slots from the dedup kernel when the buckets will be more than half full (there its
+     probing costs more than the dedup kernel's extra work: a 12.5 Gbp block at load 0.62 gains 0.4 ms, config 2 at 0.38
+     nothing); the load is estimated from the share of new k-mers the previous add saw */
+  const U64 expectNew = t->newPct > 0 ? n * (U64) t->newPct / 100 : n;
+  { const int slotEnv = mgKnobs ()->mergeSlots == MG_KNOB_UNSET ? -1 : (int) mgKnobs ()->mergeSlots;   /* test knob: 0 / 1 force it */
+    const bool dense = ((U64) t->max + expectNew) * 2 > t->nSlots;
+    a.slotShift = (t->kbits <= MG_SLOT_SHIFT && (slotEnv >= 0 ? slotEnv != 0 : dense)) ? MG_SLOT_SHIFT : 0;
+  }
+  /* An add into an EMPTY table (a set built from one batch: every step of the benchmarks, the first file of a run) does not know its
+     entries until the dedup kernel has counted them -- the table was sized from the batch's occurrences, an upper bound -- and nothing is
+     in the table yet, so its geometry is still free: after the dedup kernel R can be brought down to what the entries need at the tight
+     load, and the merge kernel streams back that much less.  The price: the dedup kernel's image is then not the merge kernel's, so no
+     slots are carried over and the merge kernel claims its own -- and a workgroup waits for its LONGEST probe chain (8 links at load 0.38,
+     30 at 0.6, 80 at 0.75; profiles/r06_ab_table_geometry.txt: the merge kernel 1.07 / 1.20 / 1.44 / 2.5 ms at tight loads 50 / 60 / 70 / 80
+     per cent on config 2, against 0.65 ms with carried slots at load 0.77).  So the table is only tightened where that pays: when the share
+     of new k-mers the previous add saw (newPct; unknown: all new) says the entries will leave a quarter of the slots and more unused even at
+     the tight load -- reads of deep coverage with few errors (config 5: a sixth of the modimizers are new; 4.3 -> 1.07 GB of bucket images). */
+  int tightPct = t->tightPct ? t->tightPct : MG_TIGHT_PCT_CLAIMS;      /* (MG_TIGHT_PCT_DEFAULT below, where the merge kernel places by scan) */
+  { const long tk = mgKnobs ()->tightLoad; if (tk != MG_KNOB_UNSET && tk >= 0 && tk <= 95) tightPct = (int) tk; }
+  bool tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
+  if (tighten && mgKnobs ()->tightLoad == MG_KNOB_UNSET)          /* (the knob forces it: tests, sweeps) */
+    tighten = expectNew * 100 / (U64) tightPct < t->nSlots - t->nSlots / 4;
+  /* a bucket that is empty before the add is laid out by prefix scan in the merge kernel (mgPlaceStarts): no probe whatever the load,
+     so an add into an empty table has no use for the dedup kernel's slots, and the tightening costs the merge kernel nothing: it is
+     done whenever the table was empty and the scan is on (DESIGN_EXPERIMENTS.md section L).  Only lists without carried slots go
+     through the scan (the kernel checks a.slotShift): a later add that carries slots puts an empty bucket's entries where they say. */
+  { const long pk = mgKnobs ()->mergePlace;                        /* MODGPU_MERGE_PLACE: 0 = claims everywhere, 1 = the scan for every fresh bucket, unset = the rule below */
+    a.place = pk == MG_KNOB_UNSET ? 1 : (pk != 0);
+    /* Left to itself the placement is for lists the kernel's spill-free instance takes whole (the uniques fetched ahead: MG_MERGE_PREFETCH
+       per thread).  Where the buckets' lists will be longer -- a config-4 block: 2500 uniques per bucket and 1024 threads -- the add goes
+       as before (carried slots; 11.06 ms a step against 11.16-11.44 with the scan's larger instance and the table at load 0.8).
+       The lists' length is estimated from the share of new k-mers the previous add saw; the FIRST add a table ever sees has none to go by,
+       is taken as all new (n / NB = 0.75 R uniques per bucket: over the limit at every default geometry) and so goes as before too: the
+       scan and the tightening start with the second set a process builds from empty, which is every timed step of the benchmarks but not
+       the first file of a run.  Which instance fits is known exactly only after the dedup kernel -- too late for the choice between
+       the scan and carried slots, which the dedup kernel's own instance depends on. */
+    if (pk == MG_KNOB_UNSET && expectNew / NB * 115 / 100 > (U64) MG_MERGE_PREFETCH * mgBucketThreads (t->R, 0)) a.place = 0;   /* (0: this rule has never looked at MODGPU_BUCKET_T) */
+    if (a.place && wasEmpty) a.slotShift = 0;
+    if (a.place && mgKnobs ()->tightLoad == MG_KNOB_UNSET)
+      { if (!t->tightPct) tightPct = MG_TIGHT_PCT_DEFAULT;
+        tighten = wasEmpty && tightPct > 0 && t->log2NB > 0 && t->pin;
+      }
+  }
+  if (tighten) a.slotShift = 0;
+  a.slots = t->slots; a.g = g; a.nBuckets = (U32) NB; a.bucketStart = bucketStart;
+  a.pK = kB; a.pT = tB; a.pC = cB; a.uniqCount = uniqCount; a.occ = t->occ; a.flags = flags;
+  a.grp = grp; a.baseMax = t->max; a.size = t->size; a.withDepth = withDepth;
+  /* slices of the ordinal range for the rank lookups: 2^sliceShift ordinals each (2^22: 1 MiB of rank records, and a
+     bucket's share of a slice is usually shorter than a wave), at most MG_RANK_GROUPS - 1 of them */
+  { a.sliceShift = 22;
+    /* a batch much smaller than the headline's would be three or four slices -- and the lookup kernel gives a slice to an XCD, so half
+       the chip would idle (1 Gbp batches, as the file entry points make them: the rank lookups 0.31 ms of 1.39, with 2^18-ordinal slices
+       0.11 of 1.11): smaller slices until there are 32 of them */
+    while (a.sliceShift > 16 && ((n - 1) >> a.sliceShift) + 1 < 32) --a.sliceShift;
+    if (mgKnobs ()->rankSliceShift != MG_KNOB_UNSET) a.sliceShift = (int) mgKnobs ()->rankSliceShift;   /* dev knob */
+    while (((n - 1) >> a.sliceShift) + 1 > (U64) (MG_RANK_GROUPS - 1)) ++a.sliceShift;
+    a.nSlices = (U32) (((n - 1) >> a.sliceShift) + 1);
+    a.sliceOff = sliceOff;
+  }
+  a.counters = t->counters; a.f = f;
+#ifdef MG_ABLATE
+  { const long dbg = mgKnobs ()->bucketDebug; a.debug = dbg != MG_KNOB_UNSET ? (int) dbg : 0; }
+#endif
+  /* depth histogram on the fly: possible when this add builds the whole set (empty before, no host depths) */
+  const bool track = t->max == 0 && t->baseZero;
+  a.liveHist = 0;
+  if (track)
+    { if (!t->liveHist) MG_HIP (hipMalloc ((void **) &t->liveHist, 65536 * sizeof (U64)));
+      MG_HIP (hipMemsetAsync (t->liveHist, 0, 65536 * sizeof (U64), st));
+      a.liveHist = (unsigned long long *) t->liveHist;
+    }
+  t->liveHistValid = track;
+  size_t lds = mgMergeLdsBytes (t->R);
+  { const size_t ldsDedup = (size_t) t->R * 16 + MG_RANK_GROUPS * 4; if (ldsDedup > lds) lds = ldsDedup; }
+  const bool bigR = t->R > MG_DEDUP_PER * 1024u;       /* R = 8192: the dedup kernel's threads take eight slots each */
+  if (t->R > MG_DEDUP_PER_BIG * 1024u) { mgSetError ("internal: bucket of %u slots", t->R); return MG_ERR_ARG; }
+  if (lds > 48 * 1024)
+    {
+#define MG_DEDUP_ATTR(PK, SL, PER) do { MG_HIP (hipFuncSetAttribute ((const void *) mgBucketDedupKernel<PK, SL, PER, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
+                                        MG_HIP (hipFuncSetAttribute ((const void *) mgBucketDedupKernel<PK, SL, PER, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); } while (0)
+      if (bigR) { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER_BIG); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER_BIG); }
+      else      { MG_DEDUP_ATTR (true, true, MG_DEDUP_PER); MG_DEDUP_ATTR (true, false, MG_DEDUP_PER); MG_DEDUP_ATTR (false, true, MG_DEDUP_PER); MG_DEDUP_ATTR (false, false, MG_DEDUP_PER); }
+#undef MG_DEDUP_ATTR
+      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_MERGE_PREFETCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+      MG_HIP (hipFuncSetAttribute ((const void *) mgBucketMergeKernel<MG_PLACE_KEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    }
+  const int bThreadsEnv = mgKnobs ()->bucketT == MG_KNOB_UNSET ? 0 : (int) mgKnobs ()->bucketT;
+  const unsigned bThreads = mgBucketThreads (t->R, bThreadsEnv);
+  U32 perBlock;
+  const unsigned bGrid = mgBucketGrid (NB, &perBlock);
+  if ((U64) bThreads * (bigR ? MG_DEDUP_PER_BIG : MG_DEDUP_PER) < t->R)      /* every slot of the image must belong to a thread of the closing sweep */
+    { mgSetError ("internal: %u threads for a bucket of %u slots", bThreads, t->R); return MG_ERR_ARG; }
+  /* oversize buckets first: their chunks reduced to weighted entries by a workgroup each (nothing to do on ordinary data:
+     the plan finds no bucket and the reduce kernel's workgroups leave at once) */
+  mgHotKnobs (&a.hotSplit, &a.hotChunk);
+  a.hotItems = hotItems; a.hotCount = hotCount; a.hotBuckets = hotBuckets;
+  MG_HIP (hipMemsetAsync (hotCount, 0, 16, st));
+  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotPlanKernel, dim3 ((unsigned) ((NB + 255) / 256)), dim3 (256), 0, st, a);
+  { const size_t ldsHot = (size_t) t->R * 16 + 16;
+    if (packed) { if (ldsHot > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgHotReduceKernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsHot));
+                  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotReduceKernel<true>, dim3 (1024), dim3 (bThreads), ldsHot, st, a); }
+    else        { if (ldsHot > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgHotReduceKernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsHot));
+                  MG_LAUNCH (MG_K_HOT_REDUCE, st, mgHotReduceKernel<false>, dim3 (1024), dim3 (bThreads), ldsHot, st, a); }
+  }
+#define MG_DEDUP_LAUNCH(PK, SL, PER) do { MG_LAUNCH (MG_K_BUCKET_DEDUP, st, (mgBucketDedupKernel<PK, SL, PER, false>), dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock); \
+                                          MG_LAUNCH (MG_K_HOT_REDUCE, st, (mgBucketDedupKernel<PK, SL, PER, true>), dim3 (64), dim3 (bThreads), lds, st, a, perBlock); } while (0)
+#define MG_DEDUP_PICK(PER) do { if (packed) { if (a.slotShift) MG_DEDUP_LAUNCH (true, true, PER); else MG_DEDUP_LAUNCH (true, false, PER); } \
+                                else        { if (a.slotShift) MG_DEDUP_LAUNCH (false, true, PER); else MG_DEDUP_LAUNCH (false, false, PER); } } while (0)
+  if (bigR) MG_DEDUP_PICK (MG_DEDUP_PER_BIG); else MG_DEDUP_PICK (MG_DEDUP_PER);
+#undef MG_DEDUP_PICK
+#undef MG_DEDUP_LAUNCH
+  U64 fullest = t->R;                                  /* the longest list a bucket may have: not known unless the tightening counts it */
+  if (tighten)
+    { unsigned long long *st2 = (unsigned long long *) (t->counters + 2);
+      MG_HIP (hipMemsetAsync (st2, 0, 16, st));
+      MG_LAUNCH (MG_K_RANK_SCAN, st, mgUniqStatsKernel, dim3 ((unsigned) (NB / 256 < 256 ? (NB + 255) / 256 : 256)), dim3 (256), 0, st, uniqCount, (U32) NB, st2);
+      MG_HIP (hipMemcpyAsync (t->pin, t->counters + 1, 24, hipMemcpyDeviceToHost, st));      /* overflow flag, entries, the fullest bucket's */
+      MG_HIP (hipStreamSynchronize (st));
+      const U64 over = t->pin[0], U = t->pin[1], M = t->pin[2];
+      if (!over)
+        { fullest = M;
+          U64 Rn = (U * 100 / ((U64) NB * (U64) tightPct) + 1 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;
+          const U64 Rfit = (M + M / 8 + 16 + MG_R_QUANTUM - 1) / MG_R_QUANTUM * MG_R_QUANTUM;      /* the fullest bucket at load 0.89 at most */
+          if (Rn < Rfit) Rn = Rfit;
+          if (Rn < MG_TIGHT_MIN_R) Rn = MG_TIGHT_MIN_R;
+          if (Rn < t->R)
+            { t->R = (U32) Rn; t->nSlots = (U64) NB * Rn; a.g = mgGeomOf (t);
+              lds = mgMergeLdsBytes (t->R);
+            }
+        }
+    }
+  MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
+  MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
+  if (segSrc)
+    MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, true>), dim3 (nRankBlocks), dim3 (256), 0, st,
+               flags, (const U64 *) 0, *segSrc, subSeg, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, (const U32 *) 0, grp);
+  else
+    MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, false>), dim3 (nRankBlocks), dim3 (256), 0, st,
+               flags, dKmer, noSrc, (const MgSubSeg *) 0, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, (const U32 *) 0, grp);
+  { const U32 groupsPerSlice = (U32) ((NB + 63) / 64);
+    const U32 blocksPerSlice = (groupsPerSlice + 3) / 4, rounds = (a.nSlices + 7) / 8;
+    MG_LAUNCH (MG_K_RANK_LOOKUP, st, mgRankLookupKernel, dim3 (8 * rounds * blocksPerSlice), dim3 (256), 0, st, a, groupsPerSlice);
+  }
+  /* the scan placement keeps a register per unique: the instance that takes only the uniques fetched ahead where no list is longer (the
+     tightening has counted the fullest bucket's; otherwise by the bucket's size), the one with MG_PLACE_KEEP otherwise (it spills a little) */
+  if (fullest <= (U64) MG_MERGE_PREFETCH * bThreads)
+    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_MERGE_PREFETCH>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
+  else
+    MG_LAUNCH (MG_K_BUCKET_MERGE, st, mgBucketMergeKernel<MG_PLACE_KEEP>, dim3 (bGrid), dim3 (bThreads), lds, st, a, perBlock);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+__global__ void mgMarkOccKernel (MgGeom g, const U64 *__restrict__ kmer, U64 n, U32 *__restrict__ occ)
+{
+  U64 o = (U64) blockIdx.x * blockDim.x + threadIdx.x;
+  const U64 stride = (U64) gridDim.x * blockDim.x;
+  for ( ; o < n ; o += stride)
+    { U32 b = mgBucketOfM (mgMixK (kmer[o], g.kbits), g);
+      if (!occ[b]) occ[b] = 1;
+    }
+}
+
+MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st)
+{
+  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgMarkOccKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, mgGeomOf (t), dKmer, n, t->occ);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipStream_t st)
+{
+  if (!n) return MG_OK;
+  /* with the never-written buckets zeroed once, a probe needs no look at occ[] first */
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  const unsigned fgrid = mgGrid ((n + MG_FIND_PER - 1) / MG_FIND_PER);
+  ++t->diag[MG_DIAG_FIND_DIRECT];
+  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableFindKernel<false>, dim3 (fgrid), dim3 (256), 0, st, t->slots, t->occ, mgGeomOf (t), dKmer, n, dIndexOut);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* A check of the table's layout that does not go through the lookups: a thread per slot walks from its key's home to the slot.
+   out[0] += keys whose walk crosses an empty slot (a lookup would stop there), out[1] += keys in a bucket other than the one they
+   imply, out[2] += keys met a second time on that walk (a duplicate inside the bucket), out[3] += keys */
+__global__ __launch_bounds__ (256)
+void mgTableCheckLayoutKernel (const MgSlot *__restrict__ slots, MgGeom g, U64 nSlots, unsigned long long *__restrict__ out)
+{
+  const U64 stride = (U64) gridDim.x * blockDim.x;
+  U32 broken = 0, stray = 0, dup = 0, keys = 0;
+  for (U64 o = (U64) blockIdx.x * blockDim.x + threadIdx.x ; o < nSlots ; o += stride)
+    { const uint4 v = *reinterpret_cast<const uint4 *> (&slots[o]);
+      const U64 key = mgKeyOf (v);
+      if (!key) continue;
+      ++keys;
+      const U32 bkt = (U32) (o / g.R), me = (U32) (o - (U64) bkt * g.R);
+      const U64 m = key - 1;
+      if (mgBucketOfM (m, g) != bkt) { ++stray; continue; }
+      const U64 base = (U64) bkt * g.R;
+      for (U32 at = mgHomeOfM (m, g) ; at != me ; at = mgNextSlot (at, g.R))
+        { const uint4 w = *reinterpret_cast<const uint4 *> (&slots[base + at]);
+          const U64 k2 = mgKeyOf (w);
+          if (!k2) { ++broken; break; }
+          if (k2 == key) { ++dup; break; }
+        }
+    }
+  if (broken) atomicAdd (&out[0], (unsigned long long) broken);
+  if (stray) atomicAdd (&out[1], (unsigned long long) stray);
+  if (dup) atomicAdd (&out[2], (unsigned long long) dup);
+  if (keys) atomicAdd (&out[3], (unsigned long long) keys);
+}
+
+/* dOut: four device words (see the kernel), zeroed here */
+MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut, hipStream_t st)
+{
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  MG_HIP (hipMemsetAsync (dOut, 0, 32, st));
+  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableCheckLayoutKernel, dim3 (mgGrid (t->nSlots)), dim3 (256), 0, st, t->slots, mgGeomOf (t), t->nSlots, (unsigned long long *) dOut);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dIndexOut, hipStream_t st)
+{
+  if (!n) return MG_OK;
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  const U64 nRows = (n + 63) / 64;
+  U64 waves = 256ull * 4 * 8;                           /* eight waves per SIMD */
+  if (waves > nRows) waves = nRows;
+  const U64 rowsPerWave = (nRows + waves - 1) / waves;
+  waves = (nRows + rowsPerWave - 1) / rowsPerWave;
+  ++t->diag[MG_DIAG_FIND_DIRECT];
+  MG_LAUNCH (MG_K_TABLE_FIND_SEG, st, mgTableFindSegKernel, dim3 ((unsigned) ((waves + 3) / 4)), dim3 (256), 0, st, t->slots, mgGeomOf (t), src, n, rowsPerWave, dIndexOut);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* scratch of the partitioned lookup for a batch of n: the run table and the partition's small arrays (the packed elements,
+   8 bytes each, go where the caller says: the scan's unused dense k-mer array) */
+size_t mgTableFindPartScratchBytes (U64 n)
+{
+  return mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8) + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 2
+       + mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16) + mgAl ((MG_PART_MAXBINS + 2) * 4)
+       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg)) + 4096;
+}
+
+/* the two-level path's extra scratch: the second pass's output (8 bytes an element), the results beside the first pass's output
+   (4), the second run table, the fine starts / cursors / counts and its chunk table */
+size_t mgTableFindPart2ScratchBytes (U64 n)
+{
+  const U64 NB = (U64) 1 << 18;
+  return mgAl (n * 8) + mgAl (n * 4) + mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8)
+       + mgAl ((NB + 2) * 8) + mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8) + mgAl ((NB + 2) * 4)
+       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + 4096;
+}
+
+/* does a lookup batch take the partitioned path?  It needs the scan's digit counts for this table geometry, elements that
+   fit one word, and a table the direct probes would have to fetch from HBM */
+/* The digit of the partitioned lookup: the top bits of the bucket id one pass sorts by; a bin's piece of the table is
+   nSlots * 16 bytes >> bits (MODGPU_FIND_BITS: dev, 3..9) */
+int mgTableFindDigitBits (const MgTable *t)
+{
+  const long kb = mgKnobs ()->findBits;
+  int hiB, loB; mgPartSplit (t->log2NB, &hiB, &loB);          /* the build's own first digit: 256 bins of 8 MB at config 3 (512 bins of 4 MB: scatter and pull-back cost 0.7 ms more, the lookups gain nothing) */
+  int bits = kb != MG_KNOB_UNSET && kb >= 3 && kb <= 9 ? (int) kb : hiB;
+  if (bits > t->log2NB) bits = t->log2NB;
+  return bits;
+}
+
+bool mgTableFindTakesPartition (const MgTable *t, U64 n, const MgHistReq *counted)
+{
+  const long kp = mgKnobs ()->findPath;                      /* test knob: 'p' / 'd' force it */
+  if (kp == 'd') return false;
+  if (!n || !counted || !counted->binCount || counted->log2NB != t->log2NB || counted->kbits != t->kbits) return false;
+  const int hiB = counted->hiB;
+  if (hiB != mgTableFindDigitBits (t)) return false;
+  if (!mgPartFmtFits (t, mgPartFmtOf (t, n, hiB)) || hiB < 3) return false;
+  if (t->kbits < 24 || mgKnobs ()->scanHist == 0) return false;          /* (the counts must be the scan's own: mgLaunchScanRange) */
+  if (kp == 'p' || kp == '2') return true;
+  /* by itself: the two-level path where the direct probes would fetch a line from HBM per lookup -- a table of 256 MB and more,
+     a batch that fills the chip (config 3: 3.5 against 4.2-4.6 ms per 1.56e8 lookups; one level ties with the direct probes) */
+  return n >= ((U64) 1 << 24) && t->nSlots >= ((U64) 1 << 24) && t->log2NB > 9;
+}
+
+MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, const MgHistReq *counted, U32 *dIndexOut, U64 *el, void *scratch, hipStream_t st,
+                                 void *scratch2)
+{
+  if (!n) return MG_OK;
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  char *wb = (char *) scratch;
+  unsigned long long *runTab = (unsigned long long *) wb;    wb += mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8);
+  U64 *binStart = (U64 *) wb;                                wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
+  U64 *whole = (U64 *) wb;                                   wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
+  unsigned long long *cursor = (unsigned long long *) wb;    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
+  U32 *binCount = (U32 *) wb;                                wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
+  U32 *chunkBase = (U32 *) wb;                               wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
+  MgSubSeg *subSeg = (MgSubSeg *) wb;                        wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
+  const int hiB = counted->hiB, loB = t->log2NB - hiB;
+  const MgPartFmt f = mgPartFmtOf (t, n, hiB);
+  const U32 nBins = (U32) 1 << hiB;
+  U64 segInit[2] = { 0, n };
+  MG_HIP (hipMemcpyAsync (whole, segInit, 16, hipMemcpyHostToDevice, st));
+  const bool twoLevels = scratch2 && loB > 0 && ((U32) 1 << loB) <= MG_PART_MAXBINS;
+  /* (two levels) the fine digits as bytes beside the first pass's output, for the second pass's counts: in idxA, which is only written by the first pull */
+  unsigned char *digits = (twoLevels && loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> ((char *) scratch2 + mgAl (n * 8)) : 0;
+  MgPartPassArgs p1 = {};                /* the build's first pass: from the scan's segments and its counts into el, by the coarse digit; runTab says where every sub-chunk went */
+  p1.inMode = MG_EL_SEG; p1.packed = true; p1.f = f; p1.n = n; p1.segStart = whole; p1.nSeg = 1; p1.shift = loB; p1.nBins = nBins;
+  p1.kOut = el; p1.binStart = binStart; p1.cursor = cursor; p1.binCount = binCount; p1.chunkBase = chunkBase;
+  p1.counted = counted->binCount; p1.segSrc = &segSrc; p1.subSeg = subSeg; p1.runTab = runTab; p1.digitOut = digits; p1.nextBins = (U32) 1 << loB;
+  MgStatus s = mgPartPass (t, p1, st);
+  if (s) return s;
+  const U32 subElems = p1.subElems;
+  if (twoLevels)      /* ---- two levels: the lookups bucket by bucket out of LDS (a table of few buckets has no fine digit: one level) ---- */
+    { char *w2 = (char *) scratch2;
+      const U64 NB = (U64) 1 << t->log2NB;
+      U64 *el2 = (U64 *) w2;                                   w2 += mgAl (n * 8);
+      U32 *idxA = (U32 *) w2;                                  w2 += mgAl (n * 4);
+      unsigned long long *runTab2 = (unsigned long long *) w2; w2 += mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8);
+      U64 *fineStart = (U64 *) w2;                             w2 += mgAl ((NB + 2) * 8);
+      unsigned long long *fineCursor = (unsigned long long *) w2; w2 += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
+      U32 *fineCount = (U32 *) w2;                             w2 += mgAl ((NB + 2) * 4);
+      U32 *chunkBase2 = (U32 *) w2;                            w2 += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
+      const U32 nBins2 = (U32) 1 << loB;
+      MgPartPassArgs p2 = {};            /* the second pass: el's bins by the fine digit into el2, every element's ordinal replaced by its place in el (runMode 1) */
+      p2.inMode = MG_EL_PACKED; p2.packed = true; p2.f = f; p2.kIn = el; p2.n = n; p2.segStart = binStart; p2.nSeg = nBins; p2.nBins = nBins2;
+      p2.kOut = el2; p2.binStart = fineStart; p2.cursor = fineCursor; p2.binCount = fineCount; p2.chunkBase = chunkBase2;
+      p2.runTab = runTab2; p2.runMode = 1; p2.digitIn = digits;
+      if ((s = mgPartPass (t, p2, st))) return s;
+      const U32 sub2 = p2.subElems;
+      U32 perBlock;
+      const unsigned bGrid = mgBucketGrid (NB, &perBlock);
+      const int remB = t->kbits - t->log2NB;
+      if (remB >= 1 && remB <= 32 && mgKnobs ()->find8 != 0)          /* (rem + 1 <= 2^32 above a 31-bit index: one word) */       /* (test knob MODGPU_FIND8=0: the 16-byte table itself) */
+        { if (!t->find8 || t->find8Version != t->version || t->find8Cap < t->nSlots)
+            { if (t->find8Cap < t->nSlots)
+                { if (t->find8) { MG_HIP (hipStreamSynchronize (st)); MG_HIP (hipFree (t->find8)); t->find8 = 0; t->find8Cap = 0; }
+                  MG_HIP (hipMalloc ((void **) &t->find8, t->nSlots * sizeof (U64)));
+                  t->find8Cap = t->nSlots;
+                }
+              ++t->diag[MG_DIAG_PACK8];
+              MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTablePack8Kernel, dim3 ((unsigned) (NB < 8192 ? NB : 8192)), dim3 (256), 0, st, t->slots, t->occ, (U32) NB, t->R, remB, t->find8);
+              t->find8Version = t->version;
+            }
+          const size_t lds8 = (size_t) t->R * 8 + 16;
+          if (lds8 > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFindKernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds8));
+          ++t->diag[MG_DIAG_FIND_PART2_8];
+          MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFindKernel<true>, dim3 (bGrid), dim3 (1024), lds8, st, t->slots, t->find8, t->occ, mgGeomOf (t), f, (U32) NB, remB, fineStart, el2, perBlock);
+        }
+      else
+        { const size_t lds = (size_t) t->R * 12 + 16;
+          if (lds > 48 * 1024) MG_HIP (hipFuncSetAttribute ((const void *) mgBucketFindKernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+          ++t->diag[MG_DIAG_FIND_PART2_16];
+          MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBucketFindKernel<false>, dim3 (bGrid), dim3 (1024), lds, st, t->slots, (const U64 *) 0, t->occ, mgGeomOf (t), f, (U32) NB, 0, fineStart, el2, perBlock);
+        }
+      const unsigned g2 = 2 * p2.maxChunks < 2048 ? 2 * p2.maxChunks : 2048;
+      mgForSub (sub2, [&] (auto S) { MG_LAUNCH (MG_K_UNPART, st, mgUnpartPosKernel<decltype (S)::value>, dim3 (g2), dim3 (1024), 0, st, el2, runTab2, nBins2, binStart, chunkBase2, nBins, 2 * sub2, idxA); });
+      const U64 nSub1 = (n + subElems - 1) / subElems;
+      const unsigned g1 = (unsigned) (nSub1 < 2048 ? nSub1 : 2048);
+      mgForSub (subElems, [&] (auto S) { MG_LAUNCH (MG_K_UNPART, st, mgUnpartOrdKernel<decltype (S)::value>, dim3 (g1), dim3 (1024), 0, st, el, idxA, f.ordBits, runTab, nBins, n, dIndexOut); });
+      MG_HIP (hipGetLastError ());
+      return MG_OK;
+    }
+  const U32 wgPerXcd = 256;                                  /* 2048 workgroups of 256: eight waves per SIMD */
+  ++t->diag[MG_DIAG_FIND_PART1];
+  MG_LAUNCH (MG_K_BUCKET_FIND, st, mgBinFindKernel, dim3 (8 * wgPerXcd), dim3 (256), 0, st, t->slots, mgGeomOf (t), f, el, binStart, nBins, wgPerXcd);
+  const U64 nSub = (n + subElems - 1) / subElems;
+  const unsigned ug = (unsigned) (nSub < 2048 ? nSub : 2048);
+  mgForSub (subElems, [&] (auto S) { MG_LAUNCH (MG_K_UNPART, st, mgUnpartKernel<decltype (S)::value>, dim3 (ug), dim3 (1024), 0, st, el, runTab, nBins, n, dIndexOut); });
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* the loader, waited for; *over != 0: a bucket had no room for one of the values (the others are in) */
+static MgStatus mgLoadLaunch (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st, U64 *over)
+{
+  MG_HIP (hipMemsetAsync (t->counters + 1, 0, 8, st));
+  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGrid ((U64) last - first + 1)), dim3 (256), 0, st,
+             t->slots, mgGeomOf (t), dValue, first, last, t->occ, t->counters);
+  MG_HIP (hipGetLastError ());
+  return mgReadOverflow (t, st, over);
+}
+
+MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st)
+{
+  if (last < first) return MG_OK;
+  t->liveHistValid = false; t->empty = false; ++t->version;
+  { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
+  U64 over = 0;
+  MgStatus s = mgLoadLaunch (t, dValue, first, last, st, &over);
+  if (s || !over) return s;
+  /* A bucket had no room: the table was sized by the mean (mgTableEnsure) and these values crowd one bucket.  The entries that found
+     a slot stay where they are; the table goes into a geometry that holds the fullest bucket of ALL the values (value[1 .. last]:
+     what is in the table and what was left out), and the values are loaded again -- those already there are met as duplicates. */
+  int lg = 0; U32 R = 0;
+  U32 *dFine = 0;
+  if (hipMalloc ((void **) &dFine, sizeof (U32) << MG_FINE_LOG2) != hipSuccess) return mgHipFail (hipGetLastError (), "hipMalloc");
+  if (hipMemsetAsync (dFine, 0, sizeof (U32) << MG_FINE_LOG2, st) != hipSuccess) s = mgHipFail (hipGetLastError (), "hipMemsetAsync");
+  else
+    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountValuesKernel, dim3 (mgGrid (last)), dim3 (256), 0, st, dValue, 1u, last, t->kbits, dFine);
+      s = mgFitGeometry (t, dFine, mgSlotsFor (t, last), &lg, &R, st);
+    }
+  (void) hipFree (dFine);
+  if (!s) s = mgTableRehashExact (t, lg, R, st);
+  if (s) return s;
+  if ((s = mgLoadLaunch (t, dValue, first, last, st, &over))) return s;
+  if (over) { mgSetError ("internal: the device table's fitted geometry (2^%d x %u) does not hold the host's entries", lg, R); return MG_ERR_CAPACITY; }
+  return MG_OK;
+}
+
+MgStatus mgTableExportDepth (MgTable *t, U16 *dDelta, hipStream_t st)
+{
+  if (!t->max) return MG_OK;
+  MG_HIP (hipMemsetAsync (dDelta, 0, (size_t) t->max * sizeof (U16), st));
+  t->baseZero = false;                                   /* the fold below writes baseDepth */
+  t->pendingDepth = false;
+  t->liveHistValid = false;
+  { const U32 NB = (U32) 1 << t->log2NB;
+    MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgTableExportDepthKernel, dim3 (NB < 8192 ? NB : 8192), dim3 (256), 0, st,
+               t->slots, NB, t->occ, t->R, t->baseDepth, dDelta, t->max);
+  }
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* dHist[i] += live[i] */
+__global__ void mgHistAddKernel (const U64 *__restrict__ live, unsigned long long *__restrict__ hist)
+{ U32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i < 65536 && live[i]) atomicAdd (&hist[i], (unsigned long long) live[i]); }
+
+MgStatus mgTableHistogram (MgTable *t, U64 *dHist, hipStream_t st)
+{
+  if (!t->max) return MG_OK;
+  if (t->liveHistValid && t->liveHist)                 /* the merge kernel kept it while it built the set */
+    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgHistAddKernel, dim3 (256), dim3 (256), 0, st, t->liveHist, (unsigned long long *) dHist);
+      MG_HIP (hipGetLastError ());
+      return MG_OK;
+    }
+  { const U32 NB = (U32) 1 << t->log2NB;
+    MG_LAUNCH (MG_K_TABLE_HIST, st, mgTableHistKernel, dim3 (NB < 2048 ? NB : 2048), dim3 (256), 0, st,
+               t->slots, NB, t->occ, t->R, t->baseZero ? (const U16 *) 0 : t->baseDepth, (unsigned long long *) dHist);
+  }
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+MgStatus mgTableReplayIndex (MgTable *t, const MgHashParams &p, int tableBits, U32 *dIndex, hipStream_t st)
+{
+  U64 n = (U64) 1 << tableBits;
+  MG_HIP (hipMemsetAsync (dIndex, 0xff, n * sizeof (U32), st));
+  if (t->max)
+    { MG_LAUNCH (MG_K_INDEX_REPLAY, st, mgReplayIndexKernel, dim3 (mgGrid (t->max)), dim3 (256), 0, st,
+                          t->value, t->max, p.factor1, p.shift1, tableBits, dIndex);
+      MG_HIP (hipGetLastError ());
+    }
+  MG_LAUNCH (MG_K_INDEX_FINISH, st, mgIndexFinishKernel, dim3 (mgGrid (n, 256, 8192)), dim3 (256), 0, st, dIndex, n);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+
+/* ======================================================================================== */
 /* whole-set passes on the device: merge (modset.c:106-128) and depth prune (modset.c:64-77)  */
 
 /* after ms2's values were inserted (idx[i] = their index in ms1): depth adds saturate at 65535;
@@ -2980,7 +2961,7 @@ MgStatus mgTablePrune (MgTable *t, const U8 *dInfo, int lo, int hi, U64 *dNewVal
   MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nBlocks), dim3 (256), 0, st, keep, (U64) n, rows, unitCount);
   MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, unitCount, nBlocks * 4, unitBase, t->counters);
   /* value[i+1] of survivor i -> newValue[1 + rank]: the assign kernel with "kmer" = value + 1, base 0 */
-  MgSegSrc noSrc; noSrc.segKmer = 0; noSrc.segCount = 0; noSrc.segStart = 0; noSrc.segCap = 0; noSrc.nSegs = 0;
+  const MgSegSrc noSrc = {};
   MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, false>), dim3 (nBlocks), dim3 (256), 0, st,
              keep, t->value + 1, noSrc, (const MgSubSeg *) 0, (U64) n, rows, unitBase, 0u, 0xffffffffu, dNewValue, t->slots, (const U32 *) 0, grp);
   MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgPruneMoveKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, keep, grp, n, t->baseDepth, dInfo, dNewDepth, dNewInfo);

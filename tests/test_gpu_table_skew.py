@@ -163,6 +163,17 @@ def test_lookup_paths_really_taken(k, entries, log2nb, rem):
         want = oracle_answers(oms, q)
         assert (want != 0).sum() == len(present) and (want == 0).sum() == len(absent) + len(late)
         ask_every_path(ms, reads, len(q), want, rem, "k=%d" % k)
+        if (k, entries, rem) == (21, 200_000, 31):
+            # the scatter and the pulls at the small sub-chunk size (by default only the 16384-element instances run), and the second
+            # pass counting its digits from the elements instead of the bytes the first pass leaves
+            for knob in ({"PART_BIG": 0}, {"PART_DIGITS": 0}):
+                with mg.knobs(**knob):
+                    ask_every_path(ms, reads, len(q), want, rem, "k=%d %s" % (k, knob))
+            # a batch that ends exactly on a tile boundary of the pulls (16384 results a tile), and one result beyond it
+            for m in (16384, 16384 + 1):
+                _, sb, so = util.kmer_reads(oh, q[:m], k)
+                assert len(so) - 1 == m
+                ask_every_path(ms, Reads(sb, so), m, want[:m], rem, "k=%d, %d lookups" % (k, m))
         assert layout(ms)[:4] == [0, 0, 0, oms.max]
         with mg.knobs(FIND_PATH="2", FIND8=1):
             d1 = diag(ms)

@@ -15,5 +15,5 @@ for line in open(out):
     m = re.match(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", line)
     if m and name:
         info[m.group(1)] = int(m.group(2))
-        if m.group(1) == "LDSByteSize" and flt in name:
+        if m.group(1) == "Occupancy" and flt in name:      # the last of the five in the compiler's listing
             print("%-90s vgpr %3d agpr %3d scratch %4d occupancy %d" % (name[:90], info.get("NumVgprs", -1), info.get("NumAgprs", 0), info.get("ScratchSize", -1), info.get("Occupancy", -1)))
