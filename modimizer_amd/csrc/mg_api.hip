@@ -218,10 +218,9 @@ struct MgArena {
     return MG_OK;
   }
   void reset () { used = 0; }
-  void *take (size_t n) { size_t a = (used + 255) & ~(size_t) 255; used = a + n; return base + a; }
+  void *take (size_t n) { size_t a = mgAl256 (used); used = a + n; return base + a; }
   void release () { if (base) (void) hipFree (base); base = 0; bytes = used = 0; }
 };
-static inline size_t al256 (size_t n) { return (n + 255) & ~(size_t) 255; }
 
 static U64 mgSurvivorGuess (const Seqhash *sh, U64 totalBases)
 {
@@ -330,8 +329,8 @@ extern "C" int64_t seqhashScanBatch (const Seqhash *sh, const char *bases, const
   int64_t result = -1;
   U64 *hK = 0; U32 *hP = 0, *hR = 0;
   for (int attempt = 0 ; attempt < 3 ; ++attempt)
-    { size_t need = al256 (nw * 4) + al256 (((size_t) nReads + 1) * 8) + al256 (cap * 8) + 2 * al256 (cap * 4)
-                    + al256 (mgScanWorkBytes (total, (U32) nReads, cap)) + 4096;
+    { size_t need = mgAl256 (nw * 4) + mgAl256 (((size_t) nReads + 1) * 8) + mgAl256 (cap * 8) + 2 * mgAl256 (cap * 4)
+                    + mgAl256 (mgScanWorkBytes (total, (U32) nReads, cap)) + 4096;
       if (ar.reserve (need)) break;
       ar.reset ();
       U32 *dP = (U32 *) ar.take (nw * 4);
@@ -407,7 +406,7 @@ static int64_t mgMinimizersHost (const Seqhash *sh, const char *bases, const int
   U64 *hH = 0; U32 *hP = 0; int64_t *hS = 0;
   MgArena ar;
   for (int attempt = 0 ; attempt < 2 ; ++attempt)
-    { size_t need = al256 (nw * 4) + 2 * al256 (((size_t) nReads + 2) * 8) + al256 (cap * 8) + al256 (cap * 4) + 4096;
+    { size_t need = mgAl256 (nw * 4) + 2 * mgAl256 (((size_t) nReads + 2) * 8) + mgAl256 (cap * 8) + mgAl256 (cap * 4) + 4096;
       if (ar.reserve (need)) break;
       ar.reset ();
       U32 *dP = (U32 *) ar.take (nw * 4);
@@ -657,7 +656,7 @@ static MgStatus mgFoldCounts (MgDev *d, hipStream_t st, Modset *host = 0)
   MgTable &t = d->t;
   if (!t.max) return MG_OK;
   if (!t.pendingDepth) return MG_OK;                   /* nothing has counted since the last fold */
-  MgStatus s = d->arena.reserve (al256 ((size_t) t.max * sizeof (U16)) + 4096); if (s) return s;      /* (no call is using the arena while a whole-set pass runs) */
+  MgStatus s = d->arena.reserve (mgAl256 ((size_t) t.max * sizeof (U16)) + 4096); if (s) return s;      /* (no call is using the arena while a whole-set pass runs) */
   d->arena.reset ();
   U16 *dDelta = (U16 *) d->arena.take ((size_t) t.max * sizeof (U16));
   s = mgTableExportDepth (&t, dDelta, st);
@@ -904,7 +903,7 @@ extern "C" MgStatus modsetSyncToHost (Modset *ms, int wantIndex)
   ms->max = t.max;
   if (t.max && t.pendingDepth)
     { /* depth[i] = min (65535, depth[i] + pending)   (modutils.c:26 applied `pending` times) */
-      if ((s = d->arena.reserve (al256 ((size_t) t.max * sizeof (U16)) + 4096))) return s;
+      if ((s = d->arena.reserve (mgAl256 ((size_t) t.max * sizeof (U16)) + 4096))) return s;
       d->arena.reset ();
       U16 *dDelta = (U16 *) d->arena.take ((size_t) t.max * sizeof (U16));
       if ((s = mgTableExportDepth (&t, dDelta, st))) return s;
@@ -912,7 +911,7 @@ extern "C" MgStatus modsetSyncToHost (Modset *ms, int wantIndex)
       if ((s = mgXferD2H (ms->depth + 1, dDelta, (size_t) t.max * sizeof (U16), MG_XFER_SATADD16))) return s;
     }
   if (wantIndex && d->hostIndexMax < t.max)
-    { if ((s = d->arena.reserve (al256 (ms->tableSize * sizeof (U32)) + 4096))) return s;
+    { if ((s = d->arena.reserve (mgAl256 (ms->tableSize * sizeof (U32)) + 4096))) return s;
       d->arena.reset ();
       U32 *dIndex = (U32 *) d->arena.take (ms->tableSize * sizeof (U32));
       if ((s = mgTableReplayIndex (&t, mgMakeParams (ms->hasher), ms->tableBits, dIndex, st))) return s;
@@ -1014,7 +1013,7 @@ static MgStatus mgScanStart (MgDev *d, int slot, const MgScanReq &q, U64 cap, Mg
   const bool lookup2 = lookupHist && fp != 'p';
   MgHashParams p = mgMakeParams (q.sh);
   const size_t perS = 8 + (q.wantPos ? 8 : 0) + q.extraPerSurvivor;
-  const size_t need = al256 (cap * perS) + 4 * 4096 + 512 * MG_HIST_STRIDE * 4 + al256 (mgScanWorkBytes (q.totalBases, q.nReads, cap))
+  const size_t need = mgAl256 (cap * perS) + 4 * 4096 + 512 * MG_HIST_STRIDE * 4 + mgAl256 (mgScanWorkBytes (q.totalBases, q.nReads, cap))
                       + (q.extraPerSurvivor ? mgTableAddScratchBytes (&d->t, cap < MG_ADD_CHUNK ? cap : MG_ADD_CHUNK) + 8192 : 0) + 8 * 256
                       + (lookupHist ? mgTableFindPartScratchBytes (cap) + 8192 : 0) + (lookup2 ? mgTableFindPart2ScratchBytes (cap) + 8192 : 0);
   MgStatus s = ar.reserve (need); if (s) return s;
@@ -1256,7 +1255,6 @@ extern "C" void mgHostBatchRelease (void)
     }
   if (before >= 0) (void) hipSetDevice (before);
 }
-static double mgNowS (void) { struct timespec t; clock_gettime (CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 
 extern "C" int64_t mgAddSequenceBatch (Modset *ms, const char *bases, const int64_t *readOffsets, int nReads)
 {

@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <unordered_map>
-#include "mg_common.h"
+#include "mg_prefix.h"
 #include "mg_internal.h"
 #include "mg_xfer.h"
 #include "mg_ref.h"
@@ -290,45 +290,24 @@ extern "C" int mgChainQueryDevice (const MgReference *ref, const U32 *dPacked, U
 __global__ __launch_bounds__ (256)
 void mgRsTileCountKernel (const U32 *__restrict__ seedIx, U64 n, U32 *__restrict__ tileCnt, U32 *__restrict__ tileLast)
 {
-  __shared__ U32 sC[4], sL[4];
+  __shared__ U32 lds[4];
   const U64 base = (U64) blockIdx.x * MG_RS_TILE;
   U32 c = 0, last = 0;                                              /* last: 1 + index (inside the batch) of the tile's last hit, 0: none */
   for (int j = 0 ; j < 16 ; ++j)
     { const U64 i = base + (U64) j * 256 + threadIdx.x;
       if (i < n && seedIx[i]) { ++c; last = (U32) i + 1; }         /* (rows go up: the last assignment is the largest) */
     }
-  for (int o = 32 ; o ; o >>= 1) { c += __shfl_down (c, o); const U32 l2 = __shfl_down (last, o); last = l2 > last ? l2 : last; }
-  if ((threadIdx.x & 63) == 0) { sC[threadIdx.x >> 6] = c; sL[threadIdx.x >> 6] = last; }
-  __syncthreads ();
-  if (!threadIdx.x)
-    { tileCnt[blockIdx.x] = sC[0] + sC[1] + sC[2] + sC[3];
-      U32 m = sL[0]; for (int q = 1 ; q < 4 ; ++q) m = sL[q] > m ? sL[q] : m;
-      tileLast[blockIdx.x] = m;
-    }
+  c = mgBlockReduce<256, MgSum> (c, lds); last = mgBlockReduce<256, MgMax> (last, lds);
+  if (!threadIdx.x) { tileCnt[blockIdx.x] = c; tileLast[blockIdx.x] = last; }
 }
 /* one workgroup: cnt[0 .. nTiles) -> exclusive sums, cnt[nTiles] = total; last[0 .. nTiles) -> the running maximum BEFORE each tile */
-__global__ __launch_bounds__ (1024)
-void mgRsTileScanKernel (U32 *__restrict__ cnt, U32 *__restrict__ last, U32 nTiles)
+__global__ __launch_bounds__ (MG_GROUP_THREADS)
+void mgRsTileScanKernel (U32 *cnt, U32 *last, U32 nTiles)
 {
-  __shared__ U32 sSum[1024], sMax[1024];
-  const int tid = threadIdx.x;
-  const U32 per = (nTiles + 1023) / 1024;
-  U32 sum = 0, mx = 0;
-  for (U32 q = 0 ; q < per ; ++q) { const U32 j = tid * per + q; if (j < nTiles) { sum += cnt[j]; mx = last[j] > mx ? last[j] : mx; } }
-  sSum[tid] = sum; sMax[tid] = mx;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { const U32 a = tid >= off ? sSum[tid - off] : 0, b = tid >= off ? sMax[tid - off] : 0;
-      __syncthreads ();
-      sSum[tid] += a; sMax[tid] = b > sMax[tid] ? b : sMax[tid];
-      __syncthreads ();
-    }
-  U32 run = sSum[tid] - sum, rm = tid ? sMax[tid - 1] : 0;
-  for (U32 q = 0 ; q < per ; ++q)
-    { const U32 j = tid * per + q;
-      if (j < nTiles) { const U32 c = cnt[j], l = last[j]; cnt[j] = run; last[j] = rm; run += c; rm = l > rm ? l : rm; }
-    }
-  if (tid == 1023) cnt[nTiles] = sSum[1023];
+  __shared__ U32 lds[MG_GROUP_THREADS];
+  const U32 total = mgGroupScan<MgSum> (cnt, cnt, nTiles, 0u, lds);
+  (void) mgGroupScan<MgMax> (last, last, nTiles, 0u, lds);
+  if (!threadIdx.x) cnt[nTiles] = total;
 }
 __global__ __launch_bounds__ (256)
 void mgRsWriteKernel (const U32 *__restrict__ seedIx, const U32 *__restrict__ seedPosF, const U32 *__restrict__ seedRid, const U64 *__restrict__ seedStart, U64 n,
@@ -390,28 +369,6 @@ __global__ void mgRsPerReadKernel (const U64 *__restrict__ seedStart, const U32 
   nMiss[r] = (U32) (s1 - s0) - (h1 - h0);
 }
 
-/* exclusive scan of n counts in place, a[n] = total (one workgroup) */
-__global__ __launch_bounds__ (1024)
-void mgChainScanKernel (U64 *__restrict__ a, U32 n)
-{
-  __shared__ U64 sPart[1024];
-  const int tid = threadIdx.x;
-  const U32 per = (n + 1023) / 1024;
-  U64 sum = 0;
-  for (U32 i = 0 ; i < per ; ++i) { U32 j = tid * per + i; if (j < n) sum += a[j]; }
-  sPart[tid] = sum;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { U64 v = tid >= off ? sPart[tid - off] : 0;
-      __syncthreads ();
-      sPart[tid] += v;
-      __syncthreads ();
-    }
-  U64 run = sPart[tid] - sum;
-  for (U32 i = 0 ; i < per ; ++i) { U32 j = tid * per + i; if (j < n) { U64 c = a[j]; a[j] = run; run += c; } }
-  if (tid == 1023) a[n] = sPart[1023];
-}
-
 /* hHitStart[nReads+1], hNMiss[nReads]: host, filled here.  *dHitOut / *dDxOut: DEVICE arrays of hHitStart[nReads] entries, hipMalloc ()ed here (the
  * caller copies them where they go and frees them with mgDeviceFree).  dDepthAccum: device U32[ms->max + 1], the hits per mod of the file so
  * far (mg_refpack.hip keeps it across the batches): this batch's are added.  Returns 0, -1 on error. */
@@ -447,7 +404,7 @@ extern "C" int mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBa
     U32 totHit32 = 0;
     if (nTiles)
       { hipLaunchKernelGGL (mgRsTileCountKernel, dim3 (nTiles), dim3 (256), 0, 0, dIx, n, dTileCnt, dTileLast);
-        hipLaunchKernelGGL (mgRsTileScanKernel, dim3 (1), dim3 (1024), 0, 0, dTileCnt, dTileLast, nTiles);
+        hipLaunchKernelGGL (mgRsTileScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, 0, dTileCnt, dTileLast, nTiles);
         if (hipMemcpy (&totHit32, dTileCnt + nTiles, 4, hipMemcpyDeviceToHost)) break;
       }
     const U64 totHit = totHit32;

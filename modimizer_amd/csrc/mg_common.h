@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <time.h>
 #include "modgpu.h"
 
 #define MG_WAVE 64
@@ -89,34 +90,6 @@ __device__ __forceinline__ U64 mgRevComp (U64 f, int shift1)
   const U64 x = ((U64) mgRevComp16 ((U32) f) << 32) | mgRevComp16 ((U32) (f >> 32));
   return x >> shift1;
 }
-/* inclusive prefix sum over the 64 lanes of a wave with DPP only (no LDS traffic): Hillis-Steele inside the
- * rows of 16 (row_shr 1,2,4,8), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31
- * into rows 2 and 3 (row_bcast:31).  Lanes without a source add 0. */
-__device__ __forceinline__ U32 mgWaveInclusiveSum (U32 v)
-{
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x111, 0xf, 0xf, false);
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x112, 0xf, 0xf, false);
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x114, 0xf, 0xf, false);
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x118, 0xf, 0xf, false);
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x142, 0xa, 0xf, false);
-  v += (U32) __builtin_amdgcn_update_dpp (0, (int) v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-/* inclusive sum over a workgroup of 256 lanes (lds: 4 words, free again on return); *total = the workgroup's sum (mg_settext.hip; the
-   reports' formatter, mg_report.hip, has the same under its own name) */
-__device__ __forceinline__ U32 mgBlockInclusive256 (U32 v, U32 *lds, U32 *total)
-{
-  const U32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const U32 inc = mgWaveInclusiveSum (v);
-  if (lane == 63u) lds[wv] = inc;
-  __syncthreads ();
-  U32 before = 0, tot = 0;
-  #pragma unroll
-  for (U32 i = 0 ; i < 4 ; ++i) { const U32 s = lds[i]; before += i < wv ? s : 0u; tot += s; }
-  __syncthreads ();
-  *total = tot;
-  return before + inc;
-}
 /* The modset table's hash of a k-mer: a BIJECTION of the 2k-bit k-mer onto 2k-bit values (odd multipliers and
  * xor-shifts, all invertible modulo 2^(2k)), murmur-style.  Bucket = its top log2NB bits, home slot = its low bits, and
  * the table stores the mixed value itself (+1) as the key: being a bijection it identifies the k-mer, and a k-mer's
@@ -185,6 +158,13 @@ __device__ __forceinline__ U32 mgHomeOfM (U64 m, const MgGeom &g)
 /* the next slot of a probe sequence: linear, wrapping inside the bucket */
 __device__ __forceinline__ U32 mgNextSlot (U32 at, U32 R) { return at + 1 == R ? 0u : at + 1; }
 #endif /* __HIPCC__ */
+
+/* host one-liners every .hip file used to have its own of: a grid of workgroups of per items each for n items, at most cap of them (grid-stride kernels), sizes rounded
+   up to 256 bytes, and the monotonic clock in seconds */
+static inline unsigned mgGrid (U64 n, unsigned per = 256, unsigned cap = 4096)
+{ U64 b = (n + per - 1) / per; if (b > cap) b = cap; if (b < 1) b = 1; return (unsigned) b; }
+static inline size_t mgAl256 (size_t n) { return (n + 255) & ~(size_t) 255; }
+static inline double mgNowS (void) { struct timespec ts; clock_gettime (CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 /* The bucket id (log2NB bits) is split into a coarse digit (high bits, first partition pass) and a fine one. */
 static inline void mgPartSplit (int log2NB, int *hiB, int *loB)

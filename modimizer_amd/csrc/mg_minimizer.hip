@@ -34,7 +34,7 @@
  * positions: 33.5 / 52.1 / 58.9 / 60.2 / 46.5 / 29.2 Gbp/s -- a wave's LDS piece decides how many waves hide each other's walks).
  */
 #include <hip/hip_runtime.h>
-#include "mg_common.h"
+#include "mg_prefix.h"
 
 #define MG_MIN_NONE (~(U64) 0)
 
@@ -255,28 +255,6 @@ void mgMinimizerKernel (const U32 *__restrict__ packed, const U64 *__restrict__ 
     }
 }
 
-/* exclusive scan of n counts in place (one workgroup); a[n] = total */
-__global__ __launch_bounds__ (1024)
-void mgMinScanKernel (U64 *__restrict__ a, U32 n)
-{
-  __shared__ U64 sPart[1024];
-  const int tid = threadIdx.x;
-  const U32 per = (n + 1023) / 1024;
-  U64 sum = 0;
-  for (U32 i = 0 ; i < per ; ++i) { U32 j = tid * per + i; if (j < n) sum += a[j]; }
-  sPart[tid] = sum;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { U64 v = tid >= off ? sPart[tid - off] : 0;
-      __syncthreads ();
-      sPart[tid] += v;
-      __syncthreads ();
-    }
-  U64 run = sPart[tid] - sum;
-  for (U32 i = 0 ; i < per ; ++i) { U32 j = tid * per + i; if (j < n) { U64 c = a[j]; a[j] = run; run += c; } }
-  if (tid == 1023) a[n] = sPart[1023];
-}
-
 MgStatus mgLaunchMinimizers (const MgHashParams &p, U32 w, const U32 *dPacked, const U64 *dReadOffsets, U32 nReads,
                              U64 *dHash, U32 *dPosF, U64 *dReadStart, U64 capacity, U64 *totalOut, hipStream_t st)
 {
@@ -291,7 +269,7 @@ MgStatus mgLaunchMinimizers (const MgHashParams &p, U32 w, const U32 *dPacked, c
   const size_t lds = (size_t) waveBytes * MG_MIN_WAVES;
   if (tiled) hipLaunchKernelGGL ((mgMinimizerKernel<false, true>), dim3 (grid), dim3 (64 * MG_MIN_WAVES), lds, st, dPacked, dReadOffsets, nReads, p, w, dReadStart, (U64 *) 0, (U32 *) 0, (U64) 0, waveBytes, tile);
   else hipLaunchKernelGGL ((mgMinimizerKernel<false, false>), dim3 (grid), dim3 (64 * MG_MIN_WAVES), 0, st, dPacked, dReadOffsets, nReads, p, w, dReadStart, (U64 *) 0, (U32 *) 0, (U64) 0, 0u, 0u);
-  hipLaunchKernelGGL (mgMinScanKernel, dim3 (1), dim3 (1024), 0, st, dReadStart, nReads);
+  hipLaunchKernelGGL ((mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, dReadStart, dReadStart, nReads, dReadStart + nReads);
   MG_HIP (hipGetLastError ());
   U64 total = 0;
   MG_HIP (hipMemcpyAsync (&total, dReadStart + nReads, 8, hipMemcpyDeviceToHost, st));

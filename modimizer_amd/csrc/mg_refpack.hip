@@ -27,7 +27,7 @@
 #include <time.h>
 #include <mutex>
 #include <unordered_map>
-#include "mg_common.h"
+#include "mg_prefix.h"
 #include "mg_internal.h"
 #include "mg_xfer.h"
 #include "mg_ref.h"
@@ -111,53 +111,22 @@ MgStatus mgRefDevGet (const MgReference *ref, MgRefDev *out)
 __global__ __launch_bounds__ (256)
 void mgRefTileSumKernel (const U32 *__restrict__ in, U64 n, U32 *__restrict__ tileSum)
 {
-  __shared__ U32 sW[4];
+  __shared__ U32 lds[4];
   const U64 base = (U64) blockIdx.x * MG_SCAN_TILE;
   U32 s = 0;
   for (int j = 0 ; j < 16 ; ++j) { const U64 i = base + (U64) j * 256 + threadIdx.x; if (i < n) s += in[i]; }
-  for (int o = 32 ; o ; o >>= 1) s += __shfl_down (s, o);
-  if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = s;
-  __syncthreads ();
-  if (!threadIdx.x) tileSum[blockIdx.x] = sW[0] + sW[1] + sW[2] + sW[3];
-}
-/* one workgroup: a[0 .. n) exclusive in place, a[n] = the total */
-__global__ __launch_bounds__ (1024)
-void mgRefScanSmallKernel (U32 *__restrict__ a, U32 n)
-{
-  __shared__ U32 sPart[1024];
-  const int tid = threadIdx.x;
-  const U32 per = (n + 1023) / 1024;
-  U32 sum = 0;
-  for (U32 i = 0 ; i < per ; ++i) { const U32 j = tid * per + i; if (j < n) sum += a[j]; }
-  sPart[tid] = sum;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { const U32 v = tid >= off ? sPart[tid - off] : 0;
-      __syncthreads ();
-      sPart[tid] += v;
-      __syncthreads ();
-    }
-  U32 run = sPart[tid] - sum;
-  for (U32 i = 0 ; i < per ; ++i) { const U32 j = tid * per + i; if (j < n) { const U32 c = a[j]; a[j] = run; run += c; } }
-  if (tid == 1023) a[n] = sPart[1023];
+  s = mgBlockReduce<256, MgSum> (s, lds);
+  if (!threadIdx.x) tileSum[blockIdx.x] = s;
 }
 __global__ __launch_bounds__ (256)
 void mgRefTileScanKernel (const U32 *__restrict__ in, U64 n, const U32 *__restrict__ tileBase, U32 *__restrict__ out)
 {
-  __shared__ U32 sT[256];
+  __shared__ U32 lds[4];
   const U64 base = (U64) blockIdx.x * MG_SCAN_TILE + (U64) threadIdx.x * 16;      /* a thread's 16 items are consecutive */
   U32 v[16]; U32 s = 0;
 #pragma unroll
   for (int j = 0 ; j < 16 ; ++j) { v[j] = base + j < n ? in[base + j] : 0u; s += v[j]; }
-  sT[threadIdx.x] = s;
-  __syncthreads ();
-  for (int off = 1 ; off < 256 ; off <<= 1)
-    { const U32 x = (int) threadIdx.x >= off ? sT[threadIdx.x - off] : 0;
-      __syncthreads ();
-      sT[threadIdx.x] += x;
-      __syncthreads ();
-    }
-  U32 run = tileBase[blockIdx.x] + sT[threadIdx.x] - s;
+  U32 run = tileBase[blockIdx.x] + mgBlockExclusive<256, MgSum> (s, lds);
 #pragma unroll
   for (int j = 0 ; j < 16 ; ++j) { if (base + j < n) out[base + j] = run; run += v[j]; }
 }
@@ -167,7 +136,7 @@ static MgStatus mgRefExclusiveScan (const U32 *in, U32 *out, U64 n, U32 *tiles, 
   if (!n) return MG_OK;
   const U32 nTiles = (U32) ((n + MG_SCAN_TILE - 1) / MG_SCAN_TILE);
   hipLaunchKernelGGL (mgRefTileSumKernel, dim3 (nTiles), dim3 (256), 0, st, in, n, tiles);
-  hipLaunchKernelGGL (mgRefScanSmallKernel, dim3 (1), dim3 (1024), 0, st, tiles, nTiles);
+  hipLaunchKernelGGL ((mgGroupSumKernel<U32, U32>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, tiles, tiles, nTiles, tiles + nTiles);
   hipLaunchKernelGGL (mgRefTileScanKernel, dim3 (nTiles), dim3 (256), 0, st, in, n, tiles, out);
   MG_HIP (hipGetLastError ());
   return MG_OK;
@@ -179,14 +148,12 @@ static MgStatus mgRefExclusiveScan (const U32 *in, U32 *out, U64 n, U32 *tiles, 
 __global__ __launch_bounds__ (256)
 void mgRefCountHitsKernel (const U32 *__restrict__ ix, U64 n, U32 *__restrict__ tileCount)
 {
-  __shared__ U32 sW[4];
+  __shared__ U32 lds[4];
   const U64 base = (U64) blockIdx.x * MG_SCAN_TILE;
   U32 s = 0;
   for (int j = 0 ; j < 16 ; ++j) { const U64 i = base + (U64) j * 256 + threadIdx.x; if (i < n && ix[i]) ++s; }
-  for (int o = 32 ; o ; o >>= 1) s += __shfl_down (s, o);
-  if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = s;
-  __syncthreads ();
-  if (!threadIdx.x) tileCount[blockIdx.x] = sW[0] + sW[1] + sW[2] + sW[3];
+  s = mgBlockReduce<256, MgSum> (s, lds);
+  if (!threadIdx.x) tileCount[blockIdx.x] = s;
 }
 /* tile b's hits go to at0 + tileBase[b] .. in order: inside the tile a wave takes 64 consecutive seeds at a time (ballot + popcount),
    the four waves one after the other over the tile's 16 rows of 256 */
@@ -238,7 +205,7 @@ void mgRefClassifyKernel (const U32 *__restrict__ depth, U32 max, U8 *__restrict
       else if (dp == 2) { info[i] = (U8) ((f & 0xfc) | 2); ++c2; }
       else { info[i] = (U8) (f | 3); ++cM; }
     }
-  for (int o = 32 ; o ; o >>= 1) { c1 += __shfl_down (c1, o); c2 += __shfl_down (c2, o); cM += __shfl_down (cM, o); }
+  c1 = mgWaveReduce<MgSum> (c1); c2 = mgWaveReduce<MgSum> (c2); cM = mgWaveReduce<MgSum> (cM);
   if ((threadIdx.x & 63) == 0) { atomicAdd (&sT[0], c1); atomicAdd (&sT[1], c2); atomicAdd (&sT[2], cM); }
   __syncthreads ();
   if (threadIdx.x < 3 && sT[threadIdx.x]) atomicAdd (&tallies[threadIdx.x], sT[threadIdx.x]);
@@ -370,7 +337,7 @@ extern "C" MgStatus mgRefBuildAppend (MgReference *ref, const U32 *dIx, const U3
       U32 *tl = 0, cnt = 0;
       MG_HIP (hipMalloc ((void **) &tl, ((size_t) nT + 2) * 4));
       hipLaunchKernelGGL (mgRefCountHitsKernel, dim3 (nT), dim3 (256), 0, st, dIx, n, tl);
-      hipLaunchKernelGGL (mgRefScanSmallKernel, dim3 (1), dim3 (1024), 0, st, tl, nT);
+      hipLaunchKernelGGL ((mgGroupSumKernel<U32, U32>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, tl, tl, nT, tl + nT);
       const bool bad = hipMemcpyAsync (&cnt, tl + nT, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess;
       (void) hipFree (tl);
       if (bad) return mgHipFail (hipGetLastError (), "reference append");
@@ -397,7 +364,7 @@ extern "C" MgStatus mgRefBuildAppend (MgReference *ref, const U32 *dIx, const U3
   MgStatus s = MG_OK;
   do {
     hipLaunchKernelGGL (mgRefCountHitsKernel, dim3 (nTiles), dim3 (256), 0, st, dIx, n, tiles);
-    hipLaunchKernelGGL (mgRefScanSmallKernel, dim3 (1), dim3 (1024), 0, st, tiles, nTiles);
+    hipLaunchKernelGGL ((mgGroupSumKernel<U32, U32>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, tiles, tiles, nTiles, tiles + nTiles);
     U32 cnt = 0;
     if (hipMemcpyAsync (&cnt, tiles + nTiles, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess) { s = mgHipFail (hipGetLastError (), "reference append"); break; }
     /* modmap.c:111: an append is refused once max + 1 >= size */

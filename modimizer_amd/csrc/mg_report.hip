@@ -19,14 +19,13 @@
  */
 #include <string.h>
 #include <vector>
-#include "mg_common.h"
+#include "mg_prefix.h"
 #include "mg_internal.h"
 
 #define MG_TEXT_THREADS 256
 #define MG_TEXT_PER     4                                         /* lines per lane and pass */
 #define MG_TEXT_BLOCK   (MG_TEXT_THREADS * MG_TEXT_PER)           /* lines per workgroup */
 #define MG_TEXT_CHUNK   ((U64) 1 << 24)                           /* lines per chunk: bounds the text buffer (-d with one other set: ~0.5 GB) */
-#define MG_TEXT_SCAN_THREADS 1024
 #define MG_HDR_BIT 0x80000000u                                    /* paint item: the header of read (item & ~MG_HDR_BIT), else a seed ordinal */
 
 extern "C" void mgSetErrorText (const char *msg) { mgSetError ("%s", msg); }
@@ -142,21 +141,6 @@ struct MgSetLines {
 /* ---------------------------------------------------------------------------------------- */
 /* the formatter: length, scan, write                                                         */
 
-/* inclusive sum over the workgroup's 256 lanes; *total = the workgroup's sum */
-__device__ __forceinline__ U32 mgTextBlockInclusive (U32 v, U32 *lds, U32 *total)
-{
-  const U32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const U32 inc = mgWaveInclusiveSum (v);
-  if (lane == 63u) lds[wv] = inc;
-  __syncthreads ();
-  U32 before = 0, tot = 0;
-  #pragma unroll
-  for (U32 i = 0 ; i < MG_TEXT_THREADS / 64 ; ++i) { const U32 s = lds[i]; before += i < wv ? s : 0u; tot += s; }
-  __syncthreads ();
-  *total = tot;
-  return before + inc;
-}
-
 /* pass 1: bytes of the workgroup's 1024 lines (j0 + b * 1024 ...) -> blockSum[b] */
 template <class L>
 __global__ __launch_bounds__ (MG_TEXT_THREADS) void mgTextLenKernel (L lines, U64 j0, U64 m, U32 *__restrict__ blockSum)
@@ -167,27 +151,11 @@ __global__ __launch_bounds__ (MG_TEXT_THREADS) void mgTextLenKernel (L lines, U6
   #pragma unroll
   for (int q = 0 ; q < MG_TEXT_PER ; ++q)
     { const U64 j = base + (U64) q * MG_TEXT_THREADS + threadIdx.x; if (j < m) s += lines.len (j0 + j); }
-  U32 tot;
-  (void) mgTextBlockInclusive (s, lds, &tot);
-  if (threadIdx.x == 0) blockSum[blockIdx.x] = tot;
+  s = mgBlockReduce<MG_TEXT_THREADS, MgSum> (s, lds);
+  if (threadIdx.x == 0) blockSum[blockIdx.x] = s;
 }
 
-/* pass 2 (one workgroup): blockOff[b] = exclusive sum of blockSum[0 .. b), blockOff[nb] = the chunk's bytes */
-__global__ __launch_bounds__ (MG_TEXT_SCAN_THREADS) void mgTextScanKernel (const U32 *__restrict__ blockSum, U32 nb, U64 *__restrict__ blockOff)
-{
-  __shared__ U64 lds[MG_TEXT_SCAN_THREADS];
-  const U32 t = threadIdx.x, per = (nb + MG_TEXT_SCAN_THREADS - 1) / MG_TEXT_SCAN_THREADS;
-  const U32 a = t * per, e = a + per < nb ? a + per : nb;
-  U64 s = 0;
-  for (U32 i = a ; i < e ; ++i) s += blockSum[i];
-  lds[t] = s;
-  __syncthreads ();
-  for (U32 d = 1 ; d < MG_TEXT_SCAN_THREADS ; d <<= 1)             /* Hillis-Steele over the lanes' sums */
-    { const U64 x = t >= d ? lds[t - d] : 0; __syncthreads (); lds[t] += x; __syncthreads (); }
-  U64 at = lds[t] - s;
-  for (U32 i = a ; i < e ; ++i) { blockOff[i] = at; at += blockSum[i]; }
-  if (t == MG_TEXT_SCAN_THREADS - 1) blockOff[nb] = lds[t];
-}
+/* pass 2 (one workgroup, mgGroupSumKernel): blockOff[b] = exclusive sum of blockSum[0 .. b), blockOff[nb] = the chunk's bytes */
 
 /* pass 3: the lines' bytes at their offsets (a line is written by one lane) */
 template <class L>
@@ -201,7 +169,7 @@ __global__ __launch_bounds__ (MG_TEXT_THREADS) void mgTextWriteKernel (L lines, 
     { const U64 j = base + (U64) q * MG_TEXT_THREADS + threadIdx.x;
       const U32 n = j < m ? lines.len (j0 + j) : 0u;
       U32 tot;
-      const U32 inc = mgTextBlockInclusive (n, lds, &tot);
+      const U32 inc = mgBlockInclusive<MG_TEXT_THREADS, MgSum> (n, lds, &tot);
       if (n) lines.put (j0 + j, out + at + (inc - n));
       at += tot;
     }
@@ -239,8 +207,6 @@ __global__ void mgDepthGatherKernel (const U64 *__restrict__ value, U64 m, int k
   for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < m ; i += (U64) gridDim.x * blockDim.x)
     { const U32 ix = idx[i]; out[i] = ((value[i] >> kbits) || !ix) ? (U16) 0 : depth1[ix - 1]; }
 }
-
-static unsigned mgGrid (U64 n) { U64 g = (n + 255) / 256; if (g > 4096) g = 4096; return (unsigned) (g ? g : 1); }
 
 /* ---------------------------------------------------------------------------------------- */
 /* host side                                                                                  */
@@ -288,7 +254,7 @@ static MgStatus mgTextFormat (const L &lines, U64 n, MgReportBufs *b, MgTextOut 
     { const U64 m = n - j0 < MG_TEXT_CHUNK ? n - j0 : MG_TEXT_CHUNK;
       const U32 nb = (U32) ((m + MG_TEXT_BLOCK - 1) / MG_TEXT_BLOCK);
       MG_LAUNCH (MG_K_TEXT_LEN, st, mgTextLenKernel<L>, dim3 (nb), dim3 (MG_TEXT_THREADS), 0, st, lines, j0, m, b->blockSum);
-      MG_LAUNCH (MG_K_TEXT_SCAN, st, mgTextScanKernel, dim3 (1), dim3 (MG_TEXT_SCAN_THREADS), 0, st, b->blockSum, nb, b->blockOff);
+      MG_LAUNCH (MG_K_TEXT_SCAN, st, (mgGroupSumKernel<U32, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, b->blockSum, b->blockOff, nb, b->blockOff + nb);
       MG_HIP (hipMemcpyAsync (b->hTotal, b->blockOff + nb, 8, hipMemcpyDeviceToHost, st));
       MG_HIP (hipStreamSynchronize (st));
       const U64 bytes = *(volatile U64 *) b->hTotal;

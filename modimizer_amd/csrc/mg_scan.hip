@@ -22,7 +22,7 @@
  * double-buffered, in the wavefront's LDS with a (k-1)-base halo; each lane owns 64 consecutive k-mer starts.
  */
 #include <stdlib.h>
-#include "mg_common.h"
+#include "mg_prefix.h"
 
 /* ---------------------------------------------------------------------------------------- */
 /* K1: bytes 0..3 -> 2-bit packed words (first base in the top bits)                          */
@@ -775,10 +775,9 @@ static MgScanGeom mgScanGeometryTiles (U64 nTiles, U64 capacity)
   return g;
 }
 
-static inline size_t mgAl (size_t n) { return (n + 255) & ~(size_t) 255; }
 
 U64 mgScanTiles (U64 totalBases) { return mgNumTiles (totalBases); }
-size_t mgScanInfoBytes (U64 totalBases) { return mgAl ((mgNumTiles (totalBases) + 2) * sizeof (MgTileInfo)); }
+size_t mgScanInfoBytes (U64 totalBases) { return mgAl256 ((mgNumTiles (totalBases) + 2) * sizeof (MgTileInfo)); }
 
 /* per-tile read metadata for a whole batch (shared by every range launch over it) */
 MgStatus mgScanPrepare (const U64 *dReadOffsets, U32 nReads, U64 totalBases, void *dInfo, hipStream_t st)
@@ -796,7 +795,7 @@ size_t mgScanRangeWorkBytes (U64 nTilesRange, U64 capacity)
 {
   MgScanGeom g = mgScanGeometryTiles (nTilesRange, capacity);
   size_t segN = (size_t) g.nBlocks * g.segCap;
-  return mgAl (g.nBlocks * 8) + mgAl ((g.nBlocks + 1) * 8) + mgAl (segN * 8) + 2 * mgAl (segN * 4) + 256;
+  return mgAl256 (g.nBlocks * 8) + mgAl256 ((g.nBlocks + 1) * 8) + mgAl256 (segN * 8) + 2 * mgAl256 (segN * 4) + 256;
 }
 
 size_t mgScanWorkBytes (U64 totalBases, U32 nReads, U64 capacity)
@@ -837,10 +836,10 @@ MgStatus mgLaunchScanRange (const MgHashParams &p, const U32 *dPacked, U64 total
   MgScanGeom g = mgScanGeometryTiles (tile1 - tile0, capacity);
   char *wb = (char *) dWork;
   size_t segN = (size_t) g.nBlocks * g.segCap;
-  U64 *blockCount = (U64 *) wb;                  wb += mgAl (g.nBlocks * 8);
-  U64 *segStart = (U64 *) wb;                    wb += mgAl ((g.nBlocks + 1) * 8);
-  U64 *segKmer = (U64 *) wb;                     wb += mgAl (segN * 8);
-  U32 *segPosF = (U32 *) wb;                     wb += mgAl (segN * 4);
+  U64 *blockCount = (U64 *) wb;                  wb += mgAl256 (g.nBlocks * 8);
+  U64 *segStart = (U64 *) wb;                    wb += mgAl256 ((g.nBlocks + 1) * 8);
+  U64 *segKmer = (U64 *) wb;                     wb += mgAl256 (segN * 8);
+  U32 *segPosF = (U32 *) wb;                     wb += mgAl256 (segN * 4);
   U32 *segRead = (U32 *) wb;
 
   MgScanArgs a;

@@ -23,18 +23,16 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <sys/stat.h>
-#include <time.h>
-#include "mg_common.h"
+#include "mg_prefix.h"
 #include "mg_internal.h"
 
-static double stNow (void) { struct timespec ts; clock_gettime (CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 static bool stTiming (void) { return mgKnobs ()->textTiming == 1; }      /* dev knob (MODGPU_TEXT_TIMING, as the FASTA parser's): the phases to stderr */
 
 #define ST_THREADS 256
 #define ST_PER     16                                    /* bytes per lane: one 16-byte load */
 #define ST_TILE    (ST_THREADS * ST_PER)                 /* 4 KiB of text per workgroup */
 #define ST_CARRY   128u                                  /* bytes kept in front of a window for the line the window before left open */
-#define ST_SCAN_THREADS 1024
+#define ST_SCAN_THREADS MG_GROUP_THREADS
 #define ST_MIN_LINE 8u                                   /* "1\ta\t1\t1\n": a window of n bytes holds at most n / 8 lines of the grammar */
 
 struct StState {                                         /* device resident, carried from window to window */
@@ -45,8 +43,6 @@ struct StState {                                         /* device resident, car
   U32 lastEnd;                                           /* one past the current window's last newline (0: it has none) */
 };
 
-static_assert (ST_THREADS == 256, "mgBlockInclusive256");
-
 /* the newlines of [ST_CARRY - carry, nBytes) of the window buffer.  EMIT false: their number per tile and one past the tile's last;
    EMIT true: their positions, in order, at nl[tileOff[tile] ...] (those that have room) */
 template <bool EMIT>
@@ -55,7 +51,6 @@ __global__ __launch_bounds__ (ST_THREADS) void mgSetTextLinesKernel (const unsig
                                                                      const U32 *__restrict__ tileOff, U32 *__restrict__ nl, U32 nlCap)
 {
   __shared__ U32 lds[ST_THREADS / 64];
-  __shared__ U32 last;
   const U32 start = ST_CARRY - st->carry;
   const U32 base = blockIdx.x * ST_TILE + threadIdx.x * ST_PER;            /* (the buffer is padded to whole tiles) */
   const uint4 v = *(const uint4 *) (text + base);
@@ -67,12 +62,10 @@ __global__ __launch_bounds__ (ST_THREADS) void mgSetTextLinesKernel (const unsig
       if (c == '\n' && pos >= start && pos < nBytes) m |= 1u << b;
     }
   const U32 cnt = (U32) __popc (m);
-  if (!EMIT && threadIdx.x == 0) last = 0;
   U32 tot;
-  const U32 inc = mgBlockInclusive256 (cnt, lds, &tot);
+  const U32 inc = mgBlockInclusive<ST_THREADS, MgSum> (cnt, lds, &tot);
   if (!EMIT)
-    { if (m) atomicMax (&last, base + (32u - (U32) __clz ((int) m)));      /* one past the lane's last newline */
-      __syncthreads ();
+    { const U32 last = mgBlockReduce<ST_THREADS, MgMax> (m ? base + (32u - (U32) __clz ((int) m)) : 0u, lds);      /* one past the tile's last newline */
       if (threadIdx.x == 0) { tileCount[blockIdx.x] = tot; tileLast[blockIdx.x] = last; }
     }
   else
@@ -90,22 +83,13 @@ __global__ __launch_bounds__ (ST_SCAN_THREADS) void mgSetTextScanKernel (const U
                                                                          U32 *__restrict__ tileOff, U32 nlCap, StState *__restrict__ st)
 {
   __shared__ U32 lds[ST_SCAN_THREADS];
-  __shared__ U32 last;
-  const U32 t = threadIdx.x, per = (nTiles + ST_SCAN_THREADS - 1) / ST_SCAN_THREADS;
-  const U32 a = t * per < nTiles ? t * per : nTiles, e = a + per < nTiles ? a + per : nTiles;
-  if (t == 0) last = 0;
-  U32 s = 0, mx = 0;
-  for (U32 i = a ; i < e ; ++i) { s += tileCount[i]; const U32 l = tileLast[i]; mx = l > mx ? l : mx; }
-  lds[t] = s;
-  __syncthreads ();
-  if (mx) atomicMax (&last, mx);
-  for (U32 d = 1 ; d < ST_SCAN_THREADS ; d <<= 1)
-    { const U32 x = t >= d ? lds[t - d] : 0; __syncthreads (); lds[t] += x; __syncthreads (); }
-  U32 at = lds[t] - s;
-  for (U32 i = a ; i < e ; ++i) { tileOff[i] = at; at += tileCount[i]; }
-  if (t == ST_SCAN_THREADS - 1)
+  const U32 lines = mgGroupScan<MgSum> (tileCount, tileOff, nTiles, 0u, lds);
+  U32 mx = 0;
+  for (U32 i = threadIdx.x ; i < nTiles ; i += ST_SCAN_THREADS) { const U32 l = tileLast[i]; mx = l > mx ? l : mx; }
+  const U32 last = mgBlockReduce<ST_SCAN_THREADS, MgMax> (mx, lds);
+  if (threadIdx.x == 0)
     { const U64 left = st->want - st->linesDone;
-      U32 n = (U64) lds[t] < left ? lds[t] : (U32) left;
+      U32 n = (U64) lines < left ? lines : (U32) left;
       if (n > nlCap) { n = nlCap; st->bad = 1; }         /* more lines than lines of the grammar fit: some line is shorter than any of them */
       st->nLines = n; st->lastEnd = last;
     }
@@ -187,8 +171,6 @@ __global__ void mgSetTextPlaceKernel (const U32 *__restrict__ idx, U64 n, const 
     }
 }
 
-static unsigned stGrid (U64 n) { U64 g = (n + 255) / 256; if (g > 4096) g = 4096; return (unsigned) (g ? g : 1); }
-
 /* ---------------------------------------------------------------------------------------- */
 /* host side                                                                                  */
 
@@ -223,7 +205,7 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
   const size_t bufBytes = ST_CARRY + window + ST_TILE;
   const U32 maxTiles = (U32) (bufBytes / ST_TILE + 1);
   hipStream_t st = 0;
-  const double t0 = stNow (); double tRead = 0, tWait = 0;
+  const double t0 = mgNowS (); double tRead = 0, tWait = 0;
   for (int i = 0 ; i < 2 ; ++i)
     { MG_HIP (hipHostMalloc ((void **) &b.hPin[i], window, hipHostMallocDefault));
       MG_HIP (hipMalloc ((void **) &b.dText[i], bufBytes));
@@ -237,16 +219,16 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
   StState init; memset (&init, 0, sizeof (init)); init.want = want;
   MG_HIP (hipMemcpyAsync (b.dState, &init, sizeof (init), hipMemcpyHostToDevice, st));
   MG_HIP (hipStreamSynchronize (st));                    /* (init is on this stack) */
-  const double t1 = stNow ();
+  const double t1 = mgNowS ();
   int w = 0;
   for (U64 off = 0 ; off < body ; ++w)
     { const int cur = w & 1;
       const size_t nCur = body - off < window ? (size_t) (body - off) : window;
-      const double r0 = stNow ();
+      const double r0 = mgNowS ();
       if (w >= 2) MG_HIP (hipEventSynchronize (b.copied[cur]));            /* the buffer's last copy to the device is over */
-      const double r1 = stNow ();
+      const double r1 = mgNowS ();
       if (mgTextReadParallel (b.fd, b.hPin[cur], nCur, (int64_t) (bodyOff + off))) { mgSetError ("failed to read text file %s", filename); return MG_ERR_ARG; }
-      tWait += r1 - r0; tRead += stNow () - r1;
+      tWait += r1 - r0; tRead += mgNowS () - r1;
       MG_HIP (hipMemcpyAsync (b.dText[cur] + ST_CARRY, b.hPin[cur], nCur, hipMemcpyHostToDevice, st));
       MG_HIP (hipEventRecord (b.copied[cur], st));
       const U32 nBytes = ST_CARRY + (U32) nCur, nTiles = (nBytes + ST_TILE - 1) / ST_TILE;
@@ -255,7 +237,7 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
       MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextScanKernel, dim3 (1), dim3 (ST_SCAN_THREADS), 0, st, b.dTileCount, b.dTileLast, nTiles, b.dTileOff, nlCap, b.dState);
       MG_LAUNCH (MG_K_SETTEXT_LINES, st, mgSetTextLinesKernel<true>, dim3 (nTiles), dim3 (ST_THREADS), 0, st, b.dText[cur], nBytes, b.dState,
                  b.dTileCount, b.dTileLast, b.dTileOff, b.dNl, nlCap);
-      MG_LAUNCH (MG_K_SETTEXT_PARSE, st, mgSetTextParseKernel, dim3 (stGrid (nlCap)), dim3 (256), 0, st, b.dText[cur], b.dNl, b.dState, k, b.dKey, b.dDepth, b.dInfo);
+      MG_LAUNCH (MG_K_SETTEXT_PARSE, st, mgSetTextParseKernel, dim3 (mgGrid (nlCap)), dim3 (256), 0, st, b.dText[cur], b.dNl, b.dState, k, b.dKey, b.dDepth, b.dInfo);
       MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextCarryKernel, dim3 (1), dim3 (64), 0, st, b.dText[cur], nBytes, b.dText[cur ^ 1], b.dState);
       MG_HIP (hipMemcpyAsync (b.hState, b.dState, sizeof (StState), hipMemcpyDeviceToHost, st));
       MG_HIP (hipGetLastError ());
@@ -264,12 +246,12 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
       if (w >= 2 && ((volatile StState *) b.hState)->linesDone >= want) break;
       if (w >= 2 && ((volatile StState *) b.hState)->bad) break;
     }
-  const double t2 = stNow ();
+  const double t2 = mgNowS ();
   MG_HIP (hipStreamSynchronize (st));
   MG_HIP (hipMemcpy (b.hState, b.dState, sizeof (StState), hipMemcpyDeviceToHost));
   if (stTiming ())
     fprintf (stderr, "  [set text] parse: %d windows of %zu bytes; buffers %.3f s, file read %.3f, waits for a window's copy %.3f, enqueue + rest %.3f, wait at the end %.3f\n",
-             w, window, t1 - t0, tRead, tWait, t2 - t1 - tRead - tWait, stNow () - t2);
+             w, window, t1 - t0, tRead, tWait, t2 - t1 - tRead - tWait, mgNowS () - t2);
   *verdict = (b.hState->bad || b.hState->linesDone < want) ? 1 : 0;
   return MG_OK;
 }
@@ -298,26 +280,26 @@ static MgStatus stFill (Modset *ms, const U64 *dKey, const U16 *dDepth, const U8
   if (!n) return MG_OK;
   hipStream_t st = 0;
   StFill f;
-  const double t0 = stNow ();
+  const double t0 = mgNowS ();
   MG_HIP (hipMalloc ((void **) &f.dIdx, n * 4));
   const U64 piece = (U64) 1 << 30;                       /* modsetAddBatchDevice takes fewer than 2^31 a call */
   for (U64 off = 0 ; off < n ; off += piece)
     if ((s = modsetAddBatchDevice (ms, dKey + off, n - off < piece ? n - off : piece, f.dIdx + off, 0, (void *) st))) return s;
   MG_HIP (hipStreamSynchronize (st));
-  const double t1 = stNow ();
+  const double t1 = mgNowS ();
   const size_t m1 = (size_t) ms->max + 1;
   MG_HIP (hipMalloc ((void **) &f.dWin, m1 * 4)); MG_HIP (hipMalloc ((void **) &f.dOutDepth, m1 * 2)); MG_HIP (hipMalloc ((void **) &f.dOutInfo, m1));
   MG_HIP (hipMemsetAsync (f.dWin, 0, m1 * 4, st)); MG_HIP (hipMemsetAsync (f.dOutDepth, 0, m1 * 2, st)); MG_HIP (hipMemsetAsync (f.dOutInfo, 0, m1, st));
-  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextLastKernel, dim3 (stGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin);
-  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextPlaceKernel, dim3 (stGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin, dDepth, dInfo, f.dOutDepth, f.dOutInfo);
+  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextLastKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin);
+  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextPlaceKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin, dDepth, dInfo, f.dOutDepth, f.dOutInfo);
   MG_HIP (hipGetLastError ());
   MG_HIP (hipStreamSynchronize (st));
-  const double t2 = stNow ();
+  const double t2 = mgNowS ();
   /* the host's depth[] and info[] are the authority; the device table's depth copy follows them */
   if ((s = mgCopyD2HBig (ms->depth, f.dOutDepth, m1 * 2)) || (s = mgCopyD2HBig (ms->info, f.dOutInfo, m1))) return s;
   s = mgModsetAdoptDepthDevice (ms, f.dOutDepth);
   if (stTiming ())
-    fprintf (stderr, "  [set text] fill: insert (device table made) %.3f s, last line wins %.3f, depth[] + info[] to the host %.3f\n", t1 - t0, t2 - t1, stNow () - t2);
+    fprintf (stderr, "  [set text] fill: insert (device table made) %.3f s, last line wins %.3f, depth[] + info[] to the host %.3f\n", t1 - t0, t2 - t1, mgNowS () - t2);
   return s;
 }
 

@@ -37,8 +37,7 @@
  */
 #include <stdlib.h>
 #include <string.h>
-#include "mg_common.h"
-#include <type_traits>
+#include "mg_prefix.h"
 
 #define MG_ASSIGNED 0x80000000u
 #define MG_R_QUANTUM 64u              /* slots per bucket come in multiples of this (a bucket starts on a 1 KiB boundary) */
@@ -154,30 +153,8 @@ void mgRankCountKernel (const unsigned char *__restrict__ flags, U64 n, U64 rows
       c += v[0] + v[1] + v[2] + v[3];
     }
   for ( ; row < rEnd ; ++row) { U64 o = row * 64 + lane; c += (o < n) ? (flags[o] & 1) : 0; }
-  for (int off = 32 ; off ; off >>= 1) c += __shfl_xor (c, off);
+  c = mgWaveReduce<MgSum> (c);
   if (lane == 0) unitCount[unit] = c;
-}
-
-/* exclusive scan of up to a few thousand block counts (one workgroup); counters[0] = total */
-__global__ __launch_bounds__ (1024)
-void mgRankScanKernel (const U64 *__restrict__ blockCount, U32 nBlocks, U64 *__restrict__ blockBase, U64 *__restrict__ counters)
-{
-  __shared__ U64 sPart[1024];
-  const int tid = threadIdx.x;
-  const U32 per = (nBlocks + 1023) / 1024;
-  U64 sum = 0;
-  for (U32 i = 0 ; i < per ; ++i) { U32 b = tid * per + i; if (b < nBlocks) sum += blockCount[b]; }
-  sPart[tid] = sum;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { U64 v = tid >= off ? sPart[tid - off] : 0;
-      __syncthreads ();
-      sPart[tid] += v;
-      __syncthreads ();
-    }
-  U64 run = sPart[tid] - sum;
-  for (U32 i = 0 ; i < per ; ++i) { U32 b = tid * per + i; if (b < nBlocks) { blockBase[b] = run; run += blockCount[b]; } }
-  if (tid == 1023) counters[0] = sPart[1023];
 }
 
 /* ---- k-mers read from the scan's segments (MgSegSrc) instead of a dense array ---------------------------------
@@ -1800,9 +1777,7 @@ void mgUnpartOrdKernel (const U64 *__restrict__ el, const U32 *__restrict__ idx,
 /* ======================================================================================== */
 /* host side                                                                                  */
 
-static inline unsigned mgGrid (U64 n, unsigned per = 256, unsigned cap = 16384)
-{ U64 b = (n + per - 1) / per; if (b > cap) b = cap; if (b < 1) b = 1; return (unsigned) b; }
-static inline size_t mgAl (size_t n) { return (n + 255) & ~(size_t) 255; }
+static inline unsigned mgGridWide (U64 n) { return mgGrid (n, 256, 16384); }      /* the table's kernels take up to 16384 workgroups */
 static inline int mgLog2 (U64 x) { int l = 0; while (((U64) 1 << l) < x) ++l; return l; }
 static inline MgGeom mgGeomOf (const MgTable *t) { MgGeom g; g.R = t->R; g.log2NB = t->log2NB; g.kbits = t->kbits; return g; }
 
@@ -2213,13 +2188,13 @@ size_t mgTableAddScratchBytes (const MgTable *t, U64 n)
 {
   (void) t;
   U64 NB = (U64) 1 << 18;               /* the largest bucket count: the table may grow between passes of one call */
-  size_t rank = mgAl (n) /*flags*/ + 2 * mgAl ((MG_RANK_UNITS + 8) * 8) + mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
-  size_t direct = mgAl (n * 4);
-  size_t part = 2 * (mgAl (n * 8) + mgAl (n * 4)) + mgAl (n * 4)
-              + mgAl ((NB + 2) * 8) * 3 + mgAl ((NB + 2) * 4) * 2 + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 3 + 2 * mgAl ((U64) MG_PART_MAXBINS * 16 * 8 + 4096)
-              + mgAl ((MG_PART_MAXBINS + 2) * 4) + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4)
-              + mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short)) + mgAl ((n / MG_PART_SUB + 2) * 24)
-              + mgAl (mgHotItemsCap (n) * 8) + mgAl (mgHotItemsCap (n) * 4) + 256;
+  size_t rank = mgAl256 (n) /*flags*/ + 2 * mgAl256 ((MG_RANK_UNITS + 8) * 8) + mgAl256 ((n / 64 + 2) * sizeof (MgRankGrp));
+  size_t direct = mgAl256 (n * 4);
+  size_t part = 2 * (mgAl256 (n * 8) + mgAl256 (n * 4)) + mgAl256 (n * 4)
+              + mgAl256 ((NB + 2) * 8) * 3 + mgAl256 ((NB + 2) * 4) * 2 + mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8) * 3 + 2 * mgAl256 ((U64) MG_PART_MAXBINS * 16 * 8 + 4096)
+              + mgAl256 ((MG_PART_MAXBINS + 2) * 4) + mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4)
+              + mgAl256 ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short)) + mgAl256 ((n / MG_PART_SUB + 2) * 24)
+              + mgAl256 (mgHotItemsCap (n) * 8) + mgAl256 (mgHotItemsCap (n) * 4) + 256;
   return rank + (direct > part ? direct : part) + 4096;
 }
 
@@ -2317,10 +2292,7 @@ void mgUniqStatsKernel (const U32 *__restrict__ uniqCount, U32 nBuckets, unsigne
 {
   unsigned long long sum = 0; U32 mx = 0;
   for (U32 b = blockIdx.x * 256 + threadIdx.x ; b < nBuckets ; b += gridDim.x * 256) { const U32 c = uniqCount[b]; sum += c; mx = c > mx ? c : mx; }
-  for (int off = 32 ; off ; off >>= 1)
-    { sum += ((unsigned long long) (U32) __shfl_xor ((int) (U32) (sum >> 32), off) << 32) | (U32) __shfl_xor ((int) (U32) sum, off);
-      const U32 o = (U32) __shfl_xor ((int) mx, off); mx = o > mx ? o : mx;
-    }
+  sum = mgWaveReduce<MgSum> ((U64) sum); mx = mgWaveReduce<MgMax> (mx);
   if ((threadIdx.x & 63) == 0) { if (sum) atomicAdd (&out[0], sum); if (mx) atomicMax (&out[1], (unsigned long long) mx); }
 }
 
@@ -2342,20 +2314,20 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
   t->empty = false; ++t->version;
   MgGeom g = mgGeomOf (t);
   char *wb = (char *) scratch;
-  unsigned char *flags = (unsigned char *) wb;       wb += mgAl (n);
-  U64 *blockCount = (U64 *) wb;                      wb += mgAl ((MG_RANK_UNITS + 8) * 8);
-  U64 *blockBase = (U64 *) wb;                       wb += mgAl ((MG_RANK_UNITS + 8) * 8);
-  MgRankGrp *grp = (MgRankGrp *) wb;                 wb += mgAl ((n / 64 + 2) * sizeof (MgRankGrp));
+  unsigned char *flags = (unsigned char *) wb;       wb += mgAl256 (n);
+  U64 *blockCount = (U64 *) wb;                      wb += mgAl256 ((MG_RANK_UNITS + 8) * 8);
+  U64 *blockBase = (U64 *) wb;                       wb += mgAl256 ((MG_RANK_UNITS + 8) * 8);
+  MgRankGrp *grp = (MgRankGrp *) wb;                 wb += mgAl256 ((n / 64 + 2) * sizeof (MgRankGrp));
   U32 nRankBlocks; U64 rankTiles = mgRankRowsPerUnit (n, &nRankBlocks);
   MG_HIP (hipMemsetAsync (blockCount, 0, (MG_RANK_UNITS + 8) * 8, st));
 
   if (!mgTableUseBuckets (t, n))
     { U32 *slotId = (U32 *) wb;
       { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-      MG_LAUNCH (MG_K_TABLE_INSERT, st, mgTableInsertKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, g, dKmer, n, slotId, withDepth, t->counters);
-      MG_LAUNCH (MG_K_TABLE_FLAG, st, mgDirectFlagKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->slots, slotId, n, flags);
+      MG_LAUNCH (MG_K_TABLE_INSERT, st, mgTableInsertKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, t->slots, g, dKmer, n, slotId, withDepth, t->counters);
+      MG_LAUNCH (MG_K_TABLE_FLAG, st, mgDirectFlagKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, t->slots, slotId, n, flags);
       MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
-      MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
+      MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, blockCount, blockBase, nRankBlocks * 4, t->counters);
       MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<true, false>), dim3 (nRankBlocks), dim3 (256), 0, st,
                  flags, dKmer, noSrc, (const MgSubSeg *) 0, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, slotId, grp);
       MG_HIP (hipGetLastError ());
@@ -2365,25 +2337,25 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
 
   /* ---- bucketed ---- */
   const U64 NB = (U64) 1 << t->log2NB;
-  U64 *kA = (U64 *) wb;  wb += mgAl (n * 8);
-  U32 *tA = (U32 *) wb;  wb += mgAl (n * 4);
-  U64 *kB = (U64 *) wb;  wb += mgAl (n * 8);
-  U32 *tB = (U32 *) wb;  wb += mgAl (n * 4);
-  U32 *cB = (U32 *) wb;  wb += mgAl (n * 4);
-  U64 *fineStart = (U64 *) wb;                wb += mgAl ((NB + 2) * 8);
-  unsigned long long *fineCursor = (unsigned long long *) wb; wb += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
-  U64 *spare64 = (U64 *) wb;                  wb += mgAl ((NB + 2) * 8);
-  U32 *fineCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
-  U32 *uniqCount = (U32 *) wb;                wb += mgAl ((NB + 2) * 4);
-  U64 *coarseStart = (U64 *) wb;              wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  unsigned long long *coarseCursor = (unsigned long long *) wb; wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
-  U64 *whole = (U64 *) wb;                    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  U32 *coarseCount = (U32 *) wb;              wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
-  U32 *chunkBase = (U32 *) wb;                wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);   /* + the segment of every chunk */
-  unsigned short *sliceOff = (unsigned short *) wb;   wb += mgAl ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short));
-  MgSubSeg *subSeg = (MgSubSeg *) wb;         wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
-  U64 *hotItems = (U64 *) wb;                 wb += mgAl (mgHotItemsCap (n) * 8);
-  U32 *hotBuckets = (U32 *) wb;               wb += mgAl (mgHotItemsCap (n) * 4);
+  U64 *kA = (U64 *) wb;  wb += mgAl256 (n * 8);
+  U32 *tA = (U32 *) wb;  wb += mgAl256 (n * 4);
+  U64 *kB = (U64 *) wb;  wb += mgAl256 (n * 8);
+  U32 *tB = (U32 *) wb;  wb += mgAl256 (n * 4);
+  U32 *cB = (U32 *) wb;  wb += mgAl256 (n * 4);
+  U64 *fineStart = (U64 *) wb;                wb += mgAl256 ((NB + 2) * 8);
+  unsigned long long *fineCursor = (unsigned long long *) wb; wb += mgAl256 ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
+  U64 *spare64 = (U64 *) wb;                  wb += mgAl256 ((NB + 2) * 8);
+  U32 *fineCount = (U32 *) wb;                wb += mgAl256 ((NB + 2) * 4);
+  U32 *uniqCount = (U32 *) wb;                wb += mgAl256 ((NB + 2) * 4);
+  U64 *coarseStart = (U64 *) wb;              wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8);
+  unsigned long long *coarseCursor = (unsigned long long *) wb; wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
+  U64 *whole = (U64 *) wb;                    wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8);
+  U32 *coarseCount = (U32 *) wb;              wb += mgAl256 ((MG_PART_MAXBINS + 2) * 4);
+  U32 *chunkBase = (U32 *) wb;                wb += mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);   /* + the segment of every chunk */
+  unsigned short *sliceOff = (unsigned short *) wb;   wb += mgAl256 ((size_t) (MG_RANK_GROUPS + 2) * NB * sizeof (unsigned short));
+  MgSubSeg *subSeg = (MgSubSeg *) wb;         wb += mgAl256 ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
+  U64 *hotItems = (U64 *) wb;                 wb += mgAl256 (mgHotItemsCap (n) * 8);
+  U32 *hotBuckets = (U32 *) wb;               wb += mgAl256 (mgHotItemsCap (n) * 4);
   unsigned long long *hotCount = (unsigned long long *) wb; wb += 256;
   (void) spare64;
 
@@ -2559,7 +2531,7 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
         }
     }
   MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nRankBlocks), dim3 (256), 0, st, flags, n, rankTiles, blockCount);
-  MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, nRankBlocks * 4, blockBase, t->counters);
+  MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, blockCount, blockBase, nRankBlocks * 4, t->counters);
   if (segSrc)
     MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, true>), dim3 (nRankBlocks), dim3 (256), 0, st,
                flags, (const U64 *) 0, *segSrc, subSeg, n, rankTiles, blockBase, t->max, t->size, t->value, t->slots, (const U32 *) 0, grp);
@@ -2592,7 +2564,7 @@ __global__ void mgMarkOccKernel (MgGeom g, const U64 *__restrict__ kmer, U64 n, 
 
 MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st)
 {
-  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgMarkOccKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, mgGeomOf (t), dKmer, n, t->occ);
+  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgMarkOccKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, mgGeomOf (t), dKmer, n, t->occ);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }
@@ -2602,7 +2574,7 @@ MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipSt
   if (!n) return MG_OK;
   /* with the never-written buckets zeroed once, a probe needs no look at occ[] first */
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
-  const unsigned fgrid = mgGrid ((n + MG_FIND_PER - 1) / MG_FIND_PER);
+  const unsigned fgrid = mgGridWide ((n + MG_FIND_PER - 1) / MG_FIND_PER);
   ++t->diag[MG_DIAG_FIND_DIRECT];
   MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableFindKernel<false>, dim3 (fgrid), dim3 (256), 0, st, t->slots, t->occ, mgGeomOf (t), dKmer, n, dIndexOut);
   MG_HIP (hipGetLastError ());
@@ -2644,7 +2616,7 @@ MgStatus mgTableLayoutCheck (MgTable *t, U64 *dOut, hipStream_t st)
 {
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
   MG_HIP (hipMemsetAsync (dOut, 0, 32, st));
-  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableCheckLayoutKernel, dim3 (mgGrid (t->nSlots)), dim3 (256), 0, st, t->slots, mgGeomOf (t), t->nSlots, (unsigned long long *) dOut);
+  MG_LAUNCH (MG_K_TABLE_FIND, st, mgTableCheckLayoutKernel, dim3 (mgGridWide (t->nSlots)), dim3 (256), 0, st, t->slots, mgGeomOf (t), t->nSlots, (unsigned long long *) dOut);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }
@@ -2668,9 +2640,9 @@ MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dInde
    8 bytes each, go where the caller says: the scan's unused dense k-mer array) */
 size_t mgTableFindPartScratchBytes (U64 n)
 {
-  return mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8) + mgAl (((U64) MG_PART_MAXBINS + 2) * 8) * 2
-       + mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16) + mgAl ((MG_PART_MAXBINS + 2) * 4)
-       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg)) + 4096;
+  return mgAl256 ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8) + mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8) * 2
+       + mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8 * 16) + mgAl256 ((MG_PART_MAXBINS + 2) * 4)
+       + mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + mgAl256 ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg)) + 4096;
 }
 
 /* the two-level path's extra scratch: the second pass's output (8 bytes an element), the results beside the first pass's output
@@ -2678,9 +2650,9 @@ size_t mgTableFindPartScratchBytes (U64 n)
 size_t mgTableFindPart2ScratchBytes (U64 n)
 {
   const U64 NB = (U64) 1 << 18;
-  return mgAl (n * 8) + mgAl (n * 4) + mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8)
-       + mgAl ((NB + 2) * 8) + mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8) + mgAl ((NB + 2) * 4)
-       + mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + 4096;
+  return mgAl256 (n * 8) + mgAl256 (n * 4) + mgAl256 ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8)
+       + mgAl256 ((NB + 2) * 8) + mgAl256 ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8) + mgAl256 ((NB + 2) * 4)
+       + mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4) + 4096;
 }
 
 /* does a lookup batch take the partitioned path?  It needs the scan's digit counts for this table geometry, elements that
@@ -2717,13 +2689,13 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
   if (!n) return MG_OK;
   { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
   char *wb = (char *) scratch;
-  unsigned long long *runTab = (unsigned long long *) wb;    wb += mgAl ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8);
-  U64 *binStart = (U64 *) wb;                                wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  U64 *whole = (U64 *) wb;                                   wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8);
-  unsigned long long *cursor = (unsigned long long *) wb;    wb += mgAl (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
-  U32 *binCount = (U32 *) wb;                                wb += mgAl ((MG_PART_MAXBINS + 2) * 4);
-  U32 *chunkBase = (U32 *) wb;                               wb += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
-  MgSubSeg *subSeg = (MgSubSeg *) wb;                        wb += mgAl ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
+  unsigned long long *runTab = (unsigned long long *) wb;    wb += mgAl256 ((n / MG_PART_SUB + 2) * (size_t) MG_PART_MAXBINS * 8);
+  U64 *binStart = (U64 *) wb;                                wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8);
+  U64 *whole = (U64 *) wb;                                   wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8);
+  unsigned long long *cursor = (unsigned long long *) wb;    wb += mgAl256 (((U64) MG_PART_MAXBINS + 2) * 8 * 16);
+  U32 *binCount = (U32 *) wb;                                wb += mgAl256 ((MG_PART_MAXBINS + 2) * 4);
+  U32 *chunkBase = (U32 *) wb;                               wb += mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
+  MgSubSeg *subSeg = (MgSubSeg *) wb;                        wb += mgAl256 ((n / MG_PART_SUB + 2) * sizeof (MgSubSeg));
   const int hiB = counted->hiB, loB = t->log2NB - hiB;
   const MgPartFmt f = mgPartFmtOf (t, n, hiB);
   const U32 nBins = (U32) 1 << hiB;
@@ -2731,7 +2703,7 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
   MG_HIP (hipMemcpyAsync (whole, segInit, 16, hipMemcpyHostToDevice, st));
   const bool twoLevels = scratch2 && loB > 0 && ((U32) 1 << loB) <= MG_PART_MAXBINS;
   /* (two levels) the fine digits as bytes beside the first pass's output, for the second pass's counts: in idxA, which is only written by the first pull */
-  unsigned char *digits = (twoLevels && loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> ((char *) scratch2 + mgAl (n * 8)) : 0;
+  unsigned char *digits = (twoLevels && loB <= 8 && mgKnobs ()->partDigits != 0) ? reinterpret_cast<unsigned char *> ((char *) scratch2 + mgAl256 (n * 8)) : 0;
   MgPartPassArgs p1 = {};                /* the build's first pass: from the scan's segments and its counts into el, by the coarse digit; runTab says where every sub-chunk went */
   p1.inMode = MG_EL_SEG; p1.packed = true; p1.f = f; p1.n = n; p1.segStart = whole; p1.nSeg = 1; p1.shift = loB; p1.nBins = nBins;
   p1.kOut = el; p1.binStart = binStart; p1.cursor = cursor; p1.binCount = binCount; p1.chunkBase = chunkBase;
@@ -2742,13 +2714,13 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
   if (twoLevels)      /* ---- two levels: the lookups bucket by bucket out of LDS (a table of few buckets has no fine digit: one level) ---- */
     { char *w2 = (char *) scratch2;
       const U64 NB = (U64) 1 << t->log2NB;
-      U64 *el2 = (U64 *) w2;                                   w2 += mgAl (n * 8);
-      U32 *idxA = (U32 *) w2;                                  w2 += mgAl (n * 4);
-      unsigned long long *runTab2 = (unsigned long long *) w2; w2 += mgAl ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8);
-      U64 *fineStart = (U64 *) w2;                             w2 += mgAl ((NB + 2) * 8);
-      unsigned long long *fineCursor = (unsigned long long *) w2; w2 += mgAl ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
-      U32 *fineCount = (U32 *) w2;                             w2 += mgAl ((NB + 2) * 4);
-      U32 *chunkBase2 = (U32 *) w2;                            w2 += mgAl ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
+      U64 *el2 = (U64 *) w2;                                   w2 += mgAl256 (n * 8);
+      U32 *idxA = (U32 *) w2;                                  w2 += mgAl256 (n * 4);
+      unsigned long long *runTab2 = (unsigned long long *) w2; w2 += mgAl256 ((2 * (n / (2 * (U64) MG_PART_SUB) + MG_PART_MAXBINS + 2)) * (size_t) MG_PART_MAXBINS * 8);
+      U64 *fineStart = (U64 *) w2;                             w2 += mgAl256 ((NB + 2) * 8);
+      unsigned long long *fineCursor = (unsigned long long *) w2; w2 += mgAl256 ((NB + 2 + (U64) MG_PART_MAXBINS * 16) * 8);
+      U32 *fineCount = (U32 *) w2;                             w2 += mgAl256 ((NB + 2) * 4);
+      U32 *chunkBase2 = (U32 *) w2;                            w2 += mgAl256 ((MG_PART_MAXBINS + 2 + n / MG_PART_CHUNK + MG_PART_MAXBINS + 2) * 4);
       const U32 nBins2 = (U32) 1 << loB;
       MgPartPassArgs p2 = {};            /* the second pass: el's bins by the fine digit into el2, every element's ordinal replaced by its place in el (runMode 1) */
       p2.inMode = MG_EL_PACKED; p2.packed = true; p2.f = f; p2.kIn = el; p2.n = n; p2.segStart = binStart; p2.nSeg = nBins; p2.nBins = nBins2;
@@ -2803,7 +2775,7 @@ MgStatus mgTableFindPartitioned (MgTable *t, const MgSegSrc &segSrc, U64 n, cons
 static MgStatus mgLoadLaunch (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st, U64 *over)
 {
   MG_HIP (hipMemsetAsync (t->counters + 1, 0, 8, st));
-  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGrid ((U64) last - first + 1)), dim3 (256), 0, st,
+  MG_LAUNCH (MG_K_TABLE_LOAD, st, mgTableLoadKernel, dim3 (mgGridWide ((U64) last - first + 1)), dim3 (256), 0, st,
              t->slots, mgGeomOf (t), dValue, first, last, t->occ, t->counters);
   MG_HIP (hipGetLastError ());
   return mgReadOverflow (t, st, over);
@@ -2825,7 +2797,7 @@ MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hi
   if (hipMalloc ((void **) &dFine, sizeof (U32) << MG_FINE_LOG2) != hipSuccess) return mgHipFail (hipGetLastError (), "hipMalloc");
   if (hipMemsetAsync (dFine, 0, sizeof (U32) << MG_FINE_LOG2, st) != hipSuccess) s = mgHipFail (hipGetLastError (), "hipMemsetAsync");
   else
-    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountValuesKernel, dim3 (mgGrid (last)), dim3 (256), 0, st, dValue, 1u, last, t->kbits, dFine);
+    { MG_LAUNCH (MG_K_TABLE_HIST, st, mgFineCountValuesKernel, dim3 (mgGridWide (last)), dim3 (256), 0, st, dValue, 1u, last, t->kbits, dFine);
       s = mgFitGeometry (t, dFine, mgSlotsFor (t, last), &lg, &R, st);
     }
   (void) hipFree (dFine);
@@ -2876,7 +2848,7 @@ MgStatus mgTableReplayIndex (MgTable *t, const MgHashParams &p, int tableBits, U
   U64 n = (U64) 1 << tableBits;
   MG_HIP (hipMemsetAsync (dIndex, 0xff, n * sizeof (U32), st));
   if (t->max)
-    { MG_LAUNCH (MG_K_INDEX_REPLAY, st, mgReplayIndexKernel, dim3 (mgGrid (t->max)), dim3 (256), 0, st,
+    { MG_LAUNCH (MG_K_INDEX_REPLAY, st, mgReplayIndexKernel, dim3 (mgGridWide (t->max)), dim3 (256), 0, st,
                           t->value, t->max, p.factor1, p.shift1, tableBits, dIndex);
       MG_HIP (hipGetLastError ());
     }
@@ -2935,13 +2907,13 @@ __global__ void mgPruneMoveKernel (const unsigned char *__restrict__ keep, const
 MgStatus mgTableMergeApply (const U32 *dIdx, const U16 *dDepth2, const U8 *dInfo2, U32 n2, U16 *dBaseDepth, U8 *dInfo1, hipStream_t st)
 {
   if (!n2) return MG_OK;
-  MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgMergeApplyKernel, dim3 (mgGrid (n2)), dim3 (256), 0, st, dIdx, dDepth2, dInfo2, n2, dBaseDepth, dInfo1);
+  MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgMergeApplyKernel, dim3 (mgGridWide (n2)), dim3 (256), 0, st, dIdx, dDepth2, dInfo2, n2, dBaseDepth, dInfo1);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }
 
 size_t mgTablePruneScratchBytes (U32 n)
-{ return mgAl (n) + 2 * mgAl ((MG_RANK_UNITS + 8) * 8) + mgAl (((U64) n / 64 + 2) * sizeof (MgRankGrp)) + 4096; }
+{ return mgAl256 (n) + 2 * mgAl256 ((MG_RANK_UNITS + 8) * 8) + mgAl256 (((U64) n / 64 + 2) * sizeof (MgRankGrp)) + 4096; }
 
 /* survivors of (lo <= depth < hi) keep their relative order: newValue/newDepth/newInfo[1..*]; counters[0] = how many */
 MgStatus mgTablePrune (MgTable *t, const U8 *dInfo, int lo, int hi, U64 *dNewValue, U16 *dNewDepth, U8 *dNewInfo,
@@ -2951,20 +2923,20 @@ MgStatus mgTablePrune (MgTable *t, const U8 *dInfo, int lo, int hi, U64 *dNewVal
   MG_HIP (hipMemsetAsync (t->counters, 0, 16, st));
   if (!n) return MG_OK;
   char *wb = (char *) scratch;
-  unsigned char *keep = (unsigned char *) wb;        wb += mgAl (n);
-  U64 *unitCount = (U64 *) wb;                       wb += mgAl ((MG_RANK_UNITS + 8) * 8);
-  U64 *unitBase = (U64 *) wb;                        wb += mgAl ((MG_RANK_UNITS + 8) * 8);
+  unsigned char *keep = (unsigned char *) wb;        wb += mgAl256 (n);
+  U64 *unitCount = (U64 *) wb;                       wb += mgAl256 ((MG_RANK_UNITS + 8) * 8);
+  U64 *unitBase = (U64 *) wb;                        wb += mgAl256 ((MG_RANK_UNITS + 8) * 8);
   MgRankGrp *grp = (MgRankGrp *) wb;
   U32 nBlocks; U64 rows = mgRankRowsPerUnit (n, &nBlocks);
   MG_HIP (hipMemsetAsync (unitCount, 0, (MG_RANK_UNITS + 8) * 8, st));
-  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgPruneFlagKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, t->baseDepth, n, lo, hi, keep);
+  MG_LAUNCH (MG_K_TABLE_FLAG, st, mgPruneFlagKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, t->baseDepth, n, lo, hi, keep);
   MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nBlocks), dim3 (256), 0, st, keep, (U64) n, rows, unitCount);
-  MG_LAUNCH (MG_K_RANK_SCAN, st, mgRankScanKernel, dim3 (1), dim3 (1024), 0, st, unitCount, nBlocks * 4, unitBase, t->counters);
+  MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, unitCount, unitBase, nBlocks * 4, t->counters);
   /* value[i+1] of survivor i -> newValue[1 + rank]: the assign kernel with "kmer" = value + 1, base 0 */
   const MgSegSrc noSrc = {};
   MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, false>), dim3 (nBlocks), dim3 (256), 0, st,
              keep, t->value + 1, noSrc, (const MgSubSeg *) 0, (U64) n, rows, unitBase, 0u, 0xffffffffu, dNewValue, t->slots, (const U32 *) 0, grp);
-  MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgPruneMoveKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, keep, grp, n, t->baseDepth, dInfo, dNewDepth, dNewInfo);
+  MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgPruneMoveKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, keep, grp, n, t->baseDepth, dInfo, dNewDepth, dNewInfo);
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }

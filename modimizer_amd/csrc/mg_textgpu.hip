@@ -43,7 +43,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
-#include "mg_common.h"
+#include "mg_prefix.h"
 #include "mg_internal.h"
 
 #define TX_THREADS 256
@@ -85,20 +85,6 @@ __device__ __forceinline__ U64 txEvent (U32 c, U32 prev, U64 filePos)
   return 0;
 }
 
-__device__ __forceinline__ U64 txBlockMax (U64 v, U64 *sRed)
-{
-  for (int off = 32 ; off ; off >>= 1)
-    { const U64 o = ((U64) (U32) __shfl_xor ((int) (U32) (v >> 32), off) << 32) | (U32) __shfl_xor ((int) (U32) v, off);
-      if (o > v) v = o;
-    }
-  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-  __syncthreads ();
-  U64 m = 0;
-  for (int w = 0 ; w < TX_THREADS / 64 ; ++w) if (sRed[w] > m) m = sRed[w];
-  __syncthreads ();
-  return m;
-}
-
 /* K1: the last event of every tile */
 __global__ __launch_bounds__ (TX_THREADS)
 void mgTextEventKernel (const unsigned char *__restrict__ text, U64 n, U64 textBase, U32 prevByte, U64 *__restrict__ tileEvent)
@@ -116,41 +102,16 @@ void mgTextEventKernel (const unsigned char *__restrict__ text, U64 n, U64 textB
           prev = b[j];
         }
     }
-  const U64 m = txBlockMax (last, sRed);
+  const U64 m = mgBlockReduce<TX_THREADS, MgMax> (last, sRed);
   if (threadIdx.x == 0) tileEvent[blockIdx.x] = m;
 }
 
-/* K2 / K4 helper: one workgroup scans nTiles values (inclusive), running maximum or running sum, with a carry-in */
-template <bool MAX>
-__device__ __forceinline__ void txScanTiles (U64 *v, U64 nTiles, U64 carryIn, U64 *totalOut)
-{
-  __shared__ U64 sPart[1024];
-  const int tid = threadIdx.x;
-  const U64 per = (nTiles + 1023) / 1024;
-  const U64 lo = (U64) tid * per, hi = lo + per < nTiles ? lo + per : nTiles;
-  U64 acc = 0;
-  for (U64 i = lo ; i < hi ; ++i) { const U64 x = v[i]; acc = MAX ? (x > acc ? x : acc) : acc + x; }
-  sPart[tid] = acc;
-  __syncthreads ();
-  for (int off = 1 ; off < 1024 ; off <<= 1)
-    { const U64 o = tid >= off ? sPart[tid - off] : 0;
-      __syncthreads ();
-      sPart[tid] = MAX ? (o > sPart[tid] ? o : sPart[tid]) : sPart[tid] + o;
-      __syncthreads ();
-    }
-  U64 run = tid ? sPart[tid - 1] : 0;                     /* exclusive over the threads' pieces */
-  run = MAX ? (carryIn > run ? carryIn : run) : run + carryIn;
-  for (U64 i = lo ; i < hi ; ++i)                          /* v[i] becomes the EXCLUSIVE value: what holds at the tile's first byte */
-    { const U64 x = v[i]; v[i] = run; run = MAX ? (x > run ? x : run) : run + x; }
-  if (tid == 1023) { const U64 t = sPart[1023]; *totalOut = MAX ? (carryIn > t ? carryIn : t) : t + carryIn; }
-}
-
-__global__ __launch_bounds__ (1024)
+/* K2: the running maximum over the tiles' events, on top of the state the window before ended in -> what holds at every tile's first byte */
+__global__ __launch_bounds__ (MG_GROUP_THREADS)
 void mgTextStateScanKernel (U64 *tileEvent, U64 nTiles, TxState *st)
 {
-  __shared__ U64 total;
-  txScanTiles<true> (tileEvent, nTiles, st->lastEvent, &total);
-  __syncthreads ();
+  __shared__ U64 lds[MG_GROUP_THREADS];
+  const U64 total = mgGroupScan<MgMax> (tileEvent, tileEvent, nTiles, st->lastEvent, lds);
   if (threadIdx.x == 0) st->lastEvent = total;            /* the state the next window starts in */
 }
 
@@ -158,21 +119,8 @@ void mgTextStateScanKernel (U64 *tileEvent, U64 nTiles, TxState *st)
  * the threads before it in the tile */
 __device__ __forceinline__ U64 txIncoming (U64 myLast, U64 tileIn, U64 *sScan)
 {
-  /* exclusive running maximum over the threads of the workgroup */
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  U64 v = myLast;
-  for (int off = 1 ; off < 64 ; off <<= 1)
-    { const U64 o = ((U64) (U32) __shfl_up ((int) (U32) (v >> 32), off) << 32) | (U32) __shfl_up ((int) (U32) v, off);
-      if (lane >= off && o > v) v = o;
-    }
-  if (lane == 63) sScan[wave] = v;
-  __syncthreads ();
-  U64 before = tileIn;
-  for (int w = 0 ; w < wave ; ++w) if (sScan[w] > before) before = sScan[w];
-  U64 excl = ((U64) (U32) __shfl_up ((int) (U32) (v >> 32), 1) << 32) | (U32) __shfl_up ((int) (U32) v, 1);
-  if (lane == 0) excl = 0;
-  __syncthreads ();
-  return excl > before ? excl : before;
+  const U64 excl = mgBlockExclusive<TX_THREADS, MgMax> (myLast, sScan);      /* the last event of the threads before this one */
+  return excl > tileIn ? excl : tileIn;
 }
 
 /* K3: bases and record starts of every tile */
@@ -181,7 +129,7 @@ void mgTextCountKernel (const unsigned char *__restrict__ text, U64 n, U64 textB
                         U32 *__restrict__ tileBases, U32 *__restrict__ tileStarts)
 {
   __shared__ U64 sScan[TX_THREADS / 64];
-  __shared__ U32 sB[TX_THREADS / 64], sS[TX_THREADS / 64];
+  __shared__ U32 sRed[TX_THREADS / 64];
   const U64 at = ((U64) blockIdx.x * TX_THREADS + threadIdx.x) * TX_PER;
   unsigned char b[16]; U32 prev0 = 0;
   U64 last = 0;
@@ -208,28 +156,18 @@ void mgTextCountKernel (const unsigned char *__restrict__ text, U64 n, U64 textB
           prev = b[j];
         }
     }
-  for (int off = 32 ; off ; off >>= 1) { nb += __shfl_xor (nb, off); ns += __shfl_xor (ns, off); }
-  if ((threadIdx.x & 63) == 0) { sB[threadIdx.x >> 6] = nb; sS[threadIdx.x >> 6] = ns; }
-  __syncthreads ();
-  if (threadIdx.x == 0)
-    { U32 tb = 0, ts = 0;
-      for (int w = 0 ; w < TX_THREADS / 64 ; ++w) { tb += sB[w]; ts += sS[w]; }
-      tileBases[blockIdx.x] = tb; tileStarts[blockIdx.x] = ts;
-    }
+  nb = mgBlockReduce<TX_THREADS, MgSum> (nb, sRed); ns = mgBlockReduce<TX_THREADS, MgSum> (ns, sRed);
+  if (threadIdx.x == 0) { tileBases[blockIdx.x] = nb; tileStarts[blockIdx.x] = ns; }
 }
 
 /* K4: where every tile's bases and record offsets go in the batch accumulator; the new totals */
-__global__ __launch_bounds__ (1024)
+__global__ __launch_bounds__ (MG_GROUP_THREADS)
 void mgTextOffsetScanKernel (const U32 *__restrict__ tileBases, const U32 *__restrict__ tileStarts, U64 nTiles,
                              U64 *__restrict__ tileBaseOff, U64 *__restrict__ tileStartOff, TxState *st, U64 *hostCounts)
 {
-  __shared__ U64 totB, totS;
-  for (U64 i = threadIdx.x ; i < nTiles ; i += 1024) { tileBaseOff[i] = tileBases[i]; tileStartOff[i] = tileStarts[i]; }
-  __syncthreads ();
-  txScanTiles<false> (tileBaseOff, nTiles, st->accBases, &totB);
-  __syncthreads ();
-  txScanTiles<false> (tileStartOff, nTiles, st->accRecs, &totS);
-  __syncthreads ();
+  __shared__ U64 lds[MG_GROUP_THREADS];
+  const U64 totB = mgGroupScan<MgSum> (tileBases, tileBaseOff, nTiles, st->accBases, lds);
+  const U64 totS = mgGroupScan<MgSum> (tileStarts, tileStartOff, nTiles, st->accRecs, lds);
   if (threadIdx.x == 0)
     { st->accBases = totB; st->accRecs = totS;
       hostCounts[0] = totB; hostCounts[1] = totS;           /* pinned host words: the host decides about the batch from them */
@@ -244,7 +182,7 @@ void mgTextEmitKernel (const unsigned char *__restrict__ text, U64 n, U64 textBa
                        U64 *__restrict__ recPos)      /* != 0: the file position of every record's '>' (the callers that print record ids) */
 {
   __shared__ U64 sScan[TX_THREADS / 64];
-  __shared__ U32 sB[TX_THREADS / 64], sS[TX_THREADS / 64];
+  __shared__ U32 sRed[TX_THREADS / 64];
   const U64 at = ((U64) blockIdx.x * TX_THREADS + threadIdx.x) * TX_PER;
   unsigned char b[16]; U32 prev0 = 0;
   U64 last = 0;
@@ -272,18 +210,8 @@ void mgTextEmitKernel (const unsigned char *__restrict__ text, U64 n, U64 textBa
           prev = b[j];
         }
     }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  U32 ib = nb, is = ns;
-  for (int off = 1 ; off < 64 ; off <<= 1)
-    { const U32 ob = __shfl_up (ib, off), os = __shfl_up (is, off);
-      if (lane >= off) { ib += ob; is += os; }
-    }
-  if (lane == 63) { sB[wave] = ib; sS[wave] = is; }
-  __syncthreads ();
-  U32 wb = 0, ws = 0;
-  for (int w = 0 ; w < wave ; ++w) { wb += sB[w]; ws += sS[w]; }
-  U64 myB = tileBaseOff[blockIdx.x] + wb + ib - nb;
-  U64 myS = tileStartOff[blockIdx.x] + ws + is - ns;
+  U64 myB = tileBaseOff[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nb, sRed);
+  U64 myS = tileStartOff[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (ns, sRed);
   if (!nb && !ns) return;
   if (myB + nb > basesCap || myS + ns > recCap) { *overflow = 1; return; }
   bool header = (in & 1) != 0;
@@ -353,30 +281,6 @@ struct TqState {
   U64 bad;              /* != 0: a rule was broken somewhere in the accumulator's text */
 };
 
-__device__ __forceinline__ U32 tqBlockSum (U32 v, U32 *sRed)
-{
-  for (int off = 32 ; off ; off >>= 1) v += __shfl_xor (v, off);
-  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-  __syncthreads ();
-  U32 t = 0;
-  for (int w = 0 ; w < TX_THREADS / 64 ; ++w) t += sRed[w];
-  __syncthreads ();
-  return t;
-}
-/* exclusive prefix of v over the workgroup's threads */
-__device__ __forceinline__ U32 tqBlockExcl (U32 v, U32 *sScan)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  U32 incl = v;
-  for (int off = 1 ; off < 64 ; off <<= 1) { const U32 o = __shfl_up (incl, off); if (lane >= off) incl += o; }
-  if (lane == 63) sScan[wave] = incl;
-  __syncthreads ();
-  U32 before = 0;
-  for (int w = 0 ; w < wave ; ++w) before += sScan[w];
-  __syncthreads ();
-  return before + incl - v;
-}
-
 /* Kq1: newlines per tile */
 __global__ __launch_bounds__ (TX_THREADS)
 void mgTextNewlineKernel (const unsigned char *__restrict__ text, U64 n, U64 *__restrict__ tileNL)
@@ -389,17 +293,16 @@ void mgTextNewlineKernel (const unsigned char *__restrict__ text, U64 n, U64 *__
 #pragma unroll
       for (int j = 0 ; j < 16 ; ++j) c += (at + j < n && b[j] == '\n') ? 1u : 0u;
     }
-  const U32 t = tqBlockSum (c, sRed);
+  const U32 t = mgBlockReduce<TX_THREADS, MgSum> (c, sRed);
   if (threadIdx.x == 0) tileNL[blockIdx.x] = t;
 }
 
 /* Kq2: the line number at every tile's first byte */
-__global__ __launch_bounds__ (1024)
+__global__ __launch_bounds__ (MG_GROUP_THREADS)
 void mgTextLineScanKernel (U64 *tileNL, U64 nTiles, TqState *st)
 {
-  __shared__ U64 total;
-  txScanTiles<false> (tileNL, nTiles, st->nlCount, &total);
-  __syncthreads ();
+  __shared__ U64 lds[MG_GROUP_THREADS];
+  const U64 total = mgGroupScan<MgSum> (tileNL, tileNL, nTiles, st->nlCount, lds);
   if (threadIdx.x == 0) st->nlCount = total;
 }
 
@@ -442,28 +345,23 @@ void mgTextFastqCountKernel (const unsigned char *__restrict__ text, U64 n, U32 
 #pragma unroll
       for (int j = 0 ; j < 16 ; ++j) nl += (at + j < n && b[j] == '\n') ? 1u : 0u;
     }
-  const U64 line = tileLine[blockIdx.x] + tqBlockExcl (nl, sScan);
+  const U64 line = tileLine[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nl, sScan);
   U32 nb = 0, nq = 0, ne = 0, bad = 0;
   if (at < n) tqWalk<false> (b, at, n, prev, line, 0, &nb, &nq, &ne, &bad, 0, 0, 0, 0, 0, 0, 0);
   if (bad) st->bad = 1;
-  const U32 tb = tqBlockSum (nb, sRed), tq = tqBlockSum (nq, sRed), te = tqBlockSum (ne, sRed);
+  const U32 tb = mgBlockReduce<TX_THREADS, MgSum> (nb, sRed), tq = mgBlockReduce<TX_THREADS, MgSum> (nq, sRed), te = mgBlockReduce<TX_THREADS, MgSum> (ne, sRed);
   if (threadIdx.x == 0) { tileBases[blockIdx.x] = tb; tileQual[blockIdx.x] = tq; tileEnds[blockIdx.x] = te; }
 }
 
 /* Kq4: where the tiles' bases / quality counts / record ends go; the new totals */
-__global__ __launch_bounds__ (1024)
+__global__ __launch_bounds__ (MG_GROUP_THREADS)
 void mgTextFastqOffsetKernel (const U32 *__restrict__ tileBases, const U32 *__restrict__ tileQual, const U32 *__restrict__ tileEnds, U64 nTiles,
                               U64 *__restrict__ offB, U64 *__restrict__ offQ, U64 *__restrict__ offE, TqState *st, U64 *hostCounts)
 {
-  __shared__ U64 totB, totQ, totE;
-  for (U64 i = threadIdx.x ; i < nTiles ; i += 1024) { offB[i] = tileBases[i]; offQ[i] = tileQual[i]; offE[i] = tileEnds[i]; }
-  __syncthreads ();
-  txScanTiles<false> (offB, nTiles, st->accBases, &totB);
-  __syncthreads ();
-  txScanTiles<false> (offQ, nTiles, st->accQual, &totQ);
-  __syncthreads ();
-  txScanTiles<false> (offE, nTiles, st->accRecs, &totE);
-  __syncthreads ();
+  __shared__ U64 lds[MG_GROUP_THREADS];
+  const U64 totB = mgGroupScan<MgSum> (tileBases, offB, nTiles, st->accBases, lds);
+  const U64 totQ = mgGroupScan<MgSum> (tileQual, offQ, nTiles, st->accQual, lds);
+  const U64 totE = mgGroupScan<MgSum> (tileEnds, offE, nTiles, st->accRecs, lds);
   if (threadIdx.x == 0)
     { st->accBases = totB; st->accQual = totQ; st->accRecs = totE;
       hostCounts[0] = totB; hostCounts[1] = totE; hostCounts[2] = totQ; hostCounts[3] = st->nlCount; hostCounts[4] = st->bad;
@@ -486,12 +384,12 @@ void mgTextFastqEmitKernel (const unsigned char *__restrict__ text, U64 n, U64 t
 #pragma unroll
       for (int j = 0 ; j < 16 ; ++j) nl += (at + j < n && b[j] == '\n') ? 1u : 0u;
     }
-  const U64 line = tileLine[blockIdx.x] + tqBlockExcl (nl, sScan);
+  const U64 line = tileLine[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nl, sScan);
   U32 nb = 0, nq = 0, ne = 0, bad = 0;
   if (at < n) tqWalk<false> (b, at, n, prev, line, 0, &nb, &nq, &ne, &bad, 0, 0, 0, 0, 0, 0, 0);
-  const U64 myB = offB[blockIdx.x] + tqBlockExcl (nb, sScan);
-  const U64 myQ = offQ[blockIdx.x] + tqBlockExcl (nq, sScan);
-  const U64 myE = offE[blockIdx.x] + tqBlockExcl (ne, sScan) + 1;                     /* entry 0 is the accumulator's start */
+  const U64 myB = offB[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nb, sScan);
+  const U64 myQ = offQ[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nq, sScan);
+  const U64 myE = offE[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (ne, sScan) + 1;                     /* entry 0 is the accumulator's start */
   if (at >= n || (!nb && !ne)) return;
   if (myB + nb > basesCap || myE + ne > recCap) { *overflow = 1; return; }
   U32 x0 = 0, x1 = 0, x2 = 0, x3 = 0;
@@ -509,11 +407,8 @@ __global__ void mgTextFastqCheckKernel (const U64 *__restrict__ endB, const U64 
 /* ---------------------------------------------------------------------------------------- */
 /* host side                                                                                  */
 
-static inline size_t txAl (size_t n) { return (n + 255) & ~(size_t) 255; }
-#include <time.h>
-static double txNow (void) { struct timespec ts; clock_gettime (CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 static bool txTiming (void) { return mgKnobs ()->textTiming == 1; }   /* dev knob */
-struct TxClock { double reserve = 0, read = 0, wait = 0, flush = 0, ids = 0, sink = 0, t0 = 0; void lap (double &slot) { const double n = txNow (); slot += n - t0; t0 = n; } };
+struct TxClock { double reserve = 0, read = 0, wait = 0, flush = 0, ids = 0, sink = 0, t0 = 0; void lap (double &slot) { const double n = mgNowS (); slot += n - t0; t0 = n; } };
 
 struct TxBufs {
   int dev = -1;
@@ -728,10 +623,10 @@ struct TxIds {
         for (size_t i = a ; i < b ; ++i)
           { off[first + i] = (U64) o; memcpy (bytes.data () + o, win + at[i] + 1, len[i]); o += len[i]; bytes[o++] = 0; }
       };
-    const double tA = txNow ();
+    const double tA = mgNowS ();
     { std::vector<std::thread> th; for (int t = 1 ; t < nThreads ; ++t) th.emplace_back (work, t); work (0); for (auto &x : th) x.join (); }
     pthread_barrier_destroy (&bar);
-    tLens += txNow () - tA;
+    tLens += mgNowS () - tA;
     open = false;
   }
   /* the headers of a window: all but the last through the team (an id ends before the next header starts), the last one -- which may
@@ -827,7 +722,7 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
   int rc = -1;
   U64 nSeq = 0, totLen = 0;
   do {
-    TxClock ck; ck.t0 = txNow ();
+    TxClock ck; ck.t0 = mgNowS ();
     if (txReserve (t, window, 1 << 20, 4096)) { mgSetError ("device text parser: allocation failed"); break; }      /* the accumulators grow to what the windows' counts ask for */
     ck.lap (ck.reserve);
     TxState init; init.lastEvent = 0; init.accBases = 0; init.accRecs = 0;
@@ -849,10 +744,10 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
         const U64 nTiles = (nCur + TX_TILE - 1) / TX_TILE;
         if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { failed = true; break; }      /* the window's copy was started as soon as it was read (copy stream) */
         hipLaunchKernelGGL (mgTextEventKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, (U64) off, prevByte, t.dTileEvent);
-        hipLaunchKernelGGL (mgTextStateScanKernel, dim3 (1), dim3 (1024), 0, st, t.dTileEvent, nTiles, t.dState);
+        hipLaunchKernelGGL (mgTextStateScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dTileEvent, nTiles, t.dState);
         hipLaunchKernelGGL (mgTextCountKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, (U64) off, prevByte,
                             t.dTileEvent, t.dTileBases, t.dTileStarts);
-        hipLaunchKernelGGL (mgTextOffsetScanKernel, dim3 (1), dim3 (1024), 0, st, t.dTileBases, t.dTileStarts, nTiles, t.dTileBaseOff, t.dTileStartOff, t.dState, t.hCounts);
+        hipLaunchKernelGGL (mgTextOffsetScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dTileBases, t.dTileStarts, nTiles, t.dTileBaseOff, t.dTileStartOff, t.dState, t.hCounts);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
         const U32 prevOfWindow = prevByte;
         prevByte = t.hPin[cur][nCur - 1];
@@ -937,7 +832,7 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
   int rc = -1;
   U64 nSeq = 0, totLen = 0, resume = 0;
   do {
-    TxClock ck; ck.t0 = txNow ();
+    TxClock ck; ck.t0 = mgNowS ();
     if (txReserve (t, window, 1 << 20, 4096)) { mgSetError ("device text parser: allocation failed"); break; }
     ck.lap (ck.reserve);
     TqState init; memset (&init, 0, sizeof (init));
@@ -960,10 +855,10 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
         const U64 nTiles = (nCur + TX_TILE - 1) / TX_TILE;
         if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { failed = true; break; }      /* the window's copy was started as soon as it was read (copy stream) */
         hipLaunchKernelGGL (mgTextNewlineKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, t.dTileEvent);
-        hipLaunchKernelGGL (mgTextLineScanKernel, dim3 (1), dim3 (1024), 0, st, t.dTileEvent, nTiles, t.dTq);
+        hipLaunchKernelGGL (mgTextLineScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dTileEvent, nTiles, t.dTq);
         hipLaunchKernelGGL (mgTextFastqCountKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, prevByte, t.dTileEvent,
                             t.dTileBases, t.dTileQual, t.dTileStarts, t.dTq);
-        hipLaunchKernelGGL (mgTextFastqOffsetKernel, dim3 (1), dim3 (1024), 0, st, t.dTileBases, t.dTileQual, t.dTileStarts, nTiles,
+        hipLaunchKernelGGL (mgTextFastqOffsetKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dTileBases, t.dTileQual, t.dTileStarts, nTiles,
                             t.dTileBaseOff, t.dTileOffQ, t.dTileStartOff, t.dTq, t.hCounts);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
         const U32 prevOfWindow = prevByte;

@@ -1,6 +1,7 @@
 """GPU parity: the HIP scan (K1/K2) through the C ABI vs the oracle and the golden vectors.
 Bit-exact: these are integer k-mers, positions and strand flags."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -348,6 +349,39 @@ def _minimizer_batch_vs_oracle(k, w, seed):
     bases, offs = util.concat_reads(reads)
     hv, pos, isf, st = mg.minimizer_batch(sh, bases, offs)
     assert st[0] == 0 and st[-1] == len(hv) == sum(len(x[0]) for x in want)
+    for r, (a, b, c) in enumerate(want):
+        s, e = st[r], st[r + 1]
+        assert np.array_equal(hv[s:e], a) and np.array_equal(pos[s:e], b) and np.array_equal(isf[s:e], c), r
+
+
+_MANY_KW = (15, 5, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_short_reads():
+    """2049 reads of k + w + (0..5) bases, a few of them empty (the last one too), and the oracle's minimizers of each: made once, the
+    cases take prefixes of it"""
+    from oracle import pyoracle as orc
+    k, w, seed = _MANY_KW
+    rng = np.random.default_rng(2049)
+    lens = k + w + rng.integers(0, 6, 2049)
+    lens[[7, 500, 1022, 1023, 1024, 2000, 2048]] = 0
+    reads = [rng.integers(0, 4, int(n)).astype(np.uint8) for n in lens]
+    h = orc.Hasher(k, w, seed)
+    return reads, [h.minimizers(r) for r in reads]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_reads", [1, 1023, 1024, 1025, 2049])
+def test_minimizer_batch_read_counts_around_the_scan_workgroup(n_reads):
+    """the per-read counts are scanned by ONE workgroup of 1024 (mg_prefix.h, mgGroupScan): up to 1024 reads a thread takes one count, from
+    1025 on two -- and then half the threads own nothing, their pieces starting past the end; 2049 makes it three"""
+    reads, want = _many_short_reads()
+    reads, want = reads[:n_reads], want[:n_reads]
+    sh = mg.seqhashCreate(*_MANY_KW)
+    bases, offs = util.concat_reads(reads)
+    hv, pos, isf, st = mg.minimizer_batch(sh, bases, offs)
+    assert len(st) == n_reads + 1 and st[0] == 0 and st[-1] == len(hv) == sum(len(x[0]) for x in want)
     for r, (a, b, c) in enumerate(want):
         s, e = st[r], st[r + 1]
         assert np.array_equal(hv[s:e], a) and np.array_equal(pos[s:e], b) and np.array_equal(isf[s:e], c), r

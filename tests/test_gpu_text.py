@@ -121,6 +121,69 @@ def test_device_fastq_parser_equals_host_parser(n_rec, seed, crlf, window_kb, ba
         assert np.array_equal(a & 3, b & 3), (i, len(a), len(b))           # the host parser's batch keeps (char) -2 for other bytes: 2 once packed
 
 
+# ---- more tiles in a window than the tile scans' workgroup has threads (mg_prefix.h, mgGroupScan) ----
+# A window of 4100 KiB is 1025 tiles of 4 KiB: a thread of the one scanning workgroup takes two tiles and half the threads none; 8192 KiB
+# is 2048 tiles, two for every thread.  The files are a little over 2 x 4100 KiB: three windows (two), so the scans start from what the
+# window before left, in the sums and in the running maximum.
+WIN_SMALL, WIN_LARGE = 4100 << 10, 8192 << 10
+LONG_LINE = 9000                                            # a header line over two whole tiles: the tile after them takes its state from two tiles back
+MANY_TILES_END = 2 * WIN_SMALL + 60_000
+# where a record starts ('>' / '@'): first byte of a tile, of a window of either size; the long header lines at a tile's and at the large
+# window's first byte, the second one running across the small window's third start
+ANCHORS = [(10 * 4096, 0), (300 * 4096, LONG_LINE), (1024 * 4096, 0), (WIN_SMALL, 0), (1500 * 4096, 0), (WIN_LARGE, LONG_LINE), (MANY_TILES_END, 0)]
+
+
+def _many_tiles_text(fmt):
+    rng = np.random.default_rng(1025)
+    out, size = [], 0
+
+    def put(b):
+        nonlocal size
+        out.append(b); size += len(b)
+
+    for at, long_hdr in ANCHORS:
+        while at - size > 400_000:                          # filler: the crafted records of the tests above
+            put(crafted_fasta(rng, 100, "mixed") if fmt == "fa" else crafted_fastq(rng, 800))
+        gap = at - size                                     # one record of exactly that many bytes, so that the next one starts at the anchor
+        assert gap >= 16
+        if fmt == "fa":
+            put(b">pad\n" + b"ACGTN" * ((gap - 6) // 5) + b"a" * ((gap - 6) % 5) + b"\n")
+        else:
+            hdr = b"@pad" if gap % 2 else b"@pad2"          # header, n bases, "+", n qualities and four newlines: an even gap takes the odd header
+            n = (gap - len(hdr) - 5) // 2
+            put(hdr + b"\n" + b"C" * n + b"\n+\n" + b"I" * n + b"\n")
+        assert size == at
+        if at == MANY_TILES_END:
+            break
+        hdr = b"anchor %d " % at + b"x>@+" * (long_hdr // 4)
+        put(b">" + hdr + b"\nACGTACGT\n" if fmt == "fa" else b"@" + hdr + b"\nACGTACGT\n+\nIIIIIIII\n")
+    return b"".join(out)
+
+
+@pytest.fixture(scope="module", params=["fa", "fq"])
+def many_tiles_file(request, tmp_path_factory):
+    """(format, path, the host parser's records): made once for both window sizes"""
+    path = str(tmp_path_factory.mktemp("many_tiles") / ("t." + request.param))
+    text = _many_tiles_text(request.param)
+    open(path, "wb").write(text)
+    for at, _ in ANCHORS[:-1]:
+        assert text[at - 1:at + 1] == (b"\n>" if request.param == "fa" else b"\n@")
+    _, want = parse_file(path, 1 << 40, 4)
+    return request.param, path, want
+
+
+@pytest.mark.parametrize("window_kb,n_tiles", [(4100, 1025), (8192, 2048)])
+def test_device_parser_with_more_tiles_than_scan_threads(many_tiles_file, window_kb, n_tiles):
+    fmt, path, want = many_tiles_file
+    assert (window_kb << 10) // 4096 == n_tiles and os.path.getsize(path) > 2 * WIN_SMALL
+    with mg.knobs(TEXT_WINDOW_KB=window_kb):
+        rc, got = device_records(path)
+    assert rc == 0, mg.lib().mgLastError()
+    assert len(got) == len(want)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert np.array_equal(a, b) if fmt == "fa" else np.array_equal(a & 3, b & 3), (i, len(a), len(b))      # (FASTQ: as in the test above)
+
+
 BROKEN = {
     "no_plus": lambda recs: recs[:700] + [recs[700].replace(b"\n+", b"\n-", 1)] + recs[701:],
     "no_at": lambda recs: recs[:901] + [b"#" + recs[901][1:]] + recs[902:],

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dev: VGPRs / scratch / occupancy of every kernel of a .hip file (hipcc -S, device only): python tools/kernel_regs.py mg_table.hip [filter]"""
+"""dev: VGPRs / scratch / LDS / occupancy of every kernel of a .hip file (hipcc -S, device only): python tools/kernel_regs.py mg_table.hip [filter]"""
 import re, subprocess, sys, os
 src = sys.argv[1]; flt = sys.argv[2] if len(sys.argv) > 2 else ""
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "modimizer_amd", "csrc")
@@ -16,4 +16,4 @@ for line in open(out):
     if m and name:
         info[m.group(1)] = int(m.group(2))
         if m.group(1) == "Occupancy" and flt in name:      # the last of the five in the compiler's listing
-            print("%-90s vgpr %3d agpr %3d scratch %4d occupancy %d" % (name[:90], info.get("NumVgprs", -1), info.get("NumAgprs", 0), info.get("ScratchSize", -1), info.get("Occupancy", -1)))
+            print("%-90s vgpr %3d agpr %3d scratch %4d lds %5d occupancy %d" % (name[:90], info.get("NumVgprs", -1), info.get("NumAgprs", 0), info.get("ScratchSize", -1), info.get("LDSByteSize", -1), info.get("Occupancy", -1)))
