@@ -102,7 +102,9 @@ template <int THREADS, class Op, class T> __device__ __forceinline__ T mgBlockEx
 /* ---- one workgroup of MG_GROUP_THREADS, n counts -----------------------------------------
  * out[i] = carryIn op in[0] op ... op in[i - 1] for i < n; every thread returns carryIn op in[0] op ... op in[n - 1].  in == out is allowed,
  * and TO may be wider than TI.  Thread t takes the ceil (n / 1024) counts from t * that on (none, if they start at n or beyond), the
- * threads' values are scanned by Hillis-Steele over lds (1024 words, free again on return).  N: the width of n and of the index arithmetic. */
+ * threads' values are scanned by Hillis-Steele over lds (1024 words, free again on return).  N: the width of n and of the index arithmetic.
+ * Precondition: n + 1023 and lo + per (at most n + per - 1, per <= n / 1024 + 1) must not overflow N.  Every present caller holds n far below
+ * that: n is a number of tiles, blocks or reads of one batch. */
 template <class Op, class TI, class TO, class N> __device__ __forceinline__ TO mgGroupScan (const TI *in, TO *out, N n, TO carryIn, TO *lds)
 {
   const U32 tid = threadIdx.x;

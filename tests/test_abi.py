@@ -113,3 +113,54 @@ def test_binary_carries_the_hash_of_its_sources(tmp_path, monkeypatch):
         assert mg.source_hash() == h
     # a library file without the marker (or none at all) has no hash
     assert mg.binary_hash(str(tmp_path / "nothing.so")) is None
+
+
+def block_uses():
+    """every mgBlockReduce / mgBlockInclusive / mgBlockExclusive<THREADS, Op> the library's kernels call, THREADS as a number: a macro is
+    resolved through the #define of its file or of mg_prefix.h (MG_GROUP_THREADS), one macro may name another"""
+    csrc = mg.CSRC
+    define = re.compile(r"^#define[ \t]+(\w+)[ \t]+(\w+)", re.M)
+    common = dict(define.findall(open(os.path.join(csrc, "mg_prefix.h")).read()))
+    uses = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(".hip"):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        macros = dict(common, **dict(define.findall(src)))
+        for m in re.finditer(r"\bmgBlock(Reduce|Inclusive|Exclusive)\s*<\s*(\w+)\s*,\s*(\w+)\s*>", src):
+            t = m.group(2)
+            for _ in range(8):
+                if t.isdigit():
+                    break
+                assert t in macros, (f, m.group(0), "what is %s?" % t)
+                t = macros[t]
+            assert t.isdigit(), (f, m.group(0))
+            uses.append((f, m.group(1), int(t), m.group(3)))
+    return uses
+
+
+def test_probe_covers_every_block_instantiation_of_the_library():
+    """what the library instantiates of mg_prefix.h's workgroup primitives is what tests/test_gpu_prefix.py drives through the probe: a
+    kernel that starts to call, say, mgBlockExclusive<512, MgMax> fails here until the probe and its table cover that pair"""
+    import test_gpu_prefix as tp
+    uses = block_uses()
+    assert len(uses) >= 20 and {u[1] for u in uses} == {"Reduce", "Inclusive", "Exclusive"}      # the regex still finds them
+    assert ("mg_settext.hip", "Reduce", 1024, "MgMax") in uses                                      # ST_SCAN_THREADS -> MG_GROUP_THREADS -> 1024
+    pairs = tp.block_pairs()
+    missing = sorted({u for u in uses if (u[2], u[3]) not in pairs})
+    assert not missing, missing
+    # and the probe's source instantiates what the table lists
+    src = open(os.path.join(ROOT, "oracle", "prefix_probe.hip")).read()
+    for t, op, bits in tp.BLOCK_INSTANTIATIONS:
+        assert re.search(r"case %d:" % t, src) and "probeBlockThreads<%s, U%d>" % (tp.OPS[op], bits) in src, (t, op, bits)
+
+
+def test_probe_carries_the_hash_of_its_sources():
+    """libprefixprobe.so is git-ignored and rides along like libmodgpu.so: oracle/Makefile bakes a hash of prefix_probe.hip and
+    mg_prefix.h into it, the tests recompute it from the tree, and a probe of other sources is rebuilt before it is used"""
+    import test_gpu_prefix as tp
+    h = tp.probe_source_hash()
+    assert re.fullmatch(r"[0-9a-f]{16}", h)
+    tp.build_probe()
+    assert tp.probe_binary_hash() == h
+    assert tp.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None

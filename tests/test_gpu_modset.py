@@ -962,3 +962,90 @@ def _modmap_randomized(L, k, w, seed, tmp_path, pad=0):
         oref.close()
     assert n_reads_total >= 42 and n_m_lines > 20
     assert n_overflow >= 1 or w >= 31, "no read with more than 16 M blocks: the overflow path was not exercised"
+
+
+# ---- the reference build past 1024 / 2048 tiles: mg_refpack.hip's three launches of mgGroupSumKernel<U32, U32> ----
+
+REF_TILE = 4096                # mg_refpack.hip MG_SCAN_TILE
+
+
+@pytest.mark.gpu
+def test_reference_build_past_2048_tiles_vs_oracle(tmp_path):
+    """mgReferenceRead on 8.5 Mbp in memory, k = 15, w = 1 (every k-mer a seed, one append batch), against the oracle's Reference: the
+    append's scan of tile counts runs over more than 2048 tiles (three counts per thread of mgGroupScan), mgRefExclusiveScan's over more
+    than 1024 (ms->max + 1 entries), and a further read of 4.3 M seeds that have no index goes through the packed branch's count over
+    more than 1024 tiles, which has to come out as exactly 0 (anything else is `reference size overflow`).  All three tile counts are
+    asserted.  Table bits 25, not 24: a set of 24 bits holds 2^22 - 2 entries at most (modset.c:24-26), which is 1024 tiles of 4096 and
+    no more.  Segments of 100 kb copied once and three times (one copy reverse-complemented) give the copy-2 and copy-M classes; five reads
+    through mgQueryProcess show that the packed reference is the reference's."""
+    L = mg.lib()
+    k, w, seed, bits = 15, 1, 17, 25
+    rng = np.random.default_rng(20251)
+    main = rng.integers(0, 4, 8_450_000).astype(np.uint8)
+    seg = 100_000
+    a2, a3 = 1_000_000, 3_000_000                                   # the sources; the copies lie clear of them and of one another
+    main[5_000_000:5_000_000 + seg] = main[a2:a2 + seg]                                     # copied once: copy 2
+    main[6_000_000:6_000_000 + seg] = main[a3:a3 + seg]                                     # copied three times: copy M
+    main[7_000_000:7_000_000 + seg] = _revcomp(main[a3:a3 + seg])
+    main[8_000_000:8_000_000 + seg] = main[a3:a3 + seg]
+    main = util.without_two_letter_windows(main, k)
+    second = util.without_two_letter_windows(np.concatenate([rng.integers(0, 4, 40_000).astype(np.uint8), main[a2 + 500:a2 + 10_500]]), k)
+    seqs, names = [main, second], ["main", "second"]
+    # ---- oracle ----
+    oh = po.Hasher(k, w, seed); oms = po.Modset(oh, bits); oref = po.Reference(oms)
+    for nm, s in zip(names, seqs):
+        oref.add_sequence(nm, s)
+    assert not oms.p.contents.overflow
+    oref.finish()
+    oa = oref.arrays()
+    # ---- the library ----
+    sh = mg.seqhashCreate(k, w, seed); ms = mg.modsetCreate(sh, bits)
+    ref = L.mgReferenceCreate(ms, 1 << 26)
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    g = np.concatenate(seqs)
+    cn = (C.c_char_p * 2)(*[n.encode() for n in names])
+    with mg.CFile(str(tmp_path / "r.txt"), "w") as f:
+        assert L.mgReferenceRead(ref, g.ctypes.data, offs.ctypes.data, 2, cn, True, f) == 0
+    R = C.cast(ref, C.POINTER(mg.MgReference)).contents
+    U, occ = ms.contents.max, R.max
+    n_seeds = sum(len(s) - k + 1 for s in seqs)
+    assert occ == n_seeds and occ + 2 <= 1 << 26           # adding: every seed has an index, so the batch of the append IS the occurrences
+    assert (occ + REF_TILE - 1) // REF_TILE > 2048         # mgRefBuildAppend's scan: tiles of the batch
+    assert (U + 1 + REF_TILE - 1) // REF_TILE > 1024       # mgRefExclusiveScan over depth[0 .. ms->max]
+    as_np = lambda p, n: np.ctypeslib.as_array(p, (max(n, 1),))[:n]
+
+    def same_as_the_oracle():
+        assert ms.contents.max == U == oms.max and R.max == occ == len(oa["index"])
+        for key, n in (("index", occ), ("offset", occ), ("id", occ), ("rev", occ), ("depth", U + 1), ("loc", U + 1)):
+            assert np.array_equal(as_np(getattr(R, key), n), oa[key]), key
+        assert np.array_equal(as_np(ms.contents.value, U + 1)[1:], oms.values()[1:])
+        assert np.array_equal(as_np(ms.contents.info, U + 1)[1:], oms.infos()[1:])           # copy classes, modmap.c:125-129
+    same_as_the_oracle()
+    cls = np.bincount(oms.infos()[1:] & 3, minlength=4)
+    assert cls[1] > 7_000_000 and cls[2] > seg // 2 and cls[3] > seg // 2                    # copy 1, copy 2, copy M: all there
+    # ---- the packed branch: 4.3 M seeds, none with an index, nothing added ----
+    none = np.random.default_rng(3).integers(0, 2, 4_300_000).astype(np.uint8)              # over {A, C}: no k-mer of the reference
+    assert (len(none) - k + 1 + REF_TILE - 1) // REF_TILE > 1024
+    assert oref.p.contents.max == occ
+    oref.add_sequence("none", none, is_add=False)
+    assert oref.p.contents.max == occ                                                       # (the oracle finds none either)
+    o2 = np.array([0, len(none)], np.int64)
+    cn2 = (C.c_char_p * 1)(b"none")
+    with mg.CFile(str(tmp_path / "r2.txt"), "w") as f:
+        assert L.mgReferenceRead(ref, none.ctypes.data, o2.ctypes.data, 1, cn2, False, f) == 0
+    same_as_the_oracle()
+    # ---- five reads through the packed reference ----
+    reads = [main[2_000_000:2_008_000].copy(), _revcomp(main[4_100_000:4_109_000]), main[a2 + seg - 4_000:a2 + seg + 4_000].copy(),
+             main[7_000_000 - 3_000:7_000_000 + 5_000].copy(), _mutate(rng, second[35_000:45_000], 0.02)]
+    rnames = ["q%d" % i for i in range(len(reads))]
+    want = "".join(oref.query(nm, r, str(tmp_path / "o.txt"))[0] for nm, r in zip(rnames, reads))
+    assert sum(l.startswith("M\t") for l in want.splitlines()) >= 5
+    qb, qo = util.concat_reads(reads)
+    cq = (C.c_char_p * len(reads))(*[n.encode() for n in rnames])
+    out = str(tmp_path / "q.txt")
+    with mg.CFile(out, "w") as f:
+        assert L.mgQueryProcess(ref, qb.ctypes.data, qo.ctypes.data, len(reads), cq, f) == 0
+    got = open(out).read()
+    assert got == want, [x for x in zip(got.splitlines(), want.splitlines()) if x[0] != x[1]][:3]
+    L.mgReferenceDestroy(ref); L.modsetDestroy(ms)
+    oref.close(); oms.close()

@@ -185,3 +185,118 @@ def test_readset_vs_oracle_saturation_and_batches(tmp_path):
         assert rs_lines(stats_text(rs, str(tmp_path / "s.txt"))) == rs_lines(ors.stats_text(str(tmp_path / "o.txt")))
         L.mgReadsetDestroy(rs)
     ors.close(); oms.close()
+
+
+# ---- more than 1024 tiles of seeds in one batch: the tile scan (mgRsTileScanKernel) past one count per thread ----
+
+RS_TILE = 4096                 # mg_chain.hip MG_RS_TILE: seeds per tile
+RS_K = 15
+# tiles -> seeds of the batch: a last tile that holds the end of a gap read and little more, a last tile that is exactly full, one more tile than that
+RS_TILE_CASES = {1025: 1024 * RS_TILE + 4000, 2048: 2048 * RS_TILE, 2049: 2048 * RS_TILE + 4000}
+_rs_shared = {}
+
+
+def _rs_genome_and_mod():
+    """the genome and the oracle's modset of its k-mers as .mod bytes, made once for the cases (the oracle's set itself is kept too: a read
+    set zeroes its depths when it begins, modasm.c:158, and leaves the rest as it is)"""
+    if not _rs_shared:
+        from oracle import pyoracle as orc
+        import tempfile
+        g = util.without_two_letter_windows(np.random.default_rng(2024).integers(0, 4, 200_000).astype(np.uint8), RS_K)
+        h = orc.Hasher(RS_K, 1, 17); oms = orc.Modset(h, 20)
+        oms.add_sequence(g)
+        oms.set_copy(1, 2, 3)
+        with tempfile.TemporaryDirectory() as d:
+            oms.write_mod(os.path.join(d, "m.mod"))
+            _rs_shared.update(g=g, oms=oms, mod=open(os.path.join(d, "m.mod"), "rb").read())
+    return _rs_shared["g"], _rs_shared["mod"]
+
+
+def rs_tile_case(n_tiles):
+    """(reads, tiles of the gap reads' second hits, tiles at whose first seed a read begins) for a batch of n_tiles tiles of seeds.
+    k = 15, w = 1: every k-mer is a seed, a read of len bases has len - 14 of them, in base order.  Reads over {A, C} hit nothing."""
+    g, _ = _rs_genome_and_mod()
+    rng = np.random.default_rng(n_tiles)
+    k, total = RS_K, RS_TILE_CASES[n_tiles]
+    reads, at = [], [0]                                   # at[0]: seeds so far
+    def add(r):
+        reads.append(np.ascontiguousarray(r, np.uint8)); at[0] += max(len(r) - k + 1, 0)
+    junk = lambda n: rng.integers(0, 2, n).astype(np.uint8)
+    def cut(n):
+        a = int(rng.integers(0, len(g) - n))
+        return (3 - g[a:a + n][::-1]) if rng.random() < 0.5 else g[a:a + n]
+    def fill_to(target):                                  # long reads that hit nothing and reads cut from g, then one that ends on the seed
+        assert at[0] <= target
+        while target - at[0] > 120_000:
+            add(junk(int(rng.integers(20_000, 60_000))))
+            add(cut(int(rng.integers(3 * RS_TILE + k, 5 * RS_TILE))))
+        if target > at[0]:
+            add(junk(target - at[0] + k - 1))
+        assert at[0] == target
+    gaps = [1024] + ([2048] if n_tiles > 2048 else [])   # the tile of the hits after the gap: tiles b - 4 .. b - 1 hold no hit
+    starts = [512] + ([1536] if n_tiles >= 2048 else [])
+    events = sorted([(b * RS_TILE, "start") for b in starts] + [((b - 4) * RS_TILE - 200, "gap") for b in gaps])
+    for seed, what in events:
+        fill_to(seed)
+        add(np.zeros(0, np.uint8)); add(g[100:110])       # an empty read and one shorter than k: no seeds, directly before
+        if what == "start":
+            add(cut(3 * RS_TILE + 500))                   # its first seed is the tile's first seed, and a hit
+        else:                                             # 186 hits, 14 seeds across the joint, 20 000 seeds that miss from the tile's first seed on, 186 hits
+            a, b = (int(x) for x in rng.integers(0, len(g) - 200, 2))
+            add(np.concatenate([g[a:a + 200], junk(20_000), g[b:b + 200]]))
+    fill_to(total)
+    return reads, gaps, starts
+
+
+def rs_tile_properties(reads, want, n_tiles, gaps, starts):
+    """the case holds what it claims, from the reads' lengths and the oracle's arrays"""
+    k = RS_K
+    seeds = np.array([max(len(r) - k + 1, 0) for r in reads], np.int64)
+    seed_start = np.concatenate([[0], np.cumsum(seeds)])
+    assert (int(seed_start[-1]) + RS_TILE - 1) // RS_TILE == n_tiles and int(seed_start[-1]) == RS_TILE_CASES[n_tiles]
+    n_hit, hs, dx = want["nHit"].astype(np.int64), want["hitStart"].astype(np.int64), want["dx"].astype(np.int64)
+    # a hit's position in its read: the sum of the read's dx so far (no distance of these reads reaches 2^16; w = 1: position = seed number)
+    c = np.concatenate([[0], np.cumsum(dx)])
+    read_of = np.repeat(np.arange(len(reads)), n_hit)
+    pos = c[1:] - c[hs[read_of]]
+    assert (pos >= 0).all() and (pos < seeds[read_of]).all()
+    first = np.zeros(len(dx), bool); first[hs[:-1][n_hit > 0]] = True
+    far = ~first & (dx > RS_TILE)                          # its predecessor in the same read lies more than a tile of seeds back
+    assert far.sum() >= len(gaps)
+    per_tile = np.bincount((seed_start[read_of] + pos) // RS_TILE, minlength=n_tiles)
+    assert len(per_tile) == n_tiles and (per_tile == 0).any() and (per_tile == RS_TILE).any()
+    far_tiles = set(((seed_start[read_of] + pos)[far] // RS_TILE).tolist())
+    for b in gaps:                                         # four whole tiles without a hit, then the read's second hits: across the threads' pieces of the tile scan
+        assert not per_tile[b - 4:b].any() and per_tile[b - 5] > 0 and b in far_tiles, b
+    for b in starts:                                       # a read begins on the tile's first seed, with a hit, behind two reads without seeds
+        r = int(np.searchsorted(seed_start, b * RS_TILE, side="right")) - 1
+        assert seed_start[r] == b * RS_TILE and seeds[r] > 0 and seeds[r - 1] == 0 and seeds[r - 2] == 0 and len(reads[r - 2]) == 0
+        assert n_hit[r] == seeds[r] and dx[hs[r]] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_tiles", list(RS_TILE_CASES))
+def test_readset_past_1024_tiles_vs_oracle(n_tiles, tmp_path):
+    """one batch of 1025 / 2048 / 2049 tiles of 4096 seeds: mgRsTileScanKernel's exclusive sum of the tiles' hit counts and running
+    maximum of `last hit before this tile`, in place, with 2 or 3 counts per thread.  Reads that hit nothing (tiles of count 0), reads
+    cut from the genome on both strands (full tiles), reads with a hit, four whole tiles without one, then a hit -- the maximum has to
+    come across empty tiles and across the threads' pieces (tiles 1023 | 1024, and 2047 | 2048) --, a read whose first seed is a tile's
+    first, reads without seeds before them.  dx is the reference's own 16-bit truncation (modasm.c:172)."""
+    from oracle import pyoracle as orc
+    _, mod = _rs_genome_and_mod()
+    reads, gaps, starts = rs_tile_case(n_tiles)
+    p = str(tmp_path / "m.mod"); open(p, "wb").write(mod)
+    oms = _rs_shared["oms"]
+    ors = orc.Readset(oms); ors.read(reads)
+    want = ors.arrays()
+    rs_tile_properties(reads, want, n_tiles, gaps, starts)
+    L = mg.lib()
+    with mg.CFile(p, "r") as f:
+        ms = L.modsetRead(f)
+    rs = L.mgReadsetCreate(ms)
+    bases, offs = util.concat_reads(reads)
+    assert L.mgReadsetRead(rs, bases.ctypes.data, offs.ctypes.data, len(reads)) == 0
+    same(want, lib_arrays(rs))
+    assert np.array_equal(np.ctypeslib.as_array(ms.contents.depth, (ms.contents.max + 1,)), oms.depths())
+    L.mgReadsetDestroy(rs)
+    ors.close()

@@ -66,6 +66,22 @@ def concat_reads(reads):
     return bases.astype(np.uint8), offs
 
 
+def without_two_letter_windows(g, k):
+    """g (bases 0..3) with no window of k bases over {A, C} alone or over {G, T} alone: a sequence over {A, C} then shares no k-mer with g
+    on either strand, so a test can build reads that are certain to miss"""
+    g = g.copy()
+    for _ in range(50):
+        low = (g < 2).astype(np.int64)
+        hit = False
+        for run, other in ((low, 2), (1 - low, 0)):
+            c = np.concatenate([[0], np.cumsum(run)])
+            for s in np.flatnonzero(c[k:] - c[:-k] == k):
+                g[s + k // 2] = other + (g[s + k // 2] & 1); hit = True
+        if not hit:
+            return g
+    raise AssertionError("the sequence keeps a two-letter window")
+
+
 def oracle_scan_batch(hasher, bases, offs):
     ks, ps, fs, st = [], [], [], [0]
     for r in range(len(offs) - 1):
