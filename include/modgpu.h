@@ -344,6 +344,17 @@ int  mgReadsetFileRead (MgReadset *rs, const char *filename) ;
 void mgReadsetStats (MgReadset *rs, FILE *out) ;                                            /* modasm.c:193-253 */
 void mgReadsetWrite (MgReadset *rs, const char *root) ;                                     /* modasm.c:108-126 */
 MgReadset *mgReadsetLoad (const char *root) ;                                               /* modasm.c:128-149; creates rs->ms, which mgReadsetDestroy leaves to the caller (modasm.c:100-107) */
+/* modasm -C (cleanMods, modasm.c:514-555): the repeat / internal / minor-variant flags of every mod from the reads' hit lists, OR-ed into
+ * ms->info (what is set stays set); rs->nCopy and the inverse lists as its invBuild leaves them (modasm.c:552); the line "set %d repeated,
+ * %d internal, %d minor_variant mods" to `out`.  As in the reference (modasm.c:522-523) the LAST read contributes no flag.  The hits are
+ * sorted by mod on the device; a set of 2^32 - 16 hits or more, or a device without room for it, takes host loops that give the same bytes.
+ * 0, or -1 with mgLastError ().  ...Path: what the calling thread's last call took: 0 = the device, 1 = the host loops, -1 = it failed before. */
+int  mgReadsetCleanMods (MgReadset *rs, FILE *out) ;
+int  mgReadsetCleanModsPath (void) ;
+/* modasm -P (readProperties, modasm.c:912-952): per read (the last one included) how its copy-1 mods repeat in it: the "MT" lines of the
+ * read in ascending mod order, its "READ" line, its "RM" line if it has one.  ms and rs are not modified.  Paths and result as above. */
+int  mgReadsetProperties (MgReadset *rs, FILE *out) ;
+int  mgReadsetPropertiesPath (void) ;
 
 /* The file front end (seqio.c:30-346 for FASTA / FASTQ text, plain, gzip or blocked gzip, with the callers'
  * dna2indexConv + N->0 conversion): records are cut out of the text and converted by a pool of

@@ -76,6 +76,7 @@ EXPORTS = [
     "mgReferenceRead", "mgQueryProcess", "mgReferenceWrite", "mgGzipOpenWrite", "mgFzOpen", "mgGzipOpenRead", "mgReferenceLoad",
     "mgCommInitAll", "mgCommGetUniqueId", "mgCommInitRank", "mgCommRank", "mgCommSize", "mgCommDestroy", "mgHistogramAllReduce", "mgDepthAllReduce", "mgModsetMergeRankOrder",
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
+    "mgReadsetCleanMods", "mgReadsetCleanModsPath", "mgReadsetProperties", "mgReadsetPropertiesPath",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgIterScanHost", "mgIterHostBelow", "mgReloadKnobs", "mgFormatF2", "mgModsetMergeArrays", "mgModsetMergeDeviceArrays", "mgModsetClear", "mgModsetDeviceSlots", "mgSetVerbose", "mgProfileEnable", "mgProfileOnly", "mgProfileReset", "mgProfileKernels", "mgProfileGet",
@@ -223,6 +224,7 @@ def lib():
     sig("mgReadsetCreate", RS, MS); sig("mgReadsetDestroy", None, RS)
     sig("mgReadsetRead", i32, RS, vp, vp, i32); sig("mgReadsetFileRead", i32, RS, C.c_char_p)
     sig("mgReadsetStats", None, RS, vp); sig("mgReadsetWrite", None, RS, C.c_char_p); sig("mgReadsetLoad", RS, C.c_char_p)
+    sig("mgReadsetCleanMods", i32, RS, vp); sig("mgReadsetCleanModsPath", i32); sig("mgReadsetProperties", i32, RS, vp); sig("mgReadsetPropertiesPath", i32)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -469,3 +471,22 @@ def read_text(path):
 
 def read_text_path():
     return lib().mgModsetReadTextPath()
+
+
+def readset_clean_mods(rs, path):
+    """mgReadsetCleanMods: modasm -C (modasm.c:514-555) on the MgReadset* `rs`, its line into the file `path`.  Returns the path taken:
+    0 the device, 1 the host loops."""
+    with CFile(path, "w") as f:
+        rc = lib().mgReadsetCleanMods(rs, f)
+    if rc:
+        raise ModgpuError("mgReadsetCleanMods failed: " + lib().mgLastError().decode())
+    return lib().mgReadsetCleanModsPath()
+
+
+def readset_properties(rs, path):
+    """mgReadsetProperties: modasm -P (modasm.c:912-952), its lines into the file `path`.  Returns the path taken as above."""
+    with CFile(path, "w") as f:
+        rc = lib().mgReadsetProperties(rs, f)
+    if rc:
+        raise ModgpuError("mgReadsetProperties failed: " + lib().mgLastError().decode())
+    return lib().mgReadsetPropertiesPath()

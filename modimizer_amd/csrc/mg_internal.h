@@ -75,6 +75,10 @@ MG_HIDDEN MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax,
                                           U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy);
 MG_HIDDEN void mgReadsetDevForget (const void *rs);
 MG_HIDDEN void mgReadsetDevAppendHits (const void *rs, const U32 *dHit, U64 n);      /* a batch's hit list kept on the device for the end of the file */
+/* modasm -C / -P over a read set on the host (mg_refpack.hip): 0 = done, 1 = no room on the device (the caller's host loops take it), -1 = failed */
+MG_HIDDEN int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
+                                    U8 *hInfo, int *hNCopy, U32 counts[3]);
+MG_HIDDEN int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv);
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;

@@ -40,6 +40,7 @@ static void readAll (void)
   k.fileBatchMbp = num ("MODGPU_FILE_BATCH_MBP");  k.fileBatchBases = num ("MODGPU_FILE_BATCH_BASES");
   k.queryHostChain = num ("MODGPU_QUERY_HOST_CHAIN");
   k.iterHostBelow = num ("MODGPU_ITER_HOST_BELOW");
+  k.readsetHost = num ("MODGPU_READSET_HOST");
   k.segSlack = num ("MODGPU_SEG_SLACK");
   k.partDigits = num ("MODGPU_PART_DIGITS");
   k.findBits = num ("MODGPU_FIND_BITS");

@@ -38,6 +38,7 @@ typedef struct {
   long textWindowKb;       /* MODGPU_TEXT_WINDOW_KB: text per window of the device parser */
   long fileBatchMbp;       /* MODGPU_FILE_BATCH_MBP */
   long fileBatchBases;     /* MODGPU_FILE_BATCH_BASES: bases per batch of the file entry points */
+  long readsetHost;        /* MODGPU_READSET_HOST: 1 = modasm -C / -P (mgReadsetCleanMods, mgReadsetProperties) by the host loops */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */
   /* development knobs */

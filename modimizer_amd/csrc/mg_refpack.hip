@@ -528,6 +528,13 @@ __global__ void mgRsCountKernel (const U32 *__restrict__ depth32, U32 msMax, U32
 }
 __global__ void mgRsWidenKernel (const U32 *__restrict__ a, U64 n, U64 *__restrict__ out)
 { for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < n ; i += (U64) gridDim.x * blockDim.x) out[i] = a[i]; }
+/* the read whose hitStart range holds hit h: the last r in 1 .. nReads with hitStart[r] <= h (an empty read never is) */
+__device__ __forceinline__ U32 mgRsReadOf (const U64 *__restrict__ hitStart, U32 nReads, U64 h)
+{
+  U32 lo = 1, hi = nReads;
+  while (lo < hi) { const U32 mid = lo + (hi - lo + 1) / 2; if (hitStart[mid] <= h) lo = mid; else hi = mid - 1; }
+  return lo;
+}
 /* per hit: key = its mod (past the last mod if that one saturated), value = its read: the one whose hitStart range holds it (reads from 1) */
 __global__ void mgRsKeyValKernel (const U32 *__restrict__ hit, U64 nHit, const U64 *__restrict__ hitStart, U32 nReads, const U32 *__restrict__ depth32, U32 msMax,
                                   U32 *__restrict__ key, U32 *__restrict__ val)
@@ -535,9 +542,7 @@ __global__ void mgRsKeyValKernel (const U32 *__restrict__ hit, U64 nHit, const U
   for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
     { const U32 y = hit[h] & MG_RS_TOPMASK;
       key[h] = depth32[y] < 0xffffu ? y : msMax + 1;
-      U32 lo = 1, hi = nReads;                                       /* the last r with hitStart[r] <= h */
-      while (lo < hi) { const U32 mid = lo + (hi - lo + 1) / 2; if (hitStart[mid] <= h) lo = mid; else hi = mid - 1; }
-      val[h] = lo;
+      val[h] = mgRsReadOf (hitStart, nReads, h);
     }
 }
 __global__ __launch_bounds__ (256)
@@ -611,4 +616,231 @@ extern "C" MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax
   if (s == MG_ERR_HIP && !mgLastError ()[0]) mgHipFail (hipGetLastError (), "read set on the device");
   if (s && *hInvSpace) { free (*hInvSpace); *hInvSpace = 0; }
   return s;
+}
+
+/* ---------------------------------------------------------------------------------------- */
+/* modasm -C and -P (cleanMods, modasm.c:514-555; readProperties, modasm.c:912-952) for a read set that is on the host: both ask how
+ * often a mod occurs in ONE read.  The reference answers with an array of ms->max + 1 entries that it clears per read; here the hits'
+ * ordinals are sorted stably by mod (mgRefStableSort, no key past the last mod: saturated mods count), which leaves the hits of one
+ * mod in read order -- the occurrences of a mod in one read are neighbours.  The flags of -C are OR-ed into the 32-bit words of info[]
+ * with integer atomics (a result that does not depend on the order); the tallies of -P are integer atomicAdd per read.  Nothing of
+ * the read set stays on the device: a call uploads what it reads. */
+
+__device__ __forceinline__ void mgRsInfoOr (U32 *__restrict__ info32, U32 y, U32 flag) { atomicOr (&info32[y >> 2], flag << (8u * (y & 3u))); }
+
+/* per hit its mod and its read (for all nHit hits); for the nClean first -- the hits of reads 1 .. nReads - 1: modasm.c:522-523 starts its
+   Read pointer at entry 0 and so never looks at the last read -- the internal and the minor-variant rule (modasm.c:533-538) */
+__global__ __launch_bounds__ (256)
+void mgRsCleanNeighbourKernel (const U32 *__restrict__ hit, const unsigned short *__restrict__ dx, U64 nHit, U64 nClean, const U64 *__restrict__ hitStart, U32 nReads,
+                               const unsigned short *__restrict__ depth, int w, U32 *__restrict__ info32, U32 *__restrict__ key, U32 *__restrict__ rd)
+{
+  for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
+    { const U32 y = hit[h] & MG_RS_TOPMASK;
+      const U32 r = mgRsReadOf (hitStart, nReads, h);
+      key[h] = y; rd[h] = r;
+      if (h >= nClean || h == hitStart[r]) continue;                 /* the rules are about a hit and the one before it in the read */
+      if (h + 1 < hitStart[r + 1] && (int) dx[h] < w && (int) dx[h + 1] < w) mgRsInfoOr (info32, y, MS_INTERNAL);
+      const U32 p = hit[h - 1] & MG_RS_TOPMASK;
+      const int lastDepth = depth[p], thisDepth = depth[y];
+      if (lastDepth > 2 * thisDepth) mgRsInfoOr (info32, y, MS_MINOR);
+      if (thisDepth > 2 * lastDepth) mgRsInfoOr (info32, p, MS_MINOR);
+    }
+}
+/* sorted[0 .. n): hit ordinals, by mod, in hit order inside a mod: a mod is in one read twice when two neighbours share mod and read */
+__global__ __launch_bounds__ (256)
+void mgRsCleanRepeatKernel (const U32 *__restrict__ sorted, U64 n, const U32 *__restrict__ key, const U32 *__restrict__ rd, U32 *__restrict__ info32)
+{
+  for (U64 i = 1 + (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < n ; i += (U64) gridDim.x * blockDim.x)
+    { const U32 a = sorted[i - 1], b = sorted[i];
+      if (key[a] == key[b] && rd[a] == rd[b]) mgRsInfoOr (info32, key[b], MS_REPEAT);
+    }
+}
+/* modasm.c:545-550: entries 0 .. max; counts[3] = repeat, internal, minor */
+__global__ __launch_bounds__ (256)
+void mgRsCleanCountKernel (const U8 *__restrict__ info, U32 max, U32 *__restrict__ counts)
+{
+  __shared__ U32 lds[4];
+  U32 c[3] = { 0, 0, 0 };
+  for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i <= max ; i += (U64) gridDim.x * blockDim.x)
+    { const U32 f = info[i]; c[0] += (f & MS_REPEAT) != 0; c[1] += (f & MS_INTERNAL) != 0; c[2] += (f & MS_MINOR) != 0; }
+  for (int j = 0 ; j < 3 ; ++j)
+    { const U32 s = mgBlockReduce<256, MgSum> (c[j], lds);
+      if (!threadIdx.x && s) atomicAdd (&counts[j], s);
+    }
+}
+
+static size_t mgRsSortScratchWords (U64 n) { return (size_t) 256 * ((n + MG_RSORT_TILE - 1) / MG_RSORT_TILE + 1); }      /* the histogram of a sort of n elements */
+/* is there room for `bytes` of arrays next to what a stable sort of n elements with keys takes itself (two value and two key arrays, its histogram)? */
+static bool mgRsRoom (size_t bytes, U64 n)
+{
+  size_t freeB = 0, total = 0;
+  if (hipMemGetInfo (&freeB, &total) != hipSuccess) { (void) hipGetLastError (); return false; }
+  const size_t need = bytes + (size_t) n * 16 + mgRsSortScratchWords (n) * 4 + ((size_t) 64 << 20);
+  return need < freeB;
+}
+
+/* hHit[totHit], hDx[totHit], hHitStart[nReads + 2] (reads from 1), hDepth16[msMax + 1]: in; hInfo[msMax + 1]: in and out; hNCopy[(nReads + 1) * 4],
+   counts[3]: out.  totHit < 2^32 - 16.  0 = done, 1 = the device has no room (nothing was changed: the caller takes its host loops), -1 = failed */
+extern "C" int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
+                                     U8 *hInfo, int *hNCopy, U32 counts[3])
+{
+  if (mgEnsureDevice ()) return -1;
+  hipStream_t st = 0;
+  const size_t m = (size_t) msMax + 1, m4 = (m + 3) / 4 * 4;
+  const U64 nClean = nReads > 1 ? hHitStart[nReads] : 0;             /* the hits of reads 1 .. nReads - 1 */
+  const size_t histWords = mgRsSortScratchWords (totHit), scanTiles = histWords / MG_SCAN_TILE + 4;
+  const size_t bytes = m4 + m * 2 + ((size_t) nReads + 3) * 8 + ((size_t) nReads + 2) * sizeof (int4) + (totHit + 1) * 14 + scanTiles * 4 + 64;
+  if (!mgRsRoom (bytes, nClean)) return 1;
+  U32 *dHit = 0, *dKey = 0, *dRd = 0, *dSorted = 0, *tiles = 0, *dCounts = 0; unsigned short *dDx = 0, *dD16 = 0; U64 *dStart = 0; U8 *dInfo = 0; int4 *dNc = 0;
+  MgStatus s = MG_ERR_HIP;
+  do {
+    if (hipMalloc ((void **) &tiles, scanTiles * 4) || hipMalloc ((void **) &dCounts, 16) || hipMalloc ((void **) &dD16, m * 2) || hipMalloc ((void **) &dInfo, m4)
+        || hipMalloc ((void **) &dStart, ((size_t) nReads + 3) * 8) || hipMalloc ((void **) &dNc, ((size_t) nReads + 2) * sizeof (int4))
+        || hipMalloc ((void **) &dHit, (totHit + 1) * 4) || hipMalloc ((void **) &dDx, (totHit + 1) * 2) || hipMalloc ((void **) &dKey, (totHit + 1) * 4)
+        || hipMalloc ((void **) &dRd, (totHit + 1) * 4) || hipMemset (dCounts, 0, 16) || hipMemset (dInfo + (m4 - 4), 0, 4) || hipDeviceSynchronize ()) break;
+    if ((s = mgXferH2D (dInfo, hInfo, m)) || (s = mgXferH2D (dD16, hDepth16, m * 2)) || (s = mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8))
+        || (totHit && ((s = mgXferH2D (dHit, hHit, totHit * 4)) || (s = mgXferH2D (dDx, hDx, totHit * 2))))) break;
+    s = MG_ERR_HIP;
+    if (totHit)
+      hipLaunchKernelGGL (mgRsCleanNeighbourKernel, dim3 (4096), dim3 (256), 0, st, dHit, dDx, totHit, nClean, dStart, nReads, dD16, w, (U32 *) dInfo, dKey, dRd);
+    if (nClean > 1)
+      { int keyBits = 1; while (keyBits < 32 && ((U64) 1 << keyBits) <= (U64) msMax) ++keyBits;
+        if ((s = mgRefStableSort (dKey, 0, (U32) nClean, keyBits, &dSorted, tiles, st))) break;
+        s = MG_ERR_HIP;
+        hipLaunchKernelGGL (mgRsCleanRepeatKernel, dim3 (4096), dim3 (256), 0, st, dSorted, nClean, dKey, dRd, (U32 *) dInfo);
+      }
+    hipLaunchKernelGGL (mgRsCleanCountKernel, dim3 (1024), dim3 (256), 0, st, dInfo, msMax, dCounts);
+    if (nReads) hipLaunchKernelGGL (mgRsCopyTallyKernel, dim3 ((nReads + 255) / 256), dim3 (256), 0, st, dHit, dStart, nReads, dInfo, dNc);      /* invBuild's nCopy[] (modasm.c:552,273-277) */
+    if (hipGetLastError () != hipSuccess || hipMemcpyAsync (counts, dCounts, 12, hipMemcpyDeviceToHost, st) || hipStreamSynchronize (st)) break;
+    if ((s = mgXferD2H (hInfo, dInfo, m, MG_XFER_COPY)) || (nReads && (s = mgXferD2H (hNCopy + 4, dNc + 1, (size_t) nReads * sizeof (int4), MG_XFER_COPY)))) break;
+    s = MG_OK;
+  } while (0);
+  (void) hipFree (dHit); (void) hipFree (dDx); (void) hipFree (dKey); (void) hipFree (dRd); (void) hipFree (dSorted); (void) hipFree (tiles); (void) hipFree (dCounts);
+  (void) hipFree (dStart); (void) hipFree (dInfo); (void) hipFree (dD16); (void) hipFree (dNc);
+  if (s == MG_ERR_HIP && !mgLastError ()[0]) mgHipFail (hipGetLastError (), "modasm -C on the device");
+  return s ? -1 : 0;
+}
+
+/* ---- -P ---- */
+
+/* flag[h] = is hit h on a copy-1 mod (modasm.c:926); rd[h] = its read */
+__global__ __launch_bounds__ (256)
+void mgRsPropFlagKernel (const U32 *__restrict__ hit, U64 nHit, const U64 *__restrict__ hitStart, U32 nReads, const U8 *__restrict__ info, U32 *__restrict__ flag, U32 *__restrict__ rd)
+{
+  for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
+    { flag[h] = (info[hit[h] & MG_RS_TOPMASK] & 3u) == 1u; rd[h] = mgRsReadOf (hitStart, nReads, h); }
+}
+/* the flagged hits in order: key = the mod, value = the hit's ordinal */
+__global__ __launch_bounds__ (256)
+void mgRsPropCompactKernel (const U32 *__restrict__ hit, U64 nHit, const U32 *__restrict__ flag, const U32 *__restrict__ place, U32 *__restrict__ key, U32 *__restrict__ val)
+{
+  for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
+    if (flag[h]) { key[place[h]] = hit[h] & MG_RS_TOPMASK; val[place[h]] = (U32) h; }
+}
+/* sorted[0 .. n): ordinals of the copy-1 hits by mod, in hit order inside a mod, so a run of equal (mod, read) is what one read holds of one mod.
+   The lane of a run's first element walks it (runs are short: a mod that a read holds three times is the rare case), counts the forward (bit 31)
+   and the reverse hits, classifies as modasm.c:932-941 does and adds to the read's tallies { n, n2Tan, n2Rev, nMoreTan, nMoreRev }; runs of more
+   than two are events: evFlag[i] = 1, evCount[i] = f + r, bit 31 of evMod[i] = all in one orientation */
+__global__ __launch_bounds__ (256)
+void mgRsPropRunKernel (const U32 *__restrict__ sorted, U64 n, const U32 *__restrict__ hit, const U32 *__restrict__ rd, int *__restrict__ tally,
+                        U32 *__restrict__ evFlag, U32 *__restrict__ evMod, U32 *__restrict__ evCount)
+{
+  for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < n ; i += (U64) gridDim.x * blockDim.x)
+    { const U32 o = sorted[i], y = hit[o] & MG_RS_TOPMASK, r = rd[o];
+      evFlag[i] = 0;
+      if (i) { const U32 q = sorted[i - 1]; if ((hit[q] & MG_RS_TOPMASK) == y && rd[q] == r) continue; }      /* not the first of its run */
+      U32 f = 0, rv = 0;
+      for (U64 j = i ; j < n ; ++j)
+        { const U32 hj = hit[sorted[j]];
+          if ((hj & MG_RS_TOPMASK) != y || rd[sorted[j]] != r) break;
+          if (hj & ~MG_RS_TOPMASK) ++f; else ++rv;
+        }
+      int *t = tally + (size_t) r * 5;
+      atomicAdd (&t[0], 1);
+      if (f + rv == 1) continue;
+      if (f == 1 && rv == 1) atomicAdd (&t[2], 1);
+      else if (f + rv == 2) atomicAdd (&t[1], 1);
+      else
+        { const bool tan = !f || !rv;
+          atomicAdd (&t[tan ? 3 : 4], 1);
+          evFlag[i] = 1; evMod[i] = y | (tan ? ~MG_RS_TOPMASK : 0u); evCount[i] = f + rv;
+        }
+    }
+}
+/* the events in order (mod order: the sort's) */
+__global__ __launch_bounds__ (256)
+void mgRsPropEventKernel (const U32 *__restrict__ sorted, U64 n, const U32 *__restrict__ rd, const U32 *__restrict__ evFlag, const U32 *__restrict__ place,
+                          const U32 *__restrict__ evMod, const U32 *__restrict__ evCount, U32 *__restrict__ outRead, U32 *__restrict__ outMod, U32 *__restrict__ outCount)
+{
+  for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < n ; i += (U64) gridDim.x * blockDim.x)
+    if (evFlag[i]) { const U32 e = place[i]; outRead[e] = rd[sorted[i]]; outMod[e] = evMod[i]; outCount[e] = evCount[i]; }
+}
+/* ev[3 * j ..] = event order[j] as (read, mod | tandem bit, count) */
+__global__ __launch_bounds__ (256)
+void mgRsPropGatherKernel (const U32 *__restrict__ order, U32 n, const U32 *__restrict__ inRead, const U32 *__restrict__ inMod, const U32 *__restrict__ inCount, U32 *__restrict__ ev)
+{
+  for (U64 j = (U64) blockIdx.x * blockDim.x + threadIdx.x ; j < n ; j += (U64) gridDim.x * blockDim.x)
+    { const U32 e = order[j]; ev[3 * j] = inRead[e]; ev[3 * j + 1] = inMod[e]; ev[3 * j + 2] = inCount[e]; }
+}
+
+/* hHit[totHit], hHitStart[nReads + 2], hInfo[msMax + 1]: in.  hTally[(nReads + 1) * 5]: out, per read { n, n2Tan, n2Rev, nMoreTan, nMoreRev }.  *hEv (malloc ()ed
+   here): *nEv triples (read, mod | bit 31 if in one orientation, count), one per mod that a read holds more than twice, by read, by mod inside a read.
+   totHit < 2^32 - 16.  0 = done, 1 = the device has no room, -1 = failed */
+extern "C" int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv)
+{
+  *hEv = 0; *nEv = 0;
+  if (mgEnsureDevice ()) return -1;
+  hipStream_t st = 0;
+  const size_t m = (size_t) msMax + 1, tallyBytes = ((size_t) nReads + 1) * 5 * sizeof (int);
+  const size_t histWords = mgRsSortScratchWords (totHit), scanTiles = (histWords > totHit ? histWords : totHit) / MG_SCAN_TILE + 4;
+  const size_t bytes = m + ((size_t) nReads + 3) * 8 + tallyBytes + (totHit + 1) * 4 * 9 + scanTiles * 4 + 64;
+  if (!mgRsRoom (bytes, totHit)) return 1;
+  U32 *dHit = 0, *dRd = 0, *dFlag = 0, *dPlace = 0, *dKey = 0, *dVal = 0, *dSorted = 0, *tiles = 0, *dEvMod = 0, *dEvCount = 0;
+  U32 *dERead = 0, *dEMod = 0, *dECount = 0, *dOrder = 0, *dEv = 0; U64 *dStart = 0; U8 *dInfo = 0; int *dTally = 0;
+  MgStatus s = MG_ERR_HIP;
+  do {
+    if (hipMalloc ((void **) &tiles, scanTiles * 4) || hipMalloc ((void **) &dInfo, m) || hipMalloc ((void **) &dStart, ((size_t) nReads + 3) * 8) || hipMalloc ((void **) &dTally, tallyBytes)
+        || hipMalloc ((void **) &dHit, (totHit + 1) * 4) || hipMalloc ((void **) &dRd, (totHit + 1) * 4) || hipMalloc ((void **) &dFlag, (totHit + 1) * 4)
+        || hipMalloc ((void **) &dPlace, (totHit + 1) * 4) || hipMalloc ((void **) &dKey, (totHit + 1) * 4) || hipMalloc ((void **) &dVal, (totHit + 1) * 4)
+        || hipMalloc ((void **) &dEvMod, (totHit + 1) * 4) || hipMalloc ((void **) &dEvCount, (totHit + 1) * 4) || hipMemset (dTally, 0, tallyBytes) || hipDeviceSynchronize ()) break;
+    if ((s = mgXferH2D (dInfo, hInfo, m)) || (s = mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8)) || (totHit && (s = mgXferH2D (dHit, hHit, totHit * 4)))) break;
+    s = MG_ERR_HIP;
+    U32 n1 = 0, nE = 0;
+    if (totHit)
+      { hipLaunchKernelGGL (mgRsPropFlagKernel, dim3 (4096), dim3 (256), 0, st, dHit, totHit, dStart, nReads, dInfo, dFlag, dRd);
+        if ((s = mgRefExclusiveScan (dFlag, dPlace, totHit, tiles, st))) break;
+        s = MG_ERR_HIP;
+        if (hipMemcpyAsync (&n1, tiles + (totHit + MG_SCAN_TILE - 1) / MG_SCAN_TILE, 4, hipMemcpyDeviceToHost, st) || hipStreamSynchronize (st)) break;
+      }
+    if (n1)
+      { hipLaunchKernelGGL (mgRsPropCompactKernel, dim3 (4096), dim3 (256), 0, st, dHit, totHit, dFlag, dPlace, dKey, dVal);
+        int keyBits = 1; while (keyBits < 32 && ((U64) 1 << keyBits) <= (U64) msMax) ++keyBits;
+        if ((s = mgRefStableSort (dKey, dVal, n1, keyBits, &dSorted, tiles, st))) break;
+        s = MG_ERR_HIP;
+        hipLaunchKernelGGL (mgRsPropRunKernel, dim3 (4096), dim3 (256), 0, st, dSorted, (U64) n1, dHit, dRd, dTally, dFlag, dEvMod, dEvCount);      /* (dFlag, dPlace: free again) */
+        if ((s = mgRefExclusiveScan (dFlag, dPlace, n1, tiles, st))) break;
+        s = MG_ERR_HIP;
+        if (hipMemcpyAsync (&nE, tiles + ((U64) n1 + MG_SCAN_TILE - 1) / MG_SCAN_TILE, 4, hipMemcpyDeviceToHost, st) || hipStreamSynchronize (st)) break;
+      }
+    if (nE)
+      { if (hipMalloc ((void **) &dERead, (size_t) nE * 4) || hipMalloc ((void **) &dEMod, (size_t) nE * 4) || hipMalloc ((void **) &dECount, (size_t) nE * 4) || hipMalloc ((void **) &dEv, (size_t) nE * 12)) break;
+        hipLaunchKernelGGL (mgRsPropEventKernel, dim3 (4096), dim3 (256), 0, st, dSorted, (U64) n1, dRd, dFlag, dPlace, dEvMod, dEvCount, dERead, dEMod, dECount);
+        int keyBits = 1; while (keyBits < 32 && ((U64) 1 << keyBits) <= (U64) nReads) ++keyBits;
+        if ((s = mgRefStableSort (dERead, 0, nE, keyBits, &dOrder, tiles, st))) break;      /* stable: the events of a read stay in mod order */
+        s = MG_ERR_HIP;
+        hipLaunchKernelGGL (mgRsPropGatherKernel, dim3 (1024), dim3 (256), 0, st, dOrder, nE, dERead, dEMod, dECount, dEv);
+      }
+    if (hipGetLastError () != hipSuccess || hipStreamSynchronize (st)) break;
+    U32 *ev = (U32 *) malloc (((size_t) nE ? nE : 1) * 12);
+    if (!ev) { s = MG_ERR_NOMEM; break; }
+    *hEv = ev; *nEv = nE;
+    if ((s = mgXferD2H (hTally, dTally, tallyBytes, MG_XFER_COPY)) || (nE && (s = mgXferD2H (ev, dEv, (size_t) nE * 12, MG_XFER_COPY)))) break;
+    s = MG_OK;
+  } while (0);
+  (void) hipFree (dHit); (void) hipFree (dRd); (void) hipFree (dFlag); (void) hipFree (dPlace); (void) hipFree (dKey); (void) hipFree (dVal); (void) hipFree (dSorted); (void) hipFree (tiles);
+  (void) hipFree (dEvMod); (void) hipFree (dEvCount); (void) hipFree (dERead); (void) hipFree (dEMod); (void) hipFree (dECount); (void) hipFree (dOrder); (void) hipFree (dEv);
+  (void) hipFree (dStart); (void) hipFree (dInfo); (void) hipFree (dTally);
+  if (s == MG_ERR_HIP && !mgLastError ()[0]) mgHipFail (hipGetLastError (), "modasm -P on the device");
+  if (s && *hEv) { free (*hEv); *hEv = 0; *nEv = 0; }
+  return s ? -1 : 0;
 }
