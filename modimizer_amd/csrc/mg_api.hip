@@ -922,7 +922,7 @@ extern "C" MgStatus modsetSyncToHost (Modset *ms, int wantIndex)
   return MG_OK;
 }
 
-/* depth[] of ms has been remade from what the device counted elsewhere (modasm's read ingest, mg_refpack.hip): the device table's own copy
+/* depth[] of ms has been remade from what the device counted elsewhere (modasm's read ingest, mg_rsdev.hip): the device table's own copy
    follows -- dDepth16[0 .. max] on the device -- instead of the whole table being dropped and rebuilt from the host arrays on its next use.
    No count is pending in the table (the caller synced before it started).  0 if there is no device table (nothing to do). */
 extern "C" MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16)

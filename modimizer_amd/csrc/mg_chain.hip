@@ -371,7 +371,7 @@ __global__ void mgRsPerReadKernel (const U64 *__restrict__ seedStart, const U32 
 
 /* hHitStart[nReads+1], hNMiss[nReads]: host, filled here.  *dHitOut / *dDxOut: DEVICE arrays of hHitStart[nReads] entries, hipMalloc ()ed here (the
  * caller copies them where they go and frees them with mgDeviceFree).  dDepthAccum: device U32[ms->max + 1], the hits per mod of the file so
- * far (mg_refpack.hip keeps it across the batches): this batch's are added.  Returns 0, -1 on error. */
+ * far (mg_rsdev.hip keeps it across the batches): this batch's are added.  Returns 0, -1 on error. */
 extern "C" int mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
                                      U64 *hHitStart, U32 *hNMiss, U32 **dHitOut, unsigned short **dDxOut, U32 *dDepthAccum)
 {

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <time.h>
+#include <algorithm>
+#include <vector>
 #include "modgpu.h"
 
 #define MG_WAVE 64
@@ -52,6 +54,23 @@ void mgProfEnd (int id, hipStream_t st);
 #define MG_LAUNCH(id, st, ...) do { mgProfBegin (id, st); hipLaunchKernelGGL (__VA_ARGS__); mgProfEnd (id, st); } while (0)
 
 #define MG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mgHipFail (e_, #call); } while (0)
+
+/* the device scratch of ONE call: typed arrays from hipMalloc, all of them freed when the owner goes out of scope -- on whichever return.  A failed
+   allocation leaves "HIP error ... in <what>" (mgHipFail), what being the call's name for itself: if (scratch.get (&a, n) || scratch.get (&b, m)) return
+   MG_ERR_HIP;  fail () says the same of any other HIP call that failed.  take () hands an array on to someone who frees it later, adopt () takes one in.
+   Arrays that outlive the call (a struct's members) are not scratch. */
+struct MgDevScratch {
+  const char *what; std::vector<void *> held;
+  explicit MgDevScratch (const char *what_) : what (what_) {}
+  MgDevScratch (const MgDevScratch &) = delete;
+  MgDevScratch &operator= (const MgDevScratch &) = delete;
+  ~MgDevScratch () { for (void *p : held) (void) hipFree (p); }
+  MgStatus fail () const { return mgHipFail (hipGetLastError (), what); }
+  void adopt (void *p) { if (p) held.push_back (p); }
+  template <class T> MgStatus get (T **p, size_t count)
+  { *p = 0; const hipError_t e = hipMalloc ((void **) p, count * sizeof (T)); if (e != hipSuccess) return mgHipFail (e, what); adopt (*p); return MG_OK; }
+  template <class T> T *take (T *p) { held.erase (std::remove (held.begin (), held.end (), (void *) p), held.end ()); return p; }
+};
 
 #ifdef __HIPCC__
 /* Exact "x % d == 0" without a division (d = dOdd * 2^dShift):

@@ -69,13 +69,13 @@ MG_HIDDEN void mgChainScratchKeep (int on);      /* 1: the query's device arrays
 /* readsetFileRead's per-read loop on the device (mg_chain.hip): hit lists, distances, counts, hits per mod */
 MG_HIDDEN int  mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
                                      U64 *hHitStart, U32 *hNMiss, U32 **dHitOut, unsigned short **dDxOut, U32 *dDepthAccum);
-/* the per-mod side of the read set on the device (mg_refpack.hip): hit counts kept across a file's batches; depth[], invStart[], invSpace[], nCopy[] at its end */
+/* the per-mod side of the read set on the device (mg_rsdev.hip): hit counts kept across a file's batches; depth[], invStart[], invSpace[], nCopy[] at its end */
 MG_HIDDEN MgStatus mgReadsetDevBegin (const void *rs, U32 msMax, U32 **dDepth);
 MG_HIDDEN MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo,
                                           U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy);
 MG_HIDDEN void mgReadsetDevForget (const void *rs);
 MG_HIDDEN void mgReadsetDevAppendHits (const void *rs, const U32 *dHit, U64 n);      /* a batch's hit list kept on the device for the end of the file */
-/* modasm -C / -P over a read set on the host (mg_refpack.hip): 0 = done, 1 = no room on the device (the caller's host loops take it), -1 = failed */
+/* modasm -C / -P over a read set on the host (mg_rsdev.hip): 0 = done, 1 = no room on the device (the caller's host loops take it), -1 = failed */
 MG_HIDDEN int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
                                     U8 *hInfo, int *hNCopy, U32 counts[3]);
 MG_HIDDEN int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv);

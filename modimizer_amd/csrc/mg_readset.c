@@ -59,7 +59,7 @@ static void reserveReads (MgReadset *rs, int more)
 }
 
 /* modasm.c:158: depth is rebuilt from the reads that follow.  The hits per mod are counted on the device across the batches of the
-   file (mg_refpack.hip); depth[] comes back, saturated, when the file is done */
+   file (mg_rsdev.hip); depth[] comes back, saturated, when the file is done */
 static U32 *gDepthAccum (MgReadset *rs)
 {
   U32 *d = 0;
@@ -127,7 +127,7 @@ static void readsetAddBatch (MgReadset *rs, U32 *dDepth, const char *bases, cons
   RS_LAP ("batch in all, + free");
 }
 
-/* invBuild (modasm.c:258-287) and the file's depth[] (modasm.c:174): on the device (mg_refpack.hip: counts saturated, the lists a stable sort
+/* invBuild (modasm.c:258-287) and the file's depth[] (modasm.c:174): on the device (mg_rsdev.hip: counts saturated, the lists a stable sort
    of the hits' read numbers by mod, a read's copy-class tallies a lane per read); a set of 2^32 hits or more takes the loops below */
 static void readsetFinishHost (MgReadset *rs);
 /* hitsBefore: rs->totHit when this file began.  A further file into a read set that holds hits already (modasm.c:158 zeroes depth[] per file
@@ -363,7 +363,7 @@ MgReadset *mgReadsetLoad (const char *root)                        /* modasm.c:1
 
 /* ---- modasm -C and -P (cleanMods, modasm.c:514-555; readProperties, modasm.c:912-952) ----
  * Both ask how often one read holds one mod; the reference clears an array of ms->max + 1 entries per read to find out.  On the device
- * (mg_refpack.hip) the hits are sorted by mod; the host loops below, for a set of 2^32 - 16 hits or more, a device without room or
+ * (mg_rsdev.hip) the hits are sorted by mod; the host loops below, for a set of 2^32 - 16 hits or more, a device without room or
  * MODGPU_READSET_HOST=1, stamp the array with the read's number instead of clearing it.  Same bytes either way. */
 
 static __thread int gCleanPath = -1, gPropertiesPath = -1;

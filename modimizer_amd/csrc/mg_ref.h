@@ -1,4 +1,4 @@
-/* mg_ref.h — the device side of modmap's Reference (mg_refpack.hip builds and keeps it, mg_chain.hip's chaining reads it) */
+/* mg_ref.h — the device side of modmap's Reference (mg_refpack.hip builds and keeps it with the scan and the sort of mg_devsort.hip, mg_chain.hip's chaining reads it) */
 #ifndef MG_REF_H
 #define MG_REF_H
 #include "mg_common.h"

@@ -964,9 +964,9 @@ def _modmap_randomized(L, k, w, seed, tmp_path, pad=0):
     assert n_overflow >= 1 or w >= 31, "no read with more than 16 M blocks: the overflow path was not exercised"
 
 
-# ---- the reference build past 1024 / 2048 tiles: mg_refpack.hip's three launches of mgGroupSumKernel<U32, U32> ----
+# ---- the reference build past 1024 / 2048 tiles: the three launches of mgGroupSumKernel<U32, U32> in mg_refpack.hip (count the hits) and mg_devsort.hip (scan, sort) ----
 
-REF_TILE = 4096                # mg_refpack.hip MG_SCAN_TILE
+REF_TILE = 4096                # mg_devsort.h MG_SCAN_TILE
 
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""modasm -C and -P on the device (mgReadsetCleanMods, mgReadsetProperties: mg_refpack.hip) against the reference program's own files and
+"""modasm -C and -P on the device (mgReadsetCleanMods, mgReadsetProperties: mg_rsdev.hip) against the reference program's own files and
 lines (tests/golden/clean_*) and, on reads built to sit on the edges, against the numpy restatement that tests/test_readset_clean.py pins
 to the same reference output.  Everything is compared exactly: bytes, integers, text."""
 import contextlib
@@ -17,7 +17,7 @@ from tests.test_readset_clean import MS_MINOR, MS_REPEAT, MS_INTERNAL, MS_RDNA, 
 
 TAGS = trc.TAGS
 K = 15
-SORT_TILE = 8192               # mg_refpack.hip MG_RSORT_TILE: elements per workgroup of a sort pass
+SORT_TILE = 8192               # mg_devsort.h MG_RSORT_TILE: elements per workgroup of a sort pass
 
 
 def read_text(p):
