@@ -164,3 +164,23 @@ def test_probe_carries_the_hash_of_its_sources():
     tp.build_probe()
     assert tp.probe_binary_hash() == h
     assert tp.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None
+
+
+def test_devsort_tiles_are_the_headers():
+    """MG_SCAN_TILE and MG_RSORT_TILE as tests/test_gpu_devsort.py states them (and the other test files take them from there) are
+    mg_devsort.h's: a tile that changes moves every edge those tests are built around"""
+    import test_gpu_devsort as td
+    header = dict(re.findall(r"^#define[ \t]+(MG_\w+_TILE)[ \t]+(\d+)\b", open(os.path.join(mg.CSRC, "mg_devsort.h")).read(), re.M))
+    assert header == {"MG_SCAN_TILE": str(td.MG_SCAN_TILE), "MG_RSORT_TILE": str(td.MG_RSORT_TILE)}
+    assert td.WAVE_PART * 4 == td.MG_RSORT_TILE and td.WAVE_PART % 64 == 0      # mg_devsort.hip: four waves a tile, 64 elements a round
+
+
+def test_devsort_probe_carries_the_hash_of_its_sources():
+    """libdevsortprobe.so rides along like libprefixprobe.so: a hash of devsort_probe.hip, mg_devsort.h and mg_common.h is baked into it,
+    the tests recompute it from the tree, and a probe of other sources is rebuilt before it is used"""
+    import test_gpu_devsort as td
+    h = td.probe_source_hash()
+    assert re.fullmatch(r"[0-9a-f]{16}", h)
+    td.build_probe()
+    assert td.probe_binary_hash() == h
+    assert td.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None

@@ -10,6 +10,7 @@ import modimizer_amd as mg
 from modimizer_amd import fasta, synth
 from oracle import pyoracle as po
 import util
+import test_gpu_devsort as tds
 
 pytestmark = pytest.mark.gpu
 
@@ -966,14 +967,14 @@ def _modmap_randomized(L, k, w, seed, tmp_path, pad=0):
 
 # ---- the reference build past 1024 / 2048 tiles: the three launches of mgGroupSumKernel<U32, U32> in mg_refpack.hip (count the hits) and mg_devsort.hip (scan, sort) ----
 
-REF_TILE = 4096                # mg_devsort.h MG_SCAN_TILE
+REF_TILE = tds.MG_SCAN_TILE    # mg_devsort.h's, which tests/test_abi.py holds it to
 
 
 @pytest.mark.gpu
 def test_reference_build_past_2048_tiles_vs_oracle(tmp_path):
     """mgReferenceRead on 8.5 Mbp in memory, k = 15, w = 1 (every k-mer a seed, one append batch), against the oracle's Reference: the
-    append's scan of tile counts runs over more than 2048 tiles (three counts per thread of mgGroupScan), mgRefExclusiveScan's over more
-    than 1024 (ms->max + 1 entries), and a further read of 4.3 M seeds that have no index goes through the packed branch's count over
+    append's scan of tile counts runs over more than 2048 tiles (three counts per thread of mgGroupScan), mgExclusiveScan's (mg_devsort.hip:
+    loc[] from depth[]) over more than 1024 (ms->max + 1 entries), and a further read of 4.3 M seeds that have no index goes through the packed branch's count over
     more than 1024 tiles, which has to come out as exactly 0 (anything else is `reference size overflow`).  All three tile counts are
     asserted.  Table bits 25, not 24: a set of 24 bits holds 2^22 - 2 entries at most (modset.c:24-26), which is 1024 tiles of 4096 and
     no more.  Segments of 100 kb copied once and three times (one copy reverse-complemented) give the copy-2 and copy-M classes; five reads
@@ -1011,7 +1012,7 @@ def test_reference_build_past_2048_tiles_vs_oracle(tmp_path):
     n_seeds = sum(len(s) - k + 1 for s in seqs)
     assert occ == n_seeds and occ + 2 <= 1 << 26           # adding: every seed has an index, so the batch of the append IS the occurrences
     assert (occ + REF_TILE - 1) // REF_TILE > 2048         # mgRefBuildAppend's scan: tiles of the batch
-    assert (U + 1 + REF_TILE - 1) // REF_TILE > 1024       # mgRefExclusiveScan over depth[0 .. ms->max]
+    assert (U + 1 + REF_TILE - 1) // REF_TILE > 1024       # mgExclusiveScan over depth[0 .. ms->max]
     as_np = lambda p, n: np.ctypeslib.as_array(p, (max(n, 1),))[:n]
 
     def same_as_the_oracle():

@@ -7,15 +7,13 @@ of mgGroupScan.  Everything is integer arithmetic and numpy wraps as the hardwar
 BLOCK_INSTANTIATIONS is plain data (no GPU, no library needed to import this module): tests/test_abi.py asserts that every
 mgBlock*<THREADS, Op> the library's kernels use is in it."""
 import ctypes as C
-import hashlib
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import modimizer_amd as mg
+import util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE = os.path.join(ROOT, "oracle")
@@ -43,27 +41,23 @@ def block_pairs():
 
 # ---- the probe ----------------------------------------------------------------------------------
 
+PROBE_SOURCES = ["prefix_probe.hip", "../modimizer_amd/csrc/mg_prefix.h"]
+PROBE_MARKER = "PREFIX_PROBE_HASH"
+
+
 def probe_source_hash():
-    """the hash oracle/Makefile bakes into the probe: sha256 over the `sha256sum` listing of its two sources, 16 hex digits"""
-    names = ["prefix_probe.hip", "../modimizer_amd/csrc/mg_prefix.h"]
-    listing = "".join("%s  %s\n" % (hashlib.sha256(open(os.path.join(ORACLE, n), "rb").read()).hexdigest(), n) for n in names)
-    return hashlib.sha256(listing.encode()).hexdigest()[:16]
+    """the hash oracle/Makefile bakes into the probe, over its two sources"""
+    return util.probe_source_hash(PROBE_SOURCES)
 
 
 def probe_binary_hash(path=None):
     """the hash a built probe carries, read out of the file (no dlopen); None if there is no such file or marker"""
-    try:
-        m = re.search(rb"PREFIX_PROBE_HASH=([0-9a-f]{16})", open(path or PROBE_PATH, "rb").read())
-    except OSError:
-        return None
-    return m.group(1).decode() if m else None
+    return util.probe_binary_hash(path or PROBE_PATH, PROBE_MARKER)
 
 
 def build_probe():
-    """make the probe if the one in the tree is not the build of the tree's sources (build() of the entry point makes it with the rest)"""
-    if probe_binary_hash() != probe_source_hash():
-        subprocess.check_call(["make", "-C", ORACLE, "-s", "libprefixprobe.so"])
-    return PROBE_PATH
+    """make the probe if the one in the tree is not the build of the tree's sources"""
+    return util.build_probe("libprefixprobe.so", PROBE_MARKER, PROBE_SOURCES)
 
 
 _probe = None

@@ -14,10 +14,11 @@ from tests import util
 from tests import test_readset as trs
 from tests import test_readset_clean as trc
 from tests.test_readset_clean import MS_MINOR, MS_REPEAT, MS_INTERNAL, MS_RDNA, TOPMASK
+from tests import test_gpu_devsort as tds
 
 TAGS = trc.TAGS
 K = 15
-SORT_TILE = 8192               # mg_devsort.h MG_RSORT_TILE: elements per workgroup of a sort pass
+SORT_TILE = tds.MG_RSORT_TILE   # mg_devsort.h's (tests/test_abi.py holds it to the header): elements per workgroup of a sort pass
 
 
 def read_text(p):

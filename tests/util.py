@@ -2,6 +2,8 @@
 import hashlib
 import json
 import os
+import re
+import subprocess
 
 import numpy as np
 
@@ -217,3 +219,33 @@ def table_diag(ms):
     out = (ctypes.c_uint64 * 9)()
     mg.check(mg.lib().mgTableDiag(ms, out))
     return dict(zip(DIAG, (int(x) for x in out)))
+
+
+# ---- the probe libraries of oracle/ (prefix_probe.hip, devsort_probe.hip): a hash of their sources is baked into them ----
+
+ORACLE = os.path.join(ROOT, "oracle")
+
+
+def probe_source_hash(sources):
+    """the hash oracle/Makefile bakes into a probe: sha256 over the `sha256sum` listing of its sources (paths as the Makefile names them,
+    relative to oracle/), 16 hex digits"""
+    listing = "".join("%s  %s\n" % (hashlib.sha256(open(os.path.join(ORACLE, n), "rb").read()).hexdigest(), n) for n in sources)
+    return hashlib.sha256(listing.encode()).hexdigest()[:16]
+
+
+def probe_binary_hash(path, marker):
+    """the hash a built probe carries behind `<marker>=`, read out of the file (no dlopen); None if there is no such file or marker"""
+    try:
+        m = re.search(marker.encode() + rb"=([0-9a-f]{16})", open(path, "rb").read())
+    except OSError:
+        return None
+    return m.group(1).decode() if m else None
+
+
+def build_probe(lib_name, marker, sources):
+    """make oracle/<lib_name> if the one in the tree is not the build of the tree's sources (build() of the entry point makes it with
+    the rest); its path"""
+    path = os.path.join(ORACLE, lib_name)
+    if probe_binary_hash(path, marker) != probe_source_hash(sources):
+        subprocess.check_call(["make", "-C", ORACLE, "-s", lib_name])
+    return path
