@@ -672,34 +672,30 @@ static int mgMergeDeviceCore (Modset *ms1, MgDev *d, const U64 *dV2, const U16 *
 {
   MgTable &t = d->t;
   const U32 max1 = t.max;
-  U8 *dI1 = 0; U32 *dIdx = 0;
-  int rc = -1;
+  const char *const sorry = "device merge failed";
+  MgDevScratch scratch ("device merge");
+  U8 *dI1; U32 *dIdx;
   const size_t cap1 = (size_t) max1 + n2 + 2;
-  do {
-    if (hipMalloc ((void **) &dI1, cap1) || hipMalloc ((void **) &dIdx, (size_t) n2 * 4)) break;
-    if (hipMemset (dI1, 0, cap1) || hipDeviceSynchronize ()) break;
-    if (mgXferH2D (dI1, ms1->info, (size_t) max1 + 1)) break;
-    /* ms2's values in ms2 index order: existing ones are found, new ones get max1+1, max1+2, ... (modset.c:120) */
-    MgStatus as = mgAddBatch (ms1, d, dV2, n2, dIdx, 0, false, st);
-    if (as == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: %s\n", mgLastError ()); exit (-1); }
-    if (as) break;
-    t.baseZero = false; t.liveHistValid = false;
-    if (mgTableMergeApply (dIdx, dD2, dI2, n2, t.baseDepth, dI1, st)) break;
-    if (hipStreamSynchronize (st)) break;
-    /* bring the host mirror up to date wholesale: values of the new entries, all depths and info */
-    if (t.max > t.syncedMax)
-      { if (mgXferD2H (ms1->value + t.syncedMax + 1, t.value + t.syncedMax + 1, (size_t) (t.max - t.syncedMax) * 8, MG_XFER_COPY)) break;
-        t.syncedMax = t.max;
-      }
-    if (mgXferD2H (ms1->depth, t.baseDepth, ((size_t) t.max + 1) * 2, MG_XFER_COPY)) break;
-    if (mgXferD2H (ms1->info, dI1, (size_t) t.max + 1, MG_XFER_COPY)) break;
-    ms1->depth[0] = 0;
-    ms1->max = t.max;
-    rc = 0;
-  } while (0);
-  if (rc && !gErr[0]) mgSetError ("device merge failed");
-  (void) hipFree (dI1); (void) hipFree (dIdx);
-  return rc;
+  if (scratch.get (&dI1, cap1) || scratch.get (&dIdx, n2)) return -1;
+  if (hipMemset (dI1, 0, cap1) || hipDeviceSynchronize ()) return mgFailedWith (sorry);
+  if (mgXferH2D (dI1, ms1->info, (size_t) max1 + 1)) return mgFailedWith (sorry);
+  /* ms2's values in ms2 index order: existing ones are found, new ones get max1+1, max1+2, ... (modset.c:120) */
+  MgStatus as = mgAddBatch (ms1, d, dV2, n2, dIdx, 0, false, st);
+  if (as == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: %s\n", mgLastError ()); exit (-1); }
+  if (as) return mgFailedWith (sorry);
+  t.baseZero = false; t.liveHistValid = false;
+  if (mgTableMergeApply (dIdx, dD2, dI2, n2, t.baseDepth, dI1, st)) return mgFailedWith (sorry);
+  if (hipStreamSynchronize (st)) return mgFailedWith (sorry);
+  /* bring the host mirror up to date wholesale: values of the new entries, all depths and info */
+  if (t.max > t.syncedMax)
+    { if (mgXferD2H (ms1->value + t.syncedMax + 1, t.value + t.syncedMax + 1, (size_t) (t.max - t.syncedMax) * 8, MG_XFER_COPY)) return mgFailedWith (sorry);
+      t.syncedMax = t.max;
+    }
+  if (mgXferD2H (ms1->depth, t.baseDepth, ((size_t) t.max + 1) * 2, MG_XFER_COPY)) return mgFailedWith (sorry);
+  if (mgXferD2H (ms1->info, dI1, (size_t) t.max + 1, MG_XFER_COPY)) return mgFailedWith (sorry);
+  ms1->depth[0] = 0;
+  ms1->max = t.max;
+  return 0;
 }
 
 extern "C" int mgHookMergeDevice (Modset *ms1, Modset *ms2)
@@ -709,16 +705,11 @@ extern "C" int mgHookMergeDevice (Modset *ms1, Modset *ms2)
   const U32 n2 = ms2->max;
   if (mgFoldCounts (d, st)) return -1;
   if (!n2) return 0;
-  U64 *dV2 = 0; U16 *dD2 = 0; U8 *dI2 = 0;
-  int rc = -1;
-  do {
-    if (hipMalloc ((void **) &dV2, (size_t) n2 * 8) || hipMalloc ((void **) &dD2, (size_t) n2 * 2) || hipMalloc ((void **) &dI2, n2)) break;
-    if (mgXferH2D (dV2, ms2->value + 1, (size_t) n2 * 8) || mgXferH2D (dD2, ms2->depth + 1, (size_t) n2 * 2) || mgXferH2D (dI2, ms2->info + 1, n2)) break;
-    rc = mgMergeDeviceCore (ms1, d, dV2, dD2, dI2, n2, st);
-  } while (0);
-  if (rc && !gErr[0]) mgSetError ("device merge failed");
-  (void) hipFree (dV2); (void) hipFree (dD2); (void) hipFree (dI2);
-  return rc;
+  MgDevScratch scratch ("device merge: the second set");
+  U64 *dV2; U16 *dD2; U8 *dI2;
+  if (scratch.get (&dV2, n2) || scratch.get (&dD2, n2) || scratch.get (&dI2, n2)) return -1;
+  if (mgXferH2D (dV2, ms2->value + 1, (size_t) n2 * 8) || mgXferH2D (dD2, ms2->depth + 1, (size_t) n2 * 2) || mgXferH2D (dI2, ms2->info + 1, n2)) return mgFailedWith ("device merge failed");
+  return mgMergeDeviceCore (ms1, d, dV2, dD2, dI2, n2, st);
 }
 
 /* the same with the second set's arrays already in device memory (what a rank receives from its peers over xGMI, mg_comm.hip):
@@ -742,37 +733,33 @@ extern "C" int mgHookPruneDevice (Modset *ms, int lo, int hi)
   if (mgFoldCounts (d, st)) return -1;
   /* values of device-only entries must reach the host before the arrays are rewritten?  No: the
      survivors are compacted on the device and copied back as a whole. */
-  U8 *dInfo = 0, *dNewInfo = 0; U64 *dNewValue = 0; U16 *dNewDepth = 0; void *scratch = 0;
-  int rc = -1;
-  do {
-    if (hipMalloc ((void **) &dInfo, (size_t) n + 1) || hipMalloc ((void **) &dNewInfo, (size_t) n + 2) || hipMalloc ((void **) &dNewValue, ((size_t) n + 2) * 8)
-        || hipMalloc ((void **) &dNewDepth, ((size_t) n + 2) * 2) || hipMalloc (&scratch, mgTablePruneScratchBytes (n ? n : 1))) break;
-    if (mgXferH2D (dInfo, ms->info, (size_t) n + 1)) break;
-    if (mgTablePrune (&t, dInfo, lo, hi, dNewValue, dNewDepth, dNewInfo, scratch, st)) break;
-    U64 c[2];
-    if (hipMemcpyAsync (c, t.counters, 16, hipMemcpyDeviceToHost, st) || hipStreamSynchronize (st)) break;
-    const U32 m = (U32) c[0];
-    /* new arrays replace the old ones on both sides */
-    if (m)
-      { t.baseZero = false; t.liveHistValid = false;
-        if (hipMemcpy (t.value + 1, dNewValue + 1, (size_t) m * 8, hipMemcpyDeviceToDevice) || hipMemcpy (t.baseDepth + 1, dNewDepth + 1, (size_t) m * 2, hipMemcpyDeviceToDevice)
-            || mgXferD2H (ms->value + 1, dNewValue + 1, (size_t) m * 8, MG_XFER_COPY) || mgXferD2H (ms->depth + 1, dNewDepth + 1, (size_t) m * 2, MG_XFER_COPY)
-            || mgXferD2H (ms->info + 1, dNewInfo + 1, m, MG_XFER_COPY)) break;
-      }
-    if (n > m && hipMemset (t.baseDepth + m + 1, 0, (size_t) (n - m) * 2)) break;
-    mgTableForget (&t, st);
-    t.max = 0;
-    if (mgTableEnsure (&t, m, st)) break;
-    if (m && mgTableLoadHost (&t, t.value, 1, m, st)) break;
-    if (hipStreamSynchronize (st)) break;
-    t.max = t.syncedMax = m;
-    ms->max = m;
-    d->hostIndexMax = 0;                 /* index[] is rebuilt (replayed) when somebody needs it */
-    rc = 0;
-  } while (0);
-  if (rc && !gErr[0]) mgSetError ("device prune failed");
-  (void) hipFree (dInfo); (void) hipFree (dNewInfo); (void) hipFree (dNewValue); (void) hipFree (dNewDepth); (void) hipFree (scratch);
-  return rc;
+  const char *const sorry = "device prune failed";
+  MgDevScratch scratch ("device prune");
+  U8 *dInfo, *dNewInfo; U64 *dNewValue; U16 *dNewDepth; char *dWork;
+  if (scratch.get (&dInfo, (size_t) n + 1) || scratch.get (&dNewInfo, (size_t) n + 2) || scratch.get (&dNewValue, (size_t) n + 2)
+      || scratch.get (&dNewDepth, (size_t) n + 2) || scratch.get (&dWork, mgTablePruneScratchBytes (n ? n : 1))) return -1;
+  if (mgXferH2D (dInfo, ms->info, (size_t) n + 1)) return mgFailedWith (sorry);
+  if (mgTablePrune (&t, dInfo, lo, hi, dNewValue, dNewDepth, dNewInfo, dWork, st)) return mgFailedWith (sorry);
+  U64 c[2];
+  if (hipMemcpyAsync (c, t.counters, 16, hipMemcpyDeviceToHost, st) || hipStreamSynchronize (st)) return mgFailedWith (sorry);
+  const U32 m = (U32) c[0];
+  /* new arrays replace the old ones on both sides */
+  if (m)
+    { t.baseZero = false; t.liveHistValid = false;
+      if (hipMemcpy (t.value + 1, dNewValue + 1, (size_t) m * 8, hipMemcpyDeviceToDevice) || hipMemcpy (t.baseDepth + 1, dNewDepth + 1, (size_t) m * 2, hipMemcpyDeviceToDevice)
+          || mgXferD2H (ms->value + 1, dNewValue + 1, (size_t) m * 8, MG_XFER_COPY) || mgXferD2H (ms->depth + 1, dNewDepth + 1, (size_t) m * 2, MG_XFER_COPY)
+          || mgXferD2H (ms->info + 1, dNewInfo + 1, m, MG_XFER_COPY)) return mgFailedWith (sorry);
+    }
+  if (n > m && hipMemset (t.baseDepth + m + 1, 0, (size_t) (n - m) * 2)) return mgFailedWith (sorry);
+  mgTableForget (&t, st);
+  t.max = 0;
+  if (mgTableEnsure (&t, m, st)) return mgFailedWith (sorry);
+  if (m && mgTableLoadHost (&t, t.value, 1, m, st)) return mgFailedWith (sorry);
+  if (hipStreamSynchronize (st)) return mgFailedWith (sorry);
+  t.max = t.syncedMax = m;
+  ms->max = m;
+  d->hostIndexMax = 0;                 /* index[] is rebuilt (replayed) when somebody needs it */
+  return 0;
 }
 
 /* hooks for mg_host.c */
@@ -960,11 +947,11 @@ extern "C" U64 mgModsetDeviceSlots (Modset *ms) { MgDev *d = mgDevLookup (ms); r
 extern "C" MgStatus mgTableCheckLayout (Modset *ms, U64 *out6)
 {
   MgDev *d; MgStatus s = mgDevGet (ms, &d, 0); if (s) return s;
-  U64 *dOut = 0;
-  MG_HIP (hipMalloc ((void **) &dOut, 32));
+  MgDevScratch scratch ("mgTableCheckLayout");
+  U64 *dOut;
+  if (scratch.get (&dOut, 4)) return MG_ERR_HIP;
   s = mgTableLayoutCheck (&d->t, dOut, 0);
   if (!s && (hipMemcpy (out6, dOut, 32, hipMemcpyDeviceToHost) || hipMemcpy (out6 + 4, d->t.counters + 4, 16, hipMemcpyDeviceToHost))) s = MG_ERR_HIP;
-  (void) hipFree (dOut);
   return s;
 }
 
@@ -1240,18 +1227,16 @@ extern "C" MgStatus mgQueryReadsDeviceWait (void *ticket, U64 *nSeeds, void *str
 
 /* grow-only device buffers for the host-buffer entry points (a hipMalloc + hipFree of a gigabyte per call costs
  * milliseconds): the packed reads and their offsets of the batch in flight */
-static struct MgHostBatchBufs { U32 *dP = 0; size_t words = 0; U64 *dOff = 0; size_t offs = 0; std::mutex lock; } gHbs[MG_MAXDEV];   /* by device */
+static struct MgHostBatchBufs { MgDevBuf<U32> dP; MgDevBuf<U64> dOff; std::mutex lock; } gHbs[MG_MAXDEV];   /* by device */
 extern "C" void mgHostBatchRelease (void)
 {
   int before = -1; if (hipGetDevice (&before) != hipSuccess) { (void) hipGetLastError (); before = -1; }
   for (int dev = 0 ; dev < MG_MAXDEV ; ++dev)
     { MgHostBatchBufs &b = gHbs[dev];
       std::lock_guard<std::mutex> g (b.lock);
-      if (!b.dP && !b.dOff) continue;
+      if (!b.dP.p && !b.dOff.p) continue;
       (void) hipSetDevice (dev);
-      if (b.dP) (void) hipFree (b.dP);
-      if (b.dOff) (void) hipFree (b.dOff);
-      b.dP = 0; b.words = 0; b.dOff = 0; b.offs = 0;
+      b.dP.drop (); b.dOff.drop ();
     }
   if (before >= 0) (void) hipSetDevice (before);
 }
@@ -1267,25 +1252,14 @@ extern "C" int64_t mgAddSequenceBatch (Modset *ms, const char *bases, const int6
   std::lock_guard<std::mutex> g (gHb.lock);            /* the buffers of this device: one batch at a time through them; a thread on another GPU has that GPU's */
   U64 total = (U64) readOffsets[nReads];
   size_t nw = mgPackedWords (total);
-  if (nw > gHb.words)
-    { if (gHb.dP) (void) hipFree (gHb.dP);
-      gHb.dP = 0; gHb.words = 0;
-      if (hipMalloc ((void **) &gHb.dP, (nw + nw / 8) * 4) != hipSuccess) { mgSetError ("mgAddSequenceBatch: device allocation failed"); return -1; }
-      gHb.words = nw + nw / 8;
-    }
-  if ((size_t) nReads + 1 > gHb.offs)
-    { if (gHb.dOff) (void) hipFree (gHb.dOff);
-      gHb.dOff = 0; gHb.offs = 0;
-      if (hipMalloc ((void **) &gHb.dOff, ((size_t) nReads + 1) * 2 * 8) != hipSuccess) { mgSetError ("mgAddSequenceBatch: device allocation failed"); return -1; }
-      gHb.offs = ((size_t) nReads + 1) * 2;
-    }
+  if (gHb.dP.reserve (nw, nw + nw / 8, "mgAddSequenceBatch") || gHb.dOff.reserve ((size_t) nReads + 1, ((size_t) nReads + 1) * 2, "mgAddSequenceBatch")) return -1;
   int64_t res = -1;
   const double t0 = mgNowS ();
-  if (hipMemcpyAsync (gHb.dOff, readOffsets, ((size_t) nReads + 1) * 8, hipMemcpyHostToDevice, 0) == hipSuccess
-      && mgUploadPack (bases, total, gHb.dP, 0) == MG_OK)
+  if (hipMemcpyAsync (gHb.dOff.p, readOffsets, ((size_t) nReads + 1) * 8, hipMemcpyHostToDevice, 0) == hipSuccess
+      && mgUploadPack (bases, total, gHb.dP.p, 0) == MG_OK)
     { const double t1 = mgNowS ();
       U64 nHash = 0;
-      if (mgAddReadsDevice (ms, gHb.dP, total, gHb.dOff, (U32) nReads, &nHash, 0) == MG_OK) res = (int64_t) nHash;
+      if (mgAddReadsDevice (ms, gHb.dP.p, total, gHb.dOff.p, (U32) nReads, &nHash, 0) == MG_OK) res = (int64_t) nHash;
       if (timing) fprintf (stderr, "mgAddSequenceBatch: %.3f Gbp  pack+upload %.2f ms  scan+build %.2f ms\n", total / 1e9, (t1 - t0) * 1e3, (mgNowS () - t1) * 1e3);
     }
   else mgSetError ("mgAddSequenceBatch: copy to the device failed");
@@ -1298,12 +1272,10 @@ extern "C" void mgDepthHistogram (Modset *ms, FILE *f)
   MgDev *d = mgDevLookup (ms);
   bool done = false;
   if (d)
-    { U64 *dHist = 0;
-      if (hipMalloc ((void **) &dHist, 65536 * 8) == hipSuccess)
-        { if (hipMemset (dHist, 0, 65536 * 8) == hipSuccess && modsetDepthHistogramDevice (ms, dHist, 0) == MG_OK
-              && hipMemcpy (hist, dHist, 65536 * 8, hipMemcpyDeviceToHost) == hipSuccess) done = true;
-          (void) hipFree (dHist);
-        }
+    { MgDevScratch scratch ("depth histogram");
+      U64 *dHist;
+      if (!scratch.get (&dHist, 65536) && hipMemset (dHist, 0, 65536 * 8) == hipSuccess && modsetDepthHistogramDevice (ms, dHist, 0) == MG_OK
+          && hipMemcpy (hist, dHist, 65536 * 8, hipMemcpyDeviceToHost) == hipSuccess) done = true;
       if (!done) { fprintf (stderr, "FATAL ERROR: depth histogram on device failed: %s\n", mgLastError ()); exit (-1); }
     }
   else
@@ -1333,8 +1305,8 @@ struct MgIterScratch {
   U64 *hFlag = 0; U64 *dFlag = 0; U64 seq = 0;               /* pinned: the kernel's completion flag */
   U64 *dSegK = 0; U32 *dSegP = 0;                            /* device: the workers' segments */
   /* the long-read path */
-  U32 *dPacked = 0; U64 *dOff = 0; U64 *dKmer = 0; U32 *dPosF = 0; void *dWork = 0; U64 *dCount = 0;
-  size_t wordsCap = 0, survCap = 0, workCap = 0;
+  MgDevBuf<U32> dPacked; MgDevBuf<U64> dKmer; MgDevBuf<U32> dPosF; MgDevBuf<char> dWork;      /* (dKmer and dPosF grow together) */
+  U64 *dOff = 0; U64 *dCount = 0;
   U32 *hPacked = 0; size_t hWordsCap = 0;
   ~MgIterScratch () { if (dev >= 0 && mgRuntimeAlive ()) release (); }      /* a host thread that ends gives its pinned buffers and its stream back */
   void release ()
@@ -1342,8 +1314,8 @@ struct MgIterScratch {
     if (hIn) (void) hipHostFree (hIn);
     if (hOut) (void) hipHostFree (hOut);
     if (hFlag) (void) hipHostFree (hFlag);
-    (void) hipFree (dSegK); (void) hipFree (dSegP); (void) hipFree (dPacked); (void) hipFree (dOff); (void) hipFree (dKmer);
-    (void) hipFree (dPosF); (void) hipFree (dWork); (void) hipFree (dCount);
+    (void) hipFree (dSegK); (void) hipFree (dSegP); (void) hipFree (dOff); (void) hipFree (dCount);
+    dPacked.drop (); dKmer.drop (); dPosF.drop (); dWork.drop ();
     if (st) (void) hipStreamDestroy (st);
     free (hPacked);
     *this = MgIterScratch ();
@@ -1392,39 +1364,28 @@ static int mgIterScanLong (MgIterScratch &g, Seqhash *sh, const char *s, U64 tot
   if (nw > g.hWordsCap) { free (g.hPacked); g.hPacked = (U32 *) malloc (2 * nw * 4); g.hWordsCap = 2 * nw; }
   mgPackHost (s, total, g.hPacked);
   if (!g.dOff) { if (hipMalloc ((void **) &g.dOff, 16) != hipSuccess || hipMalloc ((void **) &g.dCount, 8 * MG_COUNT_WORDS) != hipSuccess) return -1; }
-  if (nw > g.wordsCap)
-    { if (g.dPacked) (void) hipFree (g.dPacked);
-      if (hipMalloc ((void **) &g.dPacked, 2 * nw * 4) != hipSuccess) return -1;
-      g.wordsCap = 2 * nw;
-    }
+  const char *const what = "iterator scan of a long read";
+  if (g.dPacked.reserve (nw, 2 * nw, what)) return -1;
   U64 cap = mgSurvivorGuess (sh, total);
   MgHashParams p = mgMakeParams (sh);
   U64 off[2] = { 0, total };
   for (int attempt = 0 ; attempt < 3 ; ++attempt)
-    { if (cap > g.survCap)
-        { if (g.dKmer) (void) hipFree (g.dKmer);
-          if (g.dPosF) (void) hipFree (g.dPosF);
-          if (hipMalloc ((void **) &g.dKmer, 2 * cap * 8) != hipSuccess || hipMalloc ((void **) &g.dPosF, 2 * cap * 4) != hipSuccess) return -1;
-          g.survCap = 2 * cap;
-        }
-      size_t wb = mgScanWorkBytes (total, 1, g.survCap);
-      if (wb > g.workCap)
-        { if (g.dWork) (void) hipFree (g.dWork);
-          if (hipMalloc (&g.dWork, 2 * wb) != hipSuccess) return -1;
-          g.workCap = 2 * wb;
-        }
-      if (hipMemcpyAsync (g.dPacked, g.hPacked, nw * 4, hipMemcpyHostToDevice, g.st) != hipSuccess) return -1;
+    { if (g.dKmer.reserve (cap, 2 * cap, what) || g.dPosF.reserve (cap, 2 * cap, what)) return -1;
+      const U64 survCap = std::min (g.dKmer.cap, g.dPosF.cap);
+      const size_t wb = mgScanWorkBytes (total, 1, survCap);
+      if (g.dWork.reserve (wb, 2 * wb, what)) return -1;
+      if (hipMemcpyAsync (g.dPacked.p, g.hPacked, nw * 4, hipMemcpyHostToDevice, g.st) != hipSuccess) return -1;
       if (hipMemcpyAsync (g.dOff, off, 16, hipMemcpyHostToDevice, g.st) != hipSuccess) return -1;
-      if (mgLaunchScan (p, g.dPacked, total, g.dOff, 1, g.dKmer, g.dPosF, 0, g.survCap, g.dCount, g.dWork, g.st)) return -1;
+      if (mgLaunchScan (p, g.dPacked.p, total, g.dOff, 1, g.dKmer.p, g.dPosF.p, 0, survCap, g.dCount, g.dWork.p, g.st)) return -1;
       U64 c[MG_COUNT_WORDS];
       if (hipMemcpyAsync (c, g.dCount, sizeof (c), hipMemcpyDeviceToHost, g.st) != hipSuccess || hipStreamSynchronize (g.st) != hipSuccess) return -1;
-      if (c[1] || c[0] > g.survCap) { cap = c[3]; continue; }
+      if (c[1] || c[0] > survCap) { cap = c[3]; continue; }
       const U64 n = c[0];
       U64 *blk = (U64 *) malloc ((size_t) (n + 1) * 8 + (size_t) n * 4 + 8);
       if (!blk) return -1;
       blk[0] = n;
-      if (n && (hipMemcpyAsync (blk + 1, g.dKmer, n * 8, hipMemcpyDeviceToHost, g.st) != hipSuccess
-                || hipMemcpyAsync (blk + 1 + n, g.dPosF, n * 4, hipMemcpyDeviceToHost, g.st) != hipSuccess
+      if (n && (hipMemcpyAsync (blk + 1, g.dKmer.p, n * 8, hipMemcpyDeviceToHost, g.st) != hipSuccess
+                || hipMemcpyAsync (blk + 1 + n, g.dPosF.p, n * 4, hipMemcpyDeviceToHost, g.st) != hipSuccess
                 || hipStreamSynchronize (g.st) != hipSuccess)) { free (blk); return -1; }
       *blkOut = blk;
       return 0;

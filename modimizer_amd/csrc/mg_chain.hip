@@ -380,48 +380,40 @@ extern "C" int mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBa
   struct timespec lq0; clock_gettime (CLOCK_MONOTONIC, &lq0);
 #define RS_LAP(what) do { if (lapOn) { (void) hipDeviceSynchronize (); struct timespec q_; clock_gettime (CLOCK_MONOTONIC, &q_); fprintf (stderr, "mgReadsetSeedsDevice: %s at %.2f ms\n", what, (q_.tv_sec - lq0.tv_sec) * 1e3 + (q_.tv_nsec - lq0.tv_nsec) * 1e-6); } } while (0)
   U64 guess = totalBases / (U64) ms->hasher->w; guess += guess / 2 + 65536; if (guess > totalBases + 1) guess = totalBases + 1;
+  const char *const sorry = "readset seeds on the device failed";
+  MgDevScratch scratch ("readset seeds on the device");
   U32 *dIx = 0, *dPos = 0, *dRid = 0, *dMiss = 0, *dHit = 0, *dFirst = 0, *dTileCnt = 0, *dTileLast = 0; unsigned short *dDx = 0; U64 *dStart = 0, *dHitStart = 0;
   U64 n = 0;
-  int rc = -1;
-  do {
-    for (int attempt = 0 ; attempt < 2 ; ++attempt)
-      { if (hipMalloc ((void **) &dIx, guess * 4) || hipMalloc ((void **) &dPos, guess * 4) || hipMalloc ((void **) &dRid, guess * 4)) break;
-        MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, dIx, dPos, dRid, guess, &n, 0);
-        if (s == MG_OK) break;
-        (void) hipFree (dIx); (void) hipFree (dPos); (void) hipFree (dRid); dIx = dPos = dRid = 0;
-        if (s == MG_ERR_CAPACITY && attempt == 0) { guess = n; continue; }
-        break;
-      }
-    if (!dIx) break;
-    RS_LAP ("seeds");
-    if (n >= ((U64) 1 << 32) - 1) { mgSetError ("too many seeds in one batch"); break; }
-    const U32 nTiles = (U32) ((n + MG_RS_TILE - 1) / MG_RS_TILE);
-    if (hipMalloc ((void **) &dStart, ((size_t) nReads + 2) * 8) || hipMalloc ((void **) &dHitStart, ((size_t) nReads + 2) * 8)
-        || hipMalloc ((void **) &dMiss, ((size_t) nReads + 1) * 4) || hipMalloc ((void **) &dFirst, ((size_t) nReads + 1) * 4)
-        || hipMalloc ((void **) &dTileCnt, ((size_t) nTiles + 2) * 4) || hipMalloc ((void **) &dTileLast, ((size_t) nTiles + 2) * 4)) break;
-    unsigned grid = (unsigned) ((n + 1 + 255) / 256); if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL (mgSeedStartKernel, dim3 (grid), dim3 (256), 0, 0, dRid, n, nReads, dStart);
-    U32 totHit32 = 0;
-    if (nTiles)
-      { hipLaunchKernelGGL (mgRsTileCountKernel, dim3 (nTiles), dim3 (256), 0, 0, dIx, n, dTileCnt, dTileLast);
-        hipLaunchKernelGGL (mgRsTileScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, 0, dTileCnt, dTileLast, nTiles);
-        if (hipMemcpy (&totHit32, dTileCnt + nTiles, 4, hipMemcpyDeviceToHost)) break;
-      }
-    const U64 totHit = totHit32;
-    RS_LAP ("counted");
-    if (hipMalloc ((void **) &dHit, (totHit + 1) * 4) || hipMalloc ((void **) &dDx, (totHit + 1) * 2)) break;
-    if (nTiles) hipLaunchKernelGGL (mgRsWriteKernel, dim3 (nTiles), dim3 (256), 0, 0, dIx, dPos, dRid, dStart, n, dTileCnt, dTileLast, dFirst, dHit, dDx, dDepthAccum);
-    hipLaunchKernelGGL (mgRsPerReadKernel, dim3 (nReads / 256 + 1), dim3 (256), 0, 0, dStart, dRid, dFirst, n, totHit32, nReads, dHitStart, dMiss);
-    if (hipGetLastError () != hipSuccess) break;
-    if (hipMemcpy (hHitStart, dHitStart, ((size_t) nReads + 1) * 8, hipMemcpyDeviceToHost) || hipMemcpy (hNMiss, dMiss, (size_t) nReads * 4, hipMemcpyDeviceToHost)) break;
-    *dHitOut = dHit; *dDxOut = dDx; dHit = 0; dDx = 0;
-    RS_LAP ("written");
-    rc = 0;
-  } while (0);
-  (void) hipFree (dIx); (void) hipFree (dPos); (void) hipFree (dRid); (void) hipFree (dStart); (void) hipFree (dHitStart);
-  (void) hipFree (dMiss); (void) hipFree (dHit); (void) hipFree (dDx); (void) hipFree (dFirst); (void) hipFree (dTileCnt); (void) hipFree (dTileLast);
-  RS_LAP ("freed");
-#undef RS_LAP
-  if (rc < 0 && !mgLastError ()[0]) mgSetError ("readset seeds on the device failed");
-  return rc;
+  for (int attempt = 0 ; ; ++attempt)
+    { MgDevScratch seeds (scratch.what);                    /* of this attempt: a guess that was too small is freed before the next one is made */
+      if (seeds.get (&dIx, guess) || seeds.get (&dPos, guess) || seeds.get (&dRid, guess)) return -1;
+      const MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, dIx, dPos, dRid, guess, &n, 0);
+      if (s == MG_OK) { scratch.adopt (seeds.take (dIx)); scratch.adopt (seeds.take (dPos)); scratch.adopt (seeds.take (dRid)); break; }
+      if (s != MG_ERR_CAPACITY || attempt) return mgFailedWith (sorry);
+      guess = n;
+    }
+  RS_LAP ("seeds");
+  if (n >= ((U64) 1 << 32) - 1) { mgSetError ("too many seeds in one batch"); return -1; }
+  const U32 nTiles = (U32) ((n + MG_RS_TILE - 1) / MG_RS_TILE);
+  if (scratch.get (&dStart, (size_t) nReads + 2) || scratch.get (&dHitStart, (size_t) nReads + 2) || scratch.get (&dMiss, (size_t) nReads + 1) || scratch.get (&dFirst, (size_t) nReads + 1)
+      || scratch.get (&dTileCnt, (size_t) nTiles + 2) || scratch.get (&dTileLast, (size_t) nTiles + 2)) return -1;
+  unsigned grid = (unsigned) ((n + 1 + 255) / 256); if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL (mgSeedStartKernel, dim3 (grid), dim3 (256), 0, 0, dRid, n, nReads, dStart);
+  U32 totHit32 = 0;
+  if (nTiles)
+    { hipLaunchKernelGGL (mgRsTileCountKernel, dim3 (nTiles), dim3 (256), 0, 0, dIx, n, dTileCnt, dTileLast);
+      hipLaunchKernelGGL (mgRsTileScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, 0, dTileCnt, dTileLast, nTiles);
+      if (hipMemcpy (&totHit32, dTileCnt + nTiles, 4, hipMemcpyDeviceToHost)) return mgFailedWith (sorry);
+    }
+  const U64 totHit = totHit32;
+  RS_LAP ("counted");
+  if (scratch.get (&dHit, totHit + 1) || scratch.get (&dDx, totHit + 1)) return -1;
+  if (nTiles) hipLaunchKernelGGL (mgRsWriteKernel, dim3 (nTiles), dim3 (256), 0, 0, dIx, dPos, dRid, dStart, n, dTileCnt, dTileLast, dFirst, dHit, dDx, dDepthAccum);
+  hipLaunchKernelGGL (mgRsPerReadKernel, dim3 (nReads / 256 + 1), dim3 (256), 0, 0, dStart, dRid, dFirst, n, totHit32, nReads, dHitStart, dMiss);
+  if (hipGetLastError () != hipSuccess) return mgFailedWith (sorry);
+  if (hipMemcpy (hHitStart, dHitStart, ((size_t) nReads + 1) * 8, hipMemcpyDeviceToHost) || hipMemcpy (hNMiss, dMiss, (size_t) nReads * 4, hipMemcpyDeviceToHost)) return mgFailedWith (sorry);
+  *dHitOut = scratch.take (dHit); *dDxOut = scratch.take (dDx);
+  RS_LAP ("written");
+  return 0;
 }
+#undef RS_LAP

@@ -71,6 +71,22 @@ struct MgDevScratch {
   { *p = 0; const hipError_t e = hipMalloc ((void **) p, count * sizeof (T)); if (e != hipSuccess) return mgHipFail (e, what); adopt (*p); return MG_OK; }
   template <class T> T *take (T *p) { held.erase (std::remove (held.begin (), held.end (), (void *) p), held.end ()); return p; }
 };
+/* -1 from an entry point that returns int, with its own sentence if whatever failed inside it left no error */
+static inline int mgFailedWith (const char *sentence) { if (!mgLastError ()[0]) mgSetError ("%s", sentence); return -1; }
+
+/* a device array that OUTLIVES a call and only grows: p holds cap elements.  reserve () does nothing while cap >= want; else it frees the array and makes one
+   of alloc elements (each site's own growth: the caller's number) -- what the old one held is NOT carried over.  A failed allocation leaves p and cap zero and
+   "HIP error ... in <what>".  No destructor: the owners (statics, per-thread scratch) say when, with drop (). */
+template <class T> struct MgDevBuf {
+  T *p = 0; size_t cap = 0;
+  MgStatus reserve (size_t want, size_t alloc, const char *what)
+  { if (cap >= want) return MG_OK;
+    drop ();
+    const hipError_t e = hipMalloc ((void **) &p, alloc * sizeof (T)); if (e != hipSuccess) { p = 0; return mgHipFail (e, what); }
+    cap = alloc; return MG_OK;
+  }
+  void drop () { if (p) (void) hipFree (p); p = 0; cap = 0; }
+};
 
 #ifdef __HIPCC__
 /* Exact "x % d == 0" without a division (d = dOdd * 2^dShift):

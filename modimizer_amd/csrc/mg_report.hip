@@ -214,27 +214,16 @@ __global__ void mgDepthGatherKernel (const U64 *__restrict__ value, U64 m, int k
 /* device scratch of a report call, grow-only */
 struct MgReportBufs {
   U32 *blockSum = 0; U64 *blockOff = 0; U64 *hTotal = 0;
-  char *text = 0; size_t textCap = 0;
-  U32 *ix = 0, *posF = 0, *rid = 0; U64 seedCap = 0;
-  U32 *start = 0; U64 startCap = 0;
-  U32 *item = 0; U64 itemCap = 0;
-  char *ids = 0; size_t idsCap = 0;
-  U64 *idOff = 0; U64 idOffCap = 0;
+  MgDevBuf<char> text, ids;
+  MgDevBuf<U32> ix, posF, rid;                            /* the seeds: the three grow together */
+  MgDevBuf<U32> start, item;
+  MgDevBuf<U64> idOff;
   ~MgReportBufs ()
-  { (void) hipFree (blockSum); (void) hipFree (blockOff); (void) hipHostFree (hTotal); (void) hipFree (text);
-    (void) hipFree (ix); (void) hipFree (posF); (void) hipFree (rid); (void) hipFree (start); (void) hipFree (item);
-    (void) hipFree (ids); (void) hipFree (idOff);
+  { (void) hipFree (blockSum); (void) hipFree (blockOff); (void) hipHostFree (hTotal);
+    text.drop (); ids.drop (); ix.drop (); posF.drop (); rid.drop (); start.drop (); item.drop (); idOff.drop ();
   }
 };
-template <class T> static MgStatus mgGrow (T **p, U64 *cap, U64 want)
-{
-  if (*cap >= want && *p) return MG_OK;
-  (void) hipFree (*p); *p = 0; *cap = 0;
-  const U64 n = want + want / 8 + 64;
-  MG_HIP (hipMalloc ((void **) p, n * sizeof (T)));
-  *cap = n;
-  return MG_OK;
-}
+static inline size_t mgRoomFor (size_t want) { return want + want / 8 + 64; }      /* what a report's buffers grow to */
 static MgStatus mgReportBufsInit (MgReportBufs *b)
 {
   if (b->blockSum) return MG_OK;
@@ -259,11 +248,11 @@ static MgStatus mgTextFormat (const L &lines, U64 n, MgReportBufs *b, MgTextOut 
       MG_HIP (hipStreamSynchronize (st));
       const U64 bytes = *(volatile U64 *) b->hTotal;
       if (!bytes) continue;
-      { U64 cap = b->textCap; if ((s = mgGrow (&b->text, &cap, bytes))) return s; b->textCap = cap; }
-      MG_LAUNCH (MG_K_TEXT_WRITE, st, mgTextWriteKernel<L>, dim3 (nb), dim3 (MG_TEXT_THREADS), 0, st, lines, j0, m, b->blockOff, b->text);
+      if ((s = b->text.reserve (bytes, mgRoomFor (bytes), "report text"))) return s;
+      MG_LAUNCH (MG_K_TEXT_WRITE, st, mgTextWriteKernel<L>, dim3 (nb), dim3 (MG_TEXT_THREADS), 0, st, lines, j0, m, b->blockOff, b->text.p);
       MG_HIP (hipGetLastError ());
       MG_HIP (hipStreamSynchronize (st));
-      if (mgTextOutFromDevice (w, b->text, bytes)) { mgSetError ("failed to copy or write the report text"); return MG_ERR_HIP; }
+      if (mgTextOutFromDevice (w, b->text.p, bytes)) { mgSetError ("failed to copy or write the report text"); return MG_ERR_HIP; }
     }
   return MG_OK;
 }
@@ -280,19 +269,15 @@ extern "C" int mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
   if (!*scratch) *scratch = new MgReportBufs ();
   MgReportBufs *b = (MgReportBufs *) *scratch;
   hipStream_t st = 0;
+  const char *const what = "mgRefPaint";
   const int wdt = ms && ms->hasher && ms->hasher->w > 0 ? ms->hasher->w : 1;
   U64 cap = totalBases / (U64) wdt * 2 + 4096, n = 0;
   if (cap > totalBases + 16) cap = totalBases + 16;
   for (int attempt = 0 ; ; ++attempt)
-    { if (b->seedCap < cap)                                /* the three seed arrays share one capacity */
-        { (void) hipFree (b->ix); (void) hipFree (b->posF); (void) hipFree (b->rid); b->ix = b->posF = b->rid = 0; b->seedCap = 0;
-          if (hipMalloc ((void **) &b->ix, cap * 4) != hipSuccess || hipMalloc ((void **) &b->posF, cap * 4) != hipSuccess
-              || hipMalloc ((void **) &b->rid, cap * 4) != hipSuccess)
-            { mgHipFail (hipGetLastError (), "mgRefPaint: hipMalloc"); return -1; }
-          b->seedCap = cap;
-        }
-      const MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, b->ix, b->posF, b->rid, b->seedCap, &n, (void *) st);
-      if (s == MG_ERR_CAPACITY && !attempt && n > b->seedCap) { cap = n; continue; }
+    { if (b->ix.reserve (cap, cap, what) || b->posF.reserve (cap, cap, what) || b->rid.reserve (cap, cap, what)) return -1;
+      const U64 seedCap = std::min (b->ix.cap, std::min (b->posF.cap, b->rid.cap));
+      const MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, b->ix.p, b->posF.p, b->rid.p, seedCap, &n, (void *) st);
+      if (s == MG_ERR_CAPACITY && !attempt && n > seedCap) { cap = n; continue; }
       if (s) return -1;
       break;
     }
@@ -301,17 +286,42 @@ extern "C" int mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
   if (mgHookDeviceView (ms, &dValue1, &dDepth1, &max)) { mgSetError ("mgRefPaint: the set's device view is not available"); return -1; }
   /* the batch's ids as one buffer: they are contiguous, record r's at idOff[r], each 0-terminated */
   const size_t idBytesLen = (size_t) idOff[nReads - 1] + strlen (idBytes + idOff[nReads - 1]) + 1;
-  { U64 c = b->idsCap; if (mgGrow (&b->ids, &c, idBytesLen)) return -1; b->idsCap = c; }
-  if (mgGrow (&b->idOff, &b->idOffCap, nReads) || mgGrow (&b->start, &b->startCap, (U64) nReads + 1) || mgGrow (&b->item, &b->itemCap, n + nReads)) return -1;
-  if (hipMemcpyAsync (b->ids, idBytes, idBytesLen, hipMemcpyHostToDevice, st) != hipSuccess
-      || hipMemcpyAsync (b->idOff, idOff, (size_t) nReads * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+  if (b->ids.reserve (idBytesLen, mgRoomFor (idBytesLen), what) || b->idOff.reserve (nReads, mgRoomFor (nReads), what)
+      || b->start.reserve ((size_t) nReads + 1, mgRoomFor ((size_t) nReads + 1), what) || b->item.reserve (n + nReads, mgRoomFor (n + nReads), what)) return -1;
+  if (hipMemcpyAsync (b->ids.p, idBytes, idBytesLen, hipMemcpyHostToDevice, st) != hipSuccess
+      || hipMemcpyAsync (b->idOff.p, idOff, (size_t) nReads * 8, hipMemcpyHostToDevice, st) != hipSuccess)
     { mgHipFail (hipGetLastError (), "mgRefPaint: ids to the device"); return -1; }
-  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintStartKernel, dim3 (mgGrid (n + 1)), dim3 (256), 0, st, b->rid, n, nReads, b->start);
-  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintItemsKernel, dim3 (mgGrid (n + nReads)), dim3 (256), 0, st, b->rid, n, nReads, b->start, b->item);
+  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintStartKernel, dim3 (mgGrid (n + 1)), dim3 (256), 0, st, b->rid.p, n, nReads, b->start.p);
+  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintItemsKernel, dim3 (mgGrid (n + nReads)), dim3 (256), 0, st, b->rid.p, n, nReads, b->start.p, b->item.p);
   if (hipGetLastError () != hipSuccess) { mgSetError ("mgRefPaint: kernel launch failed"); return -1; }
   MgPaintLines L;
-  L.item = b->item; L.seedIx = b->ix; L.seedPosF = b->posF; L.depth1 = dDepth1; L.readOff = dReadOffsets; L.ids = b->ids; L.idOff = b->idOff;
+  L.item = b->item.p; L.seedIx = b->ix.p; L.seedPosF = b->posF.p; L.depth1 = dDepth1; L.readOff = dReadOffsets; L.ids = b->ids.p; L.idOff = b->idOff.p;
   return mgTextFormat (L, n + nReads, b, w, st) ? -1 : 0;
+}
+
+/* the body of mgReportDepths: entries 1 .. max of the set, a chunk at a time, to the writer */
+static int mgReportDepthsTo (MgTextOut *w, Modset *ms, Modset **others, int nOthers, const U64 *dValue1, const U16 *dDepth1, U32 max,
+                             const std::vector<const U16 *> &oDepth, const std::vector<int> &oBits)
+{
+  hipStream_t st = 0;
+  MgReportBufs b;
+  MgDevScratch scratch ("mgReportDepths");
+  U8 *dInfo; U64 *dKey; U32 *dIdx; U16 *dOth;
+  const U64 chunk = max < MG_TEXT_CHUNK ? max : MG_TEXT_CHUNK;
+  if (scratch.get (&dInfo, max) || scratch.get (&dKey, chunk) || scratch.get (&dIdx, chunk) || scratch.get (&dOth, (nOthers ? nOthers : 1) * chunk)) return -1;
+  if (mgCopyH2DBig (dInfo, ms->info + 1, max)) return -1;                /* msCopy: the host info[] is the authority */
+  for (U64 i0 = 0 ; i0 < max ; i0 += chunk)
+    { const U64 m = max - i0 < chunk ? max - i0 : chunk;
+      for (int o = 0 ; o < nOthers ; ++o)
+        { MG_LAUNCH (MG_K_DEPTH_GUARD, st, mgDepthGuardKernel, dim3 (mgGrid (m)), dim3 (256), 0, st, dValue1 + i0, m, oBits[o], dKey);
+          if (modsetFindBatchDevice (others[o], dKey, m, dIdx, (void *) st)) return -1;
+          MG_LAUNCH (MG_K_DEPTH_GATHER, st, mgDepthGatherKernel, dim3 (mgGrid (m)), dim3 (256), 0, st, dValue1 + i0, m, oBits[o], dIdx, oDepth[o], dOth + (U64) o * m);
+        }
+      MgDepthLines L;
+      L.value = dValue1 + i0; L.depth = dDepth1 + i0; L.info = dInfo + i0; L.oth = dOth; L.nOth = nOthers; L.m = m;
+      if (mgTextFormat (L, m, &b, w, st)) return -1;
+    }
+  return 0;
 }
 
 /* modutils.c:65-77.  The other sets' device tables are made on first use (from their host arrays) and left resident: the caller
@@ -330,35 +340,22 @@ extern "C" int mgReportDepths (Modset *ms, Modset **others, int nOthers, FILE *f
       oBits[o] = 2 * others[o]->hasher->k;
     }
   if (!max) return 0;
-  hipStream_t st = 0;
-  MgReportBufs b;
-  U8 *dInfo = 0; U64 *dKey = 0; U32 *dIdx = 0; U16 *dOth = 0;
-  const U64 chunk = max < MG_TEXT_CHUNK ? max : MG_TEXT_CHUNK;
-  int rc = -1;
-  MgTextOut *w = mgTextOutOpen (f);
-  do {
-    if (hipMalloc ((void **) &dInfo, max) != hipSuccess || hipMalloc ((void **) &dKey, chunk * 8) != hipSuccess
-        || hipMalloc ((void **) &dIdx, chunk * 4) != hipSuccess || hipMalloc ((void **) &dOth, (nOthers ? nOthers : 1) * chunk * 2) != hipSuccess)
-      { mgHipFail (hipGetLastError (), "mgReportDepths: hipMalloc"); break; }
-    if (mgCopyH2DBig (dInfo, ms->info + 1, max)) break;                  /* msCopy: the host info[] is the authority */
-    bool ok = true;
-    for (U64 i0 = 0 ; i0 < max && ok ; i0 += chunk)
-      { const U64 m = max - i0 < chunk ? max - i0 : chunk;
-        for (int o = 0 ; o < nOthers && ok ; ++o)
-          { MG_LAUNCH (MG_K_DEPTH_GUARD, st, mgDepthGuardKernel, dim3 (mgGrid (m)), dim3 (256), 0, st, dValue1 + i0, m, oBits[o], dKey);
-            if (modsetFindBatchDevice (others[o], dKey, m, dIdx, (void *) st)) { ok = false; break; }
-            MG_LAUNCH (MG_K_DEPTH_GATHER, st, mgDepthGatherKernel, dim3 (mgGrid (m)), dim3 (256), 0, st, dValue1 + i0, m, oBits[o], dIdx, oDepth[o], dOth + (U64) o * m);
-          }
-        if (!ok) break;
-        MgDepthLines L;
-        L.value = dValue1 + i0; L.depth = dDepth1 + i0; L.info = dInfo + i0; L.oth = dOth; L.nOth = nOthers; L.m = m;
-        if (mgTextFormat (L, m, &b, w, st)) ok = false;
-      }
-    if (ok) rc = 0;
-  } while (0);
+  MgTextOut *w = mgTextOutOpen (f);                       /* closed on every path; a failed close is the error only if nothing failed before it */
+  int rc = mgReportDepthsTo (w, ms, others, nOthers, dValue1, dDepth1, max, oDepth, oBits);
   if (mgTextOutClose (w) && !rc) { mgSetError ("mgReportDepths: write failed"); rc = -1; }
-  (void) hipFree (dInfo); (void) hipFree (dKey); (void) hipFree (dIdx); (void) hipFree (dOth);
   return rc;
+}
+
+static int mgModsetWriteTextTo (MgTextOut *w, Modset *ms, const U64 *dValue1, const U16 *dDepth1, U32 max)
+{
+  MgReportBufs b;
+  MgDevScratch scratch ("mgModsetWriteTextDevice");
+  U8 *dInfo;
+  if (scratch.get (&dInfo, max)) return -1;
+  if (mgCopyH2DBig (dInfo, ms->info + 1, max)) return -1;                /* the host info[] is the authority */
+  MgSetLines L;
+  L.value = dValue1; L.depth = dDepth1; L.info = dInfo; L.k = ms->hasher->k;
+  return mgTextFormat (L, (U64) max, &b, w, 0) ? -1 : 0;
 }
 
 /* modutils.c:191-199.  The header line is the host's, written before the writer thread exists, so the bytes are in order. */
@@ -375,20 +372,8 @@ extern "C" int mgModsetWriteTextDevice (Modset *ms, FILE *f)
   if (fprintf (f, "modset bits %d size %d k %d w %d seed %d\n", ms->tableBits, max + 1, sh->k, sh->w, sh->seed) < 0)
     { mgSetError ("mgModsetWriteTextDevice: write failed"); return -1; }
   if (!max) return 0;
-  hipStream_t st = 0;
-  MgReportBufs b;
-  U8 *dInfo = 0;
-  int rc = -1;
   MgTextOut *w = mgTextOutOpen (f);
-  do {
-    if (hipMalloc ((void **) &dInfo, max) != hipSuccess) { mgHipFail (hipGetLastError (), "mgModsetWriteTextDevice: hipMalloc"); break; }
-    if (mgCopyH2DBig (dInfo, ms->info + 1, max)) break;                  /* the host info[] is the authority */
-    MgSetLines L;
-    L.value = dValue1; L.depth = dDepth1; L.info = dInfo; L.k = sh->k;
-    if (mgTextFormat (L, (U64) max, &b, w, st)) break;
-    rc = 0;
-  } while (0);
+  int rc = mgModsetWriteTextTo (w, ms, dValue1, dDepth1, max);
   if (mgTextOutClose (w) && !rc) { mgSetError ("mgModsetWriteTextDevice: write failed"); rc = -1; }
-  (void) hipFree (dInfo);
   return rc;
 }

@@ -174,18 +174,16 @@ __global__ void mgSetTextPlaceKernel (const U32 *__restrict__ idx, U64 n, const 
 /* ---------------------------------------------------------------------------------------- */
 /* host side                                                                                  */
 
-struct StBufs {                                          /* of one call */
-  unsigned char *hPin[2] = { 0, 0 }, *dText[2] = { 0, 0 };
-  hipEvent_t copied[2]; bool ev[2] = { false, false };
-  StState *dState = 0, *hState = 0;
-  U32 *dTileCount = 0, *dTileLast = 0, *dTileOff = 0, *dNl = 0;
+struct StBufs {                                          /* of one call: its device arrays are the scratch's, the three that hold the result named here */
+  MgDevScratch scratch { "set text parse on the device" };
   U64 *dKey = 0; U16 *dDepth = 0; U8 *dInfo = 0;
+  unsigned char *hPin[2] = { 0, 0 };
+  hipEvent_t copied[2]; bool ev[2] = { false, false };
+  StState *hState = 0;
   int fd = -1;
   ~StBufs ()
-  { for (int i = 0 ; i < 2 ; ++i) { if (hPin[i]) (void) hipHostFree (hPin[i]); (void) hipFree (dText[i]); if (ev[i]) (void) hipEventDestroy (copied[i]); }
-    (void) hipFree (dState); if (hState) (void) hipHostFree (hState);
-    (void) hipFree (dTileCount); (void) hipFree (dTileLast); (void) hipFree (dTileOff); (void) hipFree (dNl);
-    (void) hipFree (dKey); (void) hipFree (dDepth); (void) hipFree (dInfo);
+  { for (int i = 0 ; i < 2 ; ++i) { if (hPin[i]) (void) hipHostFree (hPin[i]); if (ev[i]) (void) hipEventDestroy (copied[i]); }
+    if (hState) (void) hipHostFree (hState);
     if (fd >= 0) close (fd);
   }
 };
@@ -206,18 +204,18 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
   const U32 maxTiles = (U32) (bufBytes / ST_TILE + 1);
   hipStream_t st = 0;
   const double t0 = mgNowS (); double tRead = 0, tWait = 0;
+  unsigned char *dText[2]; StState *dState; U32 *dTileCount, *dTileLast, *dTileOff, *dNl;
   for (int i = 0 ; i < 2 ; ++i)
     { MG_HIP (hipHostMalloc ((void **) &b.hPin[i], window, hipHostMallocDefault));
-      MG_HIP (hipMalloc ((void **) &b.dText[i], bufBytes));
+      if (b.scratch.get (&dText[i], bufBytes)) return MG_ERR_HIP;
       MG_HIP (hipEventCreateWithFlags (&b.copied[i], hipEventDisableTiming)); b.ev[i] = true;
     }
-  MG_HIP (hipMalloc ((void **) &b.dState, sizeof (StState)));
+  if (b.scratch.get (&dState, 1)) return MG_ERR_HIP;
   MG_HIP (hipHostMalloc ((void **) &b.hState, sizeof (StState), hipHostMallocDefault));
-  MG_HIP (hipMalloc ((void **) &b.dTileCount, (size_t) maxTiles * 4)); MG_HIP (hipMalloc ((void **) &b.dTileLast, (size_t) maxTiles * 4));
-  MG_HIP (hipMalloc ((void **) &b.dTileOff, (size_t) maxTiles * 4)); MG_HIP (hipMalloc ((void **) &b.dNl, (size_t) nlCap * 4));
-  MG_HIP (hipMalloc ((void **) &b.dKey, want * 8)); MG_HIP (hipMalloc ((void **) &b.dDepth, want * 2)); MG_HIP (hipMalloc ((void **) &b.dInfo, want));
+  if (b.scratch.get (&dTileCount, maxTiles) || b.scratch.get (&dTileLast, maxTiles) || b.scratch.get (&dTileOff, maxTiles) || b.scratch.get (&dNl, nlCap)
+      || b.scratch.get (&b.dKey, want) || b.scratch.get (&b.dDepth, want) || b.scratch.get (&b.dInfo, want)) return MG_ERR_HIP;
   StState init; memset (&init, 0, sizeof (init)); init.want = want;
-  MG_HIP (hipMemcpyAsync (b.dState, &init, sizeof (init), hipMemcpyHostToDevice, st));
+  MG_HIP (hipMemcpyAsync (dState, &init, sizeof (init), hipMemcpyHostToDevice, st));
   MG_HIP (hipStreamSynchronize (st));                    /* (init is on this stack) */
   const double t1 = mgNowS ();
   int w = 0;
@@ -229,17 +227,17 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
       const double r1 = mgNowS ();
       if (mgTextReadParallel (b.fd, b.hPin[cur], nCur, (int64_t) (bodyOff + off))) { mgSetError ("failed to read text file %s", filename); return MG_ERR_ARG; }
       tWait += r1 - r0; tRead += mgNowS () - r1;
-      MG_HIP (hipMemcpyAsync (b.dText[cur] + ST_CARRY, b.hPin[cur], nCur, hipMemcpyHostToDevice, st));
+      MG_HIP (hipMemcpyAsync (dText[cur] + ST_CARRY, b.hPin[cur], nCur, hipMemcpyHostToDevice, st));
       MG_HIP (hipEventRecord (b.copied[cur], st));
       const U32 nBytes = ST_CARRY + (U32) nCur, nTiles = (nBytes + ST_TILE - 1) / ST_TILE;
-      MG_LAUNCH (MG_K_SETTEXT_LINES, st, mgSetTextLinesKernel<false>, dim3 (nTiles), dim3 (ST_THREADS), 0, st, b.dText[cur], nBytes, b.dState,
-                 b.dTileCount, b.dTileLast, b.dTileOff, b.dNl, nlCap);
-      MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextScanKernel, dim3 (1), dim3 (ST_SCAN_THREADS), 0, st, b.dTileCount, b.dTileLast, nTiles, b.dTileOff, nlCap, b.dState);
-      MG_LAUNCH (MG_K_SETTEXT_LINES, st, mgSetTextLinesKernel<true>, dim3 (nTiles), dim3 (ST_THREADS), 0, st, b.dText[cur], nBytes, b.dState,
-                 b.dTileCount, b.dTileLast, b.dTileOff, b.dNl, nlCap);
-      MG_LAUNCH (MG_K_SETTEXT_PARSE, st, mgSetTextParseKernel, dim3 (mgGrid (nlCap)), dim3 (256), 0, st, b.dText[cur], b.dNl, b.dState, k, b.dKey, b.dDepth, b.dInfo);
-      MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextCarryKernel, dim3 (1), dim3 (64), 0, st, b.dText[cur], nBytes, b.dText[cur ^ 1], b.dState);
-      MG_HIP (hipMemcpyAsync (b.hState, b.dState, sizeof (StState), hipMemcpyDeviceToHost, st));
+      MG_LAUNCH (MG_K_SETTEXT_LINES, st, mgSetTextLinesKernel<false>, dim3 (nTiles), dim3 (ST_THREADS), 0, st, dText[cur], nBytes, dState,
+                 dTileCount, dTileLast, dTileOff, dNl, nlCap);
+      MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextScanKernel, dim3 (1), dim3 (ST_SCAN_THREADS), 0, st, dTileCount, dTileLast, nTiles, dTileOff, nlCap, dState);
+      MG_LAUNCH (MG_K_SETTEXT_LINES, st, mgSetTextLinesKernel<true>, dim3 (nTiles), dim3 (ST_THREADS), 0, st, dText[cur], nBytes, dState,
+                 dTileCount, dTileLast, dTileOff, dNl, nlCap);
+      MG_LAUNCH (MG_K_SETTEXT_PARSE, st, mgSetTextParseKernel, dim3 (mgGrid (nlCap)), dim3 (256), 0, st, dText[cur], dNl, dState, k, b.dKey, b.dDepth, b.dInfo);
+      MG_LAUNCH (MG_K_SETTEXT_SCAN, st, mgSetTextCarryKernel, dim3 (1), dim3 (64), 0, st, dText[cur], nBytes, dText[cur ^ 1], dState);
+      MG_HIP (hipMemcpyAsync (b.hState, dState, sizeof (StState), hipMemcpyDeviceToHost, st));
       MG_HIP (hipGetLastError ());
       off += nCur;
       /* (a look at the state as the window before last left it, without waiting: nothing after the last wanted line is read) */
@@ -248,7 +246,7 @@ static MgStatus stParse (StBufs &b, const char *filename, U64 bodyOff, U64 want,
     }
   const double t2 = mgNowS ();
   MG_HIP (hipStreamSynchronize (st));
-  MG_HIP (hipMemcpy (b.hState, b.dState, sizeof (StState), hipMemcpyDeviceToHost));
+  MG_HIP (hipMemcpy (b.hState, dState, sizeof (StState), hipMemcpyDeviceToHost));
   if (stTiming ())
     fprintf (stderr, "  [set text] parse: %d windows of %zu bytes; buffers %.3f s, file read %.3f, waits for a window's copy %.3f, enqueue + rest %.3f, wait at the end %.3f\n",
              w, window, t1 - t0, tRead, tWait, t2 - t1 - tRead - tWait, mgNowS () - t2);
@@ -264,40 +262,35 @@ extern "C" int mgSetTextParseDevice (const char *filename, U64 bodyOff, U64 want
   int verdict = 1;
   if (stParse (b, filename, bodyOff, want, k, &verdict)) return -1;
   if (verdict) return 1;
-  *dKey = b.dKey; *dDepth = b.dDepth; *dInfo = b.dInfo;                    /* the caller's from here */
-  b.dKey = 0; b.dDepth = 0; b.dInfo = 0;
+  *dKey = b.scratch.take (b.dKey); *dDepth = b.scratch.take (b.dDepth); *dInfo = b.scratch.take (b.dInfo);      /* the caller's from here */
   return 0;
 }
-
-struct StFill {
-  U32 *dIdx = 0, *dWin = 0; U16 *dOutDepth = 0; U8 *dOutInfo = 0;
-  ~StFill () { (void) hipFree (dIdx); (void) hipFree (dWin); (void) hipFree (dOutDepth); (void) hipFree (dOutInfo); }
-};
 
 static MgStatus stFill (Modset *ms, const U64 *dKey, const U16 *dDepth, const U8 *dInfo, U64 n)
 {
   MgStatus s = mgEnsureDevice (); if (s) return s;
   if (!n) return MG_OK;
   hipStream_t st = 0;
-  StFill f;
+  MgDevScratch scratch ("set text fill on the device");
+  U32 *dIdx, *dWin; U16 *dOutDepth; U8 *dOutInfo;
   const double t0 = mgNowS ();
-  MG_HIP (hipMalloc ((void **) &f.dIdx, n * 4));
+  if (scratch.get (&dIdx, n)) return MG_ERR_HIP;
   const U64 piece = (U64) 1 << 30;                       /* modsetAddBatchDevice takes fewer than 2^31 a call */
   for (U64 off = 0 ; off < n ; off += piece)
-    if ((s = modsetAddBatchDevice (ms, dKey + off, n - off < piece ? n - off : piece, f.dIdx + off, 0, (void *) st))) return s;
+    if ((s = modsetAddBatchDevice (ms, dKey + off, n - off < piece ? n - off : piece, dIdx + off, 0, (void *) st))) return s;
   MG_HIP (hipStreamSynchronize (st));
   const double t1 = mgNowS ();
   const size_t m1 = (size_t) ms->max + 1;
-  MG_HIP (hipMalloc ((void **) &f.dWin, m1 * 4)); MG_HIP (hipMalloc ((void **) &f.dOutDepth, m1 * 2)); MG_HIP (hipMalloc ((void **) &f.dOutInfo, m1));
-  MG_HIP (hipMemsetAsync (f.dWin, 0, m1 * 4, st)); MG_HIP (hipMemsetAsync (f.dOutDepth, 0, m1 * 2, st)); MG_HIP (hipMemsetAsync (f.dOutInfo, 0, m1, st));
-  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextLastKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin);
-  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextPlaceKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, f.dIdx, n, f.dWin, dDepth, dInfo, f.dOutDepth, f.dOutInfo);
+  if (scratch.get (&dWin, m1) || scratch.get (&dOutDepth, m1) || scratch.get (&dOutInfo, m1)) return MG_ERR_HIP;
+  MG_HIP (hipMemsetAsync (dWin, 0, m1 * 4, st)); MG_HIP (hipMemsetAsync (dOutDepth, 0, m1 * 2, st)); MG_HIP (hipMemsetAsync (dOutInfo, 0, m1, st));
+  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextLastKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, dIdx, n, dWin);
+  MG_LAUNCH (MG_K_SETTEXT_LAST, st, mgSetTextPlaceKernel, dim3 (mgGrid (n)), dim3 (256), 0, st, dIdx, n, dWin, dDepth, dInfo, dOutDepth, dOutInfo);
   MG_HIP (hipGetLastError ());
   MG_HIP (hipStreamSynchronize (st));
   const double t2 = mgNowS ();
   /* the host's depth[] and info[] are the authority; the device table's depth copy follows them */
-  if ((s = mgCopyD2HBig (ms->depth, f.dOutDepth, m1 * 2)) || (s = mgCopyD2HBig (ms->info, f.dOutInfo, m1))) return s;
-  s = mgModsetAdoptDepthDevice (ms, f.dOutDepth);
+  if ((s = mgCopyD2HBig (ms->depth, dOutDepth, m1 * 2)) || (s = mgCopyD2HBig (ms->info, dOutInfo, m1))) return s;
+  s = mgModsetAdoptDepthDevice (ms, dOutDepth);
   if (stTiming ())
     fprintf (stderr, "  [set text] fill: insert (device table made) %.3f s, last line wins %.3f, depth[] + info[] to the host %.3f\n", t1 - t0, t2 - t1, mgNowS () - t2);
   return s;
@@ -310,12 +303,9 @@ extern "C" int mgSetTextFillHostArrays (Modset *ms, const U64 *key, const U16 *d
 {
   if (mgEnsureDevice ()) return -1;
   if (!n) return 0;
-  U64 *dKey = 0; U16 *dDepth = 0; U8 *dInfo = 0;
-  int rc = -1;
-  if (hipMalloc ((void **) &dKey, n * 8) != hipSuccess || hipMalloc ((void **) &dDepth, n * 2) != hipSuccess || hipMalloc ((void **) &dInfo, n) != hipSuccess)
-    mgHipFail (hipGetLastError (), "mgModsetReadText: hipMalloc");
-  else if (!mgCopyH2DBig (dKey, key, n * 8) && !mgCopyH2DBig (dDepth, depth, n * 2) && !mgCopyH2DBig (dInfo, info, n))
-    rc = stFill (ms, dKey, dDepth, dInfo, n) ? -1 : 0;
-  (void) hipFree (dKey); (void) hipFree (dDepth); (void) hipFree (dInfo);
-  return rc;
+  MgDevScratch scratch ("mgModsetReadText");
+  U64 *dKey; U16 *dDepth; U8 *dInfo;
+  if (scratch.get (&dKey, n) || scratch.get (&dDepth, n) || scratch.get (&dInfo, n)) return -1;
+  if (mgCopyH2DBig (dKey, key, n * 8) || mgCopyH2DBig (dDepth, depth, n * 2) || mgCopyH2DBig (dInfo, info, n)) return -1;
+  return stFill (ms, dKey, dDepth, dInfo, n) ? -1 : 0;
 }

@@ -985,20 +985,16 @@ static int txHostSink (void *v, const U32 *dPacked, U64 total, const U64 *dOff, 
   TxHostCtx *c = (TxHostCtx *) v;
   std::vector<U64> o ((size_t) nReads + 1);
   if (hipMemcpy (o.data (), dOff, ((size_t) nReads + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  unsigned char *dB = 0;
-  if (hipMalloc ((void **) &dB, total ? total : 16) != hipSuccess) return -1;
-  int rc = -1;
-  if (mgLaunchUnpack (dPacked, total, dB, st) == MG_OK && hipStreamSynchronize (st) == hipSuccess)
-    { const size_t at = c->bases.size ();
-      c->bases.resize (at + total);
-      if (!total || hipMemcpy (c->bases.data () + at, dB, total, hipMemcpyDeviceToHost) == hipSuccess)
-        { if (c->offs.empty ()) c->offs.push_back (0);
-          for (U32 r = 1 ; r <= nReads ; ++r) c->offs.push_back ((int64_t) (at + o[r]));
-          rc = 0;
-        }
-    }
-  (void) hipFree (dB);
-  return rc;
+  MgDevScratch scratch ("mgTextParseFileDevice");
+  unsigned char *dB;
+  if (scratch.get (&dB, total ? total : 16)) return -1;
+  if (mgLaunchUnpack (dPacked, total, dB, st) != MG_OK || hipStreamSynchronize (st) != hipSuccess) return -1;
+  const size_t at = c->bases.size ();
+  c->bases.resize (at + total);
+  if (total && hipMemcpy (c->bases.data () + at, dB, total, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (c->offs.empty ()) c->offs.push_back (0);
+  for (U32 r = 1 ; r <= nReads ; ++r) c->offs.push_back ((int64_t) (at + o[r]));
+  return 0;
 }
 extern "C" int mgTextParseFileDevice (const char *filename, char **basesOut, int64_t **offsetsOut, int64_t *nSeqOut)
 {

@@ -397,3 +397,45 @@ def test_saturated_mod_vs_restatement(tmp_path):
     assert sat in u[c >= 2] and (c >= 2).sum() > 300 and (info2[u[c >= 2]] & MS_REPEAT).all()
     assert "MT i 2 h %d count %d\n" % (sat, 70_000 - K + 1) in read_text(tmp_path / "p.txt")
     L.mgReadsetDestroy(rs); L.modsetDestroy(ms)
+
+
+# ---- 7: more seeds than the first guess provides for ----
+
+@pytest.mark.gpu
+def test_ingest_retries_when_the_seed_guess_is_too_small(tmp_path):
+    """mgReadsetSeedsDevice sizes its three seed arrays for min (bases / w * 1.5 + 65536, bases + 1) seeds; a batch with more has them freed and
+    made again at the size the scan asked for, in the middle of the call.  w = 2 and four reads of 100 000 a, whose one k-mer is a modimizer
+    at every start: 4 x 99 986 seeds against a guess of 367 118.  Ordinary reads, one that hits nothing, an empty one and one shorter than k
+    stand between them.
+    The hit lists, distances, counts and depths against the oracle's read set, exactly."""
+    from oracle import pyoracle as orc
+    w = 2
+    h = orc.Hasher(K, w, 17)
+    assert len(h.scan(np.zeros(K, np.uint8))[0]) == 1                             # the k-mer of a run of a IS a modimizer: the run is all seeds
+    g = np.random.default_rng(4200).integers(0, 4, 20_000).astype(np.uint8)
+    poly = np.zeros(100_000, np.uint8)
+    reads = [poly, g[3000:3400], poly, rc(g[5000:5600]), poly, np.zeros(0, np.uint8), g[100:110], poly, g[900:1500], np.random.default_rng(4201).integers(0, 4, 500).astype(np.uint8)]
+    total = sum(len(r) for r in reads)
+    guess = total // w
+    guess = min(guess + guess // 2 + 65536, total + 1)                            # mg_chain.hip, mgReadsetSeedsDevice
+    oms = orc.Modset(h, 20)
+    oms.add_sequence(np.zeros(100, np.uint8)); oms.add_sequence(g)
+    oms.set_copy(1, 2, 3)
+    ors = orc.Readset(oms); ors.read(reads)
+    want = ors.arrays()
+    p = str(tmp_path / "m.mod"); oms.write_mod(p)
+    L = mg.lib()
+    with mg.CFile(p, "r") as f:
+        ms = L.modsetRead(f)
+    rs = L.mgReadsetCreate(ms)
+    bases, offs = util.concat_reads(reads)
+    assert L.mgReadsetRead(rs, bases.ctypes.data, offs.ctypes.data, len(reads)) == 0
+    got = trs.lib_arrays(rs)
+    seeds = int(got["nHit"].sum() + got["nMiss"].sum())
+    print("first guess %d, seeds of the batch %d" % (guess, seeds))
+    assert guess < seeds <= total                                                 # the first attempt was too small: the call went round again
+    trs.same(want, got)
+    assert np.array_equal(trc.ms_arrays(ms)[0], oms.depths())
+    assert int(oms.depths().max()) == 65535 and len(set(got["nHit"].tolist())) >= 5 and got["nMiss"].any()
+    L.mgReadsetDestroy(rs); L.modsetDestroy(ms)
+    ors.close(); oms.close()

@@ -235,6 +235,38 @@ def test_paint_edge_records(tmp_path):
     L.modsetDestroy(ms)
 
 
+def test_paint_retries_when_the_seed_guess_is_too_small(tmp_path):
+    """mgRefPaintBatchDevice sizes its three seed arrays for min (bases / w * 2 + 4096, bases + 16) seeds and, for a batch with more, frees
+    them and makes them again at the size the scan asked for.  With w = 2 the first term alone is the batch, so the guess is its cap and
+    never short; w = 3 is the smallest that can fall short: records of a alone (one k-mer, a modimizer at every start) hold a seed per
+    base against two per three bases provided for.  Two such records of 60 000, ordinary ones, an empty one and one of k - 1 bases
+    between them; the lines against the per-read facade."""
+    from oracle import pyoracle as po
+    L = mg.lib()
+    k, w, seed = 21, 3, 17
+    assert len(po.Hasher(k, w, seed).scan(np.zeros(k, np.uint8))[0]) == 1       # the k-mer of a run of a IS a modimizer: the run is all seeds
+    sh = mg.seqhashCreate(k, w, seed)
+    ms = mg.modsetCreate(sh, 22)
+    genome = synth.iid_bases(30000, 73)
+    b, o = util.concat_reads([genome[i:i + 3000] for i in range(0, 27000, 1500)] + [np.zeros(200, np.uint8)])
+    mg.add_sequence_batch(ms, b, o)
+    poly = np.zeros(60_000, np.uint8)
+    recs = [poly, genome[1000:3000], poly, genome[7000:7000 + k - 1], genome[:0], genome[5000:9000]]
+    names = ["q%d_%d" % (i, len(r)) for i, r in enumerate(recs)]
+    total = sum(len(r) for r in recs)
+    guess = min(total // w * 2 + 4096, total + 16)                               # mg_report.hip, mgRefPaintBatchDevice
+    bb, oo = util.concat_reads(recs)
+    out = str(tmp_path / "mem.txt")
+    mg.refpaint(ms, bb, oo, names, out)
+    mem = open(out).read()
+    lines = mem.count("\n") - len(recs)                                          # one line per seed that is in the set: no more than the batch's seeds
+    print("first guess %d, seed lines of the batch %d" % (guess, lines))
+    assert guess < lines <= total                                                # the first attempt was too small: the call went round again
+    assert mem == facade_paint(ms, names, recs)
+    assert mem.count("painting ") == len(recs) and "  59979\t180\n" in mem and len(set(l.split("\t")[1] for l in mem.splitlines() if l.startswith("  "))) > 2
+    L.modsetDestroy(ms)
+
+
 def test_saturated_depth_and_value_zero(tmp_path):
     """the all-a k-mer (value 0, printed "0" by %llx) counted past 65535 (saturated): both reports"""
     L = mg.lib()
