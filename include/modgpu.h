@@ -356,6 +356,63 @@ int  mgReadsetCleanModsPath (void) ;
 int  mgReadsetProperties (MgReadset *rs, FILE *out) ;
 int  mgReadsetPropertiesPath (void) ;
 
+/* modrep -R <ref.fa> <ref.mod> -s3 <reads.fa> <reads.mod> (modrep.c:27-63,170-268; the rest of that file is its "OLD VERSIONS").
+ * Scan, lookups and every per-read and per-mod reduction run on the device (mg_modrep.hip); the host formats the lines.  All of these
+ * need a HIP device: there is no host fallback.
+ *
+ * MgRepRef is modrep.c:20-25 as refCreate leaves it: for every entry of ms found in the one reference sequence pos[index] = the position
+ * of its LAST occurrence and isF[index] its strand there (entries not found: 0 / false); len = the largest position + 1 (0: none found).
+ * refCreate dies when it meets an entry whose pos[] is already non-zero (modrep.c:48), so an occurrence at position 0 does not protect
+ * its entry: a mod may occur once, or twice if its first occurrence is at position 0.  Both creators print modrep.c:58-59 ("found %d of
+ * %d locations in ref length %llu") to err (0: not printed) and return 0 with mgLastError () holding the program's message otherwise:
+ * "duplicate mod entry at position %d in ref", "multiple sequences in ref file - only one allowed", and those of unreadable files. */
+typedef struct {
+  Modset *ms ;
+  int len ;
+  int *pos ;                    /* [ms->max + 1] */
+  bool *isF ;                   /* [ms->max + 1] */
+  int ownsMs ;                  /* mgRepRefCreate read ms itself: mgRepRefDestroy destroys it and its hasher */
+} MgRepRef ;
+/* modrep.c:27-63: the .mod through mgFzOpen (gzip or plain), the FIRST record of seqFile with N / n read as A (modrep.c:559) */
+MgRepRef *mgRepRefCreate (const char *seqFile, const char *modFile, FILE *err) ;
+/* modrep.c:43-54 on a sequence in memory (bases 0..3); ms stays the caller's */
+MgRepRef *mgRepRefFromArrays (Modset *ms, const char *bases, int64_t len, FILE *err) ;
+void mgRepRefDestroy (MgRepRef *ref) ;
+
+/* analyzeSequences3 (modrep.c:170-268) for a file that comes in batches.  ms is the SECOND set (the .mod given to -s3); the reads are
+ * scanned with the REFERENCE set's hasher both times, as the program does, so the two sets must have one k.
+ *   per read (modrep.c:193-209): its first 100 modimizers found in ref->ms vote, seqF for the reference's strand and seqR against; the
+ *     read is bad when n < 100 || (seqF > 10 && seqR > 10) and prints "BADREAD %5d len %5d n %d F %4d R %4d";
+ *   a good read with seqF < seqR is reverse-complemented (modrep.c:215-221), scanned again and its modimizers looked up in ms
+ *     (modrep.c:223-233): hits (k = index, x = position in the ORIENTED read), ++n[k], ++nPre[k] for the second and later hit on k of a read;
+ *   after the file (modrep.c:236-258): over i = 0 .. max - 1 (entry 0 counted, entry max not: the program's arrays end there) nPre[i] != 0
+ *     counts as dup, adds to tDup and sets n[i] = 0, anything else counts as good; minMax folds max_r = the largest n[k] over a good
+ *     read's hits with `if (!minMax || max_r < minMax) minMax = max_r`, so a read with max_r == 0 starts the fold again.
+ * The library's arrays have max + 1 entries and tally entry max like any other (the program writes past its arrays there).
+ * The hits' k, x and read stay on the device from a batch to the end: n[] and nPre[] are final only then. */
+typedef struct MgRepRun MgRepRun ;
+typedef struct {
+  int nRead, nBad, nGood ;                   /* modrep.c:236 */
+  int *n, *seqF, *seqR ;                     /* [nRead]: modrep.c:196-202 */
+  bool *bad, *isF ;                          /* [nRead]: modrep.c:204; isF = good and not reverse-complemented (modrep.c:221) */
+  U32 max ;                                  /* ms->max */
+  int *modN, *modNPre ;                      /* [max + 1]: mods[].n (zeroed where nPre, modrep.c:242) and mods[].nPre */
+  int *goodI, *goodLen ;                     /* [nGood]: Read.i (the read's ordinal from 0), Read.len */
+  U64 *hitStart ;                            /* [nGood + 1]: good read g's hits are hitK / hitX [hitStart[g] .. hitStart[g + 1]) */
+  int *hitK, *hitX ;
+  int nMod, nDup, tDup, minMax ;             /* modrep.c:237-246,250-258 */
+} MgRepResult ;
+void mgRepResultFree (MgRepResult *res) ;    /* the arrays (malloc); res itself is the caller's */
+MgRepRun *mgRepRunBegin (MgRepRef *ref, Modset *ms) ;                          /* modrep.c:186-191; 0 = error */
+/* modrep.c:192-234 for a batch (bases 0..3, offsets[nReads + 1]): its BADREAD lines to out in read order; read numbers go on from the call before.  0 / -1 */
+int  mgRepRunAdd (MgRepRun *run, const char *bases, const int64_t *offsets, int nReads, FILE *out) ;
+/* modrep.c:236-258: the two lines to err (0: not printed), the results into res (0: not wanted); frees the run, also on error.  0 / -1 */
+int  mgRepRunFinish (MgRepRun *run, FILE *err, MgRepResult *res) ;
+/* modrep.c:170-268 from files: the .mod through mgFzOpen, the reads in batches through mgSeqOpen / mgSeqNextBatch (N read as A).  0 / -1 with
+ * the program's message ("failed to open mod file %s", "failed to read modset from file %s", "can't open sequence file %s") */
+int  mgRepAnalyze3File (MgRepRef *ref, const char *seqFile, const char *modFile, FILE *out, FILE *err, MgRepResult *res) ;
+int  mgRepPath (void) ;                      /* test hook: the calling thread's last run: 0 = finished through the device kernels, -1 = it failed or none ran */
+
 /* The file front end (seqio.c:30-346 for FASTA / FASTQ text, plain, gzip or blocked gzip, with the callers'
  * dna2indexConv + N->0 conversion): records are cut out of the text and converted by a pool of
  * threads, a batch at a time.  bases hold 0..3 (FASTQ keeps other bytes as (char)-2, as the

@@ -54,6 +54,20 @@ class MgReadset(C.Structure):         # include/modgpu.h (modasm.c:30-57,79-86)
                 ("totHit", C.c_uint64), ("capHit", C.c_uint64), ("invStart", U64P), ("invSpace", U32P)]
 
 
+class MgRepRef(C.Structure):          # include/modgpu.h (modrep.c:20-25)
+    _fields_ = [("ms", C.POINTER(Modset)), ("len", C.c_int), ("pos", C.POINTER(C.c_int)), ("isF", C.POINTER(C.c_bool)), ("ownsMs", C.c_int)]
+
+
+class MgRepResult(C.Structure):       # include/modgpu.h (modrep.c:170-268)
+    _fields_ = [("nRead", C.c_int), ("nBad", C.c_int), ("nGood", C.c_int),
+                ("n", C.POINTER(C.c_int)), ("seqF", C.POINTER(C.c_int)), ("seqR", C.POINTER(C.c_int)),
+                ("bad", C.POINTER(C.c_bool)), ("isF", C.POINTER(C.c_bool)), ("max", C.c_uint32),
+                ("modN", C.POINTER(C.c_int)), ("modNPre", C.POINTER(C.c_int)),
+                ("goodI", C.POINTER(C.c_int)), ("goodLen", C.POINTER(C.c_int)), ("hitStart", U64P),
+                ("hitK", C.POINTER(C.c_int)), ("hitX", C.POINTER(C.c_int)),
+                ("nMod", C.c_int), ("nDup", C.c_int), ("tDup", C.c_int), ("minMax", C.c_int)]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -77,6 +91,7 @@ EXPORTS = [
     "mgCommInitAll", "mgCommGetUniqueId", "mgCommInitRank", "mgCommRank", "mgCommSize", "mgCommDestroy", "mgHistogramAllReduce", "mgDepthAllReduce", "mgModsetMergeRankOrder",
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgReadsetCleanMods", "mgReadsetCleanModsPath", "mgReadsetProperties", "mgReadsetPropertiesPath",
+    "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgIterScanHost", "mgIterHostBelow", "mgReloadKnobs", "mgFormatF2", "mgModsetMergeArrays", "mgModsetMergeDeviceArrays", "mgModsetClear", "mgModsetDeviceSlots", "mgSetVerbose", "mgProfileEnable", "mgProfileOnly", "mgProfileReset", "mgProfileKernels", "mgProfileGet",
@@ -225,6 +240,10 @@ def lib():
     sig("mgReadsetRead", i32, RS, vp, vp, i32); sig("mgReadsetFileRead", i32, RS, C.c_char_p)
     sig("mgReadsetStats", None, RS, vp); sig("mgReadsetWrite", None, RS, C.c_char_p); sig("mgReadsetLoad", RS, C.c_char_p)
     sig("mgReadsetCleanMods", i32, RS, vp); sig("mgReadsetCleanModsPath", i32); sig("mgReadsetProperties", i32, RS, vp); sig("mgReadsetPropertiesPath", i32)
+    RR, RES = C.POINTER(MgRepRef), C.POINTER(MgRepResult)
+    sig("mgRepRefCreate", RR, C.c_char_p, C.c_char_p, vp); sig("mgRepRefFromArrays", RR, MS, vp, i64, vp); sig("mgRepRefDestroy", None, RR)
+    sig("mgRepRunBegin", vp, RR, MS); sig("mgRepRunAdd", i32, vp, vp, vp, i32, vp); sig("mgRepRunFinish", i32, vp, vp, RES); sig("mgRepResultFree", None, RES)
+    sig("mgRepAnalyze3File", i32, RR, C.c_char_p, C.c_char_p, vp, vp, RES); sig("mgRepPath", i32)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -490,3 +509,78 @@ def readset_properties(rs, path):
     if rc:
         raise ModgpuError("mgReadsetProperties failed: " + lib().mgLastError().decode())
     return lib().mgReadsetPropertiesPath()
+
+
+def rep_ref_create(seq_path, mod_path, err_path=None):
+    """mgRepRefCreate: modrep -R (modrep.c:27-63): the MgRepRef* of the one sequence of `seq_path` against the set `mod_path`; the "found"
+    line into the file `err_path` if given.  Raises with the program's message otherwise.  Destroy with lib().mgRepRefDestroy."""
+    if err_path is None:
+        ref = lib().mgRepRefCreate(seq_path.encode(), mod_path.encode(), None)
+    else:
+        with CFile(err_path, "w") as f:
+            ref = lib().mgRepRefCreate(seq_path.encode(), mod_path.encode(), f)
+    if not ref:
+        raise ModgpuError(lib().mgLastError().decode())
+    return ref
+
+
+def rep_ref_from_arrays(ms, bases, err_path=None):
+    """mgRepRefFromArrays: modrep.c:43-54 on a sequence in memory (bases 0..3); ms stays the caller's."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    if err_path is None:
+        ref = lib().mgRepRefFromArrays(ms, bases.ctypes.data, len(bases), None)
+    else:
+        with CFile(err_path, "w") as f:
+            ref = lib().mgRepRefFromArrays(ms, bases.ctypes.data, len(bases), f)
+    if not ref:
+        raise ModgpuError(lib().mgLastError().decode())
+    return ref
+
+
+def _rep_result(res):
+    """the arrays of an MgRepResult as numpy copies in a dict; frees the C arrays"""
+    def arr(ptr, count, dtype):
+        return np.ctypeslib.as_array(ptr, (max(count, 1),))[:count].astype(dtype, copy=True)
+    n_hit = int(res.hitStart[res.nGood])
+    out = dict(nRead=res.nRead, nBad=res.nBad, nGood=res.nGood, max=res.max, nMod=res.nMod, nDup=res.nDup, tDup=res.tDup, minMax=res.minMax,
+               n=arr(res.n, res.nRead, np.int32), seqF=arr(res.seqF, res.nRead, np.int32), seqR=arr(res.seqR, res.nRead, np.int32),
+               bad=arr(res.bad, res.nRead, np.uint8), isF=arr(res.isF, res.nRead, np.uint8),
+               modN=arr(res.modN, res.max + 1, np.int32), modNPre=arr(res.modNPre, res.max + 1, np.int32),
+               goodI=arr(res.goodI, res.nGood, np.int32), goodLen=arr(res.goodLen, res.nGood, np.int32),
+               hitStart=arr(res.hitStart, res.nGood + 1, np.int64), hitK=arr(res.hitK, n_hit, np.int32), hitX=arr(res.hitX, n_hit, np.int32))
+    lib().mgRepResultFree(C.byref(res))
+    return out
+
+
+def rep_analyze3_file(ref, seq_path, mod_path, out_path, err_path):
+    """mgRepAnalyze3File: modrep -s3 (modrep.c:170-268): the BADREAD lines into the file `out_path`, the two summary lines into `err_path`.
+    Returns the MgRepResult as a dict of numpy arrays and ints."""
+    res = MgRepResult()
+    with CFile(out_path, "w") as fo, CFile(err_path, "w") as fe:
+        rc = lib().mgRepAnalyze3File(ref, seq_path.encode(), mod_path.encode(), fo, fe, C.byref(res))
+    if rc:
+        raise ModgpuError("mgRepAnalyze3File failed: " + lib().mgLastError().decode())
+    return _rep_result(res)
+
+
+def rep_run(ref, ms, batches, out_path, err_path):
+    """mgRepRunBegin / mgRepRunAdd per (bases, offsets) of `batches` / mgRepRunFinish: modrep -s3 on reads in memory, lines as above.
+    Returns the MgRepResult as a dict of numpy arrays and ints."""
+    L = lib()
+    run = L.mgRepRunBegin(ref, ms)
+    if not run:
+        raise ModgpuError("mgRepRunBegin failed: " + L.mgLastError().decode())
+    res = MgRepResult()
+    with CFile(out_path, "w") as fo, CFile(err_path, "w") as fe:
+        rc = 0
+        for bases, offsets in batches:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            rc = L.mgRepRunAdd(run, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, fo)
+            if rc:
+                break
+        msg = L.mgLastError().decode() if rc else ""
+        rf = L.mgRepRunFinish(run, None if rc else fe, None if rc else C.byref(res))
+    if rc or rf:
+        raise ModgpuError("modrep -s3 failed: " + (msg or L.mgLastError().decode()))
+    return _rep_result(res)
