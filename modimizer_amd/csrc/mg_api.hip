@@ -1090,14 +1090,17 @@ extern "C" MgStatus mgAddReadsDevice (Modset *ms, const U32 *dPacked, U64 totalB
   return mgAddBatch (ms, d, b.kmer, n, 0, 1, true, st, &b.counted);
 }
 
-/* mode 0: lookup only (modmap.c:202); mode 1: insert without depth (modmap.c:109) */
-static MgStatus mgSeedReads (Modset *ms, int mode, const U32 *dPacked, U64 totalBases,
+/* mode 0: lookup only (modmap.c:202); mode 1: insert without depth (modmap.c:109).  scanWith (0: the set's own hasher) scans the batch: it has the set's k, the width of the table's keys */
+static MgStatus mgSeedReads (Modset *ms, const Seqhash *scanWith, int mode, const U32 *dPacked, U64 totalBases,
                              const U64 *dReadOffsets, U32 nReads,
                              U32 *dSeedIndex, U32 *dSeedPosF, U32 *dSeedRead, U64 capacity,
                              U64 *nSeeds, hipStream_t st)
 {
   MgDev *d; MgStatus s = mgDevGet (ms, &d, st); if (s) return s;
   if (nSeeds) *nSeeds = 0;
+  if (!scanWith) scanWith = ms->hasher;
+  if ((s = mgCheckHasher (scanWith))) return s;
+  if (scanWith->k != ms->hasher->k) { mgSetError ("a batch scanned with k %d cannot be looked up in a set of k %d", scanWith->k, ms->hasher->k); return MG_ERR_ARG; }
   if (!totalBases || !nReads) return MG_OK;
   MgScanBufs b; U64 n = 0;
   d->t.loadPct = MG_LOOKUP_LOAD_PCT;                                   /* lookups follow (or are this call): see MgTable.loadPct */
@@ -1105,7 +1108,7 @@ static MgStatus mgSeedReads (Modset *ms, int mode, const U32 *dPacked, U64 total
   const int timing = mgKnobs ()->seedTiming == 1;   /* dev */
   struct timespec q0, q1, q2; if (timing) clock_gettime (CLOCK_MONOTONIC, &q0);
   /* lookups read the k-mers from the scan's segments (no dense copy of them); pos / read are compacted as before */
-  if ((s = mgScanIntoArena (d, ms->hasher, dPacked, totalBases, dReadOffsets, nReads, true, mode ? 4 : 0, &b, &n, st,
+  if ((s = mgScanIntoArena (d, scanWith, dPacked, totalBases, dReadOffsets, nReads, true, mode ? 4 : 0, &b, &n, st,
                             dSeedPosF, dSeedRead, capacity, mode == 0))) return s;
   if (timing) clock_gettime (CLOCK_MONOTONIC, &q1);
   if (nSeeds) *nSeeds = n;
@@ -1133,13 +1136,45 @@ extern "C" MgStatus mgQueryReadsDevice (Modset *ms, const U32 *dPacked, U64 tota
                                         const U64 *dReadOffsets, U32 nReads,
                                         U32 *dSeedIndex, U32 *dSeedPosF, U32 *dSeedRead, U64 capacity,
                                         U64 *nSeeds, void *stream)
-{ return mgSeedReads (ms, 0, dPacked, totalBases, dReadOffsets, nReads, dSeedIndex, dSeedPosF, dSeedRead, capacity, nSeeds, (hipStream_t) stream); }
+{ return mgSeedReads (ms, 0, 0, dPacked, totalBases, dReadOffsets, nReads, dSeedIndex, dSeedPosF, dSeedRead, capacity, nSeeds, (hipStream_t) stream); }
 
 extern "C" MgStatus mgInsertReadsDevice (Modset *ms, const U32 *dPacked, U64 totalBases,
                                          const U64 *dReadOffsets, U32 nReads,
                                          U32 *dSeedIndex, U32 *dSeedPosF, U32 *dSeedRead, U64 capacity,
                                          U64 *nSeeds, void *stream)
-{ return mgSeedReads (ms, 1, dPacked, totalBases, dReadOffsets, nReads, dSeedIndex, dSeedPosF, dSeedRead, capacity, nSeeds, (hipStream_t) stream); }
+{ return mgSeedReads (ms, 0, 1, dPacked, totalBases, dReadOffsets, nReads, dSeedIndex, dSeedPosF, dSeedRead, capacity, nSeeds, (hipStream_t) stream); }
+
+/* the seed list of a batch in arrays that this call sizes: the contract is at the declaration (mg_internal.h) */
+extern "C" void mgSeedBufsFree (MgSeedBufs *bufs)
+{
+  (void) hipFree (bufs->ix); (void) hipFree (bufs->posF); (void) hipFree (bufs->rid);
+  bufs->ix = bufs->posF = bufs->rid = 0; bufs->cap = 0;
+}
+static MgStatus mgSeedBufsReserve (MgSeedBufs *bufs, U64 need)
+{
+  if (bufs->cap >= need) return MG_OK;
+  mgSeedBufsFree (bufs);
+  const U64 room = need + need * (U64) bufs->sparePct / 100 + 1;
+  U32 **arr[3] = { &bufs->ix, &bufs->posF, &bufs->rid };
+  for (int j = 0 ; j < 3 ; ++j)
+    { const hipError_t e = hipMalloc ((void **) arr[j], room * sizeof (U32));
+      if (e != hipSuccess) { *arr[j] = 0; mgSeedBufsFree (bufs); return mgHipFail (e, "a batch's seed arrays"); }
+    }
+  bufs->cap = room; return MG_OK;
+}
+extern "C" MgStatus mgSeedsOfBatch (Modset *ms, const Seqhash *scanWith, int insert, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
+                                    U64 guess, MgSeedBufs *bufs, U64 *nSeeds, void *stream)
+{
+  const bool empty = !totalBases || !nReads;                 /* (the inner call still runs: it validates, and brings the set's device table up) */
+  U64 offer = empty ? 0 : (guess < totalBases + 1 ? guess : totalBases + 1);
+  *nSeeds = 0;
+  for (int attempt = 0 ; ; ++attempt)
+    { MgStatus s = mgSeedBufsReserve (bufs, offer); if (s) return s;
+      s = mgSeedReads (ms, scanWith, insert ? 1 : 0, dPacked, totalBases, dReadOffsets, nReads, bufs->ix, bufs->posF, bufs->rid, offer, nSeeds, (hipStream_t) stream);
+      if (s != MG_ERR_CAPACITY || attempt || *nSeeds <= offer) return s;
+      offer = *nSeeds;
+    }
+}
 
 /* The lookup loop of queryProcess (modmap.c:197-206) for batches that follow one another, in two halves: Async starts the batch's SCAN
  * on a stream of the library's own, into the other of two scratch arenas, and returns; Wait runs its LOOKUPS on the caller's stream and

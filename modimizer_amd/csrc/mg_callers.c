@@ -200,30 +200,21 @@ int mgReferenceAddDevice (MgReference *ref, const U32 *dPacked, U64 totalBases, 
   refRegister (ref, names, offsets, nSeq);
   free (offsets);
   U64 n = 0;
-  void *dIx = 0, *dPos = 0, *dRid = 0;
-  U64 guess = totalBases / (U64) ms->hasher->w; guess += guess / 2 + 65536; if (guess > totalBases) guess = totalBases;
-  if (guess < 1) guess = 1;
+  MgSeedBufs seeds = { 0, 0, 0, 0, 0 };
   const int timing = mgKnobs ()->seedTiming == 1;          /* dev */
   struct timespec a0, a1, a2, a3; clock_gettime (CLOCK_MONOTONIC, &a0);
-  for (int attempt = 0 ; attempt < 2 ; ++attempt)
-    { if (mgDeviceAlloc (&dIx, guess * 4) || mgDeviceAlloc (&dPos, guess * 4) || mgDeviceAlloc (&dRid, guess * 4)) fatal ("device alloc");
-      MgStatus s = isAdd ? mgInsertReadsDevice (ms, dPacked, totalBases, dReadOffsets, (U32) nSeq, (U32 *) dIx, (U32 *) dPos, (U32 *) dRid, guess, &n, 0)
-                         : mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, (U32) nSeq, (U32 *) dIx, (U32 *) dPos, (U32 *) dRid, guess, &n, 0);
-      if (s == MG_OK) break;
-      if (s == MG_ERR_CAPACITY && n > guess && attempt == 0)
-        { mgDeviceFree (dIx); mgDeviceFree (dPos); mgDeviceFree (dRid); guess = n; continue; }
-      if (s == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: %s\n", mgLastError ()); exit (-1); }   /* modset.c:58 */
-      fatal ("reference scan");
-    }
+  const MgStatus s = mgSeedsOfBatch (ms, 0, isAdd, dPacked, totalBases, dReadOffsets, (U32) nSeq, mgSeedGuess (ms->hasher->w, totalBases), &seeds, &n, 0);
+  if (s == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: %s\n", mgLastError ()); exit (-1); }   /* modset.c:58 */
+  if (s) fatal ("reference scan");
   clock_gettime (CLOCK_MONOTONIC, &a1);
   /* modmap.c:110-117: the occurrences stay on the device (mg_refpack.hip), appended in order behind those of earlier batches */
   U32 added = 0;
-  MgStatus as = mgRefBuildAppend (ref, (const U32 *) dIx, (const U32 *) dPos, (const U32 *) dRid, n, (U32) ref->nSeq, &added);
+  MgStatus as = mgRefBuildAppend (ref, seeds.ix, seeds.posF, seeds.rid, n, (U32) ref->nSeq, &added);
   if (as == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: reference size overflow\n"); exit (-1); }      /* modmap.c:111 */
   if (as) fatal ("reference append");
   ref->max += added;
   clock_gettime (CLOCK_MONOTONIC, &a2);
-  mgDeviceFree (dIx); mgDeviceFree (dPos); mgDeviceFree (dRid);
+  mgSeedBufsFree (&seeds);
   clock_gettime (CLOCK_MONOTONIC, &a3);
   if (timing) fprintf (stderr, "mgReferenceAddDevice: %.3f Gbp, %d sequences: allocations + scan + insert %.1f ms, append %.1f ms, frees %.1f ms\n", totalBases / 1e9, nSeq,
                        (a1.tv_sec - a0.tv_sec) * 1e3 + (a1.tv_nsec - a0.tv_nsec) * 1e-6, (a2.tv_sec - a1.tv_sec) * 1e3 + (a2.tv_nsec - a1.tv_nsec) * 1e-6, (a3.tv_sec - a2.tv_sec) * 1e3 + (a3.tv_nsec - a2.tv_nsec) * 1e-6);
@@ -507,20 +498,12 @@ static int queryProcessHostChain (MgReference *ref, MgDevBatch *b, const int64_t
                                   const char **names, FILE *out)
 {
   Modset *ms = ref->ms;
-  U64 n = 0, guess = b->total / (U64) ms->hasher->w; guess += guess / 2 + 65536; if (guess > b->total) guess = b->total;
-  if (guess < 1) guess = 1;
-  void *dIx = 0, *dPos = 0, *dRid = 0;
-  for (int attempt = 0 ; attempt < 2 ; ++attempt)
-    { if (mgDeviceAlloc (&dIx, guess * 4) || mgDeviceAlloc (&dPos, guess * 4) || mgDeviceAlloc (&dRid, guess * 4)) fatal ("device alloc");
-      MgStatus s = mgQueryReadsDevice (ms, (U32 *) b->dPacked, b->total, (U64 *) b->dOff, b->nReads, (U32 *) dIx, (U32 *) dPos, (U32 *) dRid, guess, &n, 0);
-      if (s == MG_OK) break;
-      if (s == MG_ERR_CAPACITY && attempt == 0)
-        { mgDeviceFree (dIx); mgDeviceFree (dPos); mgDeviceFree (dRid); guess = n; continue; }
-      fatal ("query scan");
-    }
+  U64 n = 0;
+  MgSeedBufs seeds = { 0, 0, 0, 0, 0 };
+  if (mgSeedsOfBatch (ms, 0, 0, (U32 *) b->dPacked, b->total, (U64 *) b->dOff, b->nReads, mgSeedGuess (ms->hasher->w, b->total), &seeds, &n, 0)) fatal ("query scan");
   U32 *six = (U32 *) malloc ((size_t) (n + 1) * 4), *spos = (U32 *) malloc ((size_t) (n + 1) * 4), *srid = (U32 *) malloc ((size_t) (n + 1) * 4);
-  if (n && (mgMemcpyD2H (six, dIx, n * 4, 0) || mgMemcpyD2H (spos, dPos, n * 4, 0) || mgMemcpyD2H (srid, dRid, n * 4, 0))) fatal ("D2H");
-  mgDeviceFree (dIx); mgDeviceFree (dPos); mgDeviceFree (dRid);
+  if (n && (mgMemcpyD2H (six, seeds.ix, n * 4, 0) || mgMemcpyD2H (spos, seeds.posF, n * 4, 0) || mgMemcpyD2H (srid, seeds.rid, n * 4, 0))) fatal ("D2H");
+  mgSeedBufsFree (&seeds);
   for (U64 i = 0 ; i < n ; ++i) spos[i] &= MG_POS_MASK;
 
   U64 at = 0;

@@ -167,19 +167,19 @@ void mgChainCompactKernel (const MgChainQ *__restrict__ q, const MgChainM *__res
   for (U32 j = 0 ; j < n ; ++j) out[at + j] = mRec[(U64) r * maxM + j];
 }
 
-/* the device arrays of a query batch.  A call allocates and frees them; a caller with many batches in a row (mgQueryFile: one per
+/* the device arrays of a query batch (the seed list among them: mgSeedsOfBatch sizes it).  A call allocates and frees them; a caller with many batches in a row (mgQueryFile: one per
    window of the file) keeps them between its calls (mgChainScratchKeep): ten allocations and frees a batch are milliseconds.  What
    such a caller leaves stays allocated, like the text parser's windows, until mgReleaseBuffers () or a call that does not keep.
    The scratch belongs to the calling HOST THREAD and to the device it was allocated on (like the iterator's scratch, mg_api.hip): a
    thread that has moved to another GPU (mgSetDevice) drops it and starts again there, two threads driving two GPUs share nothing
    and do not wait for each other, and a thread that ends gives its blocks back. */
-enum { CS_IX, CS_POS, CS_RID, CS_START, CS_Q, CS_M, CS_OV, CS_MC, CS_REC, CS_N };
+enum { CS_START, CS_Q, CS_M, CS_OV, CS_MC, CS_REC, CS_N };
 static bool gChainAlive = true;                            /* false once the library is being unloaded: thread-local destructors that run after that leave HIP alone */
 __attribute__ ((destructor)) static void mgChainDown (void) { gChainAlive = false; }
 struct MgChainScratch
-{ void *p[CS_N] = { 0 }; size_t cap[CS_N] = { 0 }; int keep = 0; int dev = -1;
+{ void *p[CS_N] = { 0 }; size_t cap[CS_N] = { 0 }; MgSeedBufs seeds = { 0, 0, 0, 0, 0 }; int keep = 0; int dev = -1;
   void drop (int i) { if (p[i]) (void) hipFree (p[i]); p[i] = 0; cap[i] = 0; }
-  void dropAll () { for (int i = 0 ; i < CS_N ; ++i) drop (i); dev = -1; }
+  void dropAll () { for (int i = 0 ; i < CS_N ; ++i) drop (i); mgSeedBufsFree (&seeds); dev = -1; }
   ~MgChainScratch () { if (gChainAlive) dropAll (); }
 };
 static thread_local MgChainScratch gCs;
@@ -215,22 +215,14 @@ extern "C" int mgChainQueryDevice (const MgReference *ref, const U32 *dPacked, U
   Modset *ms = ref->ms;
   MgRefDev d;
   if (mgRefDevGet (ref, &d)) return -1;
-  U64 guess = totalBases / (U64) ms->hasher->w; guess += guess / 2 + 65536; if (guess > totalBases + 1) guess = totalBases + 1;
   if (csPrepare ()) { mgSetError ("query chaining: no current device"); return -1; }
-  U32 *dIx = 0, *dPos = 0, *dRid = 0; U64 *dStart = 0; MgChainQ *dQ = 0; MgChainM *dM = 0, *dMc = 0; U32 *dOv = 0;
+  U64 *dStart = 0; MgChainQ *dQ = 0; MgChainM *dM = 0, *dMc = 0; U32 *dOv = 0;
   U64 n = 0;
   int rc = -1;
   do {
-    for (int attempt = 0 ; attempt < 2 ; ++attempt)
-      { dIx = (U32 *) csGet (CS_IX, guess * 4); dPos = (U32 *) csGet (CS_POS, guess * 4); dRid = (U32 *) csGet (CS_RID, guess * 4);
-        if (!dIx || !dPos || !dRid) { dIx = 0; break; }
-        MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, dIx, dPos, dRid, guess, &n, 0);
-        if (s == MG_OK) break;
-        dIx = 0;
-        if (s == MG_ERR_CAPACITY && attempt == 0) { guess = n; continue; }
-        break;
-      }
-    if (!dIx) break;
+    gCs.seeds.sparePct = gCs.keep ? 25 : 0;                /* (as csGet: a keeper's arrays take the next, somewhat larger batch as they are) */
+    if (mgSeedsOfBatch (ms, 0, 0, dPacked, totalBases, dReadOffsets, nReads, mgSeedGuess (ms->hasher->w, totalBases), &gCs.seeds, &n, 0)) break;
+    const U32 *dIx = gCs.seeds.ix, *dPos = gCs.seeds.posF, *dRid = gCs.seeds.rid;
     dStart = (U64 *) csGet (CS_START, ((size_t) nReads + 2) * 8); dQ = (MgChainQ *) csGet (CS_Q, (size_t) nReads * sizeof (MgChainQ));
     dM = (MgChainM *) csGet (CS_M, (size_t) nReads * maxM * sizeof (MgChainM)); dOv = (U32 *) csGet (CS_OV, 4);
     uint4 *dRec = (uint4 *) csGet (CS_REC, ((size_t) n + 1) * sizeof (uint4));
@@ -379,19 +371,15 @@ extern "C" int mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBa
   const bool lapOn = mgKnobs ()->seedTiming == 1;          /* dev */
   struct timespec lq0; clock_gettime (CLOCK_MONOTONIC, &lq0);
 #define RS_LAP(what) do { if (lapOn) { (void) hipDeviceSynchronize (); struct timespec q_; clock_gettime (CLOCK_MONOTONIC, &q_); fprintf (stderr, "mgReadsetSeedsDevice: %s at %.2f ms\n", what, (q_.tv_sec - lq0.tv_sec) * 1e3 + (q_.tv_nsec - lq0.tv_nsec) * 1e-6); } } while (0)
-  U64 guess = totalBases / (U64) ms->hasher->w; guess += guess / 2 + 65536; if (guess > totalBases + 1) guess = totalBases + 1;
   const char *const sorry = "readset seeds on the device failed";
   MgDevScratch scratch ("readset seeds on the device");
-  U32 *dIx = 0, *dPos = 0, *dRid = 0, *dMiss = 0, *dHit = 0, *dFirst = 0, *dTileCnt = 0, *dTileLast = 0; unsigned short *dDx = 0; U64 *dStart = 0, *dHitStart = 0;
+  U32 *dMiss = 0, *dHit = 0, *dFirst = 0, *dTileCnt = 0, *dTileLast = 0; unsigned short *dDx = 0; U64 *dStart = 0, *dHitStart = 0;
   U64 n = 0;
-  for (int attempt = 0 ; ; ++attempt)
-    { MgDevScratch seeds (scratch.what);                    /* of this attempt: a guess that was too small is freed before the next one is made */
-      if (seeds.get (&dIx, guess) || seeds.get (&dPos, guess) || seeds.get (&dRid, guess)) return -1;
-      const MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, dIx, dPos, dRid, guess, &n, 0);
-      if (s == MG_OK) { scratch.adopt (seeds.take (dIx)); scratch.adopt (seeds.take (dPos)); scratch.adopt (seeds.take (dRid)); break; }
-      if (s != MG_ERR_CAPACITY || attempt) return mgFailedWith (sorry);
-      guess = n;
-    }
+  MgSeedBufs seeds = { 0, 0, 0, 0, 0 };
+  const MgStatus ss = mgSeedsOfBatch (ms, 0, 0, dPacked, totalBases, dReadOffsets, nReads, mgSeedGuess (ms->hasher->w, totalBases), &seeds, &n, 0);
+  const U32 *dIx = seeds.ix, *dPos = seeds.posF, *dRid = seeds.rid;
+  scratch.adopt (seeds.ix); scratch.adopt (seeds.posF); scratch.adopt (seeds.rid);      /* the scratch's from here on */
+  if (ss) return mgFailedWith (sorry);
   RS_LAP ("seeds");
   if (n >= ((U64) 1 << 32) - 1) { mgSetError ("too many seeds in one batch"); return -1; }
   const U32 nTiles = (U32) ((n + MG_RS_TILE - 1) / MG_RS_TILE);

@@ -50,6 +50,25 @@ MG_HIDDEN int mgSeqForEachBatchFrom (const char *filename, size_t startOff, U64 
 MG_HIDDEN void mgBatchUpload (MgDevBatch *b, const char *bases, const int64_t *offsets, int nReads);
 MG_HIDDEN void mgBatchFree (MgDevBatch *b);
 MG_HIDDEN FILE *mgTagOpen (const char *root, const char *tag, const char *mode);
+/* The seed list of a device batch (mg_api.hip): scan + lookups (insert: + inserts, modmap.c:109) with positions, in (read, pos) order, misses
+   included.  The ONE place that guesses a capacity, makes the three arrays, and goes round again when the guess was short.
+     arrays   device arrays of cap entries each (hipMalloc), grow-only: while cap covers what an attempt needs nothing is allocated, else all three
+              are freed and made again with room for need + need * sparePct / 100 + 1 entries.  A caller that wants them for one call starts from a
+              zeroed struct and ends with mgSeedBufsFree (or adopts the three pointers into its own scratch); one that keeps them between calls
+              keeps the struct.  A failed allocation leaves "HIP error N (..) in <what>" and the struct zeroed.
+     retry    the first attempt offers min (guess, totalBases + 1) entries.  If it ends in MG_ERR_CAPACITY with a count above what was offered, the
+              arrays grow to exactly that count and the call runs once more: one retry, for lookups and inserts alike (the count is known before
+              anything is inserted, so nothing is inserted twice).  Any other status, and a second MG_ERR_CAPACITY, comes back as it is with
+              mgLastError () as the inner call left it -- a set that is full among them, whose count is not above the capacity; *nSeeds is set then, too.
+     scanWith the hasher the batch is scanned with, 0: ms->hasher.  It has the set's k, or the call is MG_ERR_ARG.
+     empty    totalBases == 0 or nReads == 0: *nSeeds = 0, nothing is allocated.  A set with max == 0: every index is 0, *nSeeds is the scan's count.
+   The callers' kernels read the arrays below *nSeeds only. */
+typedef struct { U32 *ix, *posF, *rid; U64 cap; int sparePct; } MgSeedBufs;
+MG_HIDDEN MgStatus mgSeedsOfBatch (Modset *ms, const Seqhash *scanWith, int insert, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
+                                   U64 guess, MgSeedBufs *bufs, U64 *nSeeds, void *stream);
+MG_HIDDEN void mgSeedBufsFree (MgSeedBufs *bufs);
+static inline U64 mgSeedGuess (int w, U64 totalBases)     /* modimizers are one k-mer in w: half as many again, and room for a short batch's noise */
+{ U64 g = totalBases / (U64) (w > 0 ? w : 1); g += g / 2 + 65536; return g < totalBases + 1 ? g : totalBases + 1; }
 /* queryProcess on the device (mg_chain.hip): per read the tallies of its "Q" line and its "M" blocks */
 typedef struct { U32 nSeeds, missed, copy1, copy2, copyM, nM; } MgChainQ;
 typedef struct { U32 pos0, posN, id0, off0, offN; int n1, n2; U32 span; } MgChainM;

@@ -207,38 +207,18 @@ __global__ void mgRepMinAfterKernel (const U32 *__restrict__ readMax, U32 nGood,
 
 /* ---------------------------------------------------------------------------------------- */
 
-/* the modimizers of a device batch under hasher sh, in (read, pos) order, and their indices in ms (0: absent); every array has n + 1 entries */
-struct MgRepSeeds { U64 *kmer; U32 *posF, *rid, *ix; U64 n; };
-static MgStatus mgRepScanFind (MgDevScratch &scratch, const Seqhash *sh, Modset *ms, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, MgRepSeeds *o, hipStream_t st)
+/* the modimizers of a device batch scanned with scanWith (0: the set's own hasher), in (read, pos) order, and their indices in ms (0: absent):
+   the library's seed list (mgSeedsOfBatch) from modrep's own first guess, its arrays handed to the scratch */
+struct MgRepSeeds : MgSeedBufs { U64 n; };
+static MgStatus mgRepSeedList (MgDevScratch &scratch, Modset *ms, const Seqhash *scanWith, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, MgRepSeeds *o, hipStream_t st)
 {
-  MgStatus s;
-  memset (o, 0, sizeof (*o));
-  if (total && nReads)
-    { U64 cap = total / (U64) (sh->w > 0 ? sh->w : 1) * 2 + 4096;
-      if (cap > total + 16) cap = total + 16;
-      bool done = false;
-      for (int attempt = 0 ; attempt < 3 && !done ; ++attempt)
-        { MgDevScratch tmp ("modrep scan");
-          U64 *k, *cnt; U32 *p, *r; char *work;
-          const size_t wb = mgScanWorkBytes (total, nReads, cap);
-          if (tmp.get (&k, cap + 1) || tmp.get (&p, cap + 1) || tmp.get (&r, cap + 1) || tmp.get (&cnt, MG_COUNT_WORDS) || tmp.get (&work, wb ? wb : 1)) return MG_ERR_HIP;
-          if ((s = seqhashScanBatchDevice (sh, dPacked, total, dOff, nReads, k, p, r, cap, cnt, work, (void *) st))) return s;
-          U64 h[MG_COUNT_WORDS];
-          if (hipMemcpyAsync (h, cnt, sizeof (h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess) return tmp.fail ();
-          if (h[1] || h[0] > cap) { cap = h[3] > h[0] ? h[3] : h[0]; continue; }
-          o->n = h[0]; o->kmer = k; o->posF = p; o->rid = r;
-          scratch.adopt (tmp.take (k)); scratch.adopt (tmp.take (p)); scratch.adopt (tmp.take (r));
-          done = true;
-        }
-      if (!done) { mgSetError ("modrep: the scan's output did not fit after two retries"); return MG_ERR_CAPACITY; }
-    }
-  else if (scratch.get (&o->kmer, 1) || scratch.get (&o->posF, 1) || scratch.get (&o->rid, 1)) return MG_ERR_HIP;
+  const int w = (scanWith ? scanWith : ms->hasher)->w;
+  U64 guess = total / (U64) (w > 0 ? w : 1) * 2 + 4096; if (guess > total + 16) guess = total + 16;
+  *o = MgRepSeeds ();
+  const MgStatus s = mgSeedsOfBatch (ms, scanWith, 0, dPacked, total, dOff, nReads, guess, o, &o->n, (void *) st);
+  scratch.adopt (o->ix); scratch.adopt (o->posF); scratch.adopt (o->rid);
+  if (s) return s;
   if (o->n >= 0xfffffff0ull) { mgSetError ("modrep: %llu modimizers in one batch (at most 2^32 - 17)", (unsigned long long) o->n); return MG_ERR_ARG; }
-  if (scratch.get (&o->ix, o->n + 1)) return MG_ERR_HIP;
-  if (o->n)
-    { if (ms->max) { if ((s = modsetFindBatchDevice (ms, o->kmer, o->n, o->ix, (void *) st))) return s; }
-      else if (hipMemsetAsync (o->ix, 0, o->n * 4, st) != hipSuccess) return scratch.fail ();      /* an empty set finds nothing */
-    }
   return MG_OK;
 }
 
@@ -272,7 +252,7 @@ extern "C" MgRepRef *mgRepRefFromArrays (Modset *ms, const char *bases, int64_t 
   MgDevScratch scratch ("modrep -R on the device");
   U32 *dPacked, *dLast, *dMinNZ, *dStat; U64 *dOff; int *dPos; U8 *dIsF;
   MgRepSeeds a;
-  if (mgRepUpload (scratch, bases, offsets, 1, (U64) len, &dPacked, &dOff, st) || mgRepScanFind (scratch, ms->hasher, ms, dPacked, (U64) len, dOff, 1, &a, st)) return 0;
+  if (mgRepUpload (scratch, bases, offsets, 1, (U64) len, &dPacked, &dOff, st) || mgRepSeedList (scratch, ms, 0, dPacked, (U64) len, dOff, 1, &a, st)) return 0;
   if (scratch.get (&dLast, m) || scratch.get (&dMinNZ, m) || scratch.get (&dStat, 4) || scratch.get (&dPos, m) || scratch.get (&dIsF, m)) return 0;
   const U32 stat0[4] = { 0, 0, 0xffffffffu, 0 };
   if (hipMemsetAsync (dLast, 0, m * 4, st) != hipSuccess || hipMemsetAsync (dMinNZ, 0xff, m * 4, st) != hipSuccess
@@ -377,11 +357,10 @@ static int mgRepRunAddOnDevice (MgRepRun *run, const char *bases, const int64_t 
 {
   hipStream_t st = 0;
   const U64 total = (U64) offsets[nReads];
-  const Seqhash *sh = run->ref->ms->hasher;
   MgDevScratch scratch ("modrep -s3 on the device");
   U32 *dPacked, *flag, *place, *base, *dF, *dR, *dN, *dBad, *dFlip, *good, *goodPlace; U64 *dOff;
   MgRepSeeds a;
-  if (mgRepUpload (scratch, bases, offsets, nReads, total, &dPacked, &dOff, st) || mgRepScanFind (scratch, sh, run->ref->ms, dPacked, total, dOff, nReads, &a, st)) return -1;
+  if (mgRepUpload (scratch, bases, offsets, nReads, total, &dPacked, &dOff, st) || mgRepSeedList (scratch, run->ref->ms, 0, dPacked, total, dOff, nReads, &a, st)) return -1;
   const size_t nr = nReads;
   if (scratch.get (&flag, a.n + 1) || scratch.get (&place, a.n + 1) || scratch.get (&base, nr + 1) || scratch.get (&dF, nr) || scratch.get (&dR, nr) || scratch.get (&dN, nr)
       || scratch.get (&dBad, nr) || scratch.get (&dFlip, nr) || scratch.get (&good, nr + 1) || scratch.get (&goodPlace, nr + 1)) return -1;
@@ -426,7 +405,7 @@ static int mgRepRunAddOnDevice (MgRepRun *run, const char *bases, const int64_t 
   hipLaunchKernelGGL (mgRepOrientKernel, dim3 (mgGrid (nWords)), dim3 (256), 0, st, dPacked, dOff, goodRead, newOff, dFlip, nGood, (U64) newTotal, nWords, dPacked2);
   if (hipGetLastError () != hipSuccess || hipStreamSynchronize (st) != hipSuccess) { scratch.fail (); return -1; }
   MgRepSeeds b;
-  if (mgRepScanFind (scratch, sh, run->ms, dPacked2, newTotal, newOff64, nGood, &b, st)) return -1;
+  if (mgRepSeedList (scratch, run->ms, run->ref->ms->hasher, dPacked2, newTotal, newOff64, nGood, &b, st)) return -1;
   U32 nHitB = 0;
   if (scratch.get (&flag2, b.n + 1) || scratch.get (&place2, b.n + 1)) return -1;
   hipLaunchKernelGGL (mgRepFlagKernel, dim3 (mgGrid (b.n + 1)), dim3 (256), 0, st, b.ix, b.n, flag2);

@@ -215,12 +215,12 @@ __global__ void mgDepthGatherKernel (const U64 *__restrict__ value, U64 m, int k
 struct MgReportBufs {
   U32 *blockSum = 0; U64 *blockOff = 0; U64 *hTotal = 0;
   MgDevBuf<char> text, ids;
-  MgDevBuf<U32> ix, posF, rid;                            /* the seeds: the three grow together */
+  MgSeedBufs seeds = { 0, 0, 0, 0, 0 };                   /* the batch's seed list (mgSeedsOfBatch) */
   MgDevBuf<U32> start, item;
   MgDevBuf<U64> idOff;
   ~MgReportBufs ()
   { (void) hipFree (blockSum); (void) hipFree (blockOff); (void) hipHostFree (hTotal);
-    text.drop (); ids.drop (); ix.drop (); posF.drop (); rid.drop (); start.drop (); item.drop (); idOff.drop ();
+    text.drop (); ids.drop (); mgSeedBufsFree (&seeds); start.drop (); item.drop (); idOff.drop ();
   }
 };
 static inline size_t mgRoomFor (size_t want) { return want + want / 8 + 64; }      /* what a report's buffers grow to */
@@ -259,7 +259,7 @@ static MgStatus mgTextFormat (const L &lines, U64 n, MgReportBufs *b, MgTextOut 
 
 extern "C" void mgRefPaintScratchFree (void *scratch) { delete (MgReportBufs *) scratch; }
 
-/* modutils.c:262-270 for every record of a batch that is on the device: scan + lookups with positions (mgQueryReadsDevice: the
+/* modutils.c:262-270 for every record of a batch that is on the device: scan + lookups with positions (mgSeedsOfBatch: the
    seeds in (read, pos) order, misses included), the headers and seed lines put in one order, formatted, handed to the writer */
 extern "C" int mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
                                       const char *idBytes, const U64 *idOff, MgTextOut *w, void **scratch)
@@ -273,14 +273,7 @@ extern "C" int mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
   const int wdt = ms && ms->hasher && ms->hasher->w > 0 ? ms->hasher->w : 1;
   U64 cap = totalBases / (U64) wdt * 2 + 4096, n = 0;
   if (cap > totalBases + 16) cap = totalBases + 16;
-  for (int attempt = 0 ; ; ++attempt)
-    { if (b->ix.reserve (cap, cap, what) || b->posF.reserve (cap, cap, what) || b->rid.reserve (cap, cap, what)) return -1;
-      const U64 seedCap = std::min (b->ix.cap, std::min (b->posF.cap, b->rid.cap));
-      const MgStatus s = mgQueryReadsDevice (ms, dPacked, totalBases, dReadOffsets, nReads, b->ix.p, b->posF.p, b->rid.p, seedCap, &n, (void *) st);
-      if (s == MG_ERR_CAPACITY && !attempt && n > seedCap) { cap = n; continue; }
-      if (s) return -1;
-      break;
-    }
+  if (mgSeedsOfBatch (ms, 0, 0, dPacked, totalBases, dReadOffsets, nReads, cap, &b->seeds, &n, (void *) st)) return -1;
   if (n + nReads >= ((U64) 1 << 32)) { mgSetError ("mgRefPaint: %llu lines in one batch", (unsigned long long) (n + nReads)); return -1; }
   const U64 *dValue1; const U16 *dDepth1; U32 max;
   if (mgHookDeviceView (ms, &dValue1, &dDepth1, &max)) { mgSetError ("mgRefPaint: the set's device view is not available"); return -1; }
@@ -291,11 +284,11 @@ extern "C" int mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
   if (hipMemcpyAsync (b->ids.p, idBytes, idBytesLen, hipMemcpyHostToDevice, st) != hipSuccess
       || hipMemcpyAsync (b->idOff.p, idOff, (size_t) nReads * 8, hipMemcpyHostToDevice, st) != hipSuccess)
     { mgHipFail (hipGetLastError (), "mgRefPaint: ids to the device"); return -1; }
-  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintStartKernel, dim3 (mgGrid (n + 1)), dim3 (256), 0, st, b->rid.p, n, nReads, b->start.p);
-  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintItemsKernel, dim3 (mgGrid (n + nReads)), dim3 (256), 0, st, b->rid.p, n, nReads, b->start.p, b->item.p);
+  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintStartKernel, dim3 (mgGrid (n + 1)), dim3 (256), 0, st, b->seeds.rid, n, nReads, b->start.p);
+  MG_LAUNCH (MG_K_PAINT_ITEMS, st, mgPaintItemsKernel, dim3 (mgGrid (n + nReads)), dim3 (256), 0, st, b->seeds.rid, n, nReads, b->start.p, b->item.p);
   if (hipGetLastError () != hipSuccess) { mgSetError ("mgRefPaint: kernel launch failed"); return -1; }
   MgPaintLines L;
-  L.item = b->item.p; L.seedIx = b->ix.p; L.seedPosF = b->posF.p; L.depth1 = dDepth1; L.readOff = dReadOffsets; L.ids = b->ids.p; L.idOff = b->idOff.p;
+  L.item = b->item.p; L.seedIx = b->seeds.ix; L.seedPosF = b->seeds.posF; L.depth1 = dDepth1; L.readOff = dReadOffsets; L.ids = b->ids.p; L.idOff = b->idOff.p;
   return mgTextFormat (L, n + nReads, b, w, st) ? -1 : 0;
 }
 

@@ -258,6 +258,56 @@ def test_empty_runs(tmp_path):
     assert res["nGood"] == 2 and res["max"] == 0 and res["nMod"] == 0 and res["hitStart"][-1] == 0 and res["minMax"] == 0
 
 
+# ---- 6b: more modimizers than the first guess ----
+
+@pytest.mark.gpu
+def test_seed_lists_retry_when_the_guess_is_too_small(tmp_path):
+    """mg_modrep.hip asks mgSeedsOfBatch for min (bases / w * 2 + 4096, bases + 16) seeds.  w = 3 is the smallest that can fall short: a
+    run of a (one k-mer, a modimizer at every start, in neither set) holds a seed per base against two per three bases provided for.
+      -R     the reference sequence carries a run of 60 000 a in its middle;
+      vote   two reads of 60 000 a (BADREADs with n 0) among reads that vote, an empty one, one of k - 1 bases, one with too few hits;
+      hits   a good read that ends in a run of 60 000 a: the oriented batch falls short too.
+    Every call goes round again; pos / isF / len, the lines and the result arrays against the restatement.  Then the same reads with
+    a second set of max == 0: no hits, the totals as the restatement gives them."""
+    L = mg.lib()
+    k, w, seed = 21, 3, 17
+    h = tmr.pyoracle.Hasher(k, w, seed)
+    assert len(h.scan(np.zeros(k, np.uint8))[0]) == 1                             # the k-mer of a run of a IS a modimizer: the run is all seeds
+    guess = lambda total: min(total // w * 2 + 4096, total + 16)                  # mg_modrep.hip, mgRepSeedList
+    seeds = lambda seqs: sum(len(h.scan(s)[0]) for s in seqs)
+    g = synth.iid_bases(9000, 7300)
+    poly = np.zeros(60_000, np.uint8)
+    kmer = h.scan(g)[0]
+    assert len(np.unique(kmer)) == len(kmer) and kmer.min() > 0                   # no repeated mod (-R would die), and the run's k-mer (value 0) is not among them
+    ms = mg.modsetCreate(mg.seqhashCreate(k, w, seed), 20)
+    assert mg.add_sequence_batch(ms, *util.concat_reads([g])) == len(kmer)
+    mg.check(L.modsetSyncToHost(ms, 0))
+    rs = tmr.set_of(ms)
+    # -R
+    ref_seq = np.concatenate([g[:4000], poly, g[4000:]])
+    assert guess(len(ref_seq)) < seeds([ref_seq]) <= len(ref_seq)
+    rref = tmr.ref_create(rs, ref_seq)
+    ref = mg.rep_ref_from_arrays(ms, ref_seq, str(tmp_path / "R.err"))
+    r, m = ref.contents, rs.max
+    assert read_text(tmp_path / "R.err") == rref["line"] and r.len == rref["len"]
+    assert np.array_equal(np.ctypeslib.as_array(r.pos, (m + 1,)), rref["pos"]) and np.array_equal(np.ctypeslib.as_array(r.isF, (m + 1,)).astype(np.uint8), rref["isF"])
+    # -s3
+    reads = [g[:600], poly, tmr.rc(g[1000:1700]), g[:0], g[3000:3000 + k - 1], poly, g[2000:2200], np.concatenate([g[5000:5600], poly]), tmr.rc(g[6000:6500])]
+    total = sum(len(s) for s in reads)
+    assert guess(total) < seeds(reads) <= total                                   # the vote's batch
+    e = dict(ref=ref, rs=rs, rref=rref, ms=ms)
+    res = check_run(e, [reads], tmp_path)
+    assert res["bad"].tolist() == [0, 1, 0, 1, 1, 1, 1, 0, 0] and res["n"].tolist()[1] == res["n"].tolist()[5] == 0 and 0 < res["n"][6] < 100
+    good = [tmr.rc(reads[i]) if not res["isF"][i] else reads[i] for i in res["goodI"]]
+    assert guess(sum(len(s) for s in good)) < seeds(good)                         # the oriented batch
+    assert res["isF"].tolist() == [1, 0, 0, 0, 0, 0, 0, 1, 0] and res["hitStart"][-1] > 500
+    print("first guesses %d %d %d, seeds %d %d %d" % (guess(len(ref_seq)), guess(total), guess(sum(len(s) for s in good)), seeds([ref_seq]), seeds(reads), seeds(good)))
+    empty = mg.modsetCreate(mg.seqhashCreate(k, w, seed), 20)
+    res = check_run(e, [reads], tmp_path, ms=empty, rms=tmr.RepSet(k, w, seed, np.zeros(1, np.uint64)))
+    assert res["nGood"] == 4 and res["max"] == 0 and res["nMod"] == 0 and res["hitStart"][-1] == 0 and res["minMax"] == 0
+    L.mgRepRefDestroy(ref); L.modsetDestroy(ms); L.modsetDestroy(empty)
+
+
 # ---- 7: entry max and entry 0 ----
 
 @pytest.mark.gpu

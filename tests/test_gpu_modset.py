@@ -758,6 +758,109 @@ def test_modmap_query_many_blocks_overflow(tmp_path):
     assert sum(l.startswith("M\tstitched") for l in outs[0].splitlines()) > 16
 
 
+# ---- a batch with more seeds than the first guess: the second round of mgSeedsOfBatch (mg_api.hip) behind the reference build and both query paths ----
+
+def _seed_guess(w, total):
+    g = total // w
+    return min(g + g // 2 + 65536, total + 1)                                    # mg_internal.h, mgSeedGuess
+
+
+def _poly_a_records(k):
+    """(g, records): four records of 100 000 a -- with w = 2 a guess of 0.75 seeds per base, and a run of a is a seed at every start -- with
+    ordinary records cut from g (the last one of two pieces, so that a query chains two blocks), an empty one and one of k - 1 bases between them"""
+    g = np.random.default_rng(4300).integers(0, 4, 20_000).astype(np.uint8)
+    poly = np.zeros(100_000, np.uint8)
+    return g, [poly, g[3000:5000], poly, g[:0], _revcomp(g[7000:9500]), poly, g[100:100 + k - 1], poly, np.concatenate([g[15000:16000], g[12000:13000]])]
+
+
+@pytest.mark.gpu
+def test_reference_build_retries_when_the_seed_guess_is_too_small(tmp_path):
+    """mgReferenceAddDevice (the insert path) on a FASTA whose one batch holds more seeds than min (bases / w * 1.5 + 65536, bases + 1): the
+    arrays are made again at the size the scan asked for and the call goes round once more, before anything is inserted.  The
+    reference's arrays, the set and the report against the oracle, as test_modmap_randomized_vs_oracle compares them."""
+    L = mg.lib()
+    k, w, seed = 21, 2, 17
+    oh = po.Hasher(k, w, seed)
+    assert len(oh.scan(np.zeros(k, np.uint8))[0]) == 1                            # the k-mer of a run of a IS a modimizer: the run is all seeds
+    _, seqs = _poly_a_records(k)
+    names = ["s%d_%d" % (i, len(s)) for i, s in enumerate(seqs)]
+    total = sum(len(s) for s in seqs)
+    guess = _seed_guess(w, total)
+    oms = po.Modset(oh, 20); oref = po.Reference(oms)
+    for nm, s in zip(names, seqs):
+        oref.add_sequence(nm, s)
+    oref.finish()
+    oa = oref.arrays()
+    assert guess < len(oa["index"]) <= total                                      # (on the CPU: these inputs do exceed the guess)
+    fa = str(tmp_path / "ref.fa")
+    fasta.write_fasta(fa, names, seqs)
+    sh = mg.seqhashCreate(k, w, seed); ms = mg.modsetCreate(sh, 20)
+    ref = L.mgReferenceCreate(ms, 1 << 26)
+    with mg.CFile(str(tmp_path / "r.txt"), "w") as f:
+        assert L.mgReferenceFastaRead(ref, fa.encode(), True, f) == 0
+    R = C.cast(ref, C.POINTER(mg.MgReference)).contents
+    U, occ = ms.contents.max, R.max
+    print("first guess %d, seeds of the batch %d" % (guess, occ))
+    assert guess < occ <= total                                                   # every seed of an insert is an occurrence: the first attempt was too small
+    assert U == oms.max and occ == len(oa["index"]) and R.nSeq == len(seqs)
+    as_np = lambda p, n: np.ctypeslib.as_array(p, (max(n, 1),))[:n]
+    for key, n in (("index", occ), ("offset", occ), ("id", occ), ("rev", occ), ("depth", U + 1), ("loc", U + 1)):
+        assert np.array_equal(as_np(getattr(R, key), n), oa[key]), key
+    assert np.array_equal(as_np(ms.contents.value, U + 1)[1:], oms.values()[1:])
+    assert np.array_equal(as_np(ms.contents.info, U + 1)[1:], oms.infos()[1:])
+    assert open(str(tmp_path / "r.txt")).read() == ("  %d hashes from %d reference sequences, total length %d\n  %d copy 1, %d copy 2, %d multiple\n"
+                                                    % (occ, len(seqs), total, oa["n1"], oa["n2"], oa["nM"]))
+    assert oa["nM"] >= 1 and oa["n1"] > 1000                                      # the run's k-mer, and the ordinary records' own
+    L.mgReferenceDestroy(ref); L.modsetDestroy(ms)
+    oref.close()
+
+
+@pytest.mark.gpu
+def test_query_retries_when_the_seed_guess_is_too_small(tmp_path):
+    """mgQueryFile on reads with more seeds than the first guess, chained on the device (mgChainQueryDevice) and on the host
+    (queryProcessHostChain), each in a fresh process: the reference holds a sequence of 100 a, so the runs hit.  Both outputs against
+    the oracle's lines and each other; the seeds counted from the Q lines."""
+    import subprocess, sys
+    k, w, seed = 21, 2, 17
+    oh = po.Hasher(k, w, seed)
+    assert len(oh.scan(np.zeros(k, np.uint8))[0]) == 1
+    g, reads = _poly_a_records(k)
+    rnames = ["q%d_%d" % (i, len(r)) for i, r in enumerate(reads)]
+    total = sum(len(r) for r in reads)
+    guess = _seed_guess(w, total)
+    assert guess < sum(len(oh.scan(r)[0]) for r in reads) <= total                # (on the CPU: these inputs do exceed the guess)
+    ref_seqs, ref_names = [np.zeros(100, np.uint8), g], ["a100", "chr"]
+    oms = po.Modset(oh, 20); oref = po.Reference(oms)
+    for nm, s in zip(ref_names, ref_seqs):
+        oref.add_sequence(nm, s)
+    oref.finish()
+    want = "".join(oref.query(nm, r, str(tmp_path / "o.txt"))[0] for nm, r in zip(rnames, reads))
+    oref.close()
+    fa_ref, fa_q = str(tmp_path / "ref.fa"), str(tmp_path / "q.fa")
+    fasta.write_fasta(fa_ref, ref_names, ref_seqs); fasta.write_fasta(fa_q, rnames, reads)
+    outs = []
+    for knob in ("0", "1"):
+        out = str(tmp_path / ("o%s.txt" % knob))
+        code = (
+            "import modimizer_amd as mg\n"
+            "L = mg.lib(); sh = mg.seqhashCreate(%d, %d, %d); ms = mg.modsetCreate(sh, 20)\n"
+            "ref = L.mgReferenceCreate(ms, 1 << 26)\n"
+            "with mg.CFile(%r, 'w') as f:\n"
+            "    assert L.mgReferenceFastaRead(ref, %r, True, f) == 0\n"
+            "    assert L.mgQueryFile(ref, %r, f) == 0\n"
+        ) % (k, w, seed, out, fa_ref.encode(), fa_q.encode())
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=util.ROOT,
+                           env=dict(os.environ, MODGPU_QUERY_HOST_CHAIN=knob))
+        assert r.returncode == 0, r.stderr[-800:]
+        outs.append("".join(open(out).read().splitlines(True)[2:]))              # (behind the two lines of the reference's report)
+    q = [[int(x.split()[0]) for x in l.split("\t")[3].split(",")[:4]] for l in outs[0].splitlines() if l.startswith("Q\t")]
+    seeds = sum(sum(x) for x in q)
+    print("first guess %d, seeds of the batch %d" % (guess, seeds))
+    assert len(q) == len(reads) and guess < seeds <= total                        # the first attempt was too small: both paths went round again
+    assert outs[0] == want and outs[1] == want
+    assert sum(x[3] for x in q) > 390_000 and sum(x[1] for x in q) > 1000 and any(l.startswith("M\t") for l in want.splitlines())
+
+
 @pytest.mark.gpu
 def test_histogram_kept_by_the_build(tmp_path):
     """a set built by one add from empty keeps its depth histogram while it is built (merge kernel): depths 1, 2,
