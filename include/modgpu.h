@@ -168,6 +168,11 @@ MgStatus modsetFindBatchDevice (Modset *ms, const U64 *dKmer, U64 n, U32 *dIndex
  * rebuilt exactly as the reference's sequence of inserts would have left it (modset.c:51-57). */
 MgStatus modsetSyncToHost (Modset *ms, int wantIndex) ;
 int      mgXferThreadCount (void) ;         /* host threads that move whole arrays between the device and the Modset's own arrays (modsetSyncToHost, device rebuilds): 4 (measured best: tools/xfer_probe.py) or fewer if the process may use fewer CPUs; MODGPU_XFER_THREADS overrides, up to 16 */
+/* What that team has done on the current device since the process started (tests, diagnostics; nothing resets it, so a caller takes
+ * differences).  out8 (host): [0] transfers run, [1] pieces moved, [2] threads of the last transfer, [3] bytes per piece in force
+ * (MODGPU_XFER_PIECE_KB), [4] uploads of a mostly untouched array that went by the page map (only the pages ever written are read
+ * and sent), [5] such uploads that took the plain copy instead, [6] runs of pages the last of them sent, [7] bytes it did not send. */
+void     mgXferDiag (U64 out8[8]) ;
 /* Drop the device table (host arrays untouched; pending device depth counts are synced first). */
 MgStatus mgModsetDeviceRelease (Modset *ms) ;
 /* Tell the library the caller changed ms->value/max/depth on the host behind its back. */

@@ -83,7 +83,7 @@ EXPORTS = [
     "mgMemcpyH2D", "mgMemcpyD2H", "mgMemsetD", "mgStreamSynchronize",
     "mgPackedWords", "mgPackHost", "mgPackDevice", "mgUnpackDevice", "mgUploadPack",
     "mgScanWorkBytes", "seqhashScanBatchDevice", "seqhashScanBatch", "seqhashMinimizerBatchDevice", "seqhashMinimizerBatch",
-    "modsetAddBatchDevice", "modsetFindBatchDevice", "modsetSyncToHost", "mgXferThreadCount", "mgCopyD2HBig", "mgCopyH2DBig", "mgModsetDeviceRelease",
+    "modsetAddBatchDevice", "modsetFindBatchDevice", "modsetSyncToHost", "mgXferThreadCount", "mgXferDiag", "mgCopyD2HBig", "mgCopyH2DBig", "mgModsetDeviceRelease",
     "mgModsetHostChanged", "modsetDepthHistogramDevice", "mgTableCheckLayout", "mgTableDiag", "mgAddReadsDevice", "mgQueryReadsDevice", "mgQueryReadsDeviceAsync", "mgQueryReadsDeviceWait",
     "mgAddSequenceBatch", "mgDepthHistogram", "mgSynthGenome", "mgSynthReads",
     "mgInsertReadsDevice", "mgAddSequences", "mgModsetWriteText", "mgReferenceCreate", "mgReferenceDestroy",
@@ -221,7 +221,7 @@ def lib():
     sig("seqhashMinimizerBatch", i64, SH, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp))
     sig("modsetAddBatchDevice", i32, MS, vp, u64, vp, i32, vp)
     sig("modsetFindBatchDevice", i32, MS, vp, u64, vp, vp)
-    sig("modsetSyncToHost", i32, MS, i32); sig("mgXferThreadCount", i32); sig("mgCopyD2HBig", i32, vp, vp, C.c_size_t); sig("mgCopyH2DBig", i32, vp, vp, C.c_size_t); sig("mgModsetDeviceRelease", i32, MS)
+    sig("modsetSyncToHost", i32, MS, i32); sig("mgXferThreadCount", i32); sig("mgXferDiag", None, U64P); sig("mgCopyD2HBig", i32, vp, vp, C.c_size_t); sig("mgCopyH2DBig", i32, vp, vp, C.c_size_t); sig("mgModsetDeviceRelease", i32, MS)
     sig("mgModsetHostChanged", None, MS)
     sig("modsetDepthHistogramDevice", i32, MS, vp, vp); sig("mgTableCheckLayout", i32, MS, U64P); sig("mgTableDiag", i32, MS, U64P)
     sig("mgAddReadsDevice", i32, MS, vp, u64, vp, u32, U64P, vp)

@@ -38,6 +38,8 @@ struct MgXferCtx
   size_t piece = (size_t) 4 << 20;                         /* bytes per piece: 80 us on the link, long enough to hide a copy call (measured, 4 threads with a stream each: 1 MiB 54 GB/s, 4 MiB 49 - 54, 16 MiB 52; MODGPU_XFER_PIECE_KB: dev) */
   MgXferLane lane[MG_XFER_MAXT] = {};
   std::mutex lock;
+  U64 nXfer = 0, nPieces = 0, lastT = 0;                   /* the census (mgXferDiag), under lock: transfers the team ran, pieces its lanes moved, lanes of the last one */
+  U64 nSparse = 0, nSparsePlain = 0, lastRuns = 0, lastSkipped = 0;      /* mgXferH2DSparse: calls by the page map, calls that took the plain copy, and of the last call the runs of pages sent and the bytes not sent */
   std::mutex warmLock; std::thread warm;                   /* the thread that makes the lanes ahead of their first use: joined before another is started, on release, */
   ~MgXferCtx () { if (warm.joinable ()) warm.join (); }    /* and when the library's statics go (a std::thread destroyed while it can still be joined ends the process) */
 };
@@ -128,7 +130,7 @@ static inline void mgXferApply (char *dst, const char *src, size_t bytes, int op
 }
 
 /* thread t of T, device to host: pieces t, t + T, t + 2T, ... */
-static hipError_t mgXferLaneDown (int dev, MgXferLane &l, size_t piece, int t, int T, char *dst, const char *src, size_t bytes, int op)
+static hipError_t mgXferLaneDown (int dev, MgXferLane &l, size_t piece, int t, int T, char *dst, const char *src, size_t bytes, int op, U64 *moved)
 {
   hipError_t e = hipSetDevice (dev);
   if (e != hipSuccess || (e = mgXferLaneMake (l, piece)) != hipSuccess) return e;
@@ -146,13 +148,14 @@ static hipError_t mgXferLaneDown (int dev, MgXferLane &l, size_t piece, int t, i
       if ((e = hipEventSynchronize (l.ev[b])) != hipSuccess) return e;
       const size_t off = p * piece, len = bytes - off < piece ? bytes - off : piece;
       mgXferApply (dst + off, l.pin[b], len, op);
+      ++*moved;
     }
   return hipSuccess;
 }
 
 /* The other direction, for the arrays a device table is (re)built from (ms->value, ms->depth): the team fills the
    page-locked blocks from the pageable source and the copy engine drains them. */
-static hipError_t mgXferLaneUp (int dev, MgXferLane &l, size_t piece, int t, int T, char *dDst, const char *hSrc, size_t bytes)
+static hipError_t mgXferLaneUp (int dev, MgXferLane &l, size_t piece, int t, int T, char *dDst, const char *hSrc, size_t bytes, U64 *moved)
 {
   hipError_t e = hipSetDevice (dev);
   if (e != hipSuccess || (e = mgXferLaneMake (l, piece)) != hipSuccess) return e;
@@ -164,6 +167,7 @@ static hipError_t mgXferLaneUp (int dev, MgXferLane &l, size_t piece, int t, int
       memcpy (l.pin[b], hSrc + off, len);
       if ((e = hipMemcpyAsync (dDst + off, l.pin[b], len, hipMemcpyHostToDevice, l.st)) != hipSuccess) return e;
       if ((e = hipEventRecord (l.ev[b], l.st)) != hipSuccess) return e;
+      ++*moved;
     }
   return hipStreamSynchronize (l.st);
 }
@@ -187,10 +191,11 @@ static MgStatus mgXferRun (void *a, const void *b, size_t bytes, int op, const c
   const size_t piece = X.piece, nPieces = (bytes + piece - 1) / piece;
   if ((size_t) T > nPieces) T = (int) nPieces;
   hipError_t err[MG_XFER_MAXT];
-  for (int t = 0 ; t < T ; ++t) err[t] = hipSuccess;
+  U64 moved[MG_XFER_MAXT];                                     /* pieces by lane: each lane counts its own, they are summed when all are back */
+  for (int t = 0 ; t < T ; ++t) { err[t] = hipSuccess; moved[t] = 0; }
   auto run = [&] (int t)
-    { err[t] = op < 0 ? mgXferLaneUp (dev, X.lane[t], piece, t, T, (char *) a, (const char *) b, bytes)
-                      : mgXferLaneDown (dev, X.lane[t], piece, t, T, (char *) a, (const char *) b, bytes, op); };
+    { err[t] = op < 0 ? mgXferLaneUp (dev, X.lane[t], piece, t, T, (char *) a, (const char *) b, bytes, &moved[t])
+                      : mgXferLaneDown (dev, X.lane[t], piece, t, T, (char *) a, (const char *) b, bytes, op, &moved[t]); };
   std::vector<std::thread> th;
   int started = 1;                                             /* lane 0 is the caller's */
   try { for (int t = 1 ; t < T ; ++t) { th.emplace_back (run, t); ++started; } }
@@ -198,6 +203,8 @@ static MgStatus mgXferRun (void *a, const void *b, size_t bytes, int op, const c
   run (0);
   for (auto &x : th) x.join ();
   for (int t = started ; t < T ; ++t) run (t);
+  ++X.nXfer; X.lastT = (U64) T;
+  for (int t = 0 ; t < T ; ++t) X.nPieces += moved[t];
   for (int t = 0 ; t < T ; ++t) if (err[t] != hipSuccess) return mgHipFail (err[t], what);
   if (mgKnobs ()->uploadTiming == 1) { struct timespec q1; clock_gettime (CLOCK_MONOTONIC, &q1); fprintf (stderr, "%s: %zu bytes, device %d, %d threads, %.2f ms\n", what, bytes, dev, T, (q1.tv_sec - q0.tv_sec) * 1e3 + (q1.tv_nsec - q0.tv_nsec) * 1e-6); }
   return MG_OK;
@@ -207,6 +214,19 @@ MgStatus mgXferD2H (void *hostDst, const void *devSrc, size_t bytes, int op) { r
 MgStatus mgXferH2D (void *devDst, const void *hostSrc, size_t bytes) { return mgXferRun (devDst, hostSrc, bytes, -1, "mgXferH2D"); }
 
 /* public forms (include/modgpu.h) */
+/* The census of the current device's team, counted since the process started (nothing resets it, mgReleaseBuffers () neither: a caller
+   takes differences).  It changes nothing: tests hold it against the knobs they set, so that a case that names four threads and 64 KiB
+   pieces is known to have run on four lanes in that many pieces. */
+extern "C" void mgXferDiag (U64 out[8])
+{
+  for (int i = 0 ; i < 8 ; ++i) out[i] = 0;
+  int dev = 0;
+  MgXferCtx *Xp = mgXferCtxOf (&dev);
+  if (!Xp) return;
+  std::lock_guard<std::mutex> g (Xp->lock);
+  out[0] = Xp->nXfer; out[1] = Xp->nPieces; out[2] = Xp->lastT; out[3] = (U64) Xp->piece;
+  out[4] = Xp->nSparse; out[5] = Xp->nSparsePlain; out[6] = Xp->lastRuns; out[7] = Xp->lastSkipped;
+}
 extern "C" MgStatus mgCopyD2HBig (void *hostDst, const void *devSrc, size_t bytes)
 { MgStatus s = mgEnsureDevice (); if (s) return s; MG_HIP (hipDeviceSynchronize ()); return mgXferD2H (hostDst, devSrc, bytes, MG_XFER_COPY); }
 extern "C" MgStatus mgCopyH2DBig (void *devDst, const void *hostSrc, size_t bytes)
@@ -239,10 +259,22 @@ static bool mgRangeIsPrivateAnon (size_t a, size_t bytes)
   return ok && at >= end;
 }
 
+/* the census of a sparse call: byPageMap 0 = it took the plain copy */
+static void mgXferSparseCount (int byPageMap, U64 runs, U64 skipped)
+{
+  int dev = 0;
+  MgXferCtx *Xp = mgXferCtxOf (&dev);
+  if (!Xp) return;
+  std::lock_guard<std::mutex> g (Xp->lock);
+  ++(byPageMap ? Xp->nSparse : Xp->nSparsePlain);
+  Xp->lastRuns = runs; Xp->lastSkipped = skipped;
+}
+static MgStatus mgXferH2DPlain (void *devDst, const void *hostSrc, size_t bytes) { mgXferSparseCount (0, 0, 0); return mgXferH2D (devDst, hostSrc, bytes); }
+
 MgStatus mgXferH2DSparse (void *devDst, const void *hostSrc, size_t bytes)
 {
-  if (bytes < ((size_t) 4 << 20)) return mgXferH2D (devDst, hostSrc, bytes);
-  if (!mgRangeIsPrivateAnon ((size_t) hostSrc, bytes)) return mgXferH2D (devDst, hostSrc, bytes);
+  if (bytes < ((size_t) 4 << 20)) return mgXferH2DPlain (devDst, hostSrc, bytes);
+  if (!mgRangeIsPrivateAnon ((size_t) hostSrc, bytes)) return mgXferH2DPlain (devDst, hostSrc, bytes);
   const size_t pg = (size_t) sysconf (_SC_PAGESIZE);
   const size_t a0 = (size_t) hostSrc, firstPage = a0 / pg, lastPage = (a0 + bytes - 1) / pg, nPages = lastPage - firstPage + 1;
   U64 *ent = (U64 *) malloc (nPages * 8);
@@ -253,8 +285,9 @@ MgStatus mgXferH2DSparse (void *devDst, const void *hostSrc, size_t bytes)
       if (r <= 0) ok = false; else got += (size_t) r;
     }
   if (fd >= 0) close (fd);
-  if (!ok) { free (ent); return mgXferH2D (devDst, hostSrc, bytes); }
+  if (!ok) { free (ent); return mgXferH2DPlain (devDst, hostSrc, bytes); }
   MgStatus s = MG_OK;
+  U64 runs = 0, sent = 0;
   if (hipMemset (devDst, 0, bytes) != hipSuccess || hipDeviceSynchronize () != hipSuccess) { free (ent); return mgHipFail (hipGetLastError (), "mgXferH2DSparse"); }
   for (size_t p = 0 ; p < nPages && !s ; )
     { if (!(ent[p] >> 62)) { ++p; continue; }              /* bit 63 present, bit 62 swapped: neither = never written */
@@ -263,9 +296,11 @@ MgStatus mgXferH2DSparse (void *devDst, const void *hostSrc, size_t bytes)
       if (b0 < a0) b0 = a0;
       if (b1 > a0 + bytes) b1 = a0 + bytes;
       s = mgXferH2D ((char *) devDst + (b0 - a0), (const char *) b0, b1 - b0);
+      ++runs; sent += b1 - b0;
       p = q;
     }
   free (ent);
+  mgXferSparseCount (1, runs, (U64) bytes - sent);
   return s;
 }
 

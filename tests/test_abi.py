@@ -184,3 +184,53 @@ def test_devsort_probe_carries_the_hash_of_its_sources():
     td.build_probe()
     assert td.probe_binary_hash() == h
     assert td.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None
+
+
+def test_xfer_probe_carries_the_hash_of_its_sources():
+    """libxferprobe.so rides along like the other two probes: a hash of xfer_probe.hip, mg_xfer.h and mg_common.h is baked into it, the
+    tests recompute it from the tree, and a probe of other sources is rebuilt before it is used"""
+    import test_gpu_xfer as tx
+    h = tx.probe_source_hash()
+    assert re.fullmatch(r"[0-9a-f]{16}", h)
+    tx.build_probe()
+    assert tx.probe_binary_hash() == h
+    assert tx.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None
+    assert tx.probe().xferProbeHash().decode() == h
+
+
+def test_xfer_census_is_bound_and_counts_nothing_without_a_transfer():
+    import util
+    d = util.xfer_diag()
+    assert tuple(d) == util.XFER_DIAG and len(d) == 8
+    assert d == util.xfer_diag()
+
+
+def test_reading_an_untouched_page_makes_it_exist():
+    """what mgXferH2DSparse is for, and what tests/test_gpu_xfer.py holds it to, shown without a device: the pages of a fresh anonymous
+    mapping do not exist (xferProbePresentPages, from /proc/self/pagemap); a write makes the page written exist; a plain copy OUT of the
+    range, which only reads, makes every page of it exist"""
+    import test_gpu_xfer as tx
+    X = tx.probe()
+    n = 64 * tx.PAGE + 100
+    base = X.xferProbeMapAnon(n)
+    assert base
+    try:
+        bitmap, count = tx.present_pages(X, base, n)
+        if bitmap is None:
+            print("/proc/self/pagemap cannot be read here")
+            return
+        assert count == 0 and len(bitmap) == 65
+        host = tx.mapped(base, n)
+        host[5 * tx.PAGE + 1] = 7
+        bitmap, count = tx.present_pages(X, base, n)
+        assert bitmap[5] == 1 and 1 <= count < 65           # (one page where the kernel maps 4 KiB pages on a write, more with huge pages)
+        bitmap, _ = tx.present_pages(X, base + 16, n - 16)
+        assert len(bitmap) == 65 and bitmap[5] == 1
+        bitmap, _ = tx.present_pages(X, base + 6 * tx.PAGE, tx.PAGE)
+        assert len(bitmap) == 1
+        copy = host.copy()
+        assert copy[5 * tx.PAGE + 1] == 7 and int(copy.sum()) == 7
+        bitmap, count = tx.present_pages(X, base, n)
+        assert count == 65 and np.all(bitmap == 1)
+    finally:
+        X.xferProbeUnmap(base, n)

@@ -221,7 +221,21 @@ def table_diag(ms):
     return dict(zip(DIAG, (int(x) for x in out)))
 
 
-# ---- the probe libraries of oracle/ (prefix_probe.hip, devsort_probe.hip): a hash of their sources is baked into them ----
+XFER_DIAG = ("transfers", "pieces", "threads", "piece_bytes", "sparse_by_pagemap", "sparse_plain", "sparse_runs", "sparse_skipped")
+
+
+def xfer_diag():
+    """mgXferDiag: what the array transfers' team (csrc/mg_xfer.hip) has done on the current device since the process started: transfers
+    run, pieces moved, threads of the last transfer, bytes per piece in force, sparse uploads by the page map and by the plain copy,
+    runs of pages the last sparse upload sent and bytes it did not send"""
+    import ctypes
+    import modimizer_amd as mg
+    out = (ctypes.c_uint64 * 8)()
+    mg.lib().mgXferDiag(out)
+    return dict(zip(XFER_DIAG, (int(x) for x in out)))
+
+
+# ---- the probe libraries of oracle/ (prefix_probe.hip, devsort_probe.hip, xfer_probe.hip): a hash of their sources is baked into them ----
 
 ORACLE = os.path.join(ROOT, "oracle")
 
