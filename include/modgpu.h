@@ -196,6 +196,12 @@ MgStatus mgTableCheckLayout (Modset *ms, U64 *out6) ;
  * returns indices (modsetAddBatchDevice with dIndexOut, mgInsertReadsDevice): it finds them by the same direct probes.  All 0 when ms
  * has no device table (this call makes none). */
 MgStatus mgTableDiag (Modset *ms, U64 *out9) ;
+/* Which instance of the scan kernel has run (tests, diagnostics): launches since the process started, counted where the instance is
+ * chosen; nothing resets them, so a caller takes differences.  The hit test has six modes -- 0 any d (64-bit inverse), 1 d a power of
+ * two (mask), 2 the low-bits filter for powers of two, 3 odd d (64-bit), 4 odd d in 32-bit arithmetic, 5 any d in 32-bit arithmetic --
+ * and out18 (host) holds: [2 * mode + where] launches of the batch scan, where = 1 when positions or read ids were asked for and 0
+ * for the k-mers alone; [12 + mode] launches of the per-read iterator's kernel. */
+MgStatus mgScanDiag (U64 *out18) ;
 
 /* modutils.c:53-63 on the device: dHist[65536] (U64) += histogram of depth[1..max], where depth is
  * the host depth at last sync plus pending device counts, saturated at 65535. */

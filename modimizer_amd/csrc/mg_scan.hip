@@ -22,6 +22,7 @@
  * double-buffered, in the wavefront's LDS with a (k-1)-base halo; each lane owns 64 consecutive k-mer starts.
  */
 #include <stdlib.h>
+#include <atomic>
 #include "mg_prefix.h"
 
 /* ---------------------------------------------------------------------------------------- */
@@ -194,7 +195,8 @@ __device__ __forceinline__ U64 mgKmerAt (const U32 *sWords, U32 q, int sh1)
 #define MG_MODE_FAST  2      /* d = 2^m, shift1+m <= 32, k >= 17: low-bits filter in phase A */
 #define MG_MODE_ODD   3      /* odd d (the reference's default w = 31): the exact test is the inverse's product alone */
 #define MG_MODE_ODD32 4      /* odd d < 2^15 and k <= 20 (the reference's defaults k = 19, w = 31): that test in 32-bit arithmetic (mgDivisibleOdd32) */
-#define MG_MODE_ANY32 5      /* d = odd 2^s, d < 2^15, k <= 20: low s bits zero and the 32-bit test on the rest */
+#define MG_MODE_ANY32 5      /* d = odd 2^s with the ODD PART below 2^15 (d itself up to 32767 2^16), k <= 20: low s bits zero and the 32-bit test on the rest (mgDivisibleAny32) */
+#define MG_MODE_COUNT 6
 #define MG_LIST_UNROLL 4     /* candidates per half of a lane's mask listed by straight-line code */
 #define MG_CAND_CAP   320    /* candidate list entries (LDS, per wavefront): up to 63 waiting from the tile before + a pass of this tile's */
 #define MG_WAVES      (MG_SCAN_THREADS / 64)
@@ -394,9 +396,9 @@ __device__ __forceinline__ U64 mgScanWorker (const MgScanArgs &a, const U64 work
                   U64 h = hF < hR ? hF : hR;
                   bool hit;
                   if (MODE == MG_MODE_POW2)     hit = (h & dMask) == 0;
-                  else if (MODE == MG_MODE_ODD) hit = h * p.dOddInv <= p.dOddLim;
+                  else if (MODE == MG_MODE_ODD) hit = mgDivisibleOdd (h, p);
                   else if (MODE == MG_MODE_ODD32) hit = mgDivisibleOdd32 (h, p);
-                  else if (MODE == MG_MODE_ANY32) hit = !((U32) h & (((U32) 1 << p.dShift) - 1u)) && mgDivisibleOdd32 (h >> p.dShift, p);
+                  else if (MODE == MG_MODE_ANY32) hit = mgDivisibleAny32 (h, p);
                   else                          hit = mgDivisible (h, p);
                   acc = (acc << 1) | (hit ? 1u : 0u);
                 }
@@ -501,9 +503,9 @@ __device__ __forceinline__ U64 mgScanWorker (const MgScanArgs &a, const U64 work
                     fwd = hF < hR;
                     U64 h = fwd ? hF : hR;
                     if (MODE == MG_MODE_POW2)     surv = (h & dMask) == 0;
-                    else if (MODE == MG_MODE_ODD) surv = h * p.dOddInv <= p.dOddLim;
+                    else if (MODE == MG_MODE_ODD) surv = mgDivisibleOdd (h, p);
                     else if (MODE == MG_MODE_ODD32) surv = mgDivisibleOdd32 (h, p);
-                    else if (MODE == MG_MODE_ANY32) surv = !((U32) h & (((U32) 1 << p.dShift) - 1u)) && mgDivisibleOdd32 (h >> p.dShift, p);
+                    else if (MODE == MG_MODE_ANY32) surv = mgDivisibleAny32 (h, p);
                     else                          surv = mgDivisible (h, p);
                   }
                 if (!fwd) F = R;
@@ -804,6 +806,17 @@ size_t mgScanWorkBytes (U64 totalBases, U32 nReads, U64 capacity)
   return mgScanRangeWorkBytes (mgNumTiles (totalBases), capacity) + mgScanInfoBytes (totalBases);
 }
 
+/* launches since the process started, by the template instance that was chosen (mgScanDiag): [2 * mode + where] the batch scan's,
+   [2 * MG_MODE_COUNT + mode] the iterator's.  Relaxed: they order nothing, tests take differences around a call. */
+static std::atomic<U64> gScanLaunches[3 * MG_MODE_COUNT];
+#define MG_SCAN_COUNTED(i) gScanLaunches[i].fetch_add (1, std::memory_order_relaxed)
+
+extern "C" MgStatus mgScanDiag (U64 *out18)
+{
+  for (int i = 0 ; i < 3 * MG_MODE_COUNT ; ++i) out18[i] = gScanLaunches[i].load (std::memory_order_relaxed);
+  return MG_OK;
+}
+
 /* which phase-A mode a hasher gets; sets the filter's constants in *a */
 static int mgScanMode (const MgHashParams &p, MgScanArgs *a)
 {
@@ -864,8 +877,8 @@ MgStatus mgLaunchScanRange (const MgHashParams &p, const U32 *dPacked, U64 total
   const unsigned grid = (g.nBlocks + MG_WAVES - 1) / MG_WAVES;
   const int mode = mgScanMode (p, &a);
   const bool where = a.segPosF || a.segRead;
-#define MG_SCAN_LAUNCH(M) do { if (where) MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, true>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); \
-                               else       MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, false>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } while (0)
+#define MG_SCAN_LAUNCH(M) do { if (where) { MG_SCAN_COUNTED (2 * (M) + 1); MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, true>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } \
+                               else       { MG_SCAN_COUNTED (2 * (M));     MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, false>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } } while (0)
   if (mode == MG_MODE_FAST) MG_SCAN_LAUNCH (MG_MODE_FAST); else if (mode == MG_MODE_POW2) MG_SCAN_LAUNCH (MG_MODE_POW2);
   else if (mode == MG_MODE_ODD) MG_SCAN_LAUNCH (MG_MODE_ODD); else if (mode == MG_MODE_ODD32) MG_SCAN_LAUNCH (MG_MODE_ODD32);
   else if (mode == MG_MODE_ANY32) MG_SCAN_LAUNCH (MG_MODE_ANY32); else MG_SCAN_LAUNCH (MG_MODE_ANY);
@@ -937,12 +950,11 @@ MgStatus mgLaunchIterScan (const MgHashParams &p, const U32 *dPacked, U64 totalB
 #endif
   MgIterOut o; o.out = out; o.capEntries = capEntries; o.flag = flag; o.seq = seq;
   const int mode = mgScanMode (p, &a);
-  if (mode == MG_MODE_FAST)      hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_FAST>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
-  else if (mode == MG_MODE_POW2) hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_POW2>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
-  else if (mode == MG_MODE_ODD)  hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_ODD>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
-  else if (mode == MG_MODE_ODD32) hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_ODD32>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
-  else if (mode == MG_MODE_ANY32) hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_ANY32>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
-  else                           hipLaunchKernelGGL (mgIterScanKernel<MG_MODE_ANY>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o);
+#define MG_ITER_LAUNCH(M) do { MG_SCAN_COUNTED (2 * MG_MODE_COUNT + (M)); hipLaunchKernelGGL (mgIterScanKernel<M>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o); } while (0)
+  if (mode == MG_MODE_FAST) MG_ITER_LAUNCH (MG_MODE_FAST); else if (mode == MG_MODE_POW2) MG_ITER_LAUNCH (MG_MODE_POW2);
+  else if (mode == MG_MODE_ODD) MG_ITER_LAUNCH (MG_MODE_ODD); else if (mode == MG_MODE_ODD32) MG_ITER_LAUNCH (MG_MODE_ODD32);
+  else if (mode == MG_MODE_ANY32) MG_ITER_LAUNCH (MG_MODE_ANY32); else MG_ITER_LAUNCH (MG_MODE_ANY);
+#undef MG_ITER_LAUNCH
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }

@@ -198,6 +198,28 @@ def test_xfer_probe_carries_the_hash_of_its_sources():
     assert tx.probe().xferProbeHash().decode() == h
 
 
+def test_hash_probe_carries_the_hash_of_its_sources():
+    """libhashprobe.so rides along like the other three probes: a hash of hash_probe.hip and mg_common.h is baked into it, the tests
+    recompute it from the tree, and a probe of other sources is rebuilt before it is used"""
+    import test_gpu_hashprobe as th
+    h = th.probe_source_hash()
+    assert re.fullmatch(r"[0-9a-f]{16}", h)
+    th.build_probe()
+    assert th.probe_binary_hash() == h
+    assert th.probe_binary_hash(os.path.join(ROOT, "oracle", "no_such.so")) is None
+    assert th.probe().hashProbeHash().decode() == h
+
+
+def test_scan_census_is_bound_and_counts_nothing_without_a_scan():
+    import util
+    d = util.scan_diag()
+    assert len(d) == 18 and {key[1] for key in d} == set(util.SCAN_MODES)
+    assert d == util.scan_diag() and util.scan_diag_since(d) == {}
+    # the names the tests give the counters are mg_scan.hip's mode numbers, in order
+    modes = dict(re.findall(r"^#define[ \t]+MG_MODE_(\w+)[ \t]+(\d+)\b", open(os.path.join(mg.CSRC, "mg_scan.hip")).read(), re.M))
+    assert modes.pop("COUNT") == "6" and modes == {name: str(i) for i, name in enumerate(util.SCAN_MODES)}
+
+
 def test_xfer_census_is_bound_and_counts_nothing_without_a_transfer():
     import util
     d = util.xfer_diag()

@@ -154,6 +154,19 @@ def bucket_of(kmers, k, log2nb):
     return m >> U(s) if s >= 0 else (m << U(-s)) & U(0xffffffff)
 
 
+def home_of(kmers, k, r):
+    """home slot of each k-mer in a bucket of r slots (mgHomeOfM): the low word of its mix, stirred with the top MIX_TOP bits where the
+    mix has them (2k >= 24), once more multiplied, and the high half of that times r -- so r need be no power of two"""
+    b = 2 * k
+    m = mix_k(kmers, b)
+    w = U(0xffffffff)
+    x = m & w
+    if b >= 24:
+        x = x ^ (((m >> U(b - MIX_TOP)) * U(0x9E5)) & w)
+    x = (x * U(0x85EBCA6B)) & w
+    return (x * U(r)) >> U(32)
+
+
 def kmers_with_mix_prefix(rng, n, prefix, prefix_bits, k):
     """n distinct k-mers (2k >= 24) whose table hash starts with the prefix_bits <= 10 bits of `prefix`: they share a bucket in every
     table of up to 2^prefix_bits buckets, and spread evenly over the buckets below it in a larger one"""
@@ -221,6 +234,28 @@ def table_diag(ms):
     return dict(zip(DIAG, (int(x) for x in out)))
 
 
+SCAN_MODES = ("ANY", "POW2", "FAST", "ODD", "ODD32", "ANY32")      # MG_MODE_* of csrc/mg_scan.hip, in their numbers' order
+
+
+def scan_diag():
+    """mgScanDiag: launches of the scan kernel since the process started, by the instance that was chosen: {("batch", mode, where): n}
+    for the batch scan (where = 1: positions / read ids asked for) and {("iter", mode): n} for the per-read iterator's kernel"""
+    import ctypes
+    import modimizer_amd as mg
+    out = (ctypes.c_uint64 * 18)()
+    mg.check(mg.lib().mgScanDiag(out))
+    d = {}
+    for m, name in enumerate(SCAN_MODES):
+        d[("batch", name, 0)] = int(out[2 * m]); d[("batch", name, 1)] = int(out[2 * m + 1]); d[("iter", name)] = int(out[12 + m])
+    return d
+
+
+def scan_diag_since(before):
+    """the instances launched since `before` (a scan_diag ()), with their counts: what did not run is not in it"""
+    now = scan_diag()
+    return {key: now[key] - before[key] for key in now if now[key] != before[key]}
+
+
 XFER_DIAG = ("transfers", "pieces", "threads", "piece_bytes", "sparse_by_pagemap", "sparse_plain", "sparse_runs", "sparse_skipped")
 
 
@@ -235,7 +270,7 @@ def xfer_diag():
     return dict(zip(XFER_DIAG, (int(x) for x in out)))
 
 
-# ---- the probe libraries of oracle/ (prefix_probe.hip, devsort_probe.hip, xfer_probe.hip): a hash of their sources is baked into them ----
+# ---- the probe libraries of oracle/ (prefix_probe.hip, devsort_probe.hip, xfer_probe.hip, hash_probe.hip): a hash of their sources is baked into them ----
 
 ORACLE = os.path.join(ROOT, "oracle")
 
