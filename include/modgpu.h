@@ -346,6 +346,8 @@ typedef struct {
   U64 totHit, capHit ;
   U64 *invStart ;               /* [ms->max+2]: mod i is hit by the reads invSpace[invStart[i] .. invStart[i+1]) */
   U32 *invSpace ;               /* (one entry per hit, read order; none for mods whose depth saturated, modasm.c:266,278) */
+  U8 *bad ; int *contained ;    /* [1..nReads]: Read.bad (bits from 1: badRepeat, badOrder10, badOrder1, badNoMatch, badLowHit, badLowCopy1; modasm.c:36-46) and Read.contained, as
+                                   the overlap passes below leave them; zero after create and ingest, kept by mgReadsetLoad / mgReadsetWrite */
 } MgReadset ;
 MgReadset *mgReadsetCreate (Modset *ms) ;                                                   /* modasm.c:90-98 */
 void mgReadsetDestroy (MgReadset *rs) ;
@@ -366,6 +368,30 @@ int  mgReadsetCleanModsPath (void) ;
  * read in ascending mod order, its "READ" line, its "RM" line if it has one.  ms and rs are not modified.  Paths and result as above. */
 int  mgReadsetProperties (MgReadset *rs, FILE *out) ;
 int  mgReadsetPropertiesPath (void) ;
+/* modasm's overlap passes: -o1 / -o2 / -b / -c are all findOverlaps (modasm.c:314-418).  What it works out for a query read x and a partner y that
+ * shares at least 3 of x's copy-1 mods -- nHit, the relative strand, the order and flip counts, containment -- depends on the two hit lists and on
+ * ms->info / ms->depth alone, and is made for a batch of queries at once on the device (mg_overlap.hip); what depends on the order of the calls -- a
+ * partner whose `bad` is set NOW is skipped, the query's own badRepeat / badNoMatch / badLowHit / badLowCopy1 -- is replayed on the host, query by
+ * query in the order given.  The list of x: the partners (x itself among them) by nHit descending, equal nHit in order of arrival.
+ *   mgReadsetFindOverlaps   findOverlaps (x, level) for x = reads[0 .. n): level 1 prints the "RR" line, 2 the "RH" lines too (-o1 i is one read at
+ *                           level 2).  res != 0: the lists as -b / -c see them (a skipped partner has flags 4 and zero counts); free with mgOverlapsFree.
+ *   mgReadsetOverlapStats   -o2 d: level 1 for x = d, 2d, ... (d >= 1)
+ *   mgReadsetMarkBadReads   -b (markBadReads, modasm.c:1266-1322): clears every `bad`, then sets them; the three "MB" lines
+ *   mgReadsetMarkContained  -c (markContained, modasm.c:1370-1394): sets `contained` (never reset); the "MC" line
+ * Every line goes to `out` (0: none), those the reference printf ()s included.  0, or -1 with mgLastError (): a read number outside 1 .. nReads, a
+ * read of more than 65534 hits (the reference's U16 hmap / nHit wrap), a copy-1 mod of a query whose depth saturated (it has no inverse list, and
+ * the reference reads through a null pointer); nothing has been replayed then unless a batch was done before.  A set of 2^32 - 16 hits or more,
+ * MODGPU_READSET_HOST=1 or a device without room take host loops that give the same records.  ...Path: as above.  ...Diag: the calling thread's last
+ * call: batches, candidates (entries of the inverse lists walked), pairs kept (nHit >= 3), launches of the pair kernel. */
+typedef struct { U32 n ; U64 *start ;              /* [n+1]: entries of query q at [start[q], start[q+1]) */
+                 U32 *iy ; U16 *nHit, *nBadOrder, *nBadFlip ; U8 *flags ; } MgOverlaps ;   /* flags: 1 isPlus, 2 isContained, 4 skipped (y was bad) */
+int  mgReadsetFindOverlaps (MgReadset *rs, const U32 *reads, U32 n, int level, FILE *out, MgOverlaps *res /* may be 0 */) ;
+void mgOverlapsFree (MgOverlaps *res) ;
+int  mgReadsetOverlapStats (MgReadset *rs, U32 d, FILE *out) ;      /* -o2 d */
+int  mgReadsetMarkBadReads (MgReadset *rs, FILE *out) ;             /* -b: the three MB lines */
+int  mgReadsetMarkContained (MgReadset *rs, FILE *out) ;            /* -c: the MC line */
+int  mgReadsetOverlapsPath (void) ;                                 /* 0 device, 1 host loops, -1 failed before */
+void mgReadsetOverlapsDiag (U64 out4[4]) ;                          /* last call of this thread: batches, candidates, pairs kept, pair-kernel launches */
 
 /* modrep -R <ref.fa> <ref.mod> -s3 <reads.fa> <reads.mod> (modrep.c:27-63,170-268; the rest of that file is its "OLD VERSIONS").
  * Scan, lookups and every per-read and per-mod reduction run on the device (mg_modrep.hip); the host formats the lines.  All of these

@@ -51,7 +51,13 @@ class MgReadset(C.Structure):         # include/modgpu.h (modasm.c:30-57,79-86)
     _fields_ = [("ms", C.POINTER(Modset)), ("nReads", C.c_int), ("capReads", C.c_int),
                 ("len", C.POINTER(C.c_int)), ("nHit", C.POINTER(C.c_int)), ("nMiss", C.POINTER(C.c_int)),
                 ("nCopy", C.POINTER(C.c_int * 4)), ("hitStart", U64P), ("hit", U32P), ("dx", C.POINTER(C.c_uint16)),
-                ("totHit", C.c_uint64), ("capHit", C.c_uint64), ("invStart", U64P), ("invSpace", U32P)]
+                ("totHit", C.c_uint64), ("capHit", C.c_uint64), ("invStart", U64P), ("invSpace", U32P),
+                ("bad", C.POINTER(C.c_uint8)), ("contained", C.POINTER(C.c_int))]
+
+
+class MgOverlaps(C.Structure):        # include/modgpu.h (modasm.c:291-298)
+    _fields_ = [("n", C.c_uint32), ("start", U64P), ("iy", U32P), ("nHit", C.POINTER(C.c_uint16)), ("nBadOrder", C.POINTER(C.c_uint16)),
+                ("nBadFlip", C.POINTER(C.c_uint16)), ("flags", C.POINTER(C.c_uint8))]
 
 
 class MgRepRef(C.Structure):          # include/modgpu.h (modrep.c:20-25)
@@ -91,6 +97,7 @@ EXPORTS = [
     "mgCommInitAll", "mgCommGetUniqueId", "mgCommInitRank", "mgCommRank", "mgCommSize", "mgCommDestroy", "mgHistogramAllReduce", "mgDepthAllReduce", "mgModsetMergeRankOrder",
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgReadsetCleanMods", "mgReadsetCleanModsPath", "mgReadsetProperties", "mgReadsetPropertiesPath",
+    "mgReadsetFindOverlaps", "mgOverlapsFree", "mgReadsetOverlapStats", "mgReadsetMarkBadReads", "mgReadsetMarkContained", "mgReadsetOverlapsPath", "mgReadsetOverlapsDiag",
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
@@ -240,6 +247,9 @@ def lib():
     sig("mgReadsetRead", i32, RS, vp, vp, i32); sig("mgReadsetFileRead", i32, RS, C.c_char_p)
     sig("mgReadsetStats", None, RS, vp); sig("mgReadsetWrite", None, RS, C.c_char_p); sig("mgReadsetLoad", RS, C.c_char_p)
     sig("mgReadsetCleanMods", i32, RS, vp); sig("mgReadsetCleanModsPath", i32); sig("mgReadsetProperties", i32, RS, vp); sig("mgReadsetPropertiesPath", i32)
+    sig("mgReadsetFindOverlaps", i32, RS, vp, C.c_uint32, i32, vp, C.POINTER(MgOverlaps)); sig("mgOverlapsFree", None, C.POINTER(MgOverlaps))
+    sig("mgReadsetOverlapStats", i32, RS, C.c_uint32, vp); sig("mgReadsetMarkBadReads", i32, RS, vp); sig("mgReadsetMarkContained", i32, RS, vp)
+    sig("mgReadsetOverlapsPath", i32); sig("mgReadsetOverlapsDiag", None, vp)
     RR, RES = C.POINTER(MgRepRef), C.POINTER(MgRepResult)
     sig("mgRepRefCreate", RR, C.c_char_p, C.c_char_p, vp); sig("mgRepRefFromArrays", RR, MS, vp, i64, vp); sig("mgRepRefDestroy", None, RR)
     sig("mgRepRunBegin", vp, RR, MS); sig("mgRepRunAdd", i32, vp, vp, vp, i32, vp); sig("mgRepRunFinish", i32, vp, vp, RES); sig("mgRepResultFree", None, RES)
@@ -509,6 +519,50 @@ def readset_properties(rs, path):
     if rc:
         raise ModgpuError("mgReadsetProperties failed: " + lib().mgLastError().decode())
     return lib().mgReadsetPropertiesPath()
+
+
+def _overlaps_done(rc, what):
+    if rc:
+        raise ModgpuError("%s failed: %s" % (what, lib().mgLastError().decode()))
+    return lib().mgReadsetOverlapsPath()
+
+
+def readset_find_overlaps(rs, reads, level, f, want_lists=False):
+    """mgReadsetFindOverlaps: findOverlaps (modasm.c:314-418) for the read numbers `reads` in order -- modasm -o1 i is one read at level 2 --
+    its lines into the open CFile `f` (None: none).  Returns the path taken (0 the device, 1 the host loops), or with want_lists the lists
+    as -b / -c see them: per query [(iy, nHit, nBadOrder, nBadFlip, flags)]."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint32)
+    res = MgOverlaps()
+    rc = lib().mgReadsetFindOverlaps(rs, reads.ctypes.data, len(reads), level, f, C.byref(res) if want_lists else None)
+    path = _overlaps_done(rc, "mgReadsetFindOverlaps")
+    if not want_lists:
+        return path
+    out = [[(int(res.iy[e]), int(res.nHit[e]), int(res.nBadOrder[e]), int(res.nBadFlip[e]), int(res.flags[e]))
+            for e in range(int(res.start[q]), int(res.start[q + 1]))] for q in range(res.n)]
+    lib().mgOverlapsFree(C.byref(res))
+    return out
+
+
+def readset_overlap_stats(rs, d, f):
+    """mgReadsetOverlapStats: modasm -o2 d, the "RR" lines of reads d, 2d, .. into the open CFile `f`.  Returns the path taken."""
+    return _overlaps_done(lib().mgReadsetOverlapStats(rs, d, f), "mgReadsetOverlapStats")
+
+
+def readset_mark_bad_reads(rs, f):
+    """mgReadsetMarkBadReads: modasm -b (markBadReads, modasm.c:1266-1322): rs.bad, the three "MB" lines into `f`.  Returns the path taken."""
+    return _overlaps_done(lib().mgReadsetMarkBadReads(rs, f), "mgReadsetMarkBadReads")
+
+
+def readset_mark_contained(rs, f):
+    """mgReadsetMarkContained: modasm -c (markContained, modasm.c:1370-1394): rs.contained, the "MC" line into `f`.  Returns the path taken."""
+    return _overlaps_done(lib().mgReadsetMarkContained(rs, f), "mgReadsetMarkContained")
+
+
+def readset_overlaps_diag():
+    """mgReadsetOverlapsDiag: (batches, candidates, pairs kept, pair-kernel launches) of the calling thread's last overlap call"""
+    v = (C.c_uint64 * 4)()
+    lib().mgReadsetOverlapsDiag(v)
+    return tuple(int(x) for x in v)
 
 
 def rep_ref_create(seq_path, mod_path, err_path=None):

@@ -47,7 +47,8 @@ enum MgKernelId {
   MG_K_SEG_SCAN, MG_K_SEG_COMPACT, MG_K_PART, MG_K_PART_HIST, MG_K_PART_SCATTER, MG_K_RANK_COUNT, MG_K_RANK_SCAN, MG_K_BUCKET_DEDUP,
   MG_K_BUCKET_MERGE, MG_K_RANK_LOOKUP, MG_K_TABLE_FIND_SEG, MG_K_HOT_REDUCE, MG_K_BUCKET_FIND, MG_K_UNPART, MG_K_CHAIN, MG_K_CHAIN_RESOLVE,
   MG_K_PAINT_ITEMS, MG_K_DEPTH_GUARD, MG_K_DEPTH_GATHER, MG_K_TEXT_LEN, MG_K_TEXT_SCAN, MG_K_TEXT_WRITE,
-  MG_K_SETTEXT_LINES, MG_K_SETTEXT_SCAN, MG_K_SETTEXT_PARSE, MG_K_SETTEXT_LAST, MG_K_COUNT
+  MG_K_SETTEXT_LINES, MG_K_SETTEXT_SCAN, MG_K_SETTEXT_PARSE, MG_K_SETTEXT_LAST,
+  MG_K_OVL_ACTIVE, MG_K_OVL_EMIT, MG_K_OVL_SORT, MG_K_OVL_RUNS, MG_K_OVL_PAIR, MG_K_COUNT
 };
 void mgProfBegin (int id, hipStream_t st);
 void mgProfEnd (int id, hipStream_t st);

@@ -98,6 +98,19 @@ MG_HIDDEN void mgReadsetDevAppendHits (const void *rs, const U32 *dHit, U64 n); 
 MG_HIDDEN int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
                                     U8 *hInfo, int *hNCopy, U32 counts[3]);
 MG_HIDDEN int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv);
+/* modasm's overlap passes (mg_overlap.hip): the pure record of findOverlaps (modasm.c:314-418) per (query, partner) with nHit >= 3.  nPlus / nMinus: as the
+   "RH" line prints them (after the order test's decrements); flags: 1 isPlus, 2 isContained */
+typedef struct { U32 iy; U16 nHit, nBadOrder, nBadFlip, nPlus, nMinus, flags; } MgOvlRec;
+typedef struct MgOvlDev MgOvlDev;
+/* Open: the set's arrays go to the device once per call (reads from 1: hHitStart[nReads + 2], hLen[nReads + 1]); 0 = done, 1 = the device has no room (the
+   caller's host loops take the call), -1 = failed.  Batch: queries[0 .. nq) (read numbers, checked by the caller; their hits together and their candidates
+   together below 2^31): nRepeat[nq], start[nq + 1], *recs (malloc ()ed: start[nq] records, a query's by nHit descending then arrival); diag[1..3] are added to.
+   0 / 1 (no room for this batch) / -1 */
+MG_HIDDEN int  mgOvlDevOpen (MgOvlDev **d, U32 msMax, const U8 *hInfo, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, const int *hLen, U32 nReads,
+                             const U64 *hInvStart, const U32 *hInvSpace);
+MG_HIDDEN int  mgOvlDevBatch (MgOvlDev *d, const U32 *queries, U32 nq, U32 *nRepeat, U64 *start, MgOvlRec **recs, U64 diag[4]);
+MG_HIDDEN void mgOvlDevClose (MgOvlDev *d);
+MG_HIDDEN U64  mgOvlDevCandBudget (void);      /* candidates per batch that the free device memory allows */
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;

@@ -41,6 +41,8 @@ static void readAll (void)
   k.queryHostChain = num ("MODGPU_QUERY_HOST_CHAIN");
   k.iterHostBelow = num ("MODGPU_ITER_HOST_BELOW");
   k.readsetHost = num ("MODGPU_READSET_HOST");
+  k.overlapCands = num ("MODGPU_OVERLAP_CANDS");
+  k.overlapLds = num ("MODGPU_OVERLAP_LDS");
   k.segSlack = num ("MODGPU_SEG_SLACK");
   k.partDigits = num ("MODGPU_PART_DIGITS");
   k.findBits = num ("MODGPU_FIND_BITS");
