@@ -15,6 +15,7 @@ from tests import test_readset as trs
 from tests import test_readset_overlap as tro
 from tests import test_gpu_readset_clean as tgc
 from tests import test_gpu_devsort as tds
+from tests import overlap_designs as od
 
 TAGS = tro.TAGS
 W = 8
@@ -247,3 +248,37 @@ def test_batches_and_repeated_commands(tmp_path):
         assert any(r.contained) and any(r.bad) and not all(r.bad[1:])
         mg.lib().mgReadsetDestroy(rs)
     assert got[None] == got[30000] == got[1]
+
+
+# ---- read sets built by design (tests/overlap_designs.py; the CPU leg is tests/test_readset_overlap.py) ----
+
+def designed(name, tmp_path):
+    """(rs, the restatement whose design properties are asserted) of a designed set ingested on the device: the arrays equal the oracle's (dx and
+    len of set E among them); the designs, the oracle's arrays and the restatements once per process"""
+    assert od.SORT_TILE == SORT_TILE
+    _, rs = od.ingest(name, tmp_path)
+    return rs, od.checked(name, *od.oracle_set(name))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["A", "B", "D", "E"])
+def test_designed_sets_on_the_device(name, tmp_path):
+    """A: partners of exactly 3 .. 193 hits, matches at lane 63 / lane 0, a stride without matches, a late first match, both strands, out-of-order
+    matches whose previous match is the wave's carry, nPlus == nMinus, tandem reads, runs of 2 and 3, contained / overlap on both sides of
+    equality.  B: a third of the hits not copy 1 (flag[] and place[] of the compaction are no identity; more than one scan tile), then candidate
+    budgets of exactly the first batch's bounds and one less.  D: more pairs than one sort tile, 20 equal nHit across a tile line, nPairs of 1 and
+    of every residue of 4, more than 1024 queries.  E: dx that wraps, positions past 2^16.  Every read's list in one call, then -o2 / -b / -c /
+    -o1: lists, lines, flags and the diag totals (batches, candidates, pairs, launches) against the restatement, path 0"""
+    rs, r0 = designed(name, tmp_path)
+    od.run_set(name, rs, r0, tmp_path, 0)
+    mg.lib().mgReadsetDestroy(rs)
+
+
+@pytest.mark.gpu
+def test_designed_tables_under_every_lds_setting(tmp_path):
+    """C: tables of exactly 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049 and more than 2500 entries; MODGPU_OVERLAP_LDS = 64, unset, 2048 (the
+    64 KiB launch), 4096 (clamped to 2048), 0 and -1: in each launch both paths (under 0 HBM alone), around each cap the pairs of the tables of cap
+    and cap + 1 entries in one workgroup of four; identical results"""
+    rs, r0 = designed("C", tmp_path)
+    od.run_set("C", rs, r0, tmp_path, 0)
+    mg.lib().mgReadsetDestroy(rs)

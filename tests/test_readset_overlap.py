@@ -44,10 +44,12 @@ class Restatement:
         self.out = []
         self._pure = {}
         self.cands = {}                                             # per query looked at: the entries of the inverse lists it walks
+        self.runs = {}
 
     # -- pure: depends on the hit lists and info / depth only --
     def pure(self, x):
-        """(nRepeat, [record per pair with nHit >= 3, by nHit descending then arrival]); a record is a dict"""
+        """(nRepeat, [record per pair with nHit >= 3, by nHit descending then arrival]); a record is a dict.  self.runs[x] = {y: candidates of
+        (x, y)} for every y walked, the dropped ones (fewer than 3) too"""
         if x in self._pure:
             return self._pure[x]
         a0 = self.hs[x - 1]
@@ -69,10 +71,13 @@ class Restatement:
         recs = []
         for y in sorted((y for y in n_hit if n_hit[y] >= 3), key=lambda y: (-n_hit[y], first[y])):
             b0 = self.hs[y - 1]
-            match = [(hmap[h & TOPMASK], h, self.pos[b0 + j]) for j, h in enumerate(self.hit[b0:self.hs[y]]) if (h & TOPMASK) in hmap]
+            at = [j for j, h in enumerate(self.hit[b0:self.hs[y]]) if (h & TOPMASK) in hmap]
+            match = [(hmap[self.hit[b0 + j] & TOPMASK], self.hit[b0 + j], self.pos[b0 + j]) for j in at]
             n_plus = sum(1 for ihx, h, _ in match if (h & TOPBIT) == (hx[ihx - 1] & TOPBIT))
             n_minus = len(match) - n_plus
             r = dict(iy=y, nHit=n_hit[y], isPlus=0, isContained=0, nBadOrder=0, nBadFlip=0)
+            # for the tests that design a pair: the matches as (j in y, ihx in x), and the counts before either branch adjusts them
+            r["match"], r["rawPlus"], r["rawMinus"] = [(j, m[0]) for j, m in zip(at, match)], n_plus, n_minus
             x_len, y_len = int(self.a["len"][x - 1]), int(self.a["len"][y - 1])
             if n_plus > n_minus:
                 r["isPlus"], r["nBadFlip"] = 1, n_minus
@@ -98,6 +103,7 @@ class Restatement:
             recs.append(r)
         self._pure[x] = (n_repeat, recs)
         self.cands[x] = ordinal
+        self.runs[x] = n_hit
         self.table_size = getattr(self, 'table_size', {}); self.table_size[x] = len(hmap)
         return self._pure[x]
 
@@ -360,6 +366,25 @@ def test_overlap_lists_vs_restatement(tag, golden_dir, tmp_path):
         want = [r.find_overlaps(x, 0) for x in (5, 5, 1)]
         assert mg.readset_find_overlaps(rs, [5, 5, 1], 0, None, want_lists=True) == want
     L.mgReadsetDestroy(rs)
+
+
+# ---- read sets built by design (tests/overlap_designs.py): the oracle writes them, the library loads them, the host loops run ----
+
+@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E"])
+def test_designed_sets_through_the_host_loops(name, tmp_path):
+    """set A (strides of 64 hits), B (copy classes), C (table sizes), D (many pairs, ties), E (positions past 2^16), each with its properties
+    asserted from the restatement (overlap_designs.check_*), written by the oracle, loaded by mgReadsetLoad and run by ovlBatchHost / ovlPairHost:
+    lists, -o2 / -b / -c lines and flags against the restatement; B under exact candidate budgets, D's subsets and a query list of more than 1024"""
+    from tests import overlap_designs as od
+    stem = str(tmp_path / ("set" + name))
+    a, info = od.oracle_set(name, stem)
+    rs = mg.lib().mgReadsetLoad(stem.encode())
+    trs.same(trs.lib_arrays(rs), a)
+    assert np.array_equal(ms_info(rs.contents.ms), info)
+    r0 = od.checked(name, a, info)
+    with host_loops():
+        od.run_set(name, rs, r0, tmp_path, 1)
+    mg.lib().mgReadsetDestroy(rs)
 
 
 def test_error_cases(golden_dir, tmp_path):
