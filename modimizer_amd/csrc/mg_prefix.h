@@ -2,8 +2,8 @@
  * n counts by one workgroup of 1024.  Two operations, sum and max, over U32 or U64; 0 is the identity of both.
  *
  * What is NOT here, on purpose: mgSegScanKernel (mg_scan.hip: its staged, padded layout was measured, and it is on config 2's step);
- * mgPartScanKernel (mg_table.hip: one count per thread, no pieces); MG_MAX_DPP / mgWavePrefixMax and the merge kernel's prefix-scan
- * placement (mg_table.hip); the arg-min over a struct in mg_minimizer.hip; the ballot / popcount placement of mgRsWriteKernel and
+ * mgPartScanKernel (mg_part.hip: one count per thread, no pieces); MG_MAX_DPP / mgWavePrefixMax and the merge kernel's prefix-scan
+ * placement (mg_bucket.hip); the arg-min over a struct in mg_minimizer.hip; the ballot / popcount placement of mgRsWriteKernel and
  * mgRefAppendKernel.  These are other patterns. */
 #ifndef MG_PREFIX_H
 #define MG_PREFIX_H

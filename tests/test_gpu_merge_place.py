@@ -1,5 +1,5 @@
 """GPU: the merge kernel's placement by prefix scan (MODGPU_MERGE_PLACE=1: a bucket that is empty before the add is laid out
-from its keys' home counts, one prefix sum and one prefix max, without a probe -- csrc/mg_table.hip mgPlaceStarts).  The table's
+from its keys' home counts, one prefix sum and one prefix max, without a probe -- csrc/mg_bucket.hip mgPlaceStarts).  The table's
 slot order is not part of any parity contract; value[] / depth[] / index[] and every lookup's answer are, and the layout itself is
 checked by mgTableCheckLayout, which walks the device table without going through the lookups."""
 import ctypes as C

@@ -534,7 +534,7 @@ def _table_regrown_before_lookups():
 
 
 def test_rank_slices():
-    """bucketed path: the rank lookups run per slice of the ordinal range (mg_table.hip, mgRankLookupKernel).  One slice
+    """bucketed path: the rank lookups run per slice of the ordinal range (mg_bucket.hip, mgRankLookupKernel).  One slice
     (a bucket's whole list in one group, far longer than a wave), the most slices the kernel takes (63 + the group of
     k-mers already in the table), and something in between -- two batches each, the second mostly k-mers of the first"""
     import subprocess, sys, os
@@ -901,7 +901,7 @@ def test_histogram_kept_by_the_build(tmp_path):
 
 
 def test_kmers_with_very_many_copies():
-    """bucketed path (and, last, the atomic one), the dedup kernel's loop over what was not fetched ahead (mg_table.hip, mgDedupCountWave / MG_HOT_DEPTH): buckets with
+    """bucketed path (and, last, the atomic one), the dedup kernel's loop over what was not fetched ahead (mg_bucket.hip, mgDedupCountWave / MG_HOT_DEPTH): buckets with
     far more occurrences than a workgroup fetches ahead (3 per thread) -- thousands of copies of one read (whole waves of one k-mer),
     poly-A stretches (every start a modimizer of one k-mer when it is one), and ordinary reads in between so that waves mix k-mers;
     both flag polarities, both element formats, two batches (the second finds the hot k-mers already in the table).  Against the oracle:

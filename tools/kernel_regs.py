@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dev: VGPRs / scratch / LDS / occupancy of every kernel of a .hip file (hipcc -S, device only): python tools/kernel_regs.py mg_table.hip [filter]"""
+"""dev: VGPRs / scratch / LDS / occupancy of every kernel of a .hip file (hipcc -S, device only): python tools/kernel_regs.py mg_bucket.hip [filter]"""
 import re, subprocess, sys, os
 src = sys.argv[1]; flt = sys.argv[2] if len(sys.argv) > 2 else ""
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "modimizer_amd", "csrc")
