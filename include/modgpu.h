@@ -472,6 +472,36 @@ int  mgTextParseFileDevice (const char *filename, char **bases, int64_t **offset
 /* the callers' per-file loops: parsing of the next batch overlaps the GPU work on the current one */
 int  mgAddSequenceFile (Modset *ms, const char *filename, FILE *out) ;                        /* modutils.c:33-51 */
 int  mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FILE *out) ;   /* modmap.c:93-134 */
+/* modutils -x (modutils.c:33-51 with is10x): records are numbered from 1 through the file, and a record with an odd number loses its
+ * first 23 bases -- the 10x barcode and UMI -- as the reader delivers them (FASTA: after the non-bases were dropped, so the 23 may span
+ * lines).  "total length" counts the untrimmed reads, "total hashes" what the trimmed ones give.  An odd record of fewer than 23 bases
+ * becomes an empty read (the reference aborts on it: assert (len >= 0), seqhash.c:156).
+ *   mgAddSequenceFile10x     the file loop: plain text is parsed on the device and every batch trimmed there, gzip, a last line without
+ *                            its newline and the rest of a FASTQ file that breaks a rule go through the host parser and
+ *                            mgAddSequenceBatch10x.  0 / -1 as mgAddSequenceFile, and its line to out.
+ *   mgAddSequenceBatch10x    mgAddSequenceBatch for a batch whose first record has number firstOrdinal (1 + the records before it).
+ *   mgTrim10xDevice          the trim itself, on a batch in device memory: dPackedOut (mgPackedWords (totalBases) words are enough) and
+ *                            dOffOut[nReads + 1] receive the trimmed batch, *totalOut its bases; the call waits for them.  A batch of
+ *                            more than (2^32 - 1) / 23 records is refused (MG_ERR_ARG).
+ *   mgAdd10xDiag             the calling thread's last mgAddSequenceFile10x: batches trimmed on the device, records with an odd number,
+ *                            bases dropped, 1 if the host parser took any part of the file. */
+int     mgAddSequenceFile10x (Modset *ms, const char *filename, FILE *out) ;
+int64_t mgAddSequenceBatch10x (Modset *ms, const char *bases, const int64_t *readOffsets, int nReads, uint64_t firstOrdinal) ;
+MgStatus mgTrim10xDevice (const U32 *dPacked, U64 totalBases, const U64 *dOff, U32 nReads, U64 firstOrdinal,
+                          U32 *dPackedOut, U64 *dOffOut, U64 *totalOut, void *stream) ;
+void    mgAdd10xDiag (U64 out4[4]) ;
+/* modutils -s / -sM (modutils.c:205-219) without the mirror: with a device table the depths are taken where they are -- min (65535,
+ * synced depth + pending count) -- by one kernel over the table, against info[] uploaded from the host and copied back to it; the
+ * table is left as it was (nothing is folded or synced, no byte of value[] or depth[] moves).  The class is the reference's else-if
+ * chain in int arithmetic, whatever the thresholds' order; -s keeps bits 2..7 of info[], -sM only sets bits.  A set without a device
+ * table takes the reference's loop over the host arrays.  Neither prints: follow with mgModsetSummaryDevice.  0 / -1 */
+int  mgModsetSetCopy (Modset *ms, int copy1min, int copy2min, int copyMmin) ;
+int  mgModsetSetCopyM (Modset *ms, int copyMmin) ;
+int  mgModsetSetCopyPath (void) ;   /* test hook: the calling thread's last call of the two: 0 = on the device, 1 = the host loop (the set has no device table), -1 = it failed */
+/* modsetSummary's bytes (modset.c:130-153) for a set with a device table, without bringing it to the host: the depth histogram
+ * (pending counts included) and the four copy tallies are counted on the device and 65540 counters come back.  modsetSummary itself
+ * keeps its sync; a set without a device table goes to it.  0 / -1 (nothing is printed then) */
+int  mgModsetSummaryDevice (Modset *ms, FILE *f) ;
 int  mgQueryFile (MgReference *ref, const char *filename, FILE *out) ;                        /* modmap.c:188-281 */
 /* modutils' two commands that read a set already built (the set itself is not changed: not its max, entries or depths; a lookup may
  * bring a device table to the lookup load, as modsetFindBatchDevice does).  The lookups, the depth gathers and the formatting of the

@@ -101,6 +101,8 @@ EXPORTS = [
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
+    "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
+    "mgModsetSetCopy", "mgModsetSetCopyM", "mgModsetSetCopyPath", "mgModsetSummaryDevice",
     "mgIterScanHost", "mgIterHostBelow", "mgReloadKnobs", "mgFormatF2", "mgModsetMergeArrays", "mgModsetMergeDeviceArrays", "mgModsetClear", "mgModsetDeviceSlots", "mgSetVerbose", "mgProfileEnable", "mgProfileOnly", "mgProfileReset", "mgProfileKernels", "mgProfileGet",
 ]
 
@@ -262,6 +264,10 @@ def lib():
     sig("mgReportDepths", i32, MS, C.POINTER(MS), i32, vp)
     sig("mgRefPaint", i32, MS, vp, vp, i32, C.POINTER(C.c_char_p), vp); sig("mgRefPaintFile", i32, MS, C.c_char_p, vp)
     sig("mgModsetWriteTextDevice", i32, MS, vp); sig("mgModsetReadText", MS, C.c_char_p); sig("mgModsetReadTextPath", i32)
+    sig("mgAddSequenceFile10x", i32, MS, C.c_char_p, vp); sig("mgAddSequenceBatch10x", i64, MS, vp, vp, i32, u64)
+    sig("mgTrim10xDevice", i32, vp, u64, vp, u32, u64, vp, vp, U64P, vp); sig("mgAdd10xDiag", None, U64P)
+    sig("mgModsetSetCopy", i32, MS, i32, i32, i32); sig("mgModsetSetCopyM", i32, MS, i32); sig("mgModsetSetCopyPath", i32)
+    sig("mgModsetSummaryDevice", i32, MS, vp)
     sig("mgReferenceWrite", None, vp, C.c_char_p); sig("mgGzipOpenWrite", vp, C.c_char_p); sig("mgGzipOpenRead", vp, C.c_char_p); sig("mgFzOpen", vp, C.c_char_p, C.c_char_p);
     sig("mgCommInitAll", i32, C.POINTER(vp), i32, C.POINTER(i32)); sig("mgCommGetUniqueId", i32, vp); sig("mgCommInitRank", i32, C.POINTER(vp), i32, i32, vp, i32)
     sig("mgCommRank", i32, vp); sig("mgCommSize", i32, vp); sig("mgCommDestroy", None, vp)
@@ -500,6 +506,41 @@ def read_text(path):
 
 def read_text_path():
     return lib().mgModsetReadTextPath()
+
+
+def add_sequence_file_10x(ms, path, out_path, mode="w"):
+    """mgAddSequenceFile10x: modutils -x (modutils.c:33-51 with is10x) on the file `path`, its line into `out_path`.  Returns
+    mgAdd10xDiag: (batches trimmed on the device, records with an odd number, bases dropped, 1 if the host parser took a part)."""
+    with CFile(out_path, mode) as f:
+        rc = lib().mgAddSequenceFile10x(ms, path.encode(), f)
+    if rc:
+        raise ModgpuError("mgAddSequenceFile10x failed: " + lib().mgLastError().decode())
+    out = (C.c_uint64 * 4)()
+    lib().mgAdd10xDiag(out)
+    return tuple(int(x) for x in out)
+
+
+def set_copy(ms, copy1min, copy2min, copy_m_min):
+    """mgModsetSetCopy: modutils -s (modutils.c:205-212).  Returns the path taken: 0 the device table, 1 the host loop."""
+    if lib().mgModsetSetCopy(ms, copy1min, copy2min, copy_m_min):
+        raise ModgpuError("mgModsetSetCopy failed: " + lib().mgLastError().decode())
+    return lib().mgModsetSetCopyPath()
+
+
+def set_copy_m(ms, copy_m_min):
+    """mgModsetSetCopyM: modutils -sM (modutils.c:215-217).  Returns the path taken: 0 the device table, 1 the host loop."""
+    if lib().mgModsetSetCopyM(ms, copy_m_min):
+        raise ModgpuError("mgModsetSetCopyM failed: " + lib().mgLastError().decode())
+    return lib().mgModsetSetCopyPath()
+
+
+def summary_device(ms, path, mode="w"):
+    """mgModsetSummaryDevice: modsetSummary's lines into the file `path`, counted on the device where the set has a table there."""
+    with CFile(path, mode) as f:
+        rc = lib().mgModsetSummaryDevice(ms, f)
+    if rc:
+        raise ModgpuError("mgModsetSummaryDevice failed: " + lib().mgLastError().decode())
+    return open(path).read()
 
 
 def readset_clean_mods(rs, path):

@@ -90,7 +90,8 @@ static const char *gKernelNames[MG_K_COUNT] = {
   "mgBucketMergeKernel", "mgRankLookupKernel", "mgTableFindSegKernel", "mgHotPlan+ReduceKernel", "mgBucketFindKernel", "mgUnpartKernel", "mgChainKernel", "mgChainResolveKernel",
   "mgPaintItemsKernel", "mgDepthGuardKernel", "mgDepthGatherKernel", "mgTextLenKernel", "mgTextScanKernel", "mgTextWriteKernel",
   "mgSetTextLinesKernel", "mgSetTextScanKernel", "mgSetTextParseKernel", "mgSetTextLastKernel",
-  "mgOvElem..TableKernels", "mgOvEmitKernel", "overlap sorts", "mgOvHead..PairInitKernels", "mgOvPairKernel" };
+  "mgOvElem..TableKernels", "mgOvEmitKernel", "overlap sorts", "mgOvHead..PairInitKernels", "mgOvPairKernel",
+  "mgTrimSkip+OffsetsKernel", "mgTrimGatherKernel", "mgSetCopyKernel", "mgCopyTallyKernel" };
 #define MG_PROF_POOL 8192
 struct MgProfRec { int id; hipEvent_t a, b; };
 static struct {
@@ -971,6 +972,22 @@ extern "C" MgStatus modsetDepthHistogramDevice (Modset *ms, U64 *dHist, void *st
   hipStream_t st = (hipStream_t) stream;
   MgDev *d; MgStatus s = mgDevGet (ms, &d, st); if (s) return s;
   return mgTableHistogram (&d->t, dHist, st);
+}
+
+/* the set's device table for a whole-set pass that only reads it (mg_modutils.hip): brought up to date with what the host appended, the
+   device idle, no query batch in flight.  *t = 0: the set has no device table (no HIP call is made then) */
+MgStatus mgModsetTableForPass (Modset *ms, MgTable **t)
+{
+  *t = 0;
+  if (!ms) { mgSetError ("null Modset"); return MG_ERR_ARG; }
+  if (!mgDevLookup (ms)) return MG_OK;
+  MgDev *d; MgStatus s = mgDevGet (ms, &d, 0); if (s) return s;
+  if (!d->built) return MG_OK;
+  if (d->ticketsOut) { mgSetError ("a query batch of this modset is in flight (mgQueryReadsDeviceAsync without its mgQueryReadsDeviceWait)"); return MG_ERR_ARG; }
+  MG_HIP (hipDeviceSynchronize ());
+  ms->max = d->t.max;
+  *t = &d->t;
+  return MG_OK;
 }
 
 /* ---------------------------------------------------------------------------------------- */

@@ -48,7 +48,8 @@ enum MgKernelId {
   MG_K_BUCKET_MERGE, MG_K_RANK_LOOKUP, MG_K_TABLE_FIND_SEG, MG_K_HOT_REDUCE, MG_K_BUCKET_FIND, MG_K_UNPART, MG_K_CHAIN, MG_K_CHAIN_RESOLVE,
   MG_K_PAINT_ITEMS, MG_K_DEPTH_GUARD, MG_K_DEPTH_GATHER, MG_K_TEXT_LEN, MG_K_TEXT_SCAN, MG_K_TEXT_WRITE,
   MG_K_SETTEXT_LINES, MG_K_SETTEXT_SCAN, MG_K_SETTEXT_PARSE, MG_K_SETTEXT_LAST,
-  MG_K_OVL_ACTIVE, MG_K_OVL_EMIT, MG_K_OVL_SORT, MG_K_OVL_RUNS, MG_K_OVL_PAIR, MG_K_COUNT
+  MG_K_OVL_ACTIVE, MG_K_OVL_EMIT, MG_K_OVL_SORT, MG_K_OVL_RUNS, MG_K_OVL_PAIR,
+  MG_K_TRIM_OFFSETS, MG_K_TRIM_GATHER, MG_K_SETCOPY, MG_K_COPY_TALLY, MG_K_COUNT
 };
 void mgProfBegin (int id, hipStream_t st);
 void mgProfEnd (int id, hipStream_t st);
@@ -322,6 +323,7 @@ MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dInde
 MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st);
 MgStatus mgTableExportDepth (MgTable *t, U16 *dDelta, hipStream_t st);
 MgStatus mgTableHistogram (MgTable *t, U64 *dHist, hipStream_t st);
+MgStatus mgModsetTableForPass (Modset *ms, MgTable **t);            /* mg_api.hip: a set's device table for a pass that only reads it; *t = 0: it has none */
 MgStatus mgTableReplayIndex (MgTable *t, const MgHashParams &p, int tableBits, U32 *dIndex, hipStream_t st);
 MgStatus mgTableMergeApply (const U32 *dIdx, const U16 *dDepth2, const U8 *dInfo2, U32 n2, U16 *dBaseDepth, U8 *dInfo1, hipStream_t st);
 size_t   mgTablePruneScratchBytes (U32 n);

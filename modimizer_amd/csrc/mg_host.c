@@ -453,20 +453,14 @@ bool mgModsetMergeDeviceArrays (Modset *ms1, const U64 *dValue2, const U16 *dDep
   return true;
 }
 
-void modsetSummary (Modset *ms, FILE *f)
+/* the summary's lines (modset.c:130-153) from its counters: h[d] = entries of depth d for d < bins, copy[c] = entries with info & 3 == c
+   (a set without entries has none: h and copy are not read) */
+static void summaryLines (Modset *ms, FILE *f, const U32 *h, U32 bins, const U32 *copy)
 {
-  if (mgLiveDeviceModsets) mgHookNeedHostAll (ms, 0);
   seqhashReport (ms->hasher, f);
   fprintf (f, "MS table bits %d size %llu number of entries %u",
            ms->tableBits, (unsigned long long) ms->tableSize, ms->max);
   if (!ms->max) { fputc ('\n', f); return; }
-  U32 *h = (U32 *) xalloc (65536 * sizeof (U32), 1);
-  U32 copy[4] = { 0, 0, 0, 0 }, bins = 0;
-  for (U32 i = 1 ; i <= ms->max ; ++i)
-    { U32 d = ms->depth[i];
-      ++h[d]; if (d + 1 > bins) bins = d + 1;
-      ++copy[ms->info[i] & 3];
-    }
   U64 sum = 0, tot = 0;
   for (U32 i = 0 ; i < bins ; ++i) { sum += h[i]; tot += (U32) (i * h[i]); }   /* 32-bit products, modset.c:144 */
   int64_t half = (int64_t) (tot / 2);
@@ -477,5 +471,37 @@ void modsetSummary (Modset *ms, FILE *f)
   if (copy[0] < ms->max)
     fprintf (f, " copy0 %u copy1 %u copy2 %u copyM %u", copy[0], copy[1], copy[2], copy[3]);
   fputc ('\n', f);
+}
+
+void modsetSummary (Modset *ms, FILE *f)
+{
+  if (mgLiveDeviceModsets) mgHookNeedHostAll (ms, 0);
+  if (!ms->max) { summaryLines (ms, f, 0, 0, 0); return; }
+  U32 *h = (U32 *) xalloc (65536 * sizeof (U32), 1);
+  U32 copy[4] = { 0, 0, 0, 0 }, bins = 0;
+  for (U32 i = 1 ; i <= ms->max ; ++i)
+    { U32 d = ms->depth[i];
+      ++h[d]; if (d + 1 > bins) bins = d + 1;
+      ++copy[ms->info[i] & 3];
+    }
+  summaryLines (ms, f, h, bins, copy);
   free (h);
+}
+
+/* the same bytes without the mirror: a set with a device table is counted there (mg_modutils.hip: the depth histogram with the pending
+   counts in it, four tallies of info & 3) and only the 65540 counters come back; value[] and depth[] stay where they are, nothing is
+   synced.  A set without a device table goes to modsetSummary.  0 / -1 (mgLastError; nothing is printed then) */
+int mgModsetSummaryDevice (Modset *ms, FILE *f)
+{
+  if (!mgLiveDeviceModsets || !mgHookHasDevice (ms)) { modsetSummary (ms, f); return 0; }
+  U64 *c = (U64 *) xalloc (65540 * sizeof (U64), 0);
+  const int rc = mgSummaryCountersDevice (ms, c);
+  if (rc) { free (c); if (rc < 0) return -1; modsetSummary (ms, f); return 0; }
+  U32 *h = (U32 *) xalloc (65536 * sizeof (U32), 0);
+  U32 copy[4], bins = 0;
+  for (U32 d = 0 ; d < 65536 ; ++d) { h[d] = (U32) c[d]; if (h[d]) bins = d + 1; }
+  for (int i = 0 ; i < 4 ; ++i) copy[i] = (U32) c[65536 + i];
+  summaryLines (ms, f, h, bins, copy);
+  free (h); free (c);
+  return 0;
 }

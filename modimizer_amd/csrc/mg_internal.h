@@ -28,6 +28,8 @@ int  mgIterMinScan (Seqhash *sh, const char *s, int len, U64 **rec, U64 *nOut);
    file for this path (the host parser takes it), -3 = FASTQ text this parser leaves to the host parser from byte *resumeOff (a
    record start, line *resumeLine of the file; the counts are those of the records added so far) */
 int  mgAddSequenceFileDevice (Modset *ms, const char *filename, U64 *nSeq, U64 *totLen, U64 *totHash, U64 *resumeOff, U64 *resumeLine);
+/* the same for 10x reads (modutils.c:44): every batch through mgTrim10xDevice, records numbered from 1 through the file, before it is added */
+int  mgAddSequenceFile10xDevice (Modset *ms, const char *filename, U64 *nSeq, U64 *totLen, U64 *totHash, U64 *resumeOff, U64 *resumeLine);
 int  mgTextParseFileDevice (const char *filename, char **basesOut, int64_t **offsetsOut, int64_t *nSeqOut);   /* test hook: the parser's records as host arrays (malloc) */
 /* the same parser for the callers that print record ids: every batch of complete records (device resident: packed bases, read
    offsets) with its ids (id r = idBytes + idOff[r], 0-terminated: seqio.c:303-304) to fn; a non-zero return of fn ends the file */
@@ -132,6 +134,13 @@ MG_HIDDEN int mgSetTextParseDevice (const char *filename, U64 bodyOff, U64 want,
    current on return.  0 / -1.  ...HostArrays: the same from host arrays (the lines the host parsed) */
 MG_HIDDEN int mgSetTextFillDevice (Modset *ms, const U64 *dKey, const U16 *dDepth, const U8 *dInfo, U64 n);
 MG_HIDDEN int mgSetTextFillHostArrays (Modset *ms, const U64 *key, const U16 *depth, const U8 *info, U64 n);
+/* mg_modutils.hip.  The census behind mgAdd10xDiag, kept per thread: a new file, a batch that went through the trim, a leg of the host parser */
+MG_HIDDEN void mgAdd10xDiagReset (void);
+MG_HIDDEN void mgAdd10xDiagBatch (U32 nReads, U64 firstOrdinal, U64 dropped);
+MG_HIDDEN void mgAdd10xDiagHostLeg (void);
+/* the summary's counters of a set with a device table: [0 .. 65536) entries by depth (pending counts included), [65536 .. 65540) by
+   info & 3; ms->max is brought up to date.  0 / 1 (the set has no device table) / -1 */
+MG_HIDDEN int mgSummaryCountersDevice (Modset *ms, U64 *counters);
 /* element count of the reference's Array after appending elements 0..n-1 (array.c:144-170,180-183) */
 MG_HIDDEN int mgRefArrayDim (int first, int size, int n);
 #ifdef __cplusplus

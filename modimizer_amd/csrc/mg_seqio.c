@@ -1048,6 +1048,34 @@ int mgAddSequenceFile (Modset *ms, const char *filename, FILE *out)            /
   return 0;
 }
 
+/* the host parser's legs of a 10x file: the batch's records go on from the file's count, so the odd ones stay the odd ones */
+static int addBatch10x (MgSeqBatch *b, void *v)
+{
+  AddCtx *c = (AddCtx *) v;
+  mgAdd10xDiagHostLeg ();
+  int64_t h = mgAddSequenceBatch10x (c->ms, b->bases, b->offsets, b->nSeq, c->nSeq + 1);
+  if (h < 0) return -1;
+  c->nSeq += (U64) b->nSeq; c->totLen += (U64) b->total; c->totHash += (U64) h;
+  return 0;
+}
+
+int mgAddSequenceFile10x (Modset *ms, const char *filename, FILE *out)         /* modutils.c:33-51 with is10x */
+{
+  AddCtx c; memset (&c, 0, sizeof (c)); c.ms = ms;
+  mgAdd10xDiagReset ();
+  /* as mgAddSequenceFile: plain text through the device parser, whose batches are trimmed where they lie; gzip, a last line without its
+     newline and the rest of a FASTQ file that breaks a rule through the host parser, trimmed once they are uploaded */
+  U64 resumeOff = 0, resumeLine = 1;
+  int rc = mgAddSequenceFile10xDevice (ms, filename, &c.nSeq, &c.totLen, &c.totHash, &resumeOff, &resumeLine);
+  if (rc == -1) return -1;
+  if (rc == -2) rc = forEachBatch (filename, addBatch10x, &c);
+  else if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, c.nSeq, addBatch10x, &c);
+  if (rc) return rc;
+  fprintf (out, "added %llu sequences total length %llu total hashes %llu, new max %u\n",
+           (unsigned long long) c.nSeq, (unsigned long long) c.totLen, (unsigned long long) c.totHash, ms->max);
+  return 0;
+}
+
 /* the ids of a device batch as the pointer array the callers take */
 static const char **idPointers (const char *idBytes, const U64 *idOff, U32 n)
 {

@@ -966,6 +966,34 @@ extern "C" int mgAddSequenceFileDevice (Modset *ms, const char *filename, U64 *n
   return rc;
 }
 
+/* the sink of a 10x file (modutils.c:44): a batch holds complete records only -- the FASTA path carries the open record to the front of
+   the next batch, the FASTQ path the bases of the open line -- so the records handed on so far say which of this batch's are the odd
+   ones.  The batch is trimmed into the sink's own arrays (mgTrim10xDevice, mg_modutils.hip) and added from there */
+struct TxAdd10xCtx { Modset *ms; U64 totHash, recsDone; MgDevBuf<U32> dPacked; MgDevBuf<U64> dOff; };
+static int txAdd10xSink (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *, const U64 *, hipStream_t st)
+{
+  TxAdd10xCtx *c = (TxAdd10xCtx *) v;
+  const size_t nw = mgPackedWords (total);
+  if (c->dPacked.reserve (nw, nw + nw / 8, "10x trim") || c->dOff.reserve ((size_t) nReads + 1, ((size_t) nReads + 1) * 2, "10x trim")) return -1;
+  U64 outBases = 0, nHash = 0;
+  if (mgTrim10xDevice (dPacked, total, dOff, nReads, c->recsDone + 1, c->dPacked.p, c->dOff.p, &outBases, (void *) st) != MG_OK) return -1;
+  mgAdd10xDiagBatch (nReads, c->recsDone + 1, total - outBases);
+  if (mgAddReadsDevice (c->ms, c->dPacked.p, outBases, c->dOff.p, nReads, &nHash, (void *) st) != MG_OK) return -1;
+  if (hipStreamSynchronize (st) != hipSuccess) return -1;            /* (the next batch's trim writes the same arrays) */
+  c->totHash += nHash; c->recsDone += nReads;
+  return 0;
+}
+
+extern "C" int mgAddSequenceFile10xDevice (Modset *ms, const char *filename, U64 *nSeq, U64 *totLen, U64 *totHash, U64 *resumeOff, U64 *resumeLine)
+{
+  TxAdd10xCtx c; c.ms = ms; c.totHash = 0; c.recsDone = 0;
+  TxSink sink; sink.fn = txAdd10xSink; sink.ctx = &c; sink.wantIds = false;
+  const int rc = txParseFile (filename, sink, nSeq, totLen, resumeOff, resumeLine);
+  c.dPacked.drop (); c.dOff.drop ();
+  if (totHash) *totHash = c.totHash;
+  return rc;
+}
+
 /* modmap's file entry points (mgReferenceFastaRead, mgQueryFile: modmap.c:93-134,188-281): every batch of complete records,
    device resident, with the records' ids, to a C callback.  0 / -1 / -2 / -3 as txParseFile */
 struct TxCbCtx { MgTextBatchFn fn; void *ctx; };
