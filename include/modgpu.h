@@ -392,6 +392,39 @@ int  mgReadsetMarkBadReads (MgReadset *rs, FILE *out) ;             /* -b: the t
 int  mgReadsetMarkContained (MgReadset *rs, FILE *out) ;            /* -c: the MC line */
 int  mgReadsetOverlapsPath (void) ;                                 /* 0 device, 1 host loops, -1 failed before */
 void mgReadsetOverlapsDiag (U64 out4[4]) ;                          /* last call of this thread: batches, candidates, pairs kept, pair-kernel launches */
+/* modasm -R <ref> / -T <min> <max> / -rb <n>: the rDNA flags of the mods and their LD test (refFlag, modasm.c:752-860; testMods, 595-748; resetBits,
+ * 864-908).  One pipeline: -R makes the per-mod ModInfo, which is in no file, and -T and -rb are its only readers, so all three run in one process.
+ * ModInfo, the reads' otherFlags byte (bit 1 = isRDNA) and the count of -T calls live beside the set (MgReadset has no field for them) and go with
+ * mgReadsetDestroy; mgReadsetWrite / mgReadsetLoad keep otherFlags (byte 25 of the 72-byte record), ModInfo and the count do not survive a file.
+ *   mgReadsetRefFlagHits   refFlag from the reference sequences' hits in file order (index[j] in 1 .. ms->max at position pos[j]; misses left out):
+ *                          the last hit of a mod wins rDNApos; per read the 200th core-and-ref hit from either end (mg_rdna.hip); the walk between the
+ *                          two, which depends on the order of the reads, on the host; the five counting lines (modasm.c:855-859)
+ *   mgReadsetRefFlagFile   -R: the file through the set's hasher and the device lookups (as mgRefPaintFile: N is base 0), then the above.  The
+ *                          reference maps N to 0 only after a -f in the same process and otherwise hashes a base 4 that its tables do not have
+ *   mgReadsetResetBits     -rb op, ops 1 2 3 as they stand (any other: no line, 0); nCopy[] rebuilt.  -1 without -R; -1 for op 3 on an empty set
+ *   mgReadsetTestMods      -T: per tested mod i (minDepth <= depth < maxDepth, RDNA and not REPEAT, not copy 0) and partner mod m of the same kind the
+ *                          count and the least and greatest signed distance over the reads that hold i (mg_rdna.hip: the reference's sort is not
+ *                          needed); the rules of modasm.c:658-705 per (i, m) on the device, the closing loop (708-740), "YY-TEST" lines into yFile
+ *                          and the "RUN" line into out on the host, the "ZZ-TEST" lines into zFile only if it is given.  -1, nothing modified, where
+ *                          the reference breaks: no -R yet ("need to run -R first"); a tested mod of depth 0 or 65535; a visit that would count
+ *                          before its array (len - x - w < 0) or look beyond it: none can happen with w <= k; a -T that tests no mod (the reference
+ *                          dies at its end: arrayDestroy (0)); a second tested mod whose start or end array passes 20000 cells (the reference
+ *                          clears 20000 cells between tested mods, array.c:103, and counts on stale sums beyond: reads of more than ~20 kb)
+ * Host loops give the same bytes for a set of 2^32 - 16 hits or more, MODGPU_READSET_HOST=1 or a device without room, and for a -T that walks fewer
+ * than 2^21 hits (the visited reads' hit counts together; MODGPU_READSET_HOST=0 sends it to the device).  info[] changed: the calls end in
+ * mgModsetHostChanged.  ...RdnaPath: the calling thread's last call: 0 device, 1 host loops, -1 failed before.  ...RdnaDiag: its last -T: batches of
+ * tested mods (MODGPU_TESTMODS_BATCH mods per batch; unset: by the free device memory), tested mods, visits, partner occurrences. */
+typedef struct { U8 flags ; /* 1 isRefRDNA, 2 isCoreRDNA, 4 isVarRDNA, 8 isMultiRDNA (modasm.c:61-77) */
+                 int rDNApos, nGood, nMod2, nBadLD, nSplit, nSplitLD ; } MgModInfo ;
+int  mgReadsetRefFlagFile (MgReadset *rs, const char *refFile, FILE *out) ;
+int  mgReadsetRefFlagHits (MgReadset *rs, const U32 *index, const int *pos, U64 n, FILE *out) ;
+int  mgReadsetResetBits (MgReadset *rs, int op, FILE *out) ;
+int  mgReadsetTestMods (MgReadset *rs, int minDepth, int maxDepth, FILE *yFile, FILE *zFile, FILE *out) ;      /* yFile / zFile / out may be 0 */
+const MgModInfo *mgReadsetModInfo (const MgReadset *rs) ;           /* [ms->max+1], 0 before -R */
+const U8 *mgReadsetReadFlags (const MgReadset *rs) ;                /* [1..nReads]: Read.otherFlags, bit 1 = isRDNA */
+int  mgReadsetTestModsRun (const MgReadset *rs) ;                   /* -T calls made on this set: the reference's static RUN */
+int  mgReadsetRdnaPath (void) ;
+void mgReadsetRdnaDiag (U64 out4[4]) ;
 
 /* modrep -R <ref.fa> <ref.mod> -s3 <reads.fa> <reads.mod> (modrep.c:27-63,170-268; the rest of that file is its "OLD VERSIONS").
  * Scan, lookups and every per-read and per-mod reduction run on the device (mg_modrep.hip); the host formats the lines.  All of these

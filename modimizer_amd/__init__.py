@@ -60,6 +60,10 @@ class MgOverlaps(C.Structure):        # include/modgpu.h (modasm.c:291-298)
                 ("nBadFlip", C.POINTER(C.c_uint16)), ("flags", C.POINTER(C.c_uint8))]
 
 
+class MgModInfo(C.Structure):         # include/modgpu.h (ModInfo, modasm.c:61-77)
+    _fields_ = [("flags", C.c_uint8), ("rDNApos", C.c_int), ("nGood", C.c_int), ("nMod2", C.c_int), ("nBadLD", C.c_int), ("nSplit", C.c_int), ("nSplitLD", C.c_int)]
+
+
 class MgRepRef(C.Structure):          # include/modgpu.h (modrep.c:20-25)
     _fields_ = [("ms", C.POINTER(Modset)), ("len", C.c_int), ("pos", C.POINTER(C.c_int)), ("isF", C.POINTER(C.c_bool)), ("ownsMs", C.c_int)]
 
@@ -98,6 +102,7 @@ EXPORTS = [
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgReadsetCleanMods", "mgReadsetCleanModsPath", "mgReadsetProperties", "mgReadsetPropertiesPath",
     "mgReadsetFindOverlaps", "mgOverlapsFree", "mgReadsetOverlapStats", "mgReadsetMarkBadReads", "mgReadsetMarkContained", "mgReadsetOverlapsPath", "mgReadsetOverlapsDiag",
+    "mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetModInfo", "mgReadsetReadFlags", "mgReadsetTestModsRun", "mgReadsetRdnaPath", "mgReadsetRdnaDiag",
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
@@ -252,6 +257,9 @@ def lib():
     sig("mgReadsetFindOverlaps", i32, RS, vp, C.c_uint32, i32, vp, C.POINTER(MgOverlaps)); sig("mgOverlapsFree", None, C.POINTER(MgOverlaps))
     sig("mgReadsetOverlapStats", i32, RS, C.c_uint32, vp); sig("mgReadsetMarkBadReads", i32, RS, vp); sig("mgReadsetMarkContained", i32, RS, vp)
     sig("mgReadsetOverlapsPath", i32); sig("mgReadsetOverlapsDiag", None, vp)
+    sig("mgReadsetRefFlagFile", i32, RS, C.c_char_p, vp); sig("mgReadsetRefFlagHits", i32, RS, vp, vp, u64, vp); sig("mgReadsetResetBits", i32, RS, i32, vp)
+    sig("mgReadsetTestMods", i32, RS, i32, i32, vp, vp, vp); sig("mgReadsetModInfo", C.POINTER(MgModInfo), RS); sig("mgReadsetReadFlags", C.POINTER(C.c_uint8), RS)
+    sig("mgReadsetTestModsRun", i32, RS); sig("mgReadsetRdnaPath", i32); sig("mgReadsetRdnaDiag", None, vp)
     RR, RES = C.POINTER(MgRepRef), C.POINTER(MgRepResult)
     sig("mgRepRefCreate", RR, C.c_char_p, C.c_char_p, vp); sig("mgRepRefFromArrays", RR, MS, vp, i64, vp); sig("mgRepRefDestroy", None, RR)
     sig("mgRepRunBegin", vp, RR, MS); sig("mgRepRunAdd", i32, vp, vp, vp, i32, vp); sig("mgRepRunFinish", i32, vp, vp, RES); sig("mgRepResultFree", None, RES)
@@ -603,6 +611,63 @@ def readset_overlaps_diag():
     """mgReadsetOverlapsDiag: (batches, candidates, pairs kept, pair-kernel launches) of the calling thread's last overlap call"""
     v = (C.c_uint64 * 4)()
     lib().mgReadsetOverlapsDiag(v)
+    return tuple(int(x) for x in v)
+
+
+def _rdna_done(rc, what):
+    if rc:
+        raise ModgpuError("%s failed: %s" % (what, lib().mgLastError().decode()))
+    return lib().mgReadsetRdnaPath()
+
+
+def readset_ref_flag(rs, ref_path, f):
+    """mgReadsetRefFlagFile: modasm -R <ref> (refFlag, modasm.c:752-860), its five counting lines into the open CFile `f` (None: none).  Returns the
+    path taken: 0 the device, 1 the host loops."""
+    return _rdna_done(lib().mgReadsetRefFlagFile(rs, ref_path.encode(), f), "mgReadsetRefFlagFile")
+
+
+def readset_ref_flag_hits(rs, index, pos, f):
+    """mgReadsetRefFlagHits: the same from the reference sequences' hits in file order (mod index, position), misses left out"""
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    assert len(index) == len(pos)
+    return _rdna_done(lib().mgReadsetRefFlagHits(rs, index.ctypes.data, pos.ctypes.data, len(index), f), "mgReadsetRefFlagHits")
+
+
+def readset_reset_bits(rs, op, f):
+    """mgReadsetResetBits: modasm -rb op (resetBits, modasm.c:864-908), its line into `f`.  Returns the path taken."""
+    return _rdna_done(lib().mgReadsetResetBits(rs, op, f), "mgReadsetResetBits")
+
+
+def readset_test_mods(rs, min_depth, max_depth, f, y=None, z=None):
+    """mgReadsetTestMods: modasm -T min max (testMods, modasm.c:595-748): the "RUN" line into `f`, the "YY-TEST" lines into the CFile `y` and the
+    "ZZ-TEST" lines into `z` (None: not made).  Returns the path taken."""
+    return _rdna_done(lib().mgReadsetTestMods(rs, min_depth, max_depth, y, z, f), "mgReadsetTestMods")
+
+
+def readset_mod_info(rs):
+    """mgReadsetModInfo: a numpy view (fields flags, rDNApos, nGood, nMod2, nBadLD, nSplit, nSplitLD) of the ms->max + 1 entries; None before -R.
+    The view is of the library's array: it is replaced by the next -R or -T."""
+    p = lib().mgReadsetModInfo(rs)
+    if not p:
+        return None
+    dt = np.dtype([("flags", np.uint8), ("rDNApos", np.int32), ("nGood", np.int32), ("nMod2", np.int32), ("nBadLD", np.int32), ("nSplit", np.int32),
+                   ("nSplitLD", np.int32)], align=True)
+    assert dt.itemsize == C.sizeof(MgModInfo)
+    n = rs.contents.ms.contents.max + 1
+    return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(C.addressof(p.contents)), dtype=dt)
+
+
+def readset_read_flags(rs):
+    """mgReadsetReadFlags: Read.otherFlags of reads 0 .. nReads (entry 0 unused) as a numpy copy; bit 1 = isRDNA"""
+    p = lib().mgReadsetReadFlags(rs)
+    return np.ctypeslib.as_array(p, (rs.contents.nReads + 1,)).copy()
+
+
+def readset_rdna_diag():
+    """mgReadsetRdnaDiag: (batches, tested mods, visits, partner occurrences) of the calling thread's last -T"""
+    v = (C.c_uint64 * 4)()
+    lib().mgReadsetRdnaDiag(v)
     return tuple(int(x) for x in v)
 
 

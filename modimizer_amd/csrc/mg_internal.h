@@ -113,6 +113,59 @@ MG_HIDDEN int  mgOvlDevOpen (MgOvlDev **d, U32 msMax, const U8 *hInfo, const U32
 MG_HIDDEN int  mgOvlDevBatch (MgOvlDev *d, const U32 *queries, U32 nq, U32 *nRepeat, U64 *start, MgOvlRec **recs, U64 diag[4]);
 MG_HIDDEN void mgOvlDevClose (MgOvlDev *d);
 MG_HIDDEN U64  mgOvlDevCandBudget (void);      /* candidates per batch that the free device memory allows */
+/* modasm -R / -T (mg_rdna.hip; the host loops are mg_readset.c's).  checkMod (modasm.c:564-568) and the rules of testMods per (tested mod i, partner m)
+   (modasm.c:658-705) are written once, here, for the kernels and the host loops alike */
+#ifdef __HIPCC__
+#define MG_BOTH __host__ __device__
+#else
+#define MG_BOTH
+#endif
+static inline MG_BOTH int mgRdnaCheckMod (unsigned info) { return (info & 3u) != 0 && (info & (MS_REPEAT | MS_RDNA)) == MS_RDNA; }
+enum { MG_LD_MOD2 = 1, MG_LD_GOOD = 2, MG_LD_SPLIT = 4, MG_LD_BAD_M = 8, MG_LD_BAD_I = 16, MG_LD_PLUS = 32 };
+typedef struct { U32 m; int flags, n, vmin, xmin, vmax, xmax; } MgLdCell;      /* a "ZZ-TEST" line less i and the depths; flags: what the pair adds where */
+/* n occurrences of m around i with signed distances dmin .. dmax; start[0 .. nStart), end[0 .. nEnd): the suffix-summed counts (modasm.c:651-654) of i;
+   run: the reference's RUN.  0, or -1 where the reference asserts or reads a cell beyond an array's extent */
+static inline MG_BOTH int mgRdnaLdRule (int n, int dmin, int dmax, const int *start, int nStart, const int *end, int nEnd, int depthM, int run, MgLdCell *c)
+{
+  int f = 0;
+  if (dmin > 0)
+    { const int xmin = dmin, xmax = dmax;
+      if (xmin >= nEnd || xmax >= nEnd) return -1;
+      const int e = end[xmin];
+      if (n < depthM && n * 2 < e) { f |= MG_LD_MOD2; if (run > 3) f |= MG_LD_BAD_M; }
+      if (n == depthM || n >= 0.8 * e) f |= MG_LD_GOOD;
+      if (n == 1 && e >= 10) f |= MG_LD_BAD_I;                      /* modasm.c:673: i's own entry */
+      c->flags = f | MG_LD_PLUS; c->n = n; c->vmin = e; c->xmin = xmin; c->vmax = end[xmax]; c->xmax = xmax;
+    }
+  else
+    { const int xmax = -dmin; int xmin = -dmax;
+      if (xmin < 0) { f |= MG_LD_SPLIT; xmin = xmax; }
+      if (xmin >= nStart || xmax >= nStart) return -1;
+      const int s = start[xmin];
+      if (n < depthM && n * 2 < s) { f |= MG_LD_MOD2; if (run > 3) f |= MG_LD_BAD_M; }
+      else if (n == 1 && s >= 10) f |= MG_LD_BAD_M;                 /* modasm.c:695: m's entry */
+      if (n == depthM || n >= 0.8 * s) f |= MG_LD_GOOD;
+      c->flags = f; c->n = n; c->vmin = s; c->xmin = xmin; c->vmax = start[xmax]; c->xmax = xmax;
+    }
+  return 0;
+}
+/* The reference makes its two count arrays with arrayReCreate (.., 20000, int) per tested mod (modasm.c:619-620), which clears the first 20000 cells of an
+   array that is already there (array.c:103): from the second tested mod whose array passes that extent on it counts on top of stale, suffix-summed cells.
+   That is where it breaks (its own assert at modasm.c:649-650 fires once the sums overflow); the call is refused there, by device and host loops alike */
+#define MG_RDNA_CLEARED 20000
+/* per read 1 .. nReads the hit number of the 200th hit on a mod with qual[] set, from the front (n200, 0: fewer) and, if there is one, from the back
+   without ever looking at hit 0 (m200): modasm.c:781-802.  0 / 1 (no room on the device) / -1 */
+MG_HIDDEN int mgRdnaN200Device (U32 msMax, const U8 *hQual, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, int *hN200, int *hM200);
+/* testMods over a set on the host.  tested[nTested] ascending, partner[nPartner] ascending (every tested mod is a partner).  Out: per tested mod
+   { nGood, nMod2, nSplit } in res3, badLD[msMax + 1] and splitLD[msMax + 1] added to (zeroed by the caller); wantCells: *cells (malloc ()ed) holds
+   cellStart[nTested] records, those of tested mod t at [cellStart[t], cellStart[t + 1]), m ascending.  batch: tested mods per batch, 0: by the device's
+   free memory.  diag[0] batches, [3] partner occurrences.  0 / 1 (no room) / -1; -2: a visit or a cell the reference cannot do (*badMod: the tested mod); -3: a second tested mod whose count array passes
+   MG_RDNA_CLEARED cells */
+typedef struct { U32 msMax; int w, run; const U8 *info; const U16 *depth; const U32 *hit; const U16 *dx; U64 totHit; const U64 *hitStart; const int *len; U32 nReads;
+                 const U64 *invStart; const U32 *invSpace; } MgRdnaSet;
+MG_HIDDEN int mgRdnaTestModsDevice (const MgRdnaSet *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
+                                    int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod);
+MG_HIDDEN int mgReadsetCopyTallyDevice (const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, U32 msMax, int *hNCopy);      /* invBuild's nCopy[] (mg_rsdev.hip); 0 / 1 / -1 */
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;

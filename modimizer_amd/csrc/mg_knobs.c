@@ -43,6 +43,7 @@ static void readAll (void)
   k.readsetHost = num ("MODGPU_READSET_HOST");
   k.overlapCands = num ("MODGPU_OVERLAP_CANDS");
   k.overlapLds = num ("MODGPU_OVERLAP_LDS");
+  k.testModsBatch = num ("MODGPU_TESTMODS_BATCH");
   k.segSlack = num ("MODGPU_SEG_SLACK");
   k.partDigits = num ("MODGPU_PART_DIGITS");
   k.findBits = num ("MODGPU_FIND_BITS");

@@ -38,9 +38,10 @@ typedef struct {
   long textWindowKb;       /* MODGPU_TEXT_WINDOW_KB: text per window of the device parser */
   long fileBatchMbp;       /* MODGPU_FILE_BATCH_MBP */
   long fileBatchBases;     /* MODGPU_FILE_BATCH_BASES: bases per batch of the file entry points */
-  long readsetHost;        /* MODGPU_READSET_HOST: 1 = modasm -C / -P and the overlap passes (mgReadsetCleanMods, mgReadsetProperties, mgReadsetFindOverlaps ..) by the host loops */
+  long readsetHost;        /* MODGPU_READSET_HOST: 1 = modasm -C / -P and the overlap passes (mgReadsetCleanMods, mgReadsetProperties, mgReadsetFindOverlaps ..) by the host loops; 0 = modasm -T (mgReadsetTestMods) on the device whatever its size (unset: the host loops below 2^21 hits walked) */
   long overlapCands;       /* MODGPU_OVERLAP_CANDS: candidates (entries of the inverse lists) per device batch of modasm's overlap passes; unset: from the free device memory */
-  long overlapLds;         /* MODGPU_OVERLAP_LDS: entries of a query's mod table that a wave of the pair kernel stages in LDS (default 1024, at most 2048); a longer table is searched in HBM */
+  long testModsBatch;      /* MODGPU_TESTMODS_BATCH: tested mods per device batch of modasm -T (mgReadsetTestMods); unset: as many as half of the free device memory holds, 2 GiB at most */
+  long overlapLds;        /* MODGPU_OVERLAP_LDS: entries of a query's mod table that a wave of the pair kernel stages in LDS (default 1024, at most 2048); a longer table is searched in HBM */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */
   /* development knobs */

@@ -241,6 +241,24 @@ extern "C" int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U1
   return 0;
 }
 
+/* invBuild's nCopy[] alone (modasm.c:273-277), after a pass that changed copy classes and nothing else (-rb, -T): hNCopy[(nReads + 1) * 4] out.
+   0 = done, 1 = the device has no room, -1 = failed */
+extern "C" int mgReadsetCopyTallyDevice (const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, U32 msMax, int *hNCopy)
+{
+  if (!nReads) return 0;
+  if (mgEnsureDevice ()) return -1;
+  const size_t m = (size_t) msMax + 1;
+  if (!mgRsRoom (m + ((size_t) nReads + 3) * 8 + ((size_t) nReads + 2) * sizeof (int4) + (totHit + 1) * 4, 0)) return 1;
+  MgDevScratch scratch ("read set copy tallies on the device");
+  U32 *dHit; U64 *dStart; U8 *dInfo; int4 *dNc;
+  if (scratch.get (&dInfo, m) || scratch.get (&dStart, (size_t) nReads + 3) || scratch.get (&dNc, (size_t) nReads + 2) || scratch.get (&dHit, totHit + 1)) return -1;
+  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, hHit, totHit * 4))) return -1;
+  hipLaunchKernelGGL (mgRsCopyTallyKernel, dim3 ((nReads + 255) / 256), dim3 (256), 0, 0, dHit, dStart, nReads, dInfo, dNc);
+  if (hipGetLastError () != hipSuccess || hipStreamSynchronize (0)) { scratch.fail (); return -1; }
+  if (mgXferD2H (hNCopy + 4, dNc + 1, (size_t) nReads * sizeof (int4), MG_XFER_COPY)) return -1;
+  return 0;
+}
+
 /* ---- -P ---- */
 
 /* flag[h] = is hit h on a copy-1 mod (modasm.c:926); rd[h] = its read */
