@@ -73,6 +73,10 @@ struct MgDevScratch {
   { *p = 0; const hipError_t e = hipMalloc ((void **) p, count * sizeof (T)); if (e != hipSuccess) return mgHipFail (e, what); adopt (*p); return MG_OK; }
   template <class T> T *take (T *p) { held.erase (std::remove (held.begin (), held.end (), (void *) p), held.end ()); return p; }
 };
+/* the device's free memory now, for a call that asks whether its scratch will fit before it makes any; false (and no error left behind) if the runtime
+   does not say: the caller's own margin and formula go on top */
+static inline bool mgDevFreeBytes (size_t *freeB)
+{ size_t total = 0; if (hipMemGetInfo (freeB, &total) != hipSuccess) { (void) hipGetLastError (); return false; } return true; }
 /* -1 from an entry point that returns int, with its own sentence if whatever failed inside it left no error */
 static inline int mgFailedWith (const char *sentence) { if (!mgLastError ()[0]) mgSetError ("%s", sentence); return -1; }
 

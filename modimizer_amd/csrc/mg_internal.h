@@ -45,10 +45,13 @@ void mgQueryPipeClose (MgQueryPipe *p);                    /* returns when every
 int  mgReferenceAddDevice (MgReference *ref, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, int nSeq, const char **names, bool isAdd);
 void mgReferenceFinish (MgReference *ref, U64 totLen, bool isAdd, FILE *out);
 void mgTextReleaseBuffers (void);
-/* shared by the caller mirrors (mg_callers.c, mg_readset.c): not exported */
+/* shared by the caller mirrors (mg_callers.c, the read set's files): not exported */
 #define MG_HIDDEN __attribute__ ((visibility ("hidden")))
 typedef struct { void *dPacked, *dOff; U64 total; U32 nReads; } MgDevBatch;     /* host bytes -> 2-bit words in HBM */
-MG_HIDDEN int mgSeqForEachBatchFrom (const char *filename, size_t startOff, U64 startLine, U64 startSeq, int (*fn) (MgSeqBatch *, void *), void *ctx);   /* the host parser's batches (the next one parsed while fn works), from a record start on */
+/* a file through the device text parser (devFn per batch: batchBases, batchRecs as mgTextForEachBatchDevice takes them), and where that one leaves it
+   (-2, -3 above) through the host parser, from the start or from the record it stopped at: hostFn per batch, 0: every host batch is uploaded and handed
+   to devFn with its ids.  Returns what the last leg returned */
+MG_HIDDEN int mgSeqWalkFile (const char *filename, MgTextBatchFn devFn, int (*hostFn) (MgSeqBatch *, void *), void *ctx, U64 batchBases, U64 batchRecs, U64 *nSeq, U64 *totLen);
 MG_HIDDEN void mgBatchUpload (MgDevBatch *b, const char *bases, const int64_t *offsets, int nReads);
 MG_HIDDEN void mgBatchFree (MgDevBatch *b);
 MG_HIDDEN FILE *mgTagOpen (const char *root, const char *tag, const char *mode);
@@ -87,33 +90,39 @@ MG_HIDDEN MgStatus mgCopyOutPinned (void *dstPinned, const void *srcDev, size_t 
 MG_HIDDEN void mgChainReleaseBuffers (void);
 MG_HIDDEN void mgQueryReleaseBuffers (void);           /* the query path's cached buffers: page-locked blocks (mg_callers.c), device arrays (mg_chain.hip) */
 MG_HIDDEN void mgChainScratchKeep (int on);      /* 1: the query's device arrays stay allocated between batches; 0: ends that (and frees them) */
+/* a hit of a read: its mod, bit 31 set for forward orientation (modasm.c:22) */
+#define MG_TOPBIT  0x80000000u
+#define MG_TOPMASK 0x7fffffffu
+/* a read set on the host as the device entry points below take it: the modset's info[msMax + 1] and depth[msMax + 1], hit[totHit], dx[totHit],
+   hitStart[nReads + 2] and len[nReads + 1] (reads from 1; hitStart[nReads + 1] = totHit), invStart[msMax + 2], invSpace[invStart[msMax + 1]]; w: the hasher's;
+   run: the reference's RUN for -T.  What a pass is about to write, or reads in a state that is not the set's yet, is a parameter of its own */
+typedef struct { U32 msMax; int w, run; const U8 *info; const U16 *depth; const U32 *hit; const U16 *dx; U64 totHit; const U64 *hitStart; const int *len; U32 nReads;
+                 const U64 *invStart; const U32 *invSpace; } MgRsView;
 /* readsetFileRead's per-read loop on the device (mg_chain.hip): hit lists, distances, counts, hits per mod */
 MG_HIDDEN int  mgReadsetSeedsDevice (Modset *ms, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
                                      U64 *hHitStart, U32 *hNMiss, U32 **dHitOut, unsigned short **dDxOut, U32 *dDepthAccum);
 /* the per-mod side of the read set on the device (mg_rsdev.hip): hit counts kept across a file's batches; depth[], invStart[], invSpace[], nCopy[] at its end */
 MG_HIDDEN MgStatus mgReadsetDevBegin (const void *rs, U32 msMax, U32 **dDepth);
-MG_HIDDEN MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo,
-                                          U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy);
+MG_HIDDEN MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, const MgRsView *v, U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy);
 MG_HIDDEN void mgReadsetDevForget (const void *rs);
 MG_HIDDEN void mgReadsetDevAppendHits (const void *rs, const U32 *dHit, U64 n);      /* a batch's hit list kept on the device for the end of the file */
 /* modasm -C / -P over a read set on the host (mg_rsdev.hip): 0 = done, 1 = no room on the device (the caller's host loops take it), -1 = failed */
-MG_HIDDEN int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
-                                    U8 *hInfo, int *hNCopy, U32 counts[3]);
-MG_HIDDEN int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv);
+MG_HIDDEN int mgReadsetCleanDevice (const MgRsView *v, U8 *hInfo, int *hNCopy, U32 counts[3]);      /* hInfo: in and out */
+MG_HIDDEN int mgReadsetPropertiesDevice (const MgRsView *v, int *hTally, U32 **hEv, U32 *nEv);
+MG_HIDDEN int mgReadsetCopyTallyDevice (const MgRsView *v, const U8 *hInfo, int *hNCopy);      /* invBuild's nCopy[] from hInfo[], the info[] to be */
 /* modasm's overlap passes (mg_overlap.hip): the pure record of findOverlaps (modasm.c:314-418) per (query, partner) with nHit >= 3.  nPlus / nMinus: as the
    "RH" line prints them (after the order test's decrements); flags: 1 isPlus, 2 isContained */
 typedef struct { U32 iy; U16 nHit, nBadOrder, nBadFlip, nPlus, nMinus, flags; } MgOvlRec;
 typedef struct MgOvlDev MgOvlDev;
-/* Open: the set's arrays go to the device once per call (reads from 1: hHitStart[nReads + 2], hLen[nReads + 1]); 0 = done, 1 = the device has no room (the
+/* Open: the set's arrays go to the device once per call; 0 = done, 1 = the device has no room (the
    caller's host loops take the call), -1 = failed.  Batch: queries[0 .. nq) (read numbers, checked by the caller; their hits together and their candidates
    together below 2^31): nRepeat[nq], start[nq + 1], *recs (malloc ()ed: start[nq] records, a query's by nHit descending then arrival); diag[1..3] are added to.
    0 / 1 (no room for this batch) / -1 */
-MG_HIDDEN int  mgOvlDevOpen (MgOvlDev **d, U32 msMax, const U8 *hInfo, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, const int *hLen, U32 nReads,
-                             const U64 *hInvStart, const U32 *hInvSpace);
+MG_HIDDEN int  mgOvlDevOpen (MgOvlDev **d, const MgRsView *v);
 MG_HIDDEN int  mgOvlDevBatch (MgOvlDev *d, const U32 *queries, U32 nq, U32 *nRepeat, U64 *start, MgOvlRec **recs, U64 diag[4]);
 MG_HIDDEN void mgOvlDevClose (MgOvlDev *d);
 MG_HIDDEN U64  mgOvlDevCandBudget (void);      /* candidates per batch that the free device memory allows */
-/* modasm -R / -T (mg_rdna.hip; the host loops are mg_readset.c's).  checkMod (modasm.c:564-568) and the rules of testMods per (tested mod i, partner m)
+/* modasm -R / -T (mg_rdna.hip; the host loops are mg_rs_rdna.c's).  checkMod (modasm.c:564-568) and the rules of testMods per (tested mod i, partner m)
    (modasm.c:658-705) are written once, here, for the kernels and the host loops alike */
 #ifdef __HIPCC__
 #define MG_BOTH __host__ __device__
@@ -155,17 +164,14 @@ static inline MG_BOTH int mgRdnaLdRule (int n, int dmin, int dmax, const int *st
 #define MG_RDNA_CLEARED 20000
 /* per read 1 .. nReads the hit number of the 200th hit on a mod with qual[] set, from the front (n200, 0: fewer) and, if there is one, from the back
    without ever looking at hit 0 (m200): modasm.c:781-802.  0 / 1 (no room on the device) / -1 */
-MG_HIDDEN int mgRdnaN200Device (U32 msMax, const U8 *hQual, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, int *hN200, int *hM200);
+MG_HIDDEN int mgRdnaN200Device (const MgRsView *v, const U8 *hQual, int *hN200, int *hM200);
 /* testMods over a set on the host.  tested[nTested] ascending, partner[nPartner] ascending (every tested mod is a partner).  Out: per tested mod
    { nGood, nMod2, nSplit } in res3, badLD[msMax + 1] and splitLD[msMax + 1] added to (zeroed by the caller); wantCells: *cells (malloc ()ed) holds
    cellStart[nTested] records, those of tested mod t at [cellStart[t], cellStart[t + 1]), m ascending.  batch: tested mods per batch, 0: by the device's
    free memory.  diag[0] batches, [3] partner occurrences.  0 / 1 (no room) / -1; -2: a visit or a cell the reference cannot do (*badMod: the tested mod); -3: a second tested mod whose count array passes
    MG_RDNA_CLEARED cells */
-typedef struct { U32 msMax; int w, run; const U8 *info; const U16 *depth; const U32 *hit; const U16 *dx; U64 totHit; const U64 *hitStart; const int *len; U32 nReads;
-                 const U64 *invStart; const U32 *invSpace; } MgRdnaSet;
-MG_HIDDEN int mgRdnaTestModsDevice (const MgRdnaSet *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
+MG_HIDDEN int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
                                     int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod);
-MG_HIDDEN int mgReadsetCopyTallyDevice (const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, U32 msMax, int *hNCopy);      /* invBuild's nCopy[] (mg_rsdev.hip); 0 / 1 / -1 */
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;

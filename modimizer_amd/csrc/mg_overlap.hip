@@ -1,6 +1,6 @@
 /* mg_overlap.hip — the device side of modasm's overlap passes (-o1 / -o2 / -b / -c): the part of findOverlaps (modasm.c:314-418) that depends on
  * the hit lists and on info[] / depth[] alone, for a batch of query reads at once.  What depends on the order of the calls -- the reads' `bad` --
- * is replayed by the host (mg_readset.c), so the batches need no ordering between their kernels.
+ * is replayed by the host (mg_rs_overlap.c), so the batches need no ordering between their kernels.
  *
  * Once per call (mgOvlDevOpen): hits, info[], the inverse lists, the reads' lengths; a hit's absolute position is the inclusive sum of its read's dx
  * (a wave per read).  Per batch (mgOvlDevBatch), every step a scan, a stable sort (mg_devsort.hip) or a kernel of independent threads:
@@ -19,8 +19,6 @@
 #include "mg_xfer.h"
 #include "mg_devsort.h"
 
-#define MG_OV_TOPMASK 0x7fffffffu
-#define MG_OV_TOPBIT  0x80000000u
 #define MG_OV_LDS_DEFAULT 1024     /* table entries a wave stages in LDS: 8 KiB a wave, 32 KiB a workgroup of four -- five workgroups on a CU's 160 KiB, 20 of its 32 waves */
 #define MG_OV_LDS_MAX     2048     /* 64 KiB a workgroup */
 #define MG_OV_CAND_BYTES  48       /* device bytes a candidate takes at the peak (its two words, a sort's four arrays and histogram, the run marks) */
@@ -66,7 +64,7 @@ void mgOvElemKernel (U32 nElem, const U32 *__restrict__ qStart, U32 nq, const U3
 {
   for (U64 e = (U64) blockIdx.x * blockDim.x + threadIdx.x ; e < nElem ; e += (U64) gridDim.x * blockDim.x)
     { const U32 q = mgOvLastLE (qStart, nq, (U32) e);
-      const U32 m = hit[hitStart[queries[q]] + (e - qStart[q])] & MG_OV_TOPMASK;
+      const U32 m = hit[hitStart[queries[q]] + (e - qStart[q])] & MG_TOPMASK;
       eQ[e] = q; flag[e] = (info[m] & 3u) == 1u;
     }
 }
@@ -78,7 +76,7 @@ void mgOvCompactKernel (U32 nElem, const U32 *__restrict__ flag, const U32 *__re
   for (U64 e = (U64) blockIdx.x * blockDim.x + threadIdx.x ; e < nElem ; e += (U64) gridDim.x * blockDim.x)
     if (flag[e])
       { const U32 p = place[e], q = eQ[e];
-        cMod[p] = hit[hitStart[queries[q]] + (e - qStart[q])] & MG_OV_TOPMASK; cElem[p] = (U32) e; cQ[p] = q;
+        cMod[p] = hit[hitStart[queries[q]] + (e - qStart[q])] & MG_TOPMASK; cElem[p] = (U32) e; cQ[p] = q;
       }
 }
 __global__ __launch_bounds__ (256)
@@ -110,7 +108,7 @@ void mgOvTableKernel (const U32 *__restrict__ sorted, U32 n1, const U32 *__restr
     if (tFlag[i])
       { const U32 t = tPlace[i], p = sorted[i], q = cQ[p], j = cElem[p] - qStart[q];
         tabMod[t] = cMod[p]; tabQ[t] = q;
-        tabVal[t] = (hit[hitStart[queries[q]] + j] & MG_OV_TOPBIT) | (j + 1);
+        tabVal[t] = (hit[hitStart[queries[q]] + j] & MG_TOPBIT) | (j + 1);
       }
 }
 /* start[q] = the first place of keyQ[0 .. n) (ascending) that holds q or more, for q = 0 .. nq */
@@ -198,19 +196,19 @@ void mgOvPairKernel (U32 nPairs, const U32 *__restrict__ pairQ, const U32 *__res
       U32 hy = 0, val = 0;
       if (j < yN)
         { hy = hit[ya + j];
-          const U32 m = hy & MG_OV_TOPMASK;
+          const U32 m = hy & MG_TOPMASK;
           U32 lo = 0, hi = nT;
           while (lo < hi) { const U32 mid = lo + (hi - lo) / 2; if ((inLds ? lm[mid] : tm[mid]) < m) lo = mid + 1; else hi = mid; }
           if (lo < nT && (inLds ? lm[lo] : tm[lo]) == m) val = inLds ? lv[lo] : tv[lo];
         }
       const bool match = val != 0;                                   /* (j + 1 >= 1) */
-      const U32 ihx = val & MG_OV_TOPMASK;
+      const U32 ihx = val & MG_TOPMASK;
       const U64 bal = __ballot (match);
       if (!bal) continue;
       const U64 below = bal & (((U64) 1 << lane) - 1);
       const U32 fromLane = (U32) __shfl ((int) ihx, below ? 63 - __clzll ((long long) below) : lane);
       if (match)
-        { if (((hy ^ val) & MG_OV_TOPBIT) == 0) ++cPlus; else ++cMinus;
+        { if (((hy ^ val) & MG_TOPBIT) == 0) ++cPlus; else ++cMinus;
           const bool has = below != 0 || any;
           const U32 before = below ? fromLane : prev;
           if (ihx < (has ? before : 0u)) ++cLess;
@@ -243,13 +241,10 @@ void mgOvOutKernel (const U32 *__restrict__ order, U32 n, const MgOvlRec *__rest
 
 /* ---------------------------------------------------------------------------------------- */
 
-static bool mgOvFree (size_t *freeB)
-{ size_t total = 0; if (hipMemGetInfo (freeB, &total) != hipSuccess) { (void) hipGetLastError (); return false; } return true; }
-
 extern "C" U64 mgOvlDevCandBudget (void)
 {
   size_t freeB = 0;
-  if (!mgOvFree (&freeB)) return (U64) 1 << 20;
+  if (!mgDevFreeBytes (&freeB)) return (U64) 1 << 20;
   U64 b = (U64) freeB / 3 / MG_OV_CAND_BYTES;
   if (b < ((U64) 1 << 16)) b = (U64) 1 << 16;
   if (b > ((U64) 1 << 30)) b = (U64) 1 << 30;
@@ -258,27 +253,27 @@ extern "C" U64 mgOvlDevCandBudget (void)
 
 extern "C" void mgOvlDevClose (MgOvlDev *d) { delete d; }
 
-extern "C" int mgOvlDevOpen (MgOvlDev **out, U32 msMax, const U8 *hInfo, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, const int *hLen, U32 nReads,
-                             const U64 *hInvStart, const U32 *hInvSpace)
+extern "C" int mgOvlDevOpen (MgOvlDev **out, const MgRsView *v)
 {
   *out = 0;
   if (mgEnsureDevice ()) return -1;
+  const U32 msMax = v->msMax, nReads = v->nReads; const U64 totHit = v->totHit;
   const size_t m = (size_t) msMax + 1;
-  const U64 listed = hInvStart[m];
+  const U64 listed = v->invStart[m];
   size_t freeB = 0;
   const size_t need = m + m * 8 + 16 + (totHit + 1) * 10 + (listed + 1) * 4 + ((size_t) nReads + 3) * 12 + ((size_t) 128 << 20);      /* and room for a batch */
-  if (!mgOvFree (&freeB) || need >= freeB) return 1;
+  if (!mgDevFreeBytes (&freeB) || need >= freeB) return 1;
   MgOvlDev *d = new MgOvlDev;
-  d->msMax = msMax; d->nReads = nReads; d->totHit = totHit; d->hHitStart = hHitStart;
+  d->msMax = msMax; d->nReads = nReads; d->totHit = totHit; d->hHitStart = v->hitStart;
   MgDevScratch tmp ("modasm's overlaps on the device");
   unsigned short *dDx;
   if (d->scratch.get (&d->info, m) || d->scratch.get (&d->invStart, m + 1) || d->scratch.get (&d->hit, totHit + 1) || d->scratch.get (&d->pos, totHit + 1)
       || d->scratch.get (&d->invSpace, listed + 1) || d->scratch.get (&d->hitStart, (size_t) nReads + 3) || d->scratch.get (&d->len, (size_t) nReads + 2) || tmp.get (&dDx, totHit + 1)
       || hipDeviceSynchronize ())
     { delete d; return -1; }
-  if (mgXferH2D (d->info, hInfo, m) || mgXferH2D (d->invStart, hInvStart, (m + 1) * 8) || mgXferH2D (d->hitStart, hHitStart, ((size_t) nReads + 2) * 8)
-      || mgXferH2D (d->len, hLen, ((size_t) nReads + 1) * sizeof (int))
-      || (totHit && (mgXferH2D (d->hit, hHit, totHit * 4) || mgXferH2D (dDx, hDx, totHit * 2))) || (listed && mgXferH2D (d->invSpace, hInvSpace, listed * 4)))
+  if (mgXferH2D (d->info, v->info, m) || mgXferH2D (d->invStart, v->invStart, (m + 1) * 8) || mgXferH2D (d->hitStart, v->hitStart, ((size_t) nReads + 2) * 8)
+      || mgXferH2D (d->len, v->len, ((size_t) nReads + 1) * sizeof (int))
+      || (totHit && (mgXferH2D (d->hit, v->hit, totHit * 4) || mgXferH2D (dDx, v->dx, totHit * 2))) || (listed && mgXferH2D (d->invSpace, v->invSpace, listed * 4)))
     { delete d; return -1; }
   if (nReads && totHit) MG_LAUNCH (MG_K_OVL_ACTIVE, 0, mgOvPosKernel, dim3 (mgOvGrid ((U64) nReads * 64)), dim3 (256), 0, 0, dDx, d->hitStart, nReads, d->pos);
   if (hipGetLastError () != hipSuccess || hipStreamSynchronize (0) != hipSuccess) { tmp.fail (); delete d; return -1; }
@@ -316,7 +311,7 @@ extern "C" int mgOvlDevBatch (MgOvlDev *d, const U32 *queries, U32 nq, U32 *nRep
   *recsOut = recs;
   if (!nElem) return 0;
   size_t freeB = 0;
-  if (!mgOvFree (&freeB) || (size_t) nElem * 44 + ((size_t) 64 << 20) >= freeB) { free (recs); *recsOut = 0; return 1; }
+  if (!mgDevFreeBytes (&freeB) || (size_t) nElem * 44 + ((size_t) 64 << 20) >= freeB) { free (recs); *recsOut = 0; return 1; }
   MgDevScratch scratch ("modasm's overlaps on the device");
   U32 *dQStart, *dQueries, *dRepeat, *eQ, *flag, *place;
   if (scratch.get (&dQStart, (size_t) nq + 1) || scratch.get (&dQueries, nq) || scratch.get (&dRepeat, nq) || scratch.get (&eQ, nElem) || scratch.get (&flag, nElem) || scratch.get (&place, nElem)) goto failed;
@@ -344,7 +339,7 @@ extern "C" int mgOvlDevBatch (MgOvlDev *d, const U32 *queries, U32 nq, U32 *nRep
     diag[1] += nCand;
     if (nCand >= 0x7fffffffu) { mgSetError ("overlaps: a batch of 2^31 candidates or more"); goto failed; }
     if (!nCand) return 0;
-    if (!mgOvFree (&freeB) || (size_t) nCand * MG_OV_CAND_BYTES + ((size_t) 64 << 20) >= freeB) { free (recs); *recsOut = 0; return 1; }
+    if (!mgDevFreeBytes (&freeB) || (size_t) nCand * MG_OV_CAND_BYTES + ((size_t) 64 << 20) >= freeB) { free (recs); *recsOut = 0; return 1; }
     /* ---- the candidates, grouped by (query, y) ---- */
     U32 *candY, *candQ, *byY, *keyCQ, *byQY, *head, *rid, *runStart, *keep, *kPlace;
     if (scratch.get (&candY, nCand) || scratch.get (&candQ, nCand) || scratch.get (&keyCQ, nCand) || scratch.get (&head, nCand) || scratch.get (&rid, nCand)) goto failed;

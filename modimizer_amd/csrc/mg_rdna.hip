@@ -2,7 +2,7 @@
  *
  * -R: per read the hit number of the 200th hit on a core-and-reference mod from either end (modasm.c:781-802), a wave per read: ballots of
  * 64 hits, their popcounts added up, the lane of the 200th picked by its rank in the ballot.  The walk between the two numbers depends on the
- * order of the reads and is the host's (mg_readset.c).
+ * order of the reads and is the host's (mg_rs_rdna.c).
  *
  * -T: the reference gathers, per tested mod i and per read that holds it, one (partner mod, signed distance) for every other hit that passes
  * checkMod, sorts them, and then uses per partner m only the count and the first and the last distance.  Count, min and max are commutative
@@ -25,7 +25,6 @@
 #include "mg_internal.h"
 #include "mg_xfer.h"
 
-#define MG_RD_TOPMASK 0x7fffffffu
 #define MG_RD_NONE    0xffffffffu
 #define MG_RD_TILE    4096           /* partner ordinals per workgroup: three words each, 48 KiB of LDS */
 #define MG_RD_WAVES   4              /* waves per workgroup of 256 */
@@ -50,7 +49,7 @@ void mgRdnaN200Kernel (const U32 *__restrict__ hit, const U64 *__restrict__ hitS
   U32 fwd = 0, back = 0, n = 0;
   for (U32 base = 0 ; base < nHit ; base += 64)
     { const U32 j = base + lane;
-      const bool q = j < nHit && qual[hit[h0 + j] & MG_RD_TOPMASK];
+      const bool q = j < nHit && qual[hit[h0 + j] & MG_TOPMASK];
       const U64 mask = __ballot (q);
       const U32 c = (U32) __popcll (mask);
       if (n + c >= 200) { fwd = base + mgRdnaNthLane (mask, q, lane, 200 - n); break; }
@@ -61,7 +60,7 @@ void mgRdnaN200Kernel (const U32 *__restrict__ hit, const U64 *__restrict__ hitS
       for (U32 base = 0 ; base + 1 < nHit ; base += 64)
         { const U32 o = base + lane;
           const bool v = o + 1 < nHit;
-          const bool q = v && qual[hit[h0 + (nHit - 1 - o)] & MG_RD_TOPMASK];
+          const bool q = v && qual[hit[h0 + (nHit - 1 - o)] & MG_TOPMASK];
           const U64 mask = __ballot (q);
           const U32 c = (U32) __popcll (mask);
           if (n + c >= 200) { back = nHit - 1 - (base + mgRdnaNthLane (mask, q, lane, 200 - n)); break; }
@@ -73,23 +72,24 @@ void mgRdnaN200Kernel (const U32 *__restrict__ hit, const U64 *__restrict__ hitS
 
 static bool mgRdnaRoom (size_t bytes, size_t *freeOut)
 {
-  size_t freeB = 0, total = 0;
-  if (hipMemGetInfo (&freeB, &total) != hipSuccess) { (void) hipGetLastError (); return false; }
+  size_t freeB = 0;
+  if (!mgDevFreeBytes (&freeB)) return false;
   if (freeOut) *freeOut = freeB;
   return bytes + ((size_t) 64 << 20) < freeB;
 }
 
-/* hQual[msMax + 1], hHit[totHit], hHitStart[nReads + 2] (reads from 1): in; hN200[nReads + 1], hM200[nReads + 1]: out */
-extern "C" int mgRdnaN200Device (U32 msMax, const U8 *hQual, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, int *hN200, int *hM200)
+/* hQual[msMax + 1], v's hit lists: in; hN200[nReads + 1], hM200[nReads + 1]: out */
+extern "C" int mgRdnaN200Device (const MgRsView *v, const U8 *hQual, int *hN200, int *hM200)
 {
+  const U32 nReads = v->nReads; const U64 totHit = v->totHit;
   if (!nReads) return 0;
   if (mgEnsureDevice ()) return -1;
-  const size_t m = (size_t) msMax + 1;
+  const size_t m = (size_t) v->msMax + 1;
   if (!mgRdnaRoom (m + (totHit + 1) * 4 + ((size_t) nReads + 3) * 16, 0)) return 1;
   MgDevScratch scratch ("modasm -R on the device");
   U8 *dQual; U32 *dHit; U64 *dStart; int *dN, *dM;
   if (scratch.get (&dQual, m) || scratch.get (&dHit, totHit + 1) || scratch.get (&dStart, (size_t) nReads + 3) || scratch.get (&dN, (size_t) nReads + 2) || scratch.get (&dM, (size_t) nReads + 2)) return -1;
-  if (mgXferH2D (dQual, hQual, m) || mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, hHit, totHit * 4))) return -1;
+  if (mgXferH2D (dQual, hQual, m) || mgXferH2D (dStart, v->hitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, v->hit, totHit * 4))) return -1;
   hipLaunchKernelGGL (mgRdnaN200Kernel, dim3 ((nReads + MG_RD_WAVES - 1) / MG_RD_WAVES), dim3 (256), 0, 0, dHit, dStart, nReads, dQual, dN, dM);
   if (hipGetLastError () != hipSuccess || hipStreamSynchronize (0)) { scratch.fail (); return -1; }
   if (mgXferD2H (hN200 + 1, dN + 1, (size_t) nReads * 4, MG_XFER_COPY) || mgXferD2H (hM200 + 1, dM + 1, (size_t) nReads * 4, MG_XFER_COPY)) return -1;
@@ -110,7 +110,7 @@ void mgRdnaPosKernel (const U32 *__restrict__ hit, const unsigned short *__restr
       for (U64 base = h0 ; base < h1 ; base += 64)
         { const U64 h = base + lane;
           const U32 inc = mgWaveInclusiveSum (h < h1 ? (U32) dx[h] : 0u);
-          if (h < h1) { pos[h] = (int) (carry + inc); hord[h] = ordOf[hit[h] & MG_RD_TOPMASK]; }
+          if (h < h1) { pos[h] = (int) (carry + inc); hord[h] = ordOf[hit[h] & MG_TOPMASK]; }
           carry += (U32) __shfl ((int) inc, 63);
         }
     }
@@ -132,7 +132,7 @@ void mgRdnaVisitKernel (const U32 *__restrict__ tested, const U64 *__restrict__ 
       U64 first = ~(U64) 0;
       for (U64 base = h0 ; base < h1 ; base += 64)
         { const U64 h = base + lane;
-          const U64 mask = __ballot (h < h1 && (hit[h] & MG_RD_TOPMASK) == i);
+          const U64 mask = __ballot (h < h1 && (hit[h] & MG_TOPMASK) == i);
           if (mask) { first = base + (U64) (__ffsll ((long long) mask) - 1); break; }
         }
       if (lane) continue;
@@ -142,7 +142,7 @@ void mgRdnaVisitKernel (const U32 *__restrict__ tested, const U64 *__restrict__ 
         { const int x = pos[first], o = len[r] - x - w;
           if (o < 0 || x < 0 || (U32) x >= E || (U32) o >= E) mgRdnaRaise (err, 1u, i);      /* modasm.c:630,636 would write before the array */
           else
-            { const bool fwd = (hit[first] & ~MG_RD_TOPMASK) != 0;
+            { const bool fwd = (hit[first] & ~MG_TOPMASK) != 0;
               const int s = fwd ? x : o, e = fwd ? o : x;
               atomicAdd (&startArr[(size_t) b * E + s], 1); atomicAdd (&endArr[(size_t) b * E + e], 1);
               atomicMax (&ext[2 * b], s + 1); atomicMax (&ext[2 * b + 1], e + 1);
@@ -186,7 +186,7 @@ void mgRdnaAccumKernel (const U32 *__restrict__ tested, const U64 *__restrict__ 
       const U32 r = invSpace[v];
       const U64 h0 = hitStart[r], h1 = hitStart[r + 1];
       const int x = pos[f];
-      const bool fwd = (hit[f] & ~MG_RD_TOPMASK) != 0;
+      const bool fwd = (hit[f] & ~MG_TOPMASK) != 0;
       for (U64 h = h0 + lane ; h < h1 ; h += 64)                      /* every other hit of the read, later occurrences of i itself among them */
         { const U32 o = hord[h] - tile0;
           if (h == f || o >= MG_RD_TILE) continue;                   /* (MG_RD_NONE - tile0 is no ordinal of a tile either) */
@@ -253,7 +253,7 @@ void mgRdnaEmitKernel (MgRdnaCells C, const U32 *__restrict__ cellAt, MgLdCell *
     }
 }
 
-extern "C" int mgRdnaTestModsDevice (const MgRdnaSet *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
+extern "C" int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
                                      int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod)
 {
   if (cells) *cells = 0;

@@ -19,7 +19,6 @@
 #include "mg_xfer.h"
 #include "mg_devsort.h"
 
-#define MG_RS_TOPMASK 0x7fffffffu
 struct MgReadsetDev { U32 *depth = 0; size_t cap = 0; U32 *hitAll = 0; U64 hitLen = 0, hitCap = 0; bool hitsKept = true; };      /* hitAll: the file's hit lists so far, kept on the device for the inverse lists (given up, and uploaded at the end instead, if the device has no room) */
 static std::mutex gRsLock;
 static std::unordered_map<const void *, MgReadsetDev> gRsDev;
@@ -80,7 +79,7 @@ __global__ void mgRsKeyValKernel (const U32 *__restrict__ hit, U64 nHit, const U
                                   U32 *__restrict__ key, U32 *__restrict__ val)
 {
   for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
-    { const U32 y = hit[h] & MG_RS_TOPMASK;
+    { const U32 y = hit[h] & MG_TOPMASK;
       key[h] = depth32[y] < 0xffffu ? y : msMax + 1;
       val[h] = mgRsReadOf (hitStart, nReads, h);
     }
@@ -95,18 +94,18 @@ void mgRsCopyTallyKernel (const U32 *__restrict__ hit, const U64 *__restrict__ h
   for (U64 h = h0 ; h < h1 ; h += 8)
     { U32 cl[8];
 #pragma unroll
-      for (int j = 0 ; j < 8 ; ++j) cl[j] = h + j < h1 ? (U32) info[hit[h + j] & MG_RS_TOPMASK] & 3u : 4u;      /* eight gathers in flight */
+      for (int j = 0 ; j < 8 ; ++j) cl[j] = h + j < h1 ? (U32) info[hit[h + j] & MG_TOPMASK] & 3u : 4u;      /* eight gathers in flight */
 #pragma unroll
       for (int j = 0 ; j < 8 ; ++j) { c[0] += cl[j] == 0; c[1] += cl[j] == 1; c[2] += cl[j] == 2; c[3] += cl[j] == 3; }
     }
   nCopy[r] = make_int4 (c[0], c[1], c[2], c[3]);
 }
 
-/* hHit[totHit], hHitStart[nReads + 2] (reads from 1; [nReads + 1] = totHit), hInfo[msMax + 1]: in.  hDepth16[msMax + 1], hInvStart[msMax + 2],
-   *hInvSpace (malloc ()ed here, the lists' total length words), hNCopy[(nReads + 1) * 4]: out.  totHit < 2^32 - 1. */
-extern "C" MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo,
-                                           U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy)
+/* v's hit lists and info[]: in.  hDepth16[msMax + 1], hInvStart[msMax + 2], *hInvSpace (malloc ()ed here, the lists' total length words),
+   hNCopy[(nReads + 1) * 4]: out.  totHit < 2^32 - 1. */
+extern "C" MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, const MgRsView *v, U16 *hDepth16, U64 *hInvStart, U32 **hInvSpace, int *hNCopy)
 {
+  const U32 msMax = v->msMax, nReads = v->nReads; const U64 totHit = v->totHit;
   *hInvSpace = 0;
   MgReadsetDev d;
   bool kept = false;
@@ -125,7 +124,7 @@ extern "C" MgStatus mgReadsetFinishDevice (const void *rs, Modset *ms, U32 msMax
   if (scratch.get (&dCnt, m + 2) || scratch.get (&dD16, m + 1) || scratch.get (&dInv64, m + 2) || scratch.get (&dInfo, m) || scratch.get (&dStart, (size_t) nReads + 3)
       || scratch.get (&dNc, (size_t) nReads + 2) || (!kept && scratch.get (&dHit, totHit + 1)) || scratch.get (&dKey, totHit + 1) || scratch.get (&dVal, totHit + 1)) return MG_ERR_HIP;
   if (hipDeviceSynchronize ()) return scratch.fail ();
-  if ((s = mgXferH2DSparse (dInfo, hInfo, m)) || (s = mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8)) || (totHit && !kept && (s = mgXferH2D (dHit, hHit, totHit * 4)))) return s;
+  if ((s = mgXferH2DSparse (dInfo, v->info, m)) || (s = mgXferH2D (dStart, v->hitStart, ((size_t) nReads + 2) * 8)) || (totHit && !kept && (s = mgXferH2D (dHit, v->hit, totHit * 4)))) return s;
   hipLaunchKernelGGL (mgRsCountKernel, dim3 (2048), dim3 (256), 0, st, d.depth, msMax, dCnt, dD16);
   if ((s = mgExclusiveScan (scratch, dCnt, dCnt, m + 1, st))) return s;      /* dCnt[i] = first place of mod i's list; [msMax + 1] = the lists' total */
   hipLaunchKernelGGL (mgRsWidenKernel, dim3 (2048), dim3 (256), 0, st, dCnt, (U64) m + 1, dInv64);
@@ -165,12 +164,12 @@ void mgRsCleanNeighbourKernel (const U32 *__restrict__ hit, const unsigned short
                                const unsigned short *__restrict__ depth, int w, U32 *__restrict__ info32, U32 *__restrict__ key, U32 *__restrict__ rd)
 {
   for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
-    { const U32 y = hit[h] & MG_RS_TOPMASK;
+    { const U32 y = hit[h] & MG_TOPMASK;
       const U32 r = mgRsReadOf (hitStart, nReads, h);
       key[h] = y; rd[h] = r;
       if (h >= nClean || h == hitStart[r]) continue;                 /* the rules are about a hit and the one before it in the read */
       if (h + 1 < hitStart[r + 1] && (int) dx[h] < w && (int) dx[h + 1] < w) mgRsInfoOr (info32, y, MS_INTERNAL);
-      const U32 p = hit[h - 1] & MG_RS_TOPMASK;
+      const U32 p = hit[h - 1] & MG_TOPMASK;
       const int lastDepth = depth[p], thisDepth = depth[y];
       if (lastDepth > 2 * thisDepth) mgRsInfoOr (info32, y, MS_MINOR);
       if (thisDepth > 2 * lastDepth) mgRsInfoOr (info32, p, MS_MINOR);
@@ -203,21 +202,19 @@ static size_t mgRsSortScratchWords (U64 n) { return (size_t) 256 * ((n + MG_RSOR
 /* is there room for `bytes` of arrays next to what a stable sort of n elements with keys takes itself (two value and two key arrays, its histogram)? */
 static bool mgRsRoom (size_t bytes, U64 n)
 {
-  size_t freeB = 0, total = 0;
-  if (hipMemGetInfo (&freeB, &total) != hipSuccess) { (void) hipGetLastError (); return false; }
-  const size_t need = bytes + (size_t) n * 16 + mgRsSortScratchWords (n) * 4 + ((size_t) 64 << 20);
-  return need < freeB;
+  size_t freeB = 0;
+  return mgDevFreeBytes (&freeB) && bytes + (size_t) n * 16 + mgRsSortScratchWords (n) * 4 + ((size_t) 64 << 20) < freeB;
 }
 
-/* hHit[totHit], hDx[totHit], hHitStart[nReads + 2] (reads from 1), hDepth16[msMax + 1]: in; hInfo[msMax + 1]: in and out; hNCopy[(nReads + 1) * 4],
-   counts[3]: out.  totHit < 2^32 - 16.  0 = done, 1 = the device has no room (nothing was changed: the caller takes its host loops), -1 = failed */
-extern "C" int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U16 *hDx, U64 totHit, const U64 *hHitStart, U32 nReads, const U16 *hDepth16,
-                                     U8 *hInfo, int *hNCopy, U32 counts[3])
+/* v's hit lists, distances and depth[]: in; hInfo[msMax + 1]: in and out; hNCopy[(nReads + 1) * 4], counts[3]: out.  totHit < 2^32 - 16.
+   0 = done, 1 = the device has no room (nothing was changed: the caller takes its host loops), -1 = failed */
+extern "C" int mgReadsetCleanDevice (const MgRsView *v, U8 *hInfo, int *hNCopy, U32 counts[3])
 {
   if (mgEnsureDevice ()) return -1;
+  const U32 msMax = v->msMax, nReads = v->nReads; const U64 totHit = v->totHit;
   hipStream_t st = 0;
   const size_t m = (size_t) msMax + 1, m4 = (m + 3) / 4 * 4;
-  const U64 nClean = nReads > 1 ? hHitStart[nReads] : 0;             /* the hits of reads 1 .. nReads - 1 */
+  const U64 nClean = nReads > 1 ? v->hitStart[nReads] : 0;          /* the hits of reads 1 .. nReads - 1 */
   const size_t scanTiles = mgScanScratchWords (mgRsSortScratchWords (totHit));
   const size_t bytes = m4 + m * 2 + ((size_t) nReads + 3) * 8 + ((size_t) nReads + 2) * sizeof (int4) + (totHit + 1) * 14 + scanTiles * 4 + 64;
   if (!mgRsRoom (bytes, nClean)) return 1;
@@ -226,10 +223,10 @@ extern "C" int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U1
   if (scratch.get (&dCounts, 4) || scratch.get (&dD16, m) || scratch.get (&dInfo, m4) || scratch.get (&dStart, (size_t) nReads + 3) || scratch.get (&dNc, (size_t) nReads + 2)
       || scratch.get (&dHit, totHit + 1) || scratch.get (&dDx, totHit + 1) || scratch.get (&dKey, totHit + 1) || scratch.get (&dRd, totHit + 1)) return -1;
   if (hipMemset (dCounts, 0, 16) || hipMemset (dInfo + (m4 - 4), 0, 4) || hipDeviceSynchronize ()) { scratch.fail (); return -1; }
-  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dD16, hDepth16, m * 2) || mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8)
-      || (totHit && (mgXferH2D (dHit, hHit, totHit * 4) || mgXferH2D (dDx, hDx, totHit * 2)))) return -1;
+  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dD16, v->depth, m * 2) || mgXferH2D (dStart, v->hitStart, ((size_t) nReads + 2) * 8)
+      || (totHit && (mgXferH2D (dHit, v->hit, totHit * 4) || mgXferH2D (dDx, v->dx, totHit * 2)))) return -1;
   if (totHit)
-    hipLaunchKernelGGL (mgRsCleanNeighbourKernel, dim3 (4096), dim3 (256), 0, st, dHit, dDx, totHit, nClean, dStart, nReads, dD16, w, (U32 *) dInfo, dKey, dRd);
+    hipLaunchKernelGGL (mgRsCleanNeighbourKernel, dim3 (4096), dim3 (256), 0, st, dHit, dDx, totHit, nClean, dStart, nReads, dD16, v->w, (U32 *) dInfo, dKey, dRd);
   if (nClean > 1)
     { if (mgRefStableSort (scratch, dKey, 0, (U32) nClean, mgKeyBits (msMax), &dSorted, st)) return -1;
       hipLaunchKernelGGL (mgRsCleanRepeatKernel, dim3 (4096), dim3 (256), 0, st, dSorted, nClean, dKey, dRd, (U32 *) dInfo);
@@ -243,16 +240,17 @@ extern "C" int mgReadsetCleanDevice (U32 msMax, int w, const U32 *hHit, const U1
 
 /* invBuild's nCopy[] alone (modasm.c:273-277), after a pass that changed copy classes and nothing else (-rb, -T): hNCopy[(nReads + 1) * 4] out.
    0 = done, 1 = the device has no room, -1 = failed */
-extern "C" int mgReadsetCopyTallyDevice (const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, U32 msMax, int *hNCopy)
+extern "C" int mgReadsetCopyTallyDevice (const MgRsView *v, const U8 *hInfo, int *hNCopy)
 {
+  const U32 nReads = v->nReads; const U64 totHit = v->totHit;
   if (!nReads) return 0;
   if (mgEnsureDevice ()) return -1;
-  const size_t m = (size_t) msMax + 1;
+  const size_t m = (size_t) v->msMax + 1;
   if (!mgRsRoom (m + ((size_t) nReads + 3) * 8 + ((size_t) nReads + 2) * sizeof (int4) + (totHit + 1) * 4, 0)) return 1;
   MgDevScratch scratch ("read set copy tallies on the device");
   U32 *dHit; U64 *dStart; U8 *dInfo; int4 *dNc;
   if (scratch.get (&dInfo, m) || scratch.get (&dStart, (size_t) nReads + 3) || scratch.get (&dNc, (size_t) nReads + 2) || scratch.get (&dHit, totHit + 1)) return -1;
-  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, hHit, totHit * 4))) return -1;
+  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dStart, v->hitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, v->hit, totHit * 4))) return -1;
   hipLaunchKernelGGL (mgRsCopyTallyKernel, dim3 ((nReads + 255) / 256), dim3 (256), 0, 0, dHit, dStart, nReads, dInfo, dNc);
   if (hipGetLastError () != hipSuccess || hipStreamSynchronize (0)) { scratch.fail (); return -1; }
   if (mgXferD2H (hNCopy + 4, dNc + 1, (size_t) nReads * sizeof (int4), MG_XFER_COPY)) return -1;
@@ -266,14 +264,14 @@ __global__ __launch_bounds__ (256)
 void mgRsPropFlagKernel (const U32 *__restrict__ hit, U64 nHit, const U64 *__restrict__ hitStart, U32 nReads, const U8 *__restrict__ info, U32 *__restrict__ flag, U32 *__restrict__ rd)
 {
   for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
-    { flag[h] = (info[hit[h] & MG_RS_TOPMASK] & 3u) == 1u; rd[h] = mgRsReadOf (hitStart, nReads, h); }
+    { flag[h] = (info[hit[h] & MG_TOPMASK] & 3u) == 1u; rd[h] = mgRsReadOf (hitStart, nReads, h); }
 }
 /* the flagged hits in order: key = the mod, value = the hit's ordinal */
 __global__ __launch_bounds__ (256)
 void mgRsPropCompactKernel (const U32 *__restrict__ hit, U64 nHit, const U32 *__restrict__ flag, const U32 *__restrict__ place, U32 *__restrict__ key, U32 *__restrict__ val)
 {
   for (U64 h = (U64) blockIdx.x * blockDim.x + threadIdx.x ; h < nHit ; h += (U64) gridDim.x * blockDim.x)
-    if (flag[h]) { key[place[h]] = hit[h] & MG_RS_TOPMASK; val[place[h]] = (U32) h; }
+    if (flag[h]) { key[place[h]] = hit[h] & MG_TOPMASK; val[place[h]] = (U32) h; }
 }
 /* sorted[0 .. n): ordinals of the copy-1 hits by mod, in hit order inside a mod, so a run of equal (mod, read) is what one read holds of one mod.
    The lane of a run's first element walks it (runs are short: a mod that a read holds three times is the rare case), counts the forward (bit 31)
@@ -284,14 +282,14 @@ void mgRsPropRunKernel (const U32 *__restrict__ sorted, U64 n, const U32 *__rest
                         U32 *__restrict__ evFlag, U32 *__restrict__ evMod, U32 *__restrict__ evCount)
 {
   for (U64 i = (U64) blockIdx.x * blockDim.x + threadIdx.x ; i < n ; i += (U64) gridDim.x * blockDim.x)
-    { const U32 o = sorted[i], y = hit[o] & MG_RS_TOPMASK, r = rd[o];
+    { const U32 o = sorted[i], y = hit[o] & MG_TOPMASK, r = rd[o];
       evFlag[i] = 0;
-      if (i) { const U32 q = sorted[i - 1]; if ((hit[q] & MG_RS_TOPMASK) == y && rd[q] == r) continue; }      /* not the first of its run */
+      if (i) { const U32 q = sorted[i - 1]; if ((hit[q] & MG_TOPMASK) == y && rd[q] == r) continue; }      /* not the first of its run */
       U32 f = 0, rv = 0;
       for (U64 j = i ; j < n ; ++j)
         { const U32 hj = hit[sorted[j]];
-          if ((hj & MG_RS_TOPMASK) != y || rd[sorted[j]] != r) break;
-          if (hj & ~MG_RS_TOPMASK) ++f; else ++rv;
+          if ((hj & MG_TOPMASK) != y || rd[sorted[j]] != r) break;
+          if (hj & ~MG_TOPMASK) ++f; else ++rv;
         }
       int *t = tally + (size_t) r * 5;
       atomicAdd (&t[0], 1);
@@ -301,7 +299,7 @@ void mgRsPropRunKernel (const U32 *__restrict__ sorted, U64 n, const U32 *__rest
       else
         { const bool tan = !f || !rv;
           atomicAdd (&t[tan ? 3 : 4], 1);
-          evFlag[i] = 1; evMod[i] = y | (tan ? ~MG_RS_TOPMASK : 0u); evCount[i] = f + rv;
+          evFlag[i] = 1; evMod[i] = y | (tan ? ~MG_TOPMASK : 0u); evCount[i] = f + rv;
         }
     }
 }
@@ -321,13 +319,14 @@ void mgRsPropGatherKernel (const U32 *__restrict__ order, U32 n, const U32 *__re
     { const U32 e = order[j]; ev[3 * j] = inRead[e]; ev[3 * j + 1] = inMod[e]; ev[3 * j + 2] = inCount[e]; }
 }
 
-/* hHit[totHit], hHitStart[nReads + 2], hInfo[msMax + 1]: in.  hTally[(nReads + 1) * 5]: out, per read { n, n2Tan, n2Rev, nMoreTan, nMoreRev }.  *hEv (malloc ()ed
+/* v's hit lists and info[]: in.  hTally[(nReads + 1) * 5]: out, per read { n, n2Tan, n2Rev, nMoreTan, nMoreRev }.  *hEv (malloc ()ed
    here): *nEv triples (read, mod | bit 31 if in one orientation, count), one per mod that a read holds more than twice, by read, by mod inside a read.
    totHit < 2^32 - 16.  0 = done, 1 = the device has no room, -1 = failed */
-extern "C" int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit, const U64 *hHitStart, U32 nReads, const U8 *hInfo, int *hTally, U32 **hEv, U32 *nEv)
+extern "C" int mgReadsetPropertiesDevice (const MgRsView *v, int *hTally, U32 **hEv, U32 *nEv)
 {
   *hEv = 0; *nEv = 0;
   if (mgEnsureDevice ()) return -1;
+  const U32 msMax = v->msMax, nReads = v->nReads; const U64 totHit = v->totHit;
   hipStream_t st = 0;
   const size_t m = (size_t) msMax + 1, tallyBytes = ((size_t) nReads + 1) * 5 * sizeof (int);
   const size_t histWords = mgRsSortScratchWords (totHit), scanTiles = mgScanScratchWords (histWords > totHit ? histWords : totHit);
@@ -339,7 +338,7 @@ extern "C" int mgReadsetPropertiesDevice (U32 msMax, const U32 *hHit, U64 totHit
       || scratch.get (&dRd, totHit + 1) || scratch.get (&dFlag, totHit + 1) || scratch.get (&dPlace, totHit + 1) || scratch.get (&dKey, totHit + 1) || scratch.get (&dVal, totHit + 1)
       || scratch.get (&dEvMod, totHit + 1) || scratch.get (&dEvCount, totHit + 1)) return -1;
   if (hipMemset (dTally, 0, tallyBytes) || hipDeviceSynchronize ()) { scratch.fail (); return -1; }
-  if (mgXferH2D (dInfo, hInfo, m) || mgXferH2D (dStart, hHitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, hHit, totHit * 4))) return -1;
+  if (mgXferH2D (dInfo, v->info, m) || mgXferH2D (dStart, v->hitStart, ((size_t) nReads + 2) * 8) || (totHit && mgXferH2D (dHit, v->hit, totHit * 4))) return -1;
   U32 n1 = 0, nE = 0;                                                /* the copy-1 hits; the events */
   if (totHit)
     { hipLaunchKernelGGL (mgRsPropFlagKernel, dim3 (4096), dim3 (256), 0, st, dHit, totHit, dStart, nReads, dInfo, dFlag, dRd);

@@ -1018,9 +1018,38 @@ static int forEachBatchFrom (const char *filename, size_t startOff, U64 startLin
 
 static int forEachBatch (const char *filename, int (*fn) (MgSeqBatch *, void *), void *ctx)
 { return forEachBatchFrom (filename, 0, 1, 0, fn, ctx); }
-/* for the callers in other files (mg_readset.c): the host parser from byte startOff on (0, line 1, no sequence before: the whole file) */
-int mgSeqForEachBatchFrom (const char *filename, size_t startOff, U64 startLine, U64 startSeq, int (*fn) (MgSeqBatch *, void *), void *ctx)
-{ return forEachBatchFrom (filename, startOff, startLine, startSeq, fn, ctx); }
+
+/* a host parser's batch for a callback that takes device batches: uploaded, its ids as one block and their offsets in it (the ids share one block:
+   mgSeqBatchFree) */
+typedef struct { MgTextBatchFn devFn; void *ctx; } WalkUpload;
+static int walkUploadBatch (MgSeqBatch *b, void *v)
+{
+  WalkUpload *u = (WalkUpload *) v;
+  if (b->nSeq <= 0) return 0;
+  U64 *idOff = (U64 *) malloc ((size_t) b->nSeq * 8);
+  if (!idOff) return -1;
+  for (int r = 0 ; r < b->nSeq ; ++r) idOff[r] = (U64) (b->names[r] - b->names[0]);
+  MgDevBatch d; mgBatchUpload (&d, b->bases, b->offsets, b->nSeq);
+  const int rc = u->devFn (u->ctx, (const U32 *) d.dPacked, d.total, (const U64 *) d.dOff, (U32) b->nSeq, b->names[0], idOff, 0);
+  mgBatchFree (&d);
+  free (idOff);
+  return rc;
+}
+
+/* plain FASTA / FASTQ text is parsed on the device (mg_textgpu.hip) and goes to devFn batch by batch; gzip, a last line without its newline (-2): the host
+   parser over the whole file; FASTQ that breaks a rule (-3): the host parser from the first record the device parser has not handed on.  hostFn takes the
+   host parser's batches, 0: each is uploaded and goes to devFn */
+int mgSeqWalkFile (const char *filename, MgTextBatchFn devFn, int (*hostFn) (MgSeqBatch *, void *), void *ctx, U64 batchBases, U64 batchRecs, U64 *nSeq, U64 *totLen)
+{
+  WalkUpload u; u.devFn = devFn; u.ctx = ctx;
+  void *hostCtx = hostFn ? ctx : (void *) &u;
+  if (!hostFn) hostFn = walkUploadBatch;
+  U64 resumeOff = 0, resumeLine = 1;
+  int rc = mgTextForEachBatchDevice (filename, devFn, ctx, batchBases, batchRecs, nSeq, totLen, &resumeOff, &resumeLine);
+  if (rc == -2) rc = forEachBatch (filename, hostFn, hostCtx);
+  else if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, *nSeq, hostFn, hostCtx);
+  return rc;
+}
 
 typedef struct { Modset *ms; U64 nSeq, totLen, totHash; } AddCtx;
 static int addBatch (MgSeqBatch *b, void *v)
@@ -1155,19 +1184,6 @@ int mgQueryFile (MgReference *ref, const char *filename, FILE *out)            /
 typedef struct { Modset *ms; MgTextOut *w; void *scratch; } PaintCtx;
 static int paintDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *idBytes, const U64 *idOff, void *stream)
 { PaintCtx *c = (PaintCtx *) v; (void) stream; return mgRefPaintBatchDevice (c->ms, dPacked, total, dOff, nReads, idBytes, idOff, c->w, &c->scratch); }
-static int paintHostBatch (MgSeqBatch *b, void *v)
-{
-  PaintCtx *c = (PaintCtx *) v;
-  if (b->nSeq <= 0) return 0;
-  U64 *idOff = (U64 *) malloc ((size_t) b->nSeq * 8);
-  if (!idOff) return -1;
-  for (int r = 0 ; r < b->nSeq ; ++r) idOff[r] = (U64) (b->names[r] - b->names[0]);      /* the ids share one block (mgSeqBatchFree) */
-  MgDevBatch d; mgBatchUpload (&d, b->bases, b->offsets, b->nSeq);
-  const int rc = mgRefPaintBatchDevice (c->ms, (const U32 *) d.dPacked, d.total, (const U64 *) d.dOff, (U32) b->nSeq, b->names[0], idOff, c->w, &c->scratch);
-  mgBatchFree (&d);
-  free (idOff);
-  return rc;
-}
 #define MG_PAINT_FILE_BATCH 128000000ull
 
 int mgRefPaintFile (Modset *ms, const char *filename, FILE *out)
@@ -1179,15 +1195,13 @@ int mgRefPaintFile (Modset *ms, const char *filename, FILE *out)
     fclose (f);
   }
   if (mgIterRequireDevice ()) return -1;
+  { MgSeqReader *r = mgSeqOpen (filename);                  /* (what the host parser cannot take -- and so the device parser neither: the reference's seqIOopenRead fails) */
+    if (!r) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); return -1; }
+    mgSeqClose (r);
+  }
   PaintCtx c; c.ms = ms; c.w = mgTextOutOpen (out); c.scratch = 0;
-  U64 nSeq = 0, totLen = 0, resumeOff = 0, resumeLine = 1;
-  int rc = mgTextForEachBatchDevice (filename, paintDeviceBatch, &c, MG_PAINT_FILE_BATCH, 1, &nSeq, &totLen, &resumeOff, &resumeLine);
-  if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, nSeq, paintHostBatch, &c);
-  else if (rc == -2)
-    { MgSeqReader *r = mgSeqOpen (filename);                /* (what the host parser cannot take either: the reference's seqIOopenRead fails) */
-      if (!r) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); rc = -1; }
-      else { mgSeqClose (r); rc = forEachBatch (filename, paintHostBatch, &c); }
-    }
+  U64 nSeq = 0, totLen = 0;
+  int rc = mgSeqWalkFile (filename, paintDeviceBatch, 0, &c, MG_PAINT_FILE_BATCH, 1, &nSeq, &totLen);
   if (mgTextOutClose (c.w) && !rc) { mgSetErrorText ("mgRefPaintFile: write failed"); rc = -1; }
   mgRefPaintScratchFree (c.scratch);
   return rc ? -1 : 0;

@@ -70,7 +70,7 @@ def test_oracle_readset_vs_reference_program(tag, golden_dir, tmp_path):
     rs.close(); ms.close()
 
 
-# ---- the library (mg_readset.c) ----
+# ---- the library (mg_readset.c; the passes in mg_rs_clean.c, mg_rs_overlap.c, mg_rs_rdna.c have test files of their own) ----
 
 def lib_arrays(rs):
     r = rs.contents
@@ -142,10 +142,8 @@ def test_readset_file_read_gpu(tag, golden_dir, tmp_path):
     L.mgReadsetDestroy(rs)
 
 
-@pytest.mark.gpu
-def test_readset_vs_oracle_saturation_and_batches(tmp_path):
-    """a k-mer hit more than 65535 times (depth saturates, no inverse list: modasm.c:174,266,278), empty
-    and short reads, reads on both strands; the same reads in one call and through a file in batches"""
+def saturation_case(tmp_path):
+    """eight reads and an oracle modset, written to a .mod file: a k-mer hit more than 65535 times, an empty and a short read, both strands"""
     from oracle import pyoracle as orc
     rng = np.random.default_rng(11)
     k, w = 15, 1
@@ -156,11 +154,19 @@ def test_readset_vs_oracle_saturation_and_batches(tmp_path):
     for s in (reads[0][:100], g):
         oms.add_sequence(s)
     oms.set_copy(1, 2, 3)
+    p = str(tmp_path / "m.mod"); oms.write_mod(p)
+    return reads, oms, p
+
+
+@pytest.mark.gpu
+def test_readset_vs_oracle_saturation_and_batches(tmp_path):
+    """a k-mer hit more than 65535 times (depth saturates, no inverse list: modasm.c:174,266,278), empty
+    and short reads, reads on both strands; the same reads in one call and through a file in batches"""
+    from oracle import pyoracle as orc
+    reads, oms, p = saturation_case(tmp_path)      # the same modset for the library: through a .mod file
     ors = orc.Readset(oms); ors.read(reads)
     want = ors.arrays()
     assert int(oms.depths().max()) == 65535
-    # the same modset for the library: through a .mod file
-    p = str(tmp_path / "m.mod"); oms.write_mod(p)
     L = mg.lib()
     for mode in ("memory", "file"):
         with mg.CFile(p, "r") as f:
@@ -185,6 +191,45 @@ def test_readset_vs_oracle_saturation_and_batches(tmp_path):
         assert rs_lines(stats_text(rs, str(tmp_path / "s.txt"))) == rs_lines(ors.stats_text(str(tmp_path / "o.txt")))
         L.mgReadsetDestroy(rs)
     ors.close(); oms.close()
+
+
+@pytest.mark.gpu
+def test_readset_second_read_into_a_set_with_hits(tmp_path):
+    """the same eight reads in two calls of four: the second call finds hits in the set, so depth[], the inverse lists and nCopy[] are made
+    from all the hits by the host loops; checked against their definitions over the hit lists, then written, loaded (the lists made again
+    from the file's depth[]) and compared"""
+    reads, oms, p = saturation_case(tmp_path)
+    L = mg.lib()
+    with mg.CFile(p, "r") as f:
+        ms = L.modsetRead(f)
+    rs = L.mgReadsetCreate(ms)
+    for part in (reads[:4], reads[4:]):
+        bases, offs = util.concat_reads(part)
+        assert L.mgReadsetRead(rs, bases.ctypes.data, offs.ctypes.data, len(part)) == 0
+    a = lib_arrays(rs)
+    n, m = rs.contents.nReads, ms.contents.max
+    assert n == 8 and a["totHit"] > 65535
+    info = np.ctypeslib.as_array(ms.contents.info, (m + 1,)).copy()
+    mod = (a["hit"] & np.uint32(0x7fffffff)).astype(np.int64)
+    assert mod.min() >= 1 and mod.max() <= m
+    depth = np.minimum(np.bincount(mod, minlength=m + 1), 65535)
+    assert depth.max() == 65535
+    assert np.array_equal(np.ctypeslib.as_array(ms.contents.depth, (m + 1,)), depth)
+    listed = np.where((depth > 0) & (depth < 65535), depth, 0)
+    assert np.array_equal(a["invStart"], np.concatenate(([0], np.cumsum(listed))).astype(np.uint64))
+    start = a["hitStart"].astype(np.int64)
+    read_of = np.repeat(np.arange(1, n + 1), np.diff(start))
+    keep = listed[mod] > 0
+    assert keep.any() and not keep.all()
+    assert np.array_equal(a["invSpace"], read_of[keep][np.argsort(mod[keep], kind="stable")])
+    n_copy = np.array([np.bincount(info[mod[start[r]:start[r + 1]]] & 3, minlength=4) for r in range(n)])
+    assert np.array_equal(a["nCopy"], n_copy) and (n_copy.sum(axis=0) > 0).sum() >= 2
+    out = str(tmp_path / "twice")
+    L.mgReadsetWrite(rs, out.encode())
+    rs2 = L.mgReadsetLoad(out.encode())
+    same(a, lib_arrays(rs2))
+    L.mgReadsetDestroy(rs); L.mgReadsetDestroy(rs2)
+    oms.close()
 
 
 # ---- more than 1024 tiles of seeds in one batch: the tile scan (mgRsTileScanKernel) past one count per thread ----

@@ -6,6 +6,7 @@ set; prints the runs, their median and spread, the counters of mgReadsetOverlaps
 usage: python tools/readset_overlap_probe.py [--reads N] [--len L] [--cov C] [--k K] [--w W] [--runs R] [--no-ref] [--no-host] [out.json]"""
 import argparse
 import ctypes as C
+import gzip
 import json
 import os
 import subprocess
@@ -56,6 +57,9 @@ def make_files(d, a):
     bits = max(20, int(np.ceil(np.log2(2.0 * G / a.w))) + 2)      # (a set holds a quarter of its table's slots)
     subprocess.check_call([os.path.join(REF, "modutils_ref"), "-c", str(bits), str(a.k), str(a.w), "17", "-a", "src.fa", "-s", "1", "2", "3", "-w", "src.mod"],
                           cwd=d, stdout=subprocess.DEVNULL)
+    raw = open(os.path.join(d, "src.mod"), "rb").read()
+    if raw[:2] == b"\x1f\x8b":                                     # the reference program writes gzip; modsetRead takes the plain bytes
+        open(os.path.join(d, "src.mod"), "wb").write(gzip.decompress(raw))
     L = mg.lib()
     with mg.CFile(os.path.join(d, "src.mod"), "r") as f:
         ms = L.modsetRead(f)
