@@ -170,7 +170,7 @@ void mgChainCompactKernel (const MgChainQ *__restrict__ q, const MgChainM *__res
 /* the device arrays of a query batch (the seed list among them: mgSeedsOfBatch sizes it).  A call allocates and frees them; a caller with many batches in a row (mgQueryFile: one per
    window of the file) keeps them between its calls (mgChainScratchKeep): ten allocations and frees a batch are milliseconds.  What
    such a caller leaves stays allocated, like the text parser's windows, until mgReleaseBuffers () or a call that does not keep.
-   The scratch belongs to the calling HOST THREAD and to the device it was allocated on (like the iterator's scratch, mg_api.hip): a
+   The scratch belongs to the calling HOST THREAD and to the device it was allocated on (like the iterator's scratch, mg_hostbatch.hip): a
    thread that has moved to another GPU (mgSetDevice) drops it and starts again there, two threads driving two GPUs share nothing
    and do not wait for each other, and a thread that ends gives its blocks back. */
 enum { CS_START, CS_Q, CS_M, CS_OV, CS_MC, CS_REC, CS_N };

@@ -327,7 +327,7 @@ MgStatus mgTableFindSegments (MgTable *t, const MgSegSrc &src, U64 n, U32 *dInde
 MgStatus mgTableLoadHost (MgTable *t, const U64 *dValue, U32 first, U32 last, hipStream_t st);
 MgStatus mgTableExportDepth (MgTable *t, U16 *dDelta, hipStream_t st);
 MgStatus mgTableHistogram (MgTable *t, U64 *dHist, hipStream_t st);
-MgStatus mgModsetTableForPass (Modset *ms, MgTable **t);            /* mg_api.hip: a set's device table for a pass that only reads it; *t = 0: it has none */
+MgStatus mgModsetTableForPass (Modset *ms, MgTable **t);            /* mg_modsetdev.hip: a set's device table for a pass that only reads it; *t = 0: it has none */
 MgStatus mgTableReplayIndex (MgTable *t, const MgHashParams &p, int tableBits, U32 *dIndex, hipStream_t st);
 MgStatus mgTableMergeApply (const U32 *dIdx, const U16 *dDepth2, const U8 *dInfo2, U32 n2, U16 *dBaseDepth, U8 *dInfo1, hipStream_t st);
 size_t   mgTablePruneScratchBytes (U32 n);

@@ -1,5 +1,5 @@
 /* mg_internal.h — private glue between mg_host.c (reference-compatible scalar API, plain C)
- * and mg_api.hip (device state).  Not part of the public ABI. */
+ * and mg_modsetdev.hip (device state).  Not part of the public ABI. */
 #ifndef MG_INTERNAL_H
 #define MG_INTERNAL_H
 #include "modgpu.h"
@@ -55,7 +55,7 @@ MG_HIDDEN int mgSeqWalkFile (const char *filename, MgTextBatchFn devFn, int (*ho
 MG_HIDDEN void mgBatchUpload (MgDevBatch *b, const char *bases, const int64_t *offsets, int nReads);
 MG_HIDDEN void mgBatchFree (MgDevBatch *b);
 MG_HIDDEN FILE *mgTagOpen (const char *root, const char *tag, const char *mode);
-/* The seed list of a device batch (mg_api.hip): scan + lookups (insert: + inserts, modmap.c:109) with positions, in (read, pos) order, misses
+/* The seed list of a device batch (mg_reads.hip): scan + lookups (insert: + inserts, modmap.c:109) with positions, in (read, pos) order, misses
    included.  The ONE place that guesses a capacity, makes the three arrays, and goes round again when the guess was short.
      arrays   device arrays of cap entries each (hipMalloc), grow-only: while cap covers what an attempt needs nothing is allocated, else all three
               are freed and made again with room for need + need * sparePct / 100 + 1 entries.  A caller that wants them for one call starts from a
@@ -172,7 +172,7 @@ MG_HIDDEN int mgRdnaN200Device (const MgRsView *v, const U8 *hQual, int *hN200, 
    MG_RDNA_CLEARED cells */
 MG_HIDDEN int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
                                     int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod);
-MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_api.hip) */
+MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_modsetdev.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;
 MG_HIDDEN MgTextOut *mgTextOutOpen (FILE *out);

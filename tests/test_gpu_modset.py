@@ -398,6 +398,64 @@ def test_query_batches_pipelined_equal_synchronous(path):
     L.modsetDestroy(ms)
 
 
+def test_pipelined_query_retries_when_the_scan_guess_is_too_small():
+    """mgQueryReadsDeviceWait on a batch with more modimizers than the capacity mgQueryReadsDeviceAsync scanned it with (the runs of a of
+    _poly_a_records, w = 2): the scan goes round again on the library's stream, with an ordinary batch's scan queued behind it there.  Both
+    batches against the oracle -- posF and read from its scan of each record, index from its set -- and against mgQueryReadsDevice."""
+    L = mg.lib()
+    k, w, seed = 21, 2, 17
+    oh = po.Hasher(k, w, seed)
+    g, reads = _poly_a_records(k)
+    ordinary = [g[500:2500], _revcomp(g[4000:9000]), g[10_000:10_030], g[17_000:19_000]]
+    oms = po.Modset(oh, 20)
+    for s in (np.zeros(100, np.uint8), g):                                        # a record of 100 a: the runs hit
+        oms.add_sequence(s)
+
+    def expected(recs):
+        offs = np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.int64)
+        bases = np.concatenate(recs)
+        qk, qp, qf, qst = util.oracle_scan_batch(oh, bases, offs)
+        uk, inv = np.unique(qk, return_inverse=True)
+        ix = np.array([oms.find(int(x)) for x in uk], np.uint32)[inv]
+        posf = qp.astype(np.uint32) | (qf.astype(np.uint32) << 31)
+        rid = np.repeat(np.arange(len(recs), dtype=np.uint32), np.diff(qst))
+        return bases, offs, [ix, posf, rid]
+    b1, o1, want1 = expected(reads)
+    b2, o2, want2 = expected(ordinary)
+    total = int(o1[-1])
+    print("first capacity %d, modimizers of the batch %d" % (_scan_guess(w, total), len(want1[0])))
+    assert _scan_guess(w, total) < len(want1[0]) <= total                         # (on the CPU, before any device call: the first scan is too small)
+    assert (want1[0] != 0).sum() > 390_000 and (want1[0] == 0).any() and (want2[0] != 0).all()
+
+    sh = mg.seqhashCreate(k, w, seed); ms = mg.modsetCreate(sh, 20)
+    mg.add_sequence_batch(ms, np.concatenate([np.zeros(100, np.uint8), g]), np.array([0, 100, 100 + len(g)], np.int64))
+    assert ms.contents.max == oms.max
+    dev = []
+    for bases, offs, want in ((b1, o1, want1), (b2, o2, want2)):
+        cap = len(want[0]) + 5
+        dev.append((mg.DeviceBuffer.from_numpy(mg.pack_host(bases)), mg.DeviceBuffer.from_numpy(offs.astype(np.uint64)), int(offs[-1]), len(offs) - 1, cap))
+    n = C.c_uint64()
+    d_p, d_o, tot, nr, cap = dev[0]
+    sync = [mg.DeviceBuffer(cap * 4) for _ in range(3)]
+    mg.check(L.mgQueryReadsDevice(ms, d_p.ptr, tot, d_o.ptr, nr, sync[0].ptr, sync[1].ptr, sync[2].ptr, cap, C.byref(n), None))
+    assert n.value == len(want1[0])
+    sync = [o.to_numpy(np.uint32, n.value) for o in sync]
+    tickets, outs = [], []
+    for d_p, d_o, tot, nr, cap in dev:                                            # both started before the first is waited for
+        o = [mg.DeviceBuffer(cap * 4) for _ in range(3)]
+        t = C.c_void_p()
+        mg.check(L.mgQueryReadsDeviceAsync(ms, d_p.ptr, tot, d_o.ptr, nr, o[0].ptr, o[1].ptr, o[2].ptr, cap, C.byref(t), None))
+        tickets.append(t); outs.append(o)
+    for i, want in enumerate((want1, want2)):
+        mg.check(L.mgQueryReadsDeviceWait(tickets[i], C.byref(n), None))
+        assert n.value == len(want[0]), i
+        for j, (o, w_) in enumerate(zip(outs[i], want)):
+            got = o.to_numpy(np.uint32, n.value)
+            assert np.array_equal(got, w_), (i, "index posF read".split()[j])
+            assert i or np.array_equal(got, sync[j]), j
+    L.modsetDestroy(ms)
+
+
 def test_full_size_build_properties():
     """BASELINE config 2 at full size (10 Gbp, table bits 30) plus a 1 Gbp run: properties that
     hold for any correct modset build — sum of depths == number of modimizers (no saturation here),
@@ -758,11 +816,15 @@ def test_modmap_query_many_blocks_overflow(tmp_path):
     assert sum(l.startswith("M\tstitched") for l in outs[0].splitlines()) > 16
 
 
-# ---- a batch with more seeds than the first guess: the second round of mgSeedsOfBatch (mg_api.hip) behind the reference build and both query paths ----
+# ---- a batch with more seeds than the first guess: the second round of mgSeedsOfBatch (mg_reads.hip) behind the reference build and both query paths ----
 
 def _seed_guess(w, total):
     g = total // w
     return min(g + g // 2 + 65536, total + 1)                                    # mg_internal.h, mgSeedGuess
+
+
+def _scan_guess(w, total):
+    return min(total // w * 5 // 4 + 65536, total)                               # mgSurvivorGuess: the capacity a batch is first scanned with
 
 
 def _poly_a_records(k):
