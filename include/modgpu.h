@@ -481,7 +481,57 @@ int  mgRepRunFinish (MgRepRun *run, FILE *err, MgRepResult *res) ;
 /* modrep.c:170-268 from files: the .mod through mgFzOpen, the reads in batches through mgSeqOpen / mgSeqNextBatch (N read as A).  0 / -1 with
  * the program's message ("failed to open mod file %s", "failed to read modset from file %s", "can't open sequence file %s") */
 int  mgRepAnalyze3File (MgRepRef *ref, const char *seqFile, const char *modFile, FILE *out, FILE *err, MgRepResult *res) ;
-int  mgRepPath (void) ;                      /* test hook: the calling thread's last run: 0 = finished through the device kernels, -1 = it failed or none ran */
+int  mgRepPath (void) ;                      /* test hook: the calling thread's last run (-s3, -s1 or -s2): 0 = finished through the device kernels, -1 = it failed or none ran */
+
+/* modrep -s1 <reads.fa> <reads.mod> (analyzeSequences1, modrep.c:272-489) and -s2 (analyzeSequences2, modrep.c:493-539) on the device
+ * (mg_modrep1.hip).  -s1's per-read pass is -s3's without the BADREAD lines (modrep.c:305-310 print nothing) and without the per-read
+ * duplicate array: the same MgRepRun, mgRepRunAdd called with out = 0.  The end of the file (modrep.c:354-480) runs in kernels:
+ *   cleanMods, five times (modrep.c:354,370,392,424,446), each printing "NMOD mod0 %d modSmall %d modBig %d modGood %d": over
+ *     i = 0 .. max - 1, n[i] < 5 and n[i] > reads / 2 are zeroed, then the hits on mods with n == 0 leave the reads;
+ *   the run removal (modrep.c:356-369): in a read a hit stays if x >= xNext, then xNext = x + k; the others take 1 from their mod's n;
+ *   buildPrePost, four times (modrep.c:373,395,427,449): every pair of neighbouring hits of a read is a link (k0, k1, dx); mod k0's post
+ *     list gets (k1, n, x = sum of dx), mod k1's pre list (k0, n, x), nPost[k0] and nPre[k1] count the links.  addHit (modrep.c:129-148)
+ *     moves an entry to the front when its count passes the front's; the order that leaves is computed in closed form;
+ *   the mod verdicts (modrep.c:374-391,428-445), which read pre[0] of an EMPTY pre list, too: what the last non-empty build left there;
+ *   the weak links (modrep.c:395-415): a read with a link that fewer than 5 reads share leaves, "reduced %d reads to %d reads" goes to err;
+ *     then n[] is counted again over every hit of a read but its last (modrep.c:417-423);
+ *   the report (modrep.c:449-480): "MOD .." per surviving mod, the reads sorted by their k sequences (readOrder; equal reads stay in input
+ *     order, as glibc's merge sort leaves them), "READ .." per read and "BLOCK .." after every block of equal reads but the last.
+ * The program's array of mods has max entries and is indexed by entries up to max: a file in which entry max of the second set occurs in
+ * a read is refused (-1, mgLastError () says so, nothing is printed).  err gets "read %d reads, %d bad, %d good: " and a newline where
+ * the program writes its timing. */
+typedef struct {
+  int nRead, nBad, nGood ;                   /* modrep.c:351 (0 from mgRepAnalyze1Hits but nGood) */
+  U32 max ;                                  /* ms->max */
+  int nmod[5][4] ;                           /* the five NMOD lines: mod0, modSmall, modBig, modGood */
+  int readsBefore, readsAfter ;              /* modrep.c:414 */
+  int *modN, *modNPre, *modNPost ;           /* [max + 1]: mods[].n, nPre, nPost as the report finds them */
+  U64 *preStart, *postStart ;                /* [max + 2]: mod i's lists are pre* [preStart[i] .. preStart[i + 1]) and post* likewise, in list order */
+  int *preK, *preN, *preX, *postK, *postN, *postX ;      /* Hit.k (the partner), Hit.n, Hit.x */
+  int *readI ;                               /* [readsAfter]: Read.i of the surviving reads, sorted (modrep.c:463) */
+  U64 *hitStart ;                            /* [readsAfter + 1]: sorted read r's mods are hitK [hitStart[r] .. hitStart[r + 1]) */
+  int *hitK ;
+} MgRep1Result ;
+void mgRep1ResultFree (MgRep1Result *res) ;  /* the arrays (malloc); res itself is the caller's */
+/* modrep.c:351-480 for a run whose batches were added with out = 0: the lines to out and err (0: not printed), the results into res
+ * (0: not wanted); frees the run, also on error, as mgRepRunFinish does.  0 / -1 */
+int  mgRepRunFinish1 (MgRepRun *run, FILE *out, FILE *err, MgRep1Result *res) ;
+/* modrep.c:272-489 from files, as mgRepAnalyze3File */
+int  mgRepAnalyze1File (MgRepRef *ref, const char *seqFile, const char *modFile, FILE *out, FILE *err, MgRep1Result *res) ;
+/* the file's end alone (modrep.c:354-480) on hit lists the caller holds: read r (Read.i = readI[r]) has the hits hitK / hitX
+ * [hitStart[r] .. hitStart[r + 1]), 1 <= k <= max, 0 <= x; K: the hasher's k.  Uploads them and runs the kernels.  0 / -1 */
+int  mgRepAnalyze1Hits (U32 max, int K, int nReads, const int *readI, const U64 *hitStart, const int *hitK, const int *hitX,
+                        FILE *out, FILE *err, MgRep1Result *res) ;
+/* modrep.c:520-535 for a batch (bases 0..3, offsets[nReads + 1]): the reads as they are, scanned with the reference set's hasher; a read that
+ * holds the reference's entries 1 and 961 adds to counts4[0], 961 and 1951 to [1], 1951 and 2961 to [2], 2961 and 1 to [3].  0 / -1 */
+int  mgRepCount2 (MgRepRef *ref, const char *bases, const int64_t *offsets, int nReads, int counts4[4]) ;
+/* modrep.c:498-539 from files: counts4 is zeroed, "n1 %d n2 %d n3 %d n4 %d" goes to out (0: not printed).  The second .mod file is opened
+ * and read as the program does (and fails with its messages); nothing else is done with it */
+int  mgRepAnalyze2File (MgRepRef *ref, const char *seqFile, const char *modFile, FILE *out, int counts4[4]) ;
+/* test hook: the calling thread's last -s1 end: [0] builds made, [1] links of the largest build, [2] entries of its post lists, [3] hits
+ * removed as runs, [4] reads removed for weak links, [5] mods whose verdict read a pre[0] that an earlier build had left (the list
+ * being empty now), [6] kernels launched, [7] 0 */
+void mgRep1Diag (U64 out8[8]) ;
 
 /* The file front end (seqio.c:30-346 for FASTA / FASTQ text, plain, gzip or blocked gzip, with the callers'
  * dna2indexConv + N->0 conversion): records are cut out of the text and converted by a pool of

@@ -78,6 +78,16 @@ class MgRepResult(C.Structure):       # include/modgpu.h (modrep.c:170-268)
                 ("nMod", C.c_int), ("nDup", C.c_int), ("tDup", C.c_int), ("minMax", C.c_int)]
 
 
+class MgRep1Result(C.Structure):      # include/modgpu.h (modrep.c:272-489)
+    _fields_ = [("nRead", C.c_int), ("nBad", C.c_int), ("nGood", C.c_int), ("max", C.c_uint32), ("nmod", (C.c_int * 4) * 5),
+                ("readsBefore", C.c_int), ("readsAfter", C.c_int),
+                ("modN", C.POINTER(C.c_int)), ("modNPre", C.POINTER(C.c_int)), ("modNPost", C.POINTER(C.c_int)),
+                ("preStart", U64P), ("postStart", U64P),
+                ("preK", C.POINTER(C.c_int)), ("preN", C.POINTER(C.c_int)), ("preX", C.POINTER(C.c_int)),
+                ("postK", C.POINTER(C.c_int)), ("postN", C.POINTER(C.c_int)), ("postX", C.POINTER(C.c_int)),
+                ("readI", C.POINTER(C.c_int)), ("hitStart", U64P), ("hitK", C.POINTER(C.c_int))]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -104,6 +114,7 @@ EXPORTS = [
     "mgReadsetFindOverlaps", "mgOverlapsFree", "mgReadsetOverlapStats", "mgReadsetMarkBadReads", "mgReadsetMarkContained", "mgReadsetOverlapsPath", "mgReadsetOverlapsDiag",
     "mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetModInfo", "mgReadsetReadFlags", "mgReadsetTestModsRun", "mgReadsetRdnaPath", "mgReadsetRdnaDiag",
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
+    "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
@@ -264,6 +275,10 @@ def lib():
     sig("mgRepRefCreate", RR, C.c_char_p, C.c_char_p, vp); sig("mgRepRefFromArrays", RR, MS, vp, i64, vp); sig("mgRepRefDestroy", None, RR)
     sig("mgRepRunBegin", vp, RR, MS); sig("mgRepRunAdd", i32, vp, vp, vp, i32, vp); sig("mgRepRunFinish", i32, vp, vp, RES); sig("mgRepResultFree", None, RES)
     sig("mgRepAnalyze3File", i32, RR, C.c_char_p, C.c_char_p, vp, vp, RES); sig("mgRepPath", i32)
+    RES1 = C.POINTER(MgRep1Result)
+    sig("mgRep1ResultFree", None, RES1); sig("mgRepRunFinish1", i32, vp, vp, vp, RES1); sig("mgRepAnalyze1File", i32, RR, C.c_char_p, C.c_char_p, vp, vp, RES1)
+    sig("mgRepAnalyze1Hits", i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, RES1); sig("mgRepCount2", i32, RR, vp, vp, i32, vp)
+    sig("mgRepAnalyze2File", i32, RR, C.c_char_p, C.c_char_p, vp, vp); sig("mgRep1Diag", None, vp)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -744,3 +759,96 @@ def rep_run(ref, ms, batches, out_path, err_path):
     if rc or rf:
         raise ModgpuError("modrep -s3 failed: " + (msg or L.mgLastError().decode()))
     return _rep_result(res)
+
+
+def _rep1_result(res):
+    """the arrays of an MgRep1Result as numpy copies in a dict; frees the C arrays"""
+    def arr(ptr, count, dtype):
+        return np.ctypeslib.as_array(ptr, (max(count, 1),))[:count].astype(dtype, copy=True)
+    m = res.max
+    pre_s, post_s = arr(res.preStart, m + 2, np.int64), arr(res.postStart, m + 2, np.int64)
+    hs = arr(res.hitStart, res.readsAfter + 1, np.int64)
+    out = dict(nRead=res.nRead, nBad=res.nBad, nGood=res.nGood, max=m, nmod=np.array([list(row) for row in res.nmod], np.int32),
+               readsBefore=res.readsBefore, readsAfter=res.readsAfter,
+               modN=arr(res.modN, m + 1, np.int32), modNPre=arr(res.modNPre, m + 1, np.int32), modNPost=arr(res.modNPost, m + 1, np.int32),
+               preStart=pre_s, postStart=post_s)
+    for side, start in (("pre", pre_s), ("post", post_s)):
+        for f in "KNX":
+            out[side + f] = arr(getattr(res, side + f), int(start[-1]), np.int32)
+    out.update(readI=arr(res.readI, res.readsAfter, np.int32), hitStart=hs, hitK=arr(res.hitK, int(hs[-1]), np.int32))
+    lib().mgRep1ResultFree(C.byref(res))
+    return out
+
+
+def rep_analyze1_file(ref, seq_path, mod_path, out_path, err_path):
+    """mgRepAnalyze1File: modrep -s1 (modrep.c:272-489): the NMOD / MOD / BLOCK / READ lines into the file `out_path`, the two stderr lines
+    into `err_path`.  Returns the MgRep1Result as a dict of numpy arrays and ints; raises ModgpuError with the library's message."""
+    res = MgRep1Result()
+    with CFile(out_path, "w") as fo, CFile(err_path, "w") as fe:
+        rc = lib().mgRepAnalyze1File(ref, seq_path.encode(), mod_path.encode(), fo, fe, C.byref(res))
+    if rc:
+        raise ModgpuError("mgRepAnalyze1File failed: " + lib().mgLastError().decode())
+    return _rep1_result(res)
+
+
+def rep_run1(ref, ms, batches, out_path, err_path):
+    """mgRepRunBegin / mgRepRunAdd (out = 0) per (bases, offsets) of `batches` / mgRepRunFinish1: modrep -s1 on reads in memory"""
+    L = lib()
+    run = L.mgRepRunBegin(ref, ms)
+    if not run:
+        raise ModgpuError("mgRepRunBegin failed: " + L.mgLastError().decode())
+    res = MgRep1Result()
+    with CFile(out_path, "w") as fo, CFile(err_path, "w") as fe:
+        rc = 0
+        for bases, offsets in batches:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            rc = L.mgRepRunAdd(run, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, None)
+            if rc:
+                break
+        msg = L.mgLastError().decode() if rc else ""
+        rf = L.mgRepRunFinish(run, None, None) if rc else L.mgRepRunFinish1(run, fo, fe, C.byref(res))
+    if rc or rf:
+        raise ModgpuError("modrep -s1 failed: " + (msg or L.mgLastError().decode()))
+    return _rep1_result(res)
+
+
+def rep_analyze1_hits(max_, k, read_i, hit_start, hit_k, hit_x, out_path, err_path):
+    """mgRepAnalyze1Hits: the end of a -s1 file (modrep.c:354-480) on hit lists in memory; lines and result as rep_analyze1_file"""
+    read_i = np.ascontiguousarray(read_i, dtype=np.int32)
+    hit_start = np.ascontiguousarray(hit_start, dtype=np.uint64)
+    hit_k = np.ascontiguousarray(hit_k, dtype=np.int32)
+    hit_x = np.ascontiguousarray(hit_x, dtype=np.int32)
+    res = MgRep1Result()
+    with CFile(out_path, "w") as fo, CFile(err_path, "w") as fe:
+        rc = lib().mgRepAnalyze1Hits(max_, k, len(read_i), read_i.ctypes.data, hit_start.ctypes.data, hit_k.ctypes.data, hit_x.ctypes.data, fo, fe, C.byref(res))
+    if rc:
+        raise ModgpuError("mgRepAnalyze1Hits failed: " + lib().mgLastError().decode())
+    return _rep1_result(res)
+
+
+def rep_count2(ref, bases, offsets, counts=None):
+    """mgRepCount2: modrep -s2's four counts (modrep.c:520-535) of a batch added to `counts` (a list of 4 ints; None: zeros); returns the list"""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    c = (C.c_int * 4)(*(counts or [0, 0, 0, 0]))
+    if lib().mgRepCount2(ref, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, c):
+        raise ModgpuError("mgRepCount2 failed: " + lib().mgLastError().decode())
+    return list(c)
+
+
+def rep_analyze2_file(ref, seq_path, mod_path, out_path):
+    """mgRepAnalyze2File: modrep -s2 (modrep.c:498-539): its one line into the file `out_path`; returns the four counts"""
+    c = (C.c_int * 4)()
+    with CFile(out_path, "w") as fo:
+        rc = lib().mgRepAnalyze2File(ref, seq_path.encode(), mod_path.encode(), fo, c)
+    if rc:
+        raise ModgpuError("mgRepAnalyze2File failed: " + lib().mgLastError().decode())
+    return list(c)
+
+
+def rep1_diag():
+    """mgRep1Diag: dict(builds, links, entries, runs, dropped, stale, kernels) of the calling thread's last -s1 end"""
+    v = (C.c_uint64 * 8)()
+    lib().mgRep1Diag(v)
+    return dict(zip(("builds", "links", "entries", "runs", "dropped", "stale", "kernels"), (int(x) for x in v)))

@@ -25,12 +25,14 @@
 #include "mg_prefix.h"
 #include "mg_internal.h"
 #include "mg_devsort.h"
+#include "mg_modrep_int.h"
 
 #define MG_REP_VOTES 100u         /* modrep.c:197,204 */
 #define MG_REP_MIXED 10u          /* modrep.c:204 */
 
 static thread_local int gRepPath = -1;
 extern "C" int mgRepPath (void) { return gRepPath; }
+void mgRepPathSet (int path) { gRepPath = path; }
 
 /* first i in [0, n) with rid[i] >= r, n if there is none: rid[] ascends, the scan's output being in (read, pos) order */
 __device__ __forceinline__ U64 mgRepLowerBound (const U32 *__restrict__ rid, U64 n, U32 r)
@@ -209,8 +211,7 @@ __global__ void mgRepMinAfterKernel (const U32 *__restrict__ readMax, U32 nGood,
 
 /* the modimizers of a device batch scanned with scanWith (0: the set's own hasher), in (read, pos) order, and their indices in ms (0: absent):
    the library's seed list (mgSeedsOfBatch) from modrep's own first guess, its arrays handed to the scratch */
-struct MgRepSeeds : MgSeedBufs { U64 n; };
-static MgStatus mgRepSeedList (MgDevScratch &scratch, Modset *ms, const Seqhash *scanWith, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, MgRepSeeds *o, hipStream_t st)
+MgStatus mgRepSeedList (MgDevScratch &scratch, Modset *ms, const Seqhash *scanWith, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, MgRepSeeds *o, hipStream_t st)
 {
   const int w = (scanWith ? scanWith : ms->hasher)->w;
   U64 guess = total / (U64) (w > 0 ? w : 1) * 2 + 4096; if (guess > total + 16) guess = total + 16;
@@ -223,7 +224,7 @@ static MgStatus mgRepSeedList (MgDevScratch &scratch, Modset *ms, const Seqhash 
 }
 
 /* host bases -> packed words and offsets in the scratch */
-static MgStatus mgRepUpload (MgDevScratch &scratch, const char *bases, const int64_t *offsets, U32 nReads, U64 total, U32 **dPacked, U64 **dOff, hipStream_t st)
+MgStatus mgRepUpload (MgDevScratch &scratch, const char *bases, const int64_t *offsets, U32 nReads, U64 total, U32 **dPacked, U64 **dOff, hipStream_t st)
 {
   MgStatus s;
   if (scratch.get (dPacked, mgPackedWords (total)) || scratch.get (dOff, (size_t) nReads + 1)) return MG_ERR_HIP;
@@ -276,7 +277,7 @@ extern "C" MgRepRef *mgRepRefFromArrays (Modset *ms, const char *bases, int64_t 
 }
 
 /* a .mod file, gzip or plain: 0 with the program's message if it cannot be opened */
-static Modset *mgRepReadSet (const char *modFile)
+Modset *mgRepReadSet (const char *modFile)
 {
   FILE *f = mgFzOpen (modFile, "r");
   if (!f) { mgSetError ("failed to open mod file %s", modFile); return 0; }      /* modrep.c:34,180 */
@@ -284,7 +285,7 @@ static Modset *mgRepReadSet (const char *modFile)
   fclose (f);
   return ms;
 }
-static void mgRepSetDestroy (Modset *ms) { if (ms) { Seqhash *sh = ms->hasher; modsetDestroy (ms); if (sh) mgSeqhashDestroy (sh); } }
+void mgRepSetDestroy (Modset *ms) { if (ms) { Seqhash *sh = ms->hasher; modsetDestroy (ms); if (sh) mgSeqhashDestroy (sh); } }
 
 extern "C" MgRepRef *mgRepRefCreate (const char *seqFile, const char *modFile, FILE *err)
 {
@@ -310,16 +311,6 @@ extern "C" MgRepRef *mgRepRefCreate (const char *seqFile, const char *modFile, F
 }
 
 /* ---- -s3 ---- */
-
-struct MgRepRun {
-  MgRepRef *ref = 0; Modset *ms = 0; int device = 0;
-  MgDevBuf<U8> refIsF;                                /* ref->isF[0 .. max] */
-  MgDevBuf<U32> hitK, hitX, hitRead; U64 nHit = 0;    /* the file's hits so far: modset index, position in the oriented read, good read ordinal */
-  std::vector<int> n, seqF, seqR; std::vector<U8> bad, isF;      /* per read */
-  std::vector<int> goodI, goodLen; std::vector<U64> hitStart;      /* per good read; hitStart: one more entry */
-  int nBad = 0;
-  ~MgRepRun () { refIsF.drop (); hitK.drop (); hitX.drop (); hitRead.drop (); }
-};
 
 extern "C" MgRepRun *mgRepRunBegin (MgRepRef *ref, Modset *ms)
 {
@@ -444,13 +435,6 @@ extern "C" void mgRepResultFree (MgRepResult *res)
   memset (res, 0, sizeof (*res));
 }
 
-template <class T, class S> static T *mgRepCopyOut (const std::vector<S> &v)
-{
-  T *p = (T *) malloc ((v.size () + 1) * sizeof (T));
-  if (p) for (size_t i = 0 ; i < v.size () ; ++i) p[i] = (T) v[i];
-  return p;
-}
-
 static int mgRepFinishOnDevice (MgRepRun *run, FILE *err, MgRepResult *res)
 {
   hipStream_t st = 0;
@@ -513,8 +497,6 @@ extern "C" int mgRepRunFinish (MgRepRun *run, FILE *err, MgRepResult *res)
   gRepPath = 0;
   return 0;
 }
-
-#define MG_REP_FILE_BATCH 128000000ll      /* bases per batch of a file */
 
 extern "C" int mgRepAnalyze3File (MgRepRef *ref, const char *seqFile, const char *modFile, FILE *out, FILE *err, MgRepResult *res)
 {

@@ -1,5 +1,5 @@
-"""dev probe: modrep -R / -s3 (mgRepRefCreate, mgRepAnalyze3File) at one stated size -- a 5 Mbp iid reference at k 25 w 8, 10 000 reads of
-10 kb from both strands with 1 % substitutions (100 Mbp), the second set made of the reads -- with the host's part (reading the .mod, parsing
+"""dev probe: modrep -R / -s3 / -s1 (mgRepRefCreate, mgRepAnalyze3File, mgRepAnalyze1File) at one stated size -- a 5 Mbp iid reference at k 25 w 8, 10 000 reads of
+10 kb from both strands with 1 % substitutions (100 Mbp), the second set made of the reads and a junk tail (so entry max is in no read, which -s1 needs) -- with the host's part (reading the .mod, parsing
 the FASTA) timed by itself, and the reference program on the same files where a build of it is at hand (oracle/ builds none).
 usage: python tools/modrep_probe.py [--reads N] [--modrep PATH_TO_REFERENCE_MODREP] [out_dir]   (GPU box; prints the JSON of every figure)"""
 import ctypes as C
@@ -73,11 +73,14 @@ def main():
     ref_fa, ref_mod, reads_fa, reads_mod = (os.path.join(out_dir, n) for n in ("ref.fa", "ref.mod", "reads.fa", "reads.mod"))
     write_fasta(ref_fa, ["ref"], [g]); write_fasta(reads_fa, ["r%d" % j for j in range(n_reads)], reads)
     fig = {"k": K, "w": W, "reference_bases": GENOME, "reads": n_reads, "read_bases": n_reads * READ_LEN,
-           "ref_set_entries": make_set(ref_mod, [g]), "second_set_entries": make_set(reads_mod, reads)}
+           "ref_set_entries": make_set(ref_mod, [g]), "second_set_entries": make_set(reads_mod, reads + [synth.iid_bases(1500, 999)])}
 
     def whole(tag):
         ref, fig["R_s_" + tag] = timed(lambda: mg.rep_ref_create(ref_fa, ref_mod, os.path.join(out_dir, "R.err")))
         res, fig["s3_s_" + tag] = timed(lambda: mg.rep_analyze3_file(ref, reads_fa, reads_mod, os.path.join(out_dir, "s3.out"), os.path.join(out_dir, "s3.err")))
+        res1, fig["s1_s_" + tag] = timed(lambda: mg.rep_analyze1_file(ref, reads_fa, reads_mod, os.path.join(out_dir, "s1.out"), os.path.join(out_dir, "s1.err")))
+        fig["s1_diag"] = mg.rep1_diag()
+        fig["s1_reads_kept"], fig["s1_mod_lines"] = res1["readsAfter"], int((res1["modN"][:-1] != 0).sum())
         L.mgRepRefDestroy(ref)
         return res
     whole("first"); res = whole("second")
