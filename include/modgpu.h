@@ -413,7 +413,9 @@ void mgReadsetOverlapsDiag (U64 out4[4]) ;                          /* last call
  * Host loops give the same bytes for a set of 2^32 - 16 hits or more, MODGPU_READSET_HOST=1 or a device without room, and for a -T that walks fewer
  * than 2^21 hits (the visited reads' hit counts together; MODGPU_READSET_HOST=0 sends it to the device).  info[] changed: the calls end in
  * mgModsetHostChanged.  ...RdnaPath: the calling thread's last call: 0 device, 1 host loops, -1 failed before.  ...RdnaDiag: its last -T: batches of
- * tested mods (MODGPU_TESTMODS_BATCH mods per batch; unset: by the free device memory), tested mods, visits, partner occurrences. */
+ * tested mods (MODGPU_TESTMODS_BATCH mods per batch; unset: by the free device memory), tested mods, visits, partner occurrences.  ...RdnaGrid: what
+ * its last -T on the device launched: tiles of partner ordinals, the least and the greatest share of the visits over its batches, cells per count
+ * array (the longest read + 1); zeros after the host loops. */
 typedef struct { U8 flags ; /* 1 isRefRDNA, 2 isCoreRDNA, 4 isVarRDNA, 8 isMultiRDNA (modasm.c:61-77) */
                  int rDNApos, nGood, nMod2, nBadLD, nSplit, nSplitLD ; } MgModInfo ;
 int  mgReadsetRefFlagFile (MgReadset *rs, const char *refFile, FILE *out) ;
@@ -425,6 +427,7 @@ const U8 *mgReadsetReadFlags (const MgReadset *rs) ;                /* [1..nRead
 int  mgReadsetTestModsRun (const MgReadset *rs) ;                   /* -T calls made on this set: the reference's static RUN */
 int  mgReadsetRdnaPath (void) ;
 void mgReadsetRdnaDiag (U64 out4[4]) ;
+void mgReadsetRdnaGrid (U32 out4[4]) ;
 
 /* modrep -R <ref.fa> <ref.mod> -s3 <reads.fa> <reads.mod> (modrep.c:27-63,170-268; the rest of that file is its "OLD VERSIONS").
  * Scan, lookups and every per-read and per-mod reduction run on the device (mg_modrep.hip); the host formats the lines.  All of these

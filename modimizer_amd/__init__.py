@@ -112,7 +112,7 @@ EXPORTS = [
     "mgReadsetCreate", "mgReadsetDestroy", "mgReadsetRead", "mgReadsetFileRead", "mgReadsetStats", "mgReadsetWrite", "mgReadsetLoad",
     "mgReadsetCleanMods", "mgReadsetCleanModsPath", "mgReadsetProperties", "mgReadsetPropertiesPath",
     "mgReadsetFindOverlaps", "mgOverlapsFree", "mgReadsetOverlapStats", "mgReadsetMarkBadReads", "mgReadsetMarkContained", "mgReadsetOverlapsPath", "mgReadsetOverlapsDiag",
-    "mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetModInfo", "mgReadsetReadFlags", "mgReadsetTestModsRun", "mgReadsetRdnaPath", "mgReadsetRdnaDiag",
+    "mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetModInfo", "mgReadsetReadFlags", "mgReadsetTestModsRun", "mgReadsetRdnaPath", "mgReadsetRdnaDiag", "mgReadsetRdnaGrid",
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
@@ -270,7 +270,7 @@ def lib():
     sig("mgReadsetOverlapsPath", i32); sig("mgReadsetOverlapsDiag", None, vp)
     sig("mgReadsetRefFlagFile", i32, RS, C.c_char_p, vp); sig("mgReadsetRefFlagHits", i32, RS, vp, vp, u64, vp); sig("mgReadsetResetBits", i32, RS, i32, vp)
     sig("mgReadsetTestMods", i32, RS, i32, i32, vp, vp, vp); sig("mgReadsetModInfo", C.POINTER(MgModInfo), RS); sig("mgReadsetReadFlags", C.POINTER(C.c_uint8), RS)
-    sig("mgReadsetTestModsRun", i32, RS); sig("mgReadsetRdnaPath", i32); sig("mgReadsetRdnaDiag", None, vp)
+    sig("mgReadsetTestModsRun", i32, RS); sig("mgReadsetRdnaPath", i32); sig("mgReadsetRdnaDiag", None, vp); sig("mgReadsetRdnaGrid", None, vp)
     RR, RES = C.POINTER(MgRepRef), C.POINTER(MgRepResult)
     sig("mgRepRefCreate", RR, C.c_char_p, C.c_char_p, vp); sig("mgRepRefFromArrays", RR, MS, vp, i64, vp); sig("mgRepRefDestroy", None, RR)
     sig("mgRepRunBegin", vp, RR, MS); sig("mgRepRunAdd", i32, vp, vp, vp, i32, vp); sig("mgRepRunFinish", i32, vp, vp, RES); sig("mgRepResultFree", None, RES)
@@ -683,6 +683,13 @@ def readset_rdna_diag():
     """mgReadsetRdnaDiag: (batches, tested mods, visits, partner occurrences) of the calling thread's last -T"""
     v = (C.c_uint64 * 4)()
     lib().mgReadsetRdnaDiag(v)
+    return tuple(int(x) for x in v)
+
+
+def readset_rdna_grid():
+    """mgReadsetRdnaGrid: (partner tiles, least share, greatest share, cells per count array) of the calling thread's last -T on the device"""
+    v = (C.c_uint32 * 4)()
+    lib().mgReadsetRdnaGrid(v)
     return tuple(int(x) for x in v)
 
 

@@ -168,10 +168,10 @@ MG_HIDDEN int mgRdnaN200Device (const MgRsView *v, const U8 *hQual, int *hN200, 
 /* testMods over a set on the host.  tested[nTested] ascending, partner[nPartner] ascending (every tested mod is a partner).  Out: per tested mod
    { nGood, nMod2, nSplit } in res3, badLD[msMax + 1] and splitLD[msMax + 1] added to (zeroed by the caller); wantCells: *cells (malloc ()ed) holds
    cellStart[nTested] records, those of tested mod t at [cellStart[t], cellStart[t + 1]), m ascending.  batch: tested mods per batch, 0: by the device's
-   free memory.  diag[0] batches, [3] partner occurrences.  0 / 1 (no room) / -1; -2: a visit or a cell the reference cannot do (*badMod: the tested mod); -3: a second tested mod whose count array passes
+   free memory.  diag[0] batches, [3] partner occurrences.  grid[4]: the partner tiles, the least and the greatest share of the visits over the batches, the cells per count array.  0 / 1 (no room) / -1; -2: a visit or a cell the reference cannot do (*badMod: the tested mod); -3: a second tested mod whose count array passes
    MG_RDNA_CLEARED cells */
 MG_HIDDEN int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
-                                    int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod);
+                                    int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 grid[4], U32 *badMod);
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_modsetdev.hip) */
 /* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
 typedef struct MgTextOut MgTextOut;

@@ -254,7 +254,7 @@ void mgRdnaEmitKernel (MgRdnaCells C, const U32 *__restrict__ cellAt, MgLdCell *
 }
 
 extern "C" int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
-                                     int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 *badMod)
+                                     int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 grid[4], U32 *badMod)
 {
   if (cells) *cells = 0;
   if (cellStart) cellStart[0] = 0;
@@ -266,6 +266,7 @@ extern "C" int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 n
   for (U32 r = 1 ; r <= S->nReads ; ++r) if (S->len[r] > maxLen) maxLen = S->len[r];
   if (maxLen >= 0x7f000000) return 1;                               /* (the cells' idle values are beyond every distance) */
   const U32 E = (U32) maxLen + 1, nP = nPartner, nTiles = (nP + MG_RD_TILE - 1) / MG_RD_TILE;
+  grid[0] = nTiles; grid[3] = E;
   const size_t fixed = m * 15 + (nR + 3) * 12 + (S->totHit + 1) * 14 + (m + 2) * 8 + (nInv + 1) * 8 + ((size_t) nTested + nP) * 4 + 4096;
   const size_t perMod = (size_t) nP * 12 + (size_t) E * 8 + 64;
   size_t freeB = 0;
@@ -313,6 +314,8 @@ extern "C" int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 n
     { const U32 n = (U32) (nTested - t0 < nb ? nTested - t0 : nb);
       U32 share = 1;                                                /* visits of one tested mod over several workgroups when the batch alone does not fill the device */
       while (share < 16 && (U64) n * nTiles * share < 1024) share *= 2;
+      if (!grid[1] || share < grid[1]) grid[1] = share;
+      if (share > grid[2]) grid[2] = share;
       if (hipMemsetAsync (dCnt, 0, (size_t) n * nP * 4 + 4, st) || hipMemsetAsync (dMin, 0x7f, (size_t) n * nP * 4 + 4, st) || hipMemsetAsync (dMax, 0x80, (size_t) n * nP * 4 + 4, st)
           || hipMemsetAsync (dSA, 0, (size_t) n * E * 4, st) || hipMemsetAsync (dEA, 0, (size_t) n * E * 4, st) || hipMemsetAsync (dExt, 0, (size_t) n * 8, st))
         { scratch.fail (); rc = -1; break; }

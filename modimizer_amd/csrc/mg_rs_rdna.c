@@ -9,8 +9,10 @@ static pthread_mutex_t gRdnaLock = PTHREAD_MUTEX_INITIALIZER;
 static RdnaState *gRdna;
 static __thread int gRdnaPath = -1;
 static __thread U64 gRdnaDiag[4];
+static __thread U32 gRdnaGrid[4];
 int mgReadsetRdnaPath (void) { return gRdnaPath; }
 void mgReadsetRdnaDiag (U64 out4[4]) { memcpy (out4, gRdnaDiag, sizeof (gRdnaDiag)); }
+void mgReadsetRdnaGrid (U32 out4[4]) { memcpy (out4, gRdnaGrid, sizeof (gRdnaGrid)); }
 
 static RdnaState *rdnaState (const MgReadset *rs, int create)
 {
@@ -321,7 +323,7 @@ static void rdnaTestModsClose (const MgModInfo *mi, size_t m, const U16 *depth, 
 
 int mgReadsetTestMods (MgReadset *rs, int minDepth, int maxDepth, FILE *yFile, FILE *zFile, FILE *out)      /* modasm.c:595-748 */
 {
-  gRdnaPath = -1; memset (gRdnaDiag, 0, sizeof (gRdnaDiag));
+  gRdnaPath = -1; memset (gRdnaDiag, 0, sizeof (gRdnaDiag)); memset (gRdnaGrid, 0, sizeof (gRdnaGrid));
   Modset *ms = rs->ms;
   RdnaState *s = rdnaState (rs, 0);
   if (!s || !s->mi) { mgSetErrorText ("need to run -R first"); return -1; }      /* modasm.c:609 */
@@ -366,8 +368,8 @@ int mgReadsetTestMods (MgReadset *rs, int minDepth, int maxDepth, FILE *yFile, F
       const MgKnobs *kn = mgKnobs ();
       const U32 batch = kn->testModsBatch != MG_KNOB_UNSET && kn->testModsBatch > 0 ? (U32) kn->testModsBatch : 0;
       if (!host)
-        { rc = mgRdnaTestModsDevice (&S, tested, nTested, partner, nPartner, batch, zFile != 0, res3, badLD, splitLD, cellStart, &cells, gRdnaDiag, &badMod);
-          if (rc == 1) { host = 1; rc = 0; memset (res3, 0, ((size_t) nTested * 3 + 1) * sizeof (int)); memset (badLD, 0, m * sizeof (int)); memset (splitLD, 0, m * sizeof (int)); memset (gRdnaDiag, 0, sizeof (gRdnaDiag)); }
+        { rc = mgRdnaTestModsDevice (&S, tested, nTested, partner, nPartner, batch, zFile != 0, res3, badLD, splitLD, cellStart, &cells, gRdnaDiag, gRdnaGrid, &badMod);
+          if (rc == 1) { host = 1; rc = 0; memset (res3, 0, ((size_t) nTested * 3 + 1) * sizeof (int)); memset (badLD, 0, m * sizeof (int)); memset (splitLD, 0, m * sizeof (int)); memset (gRdnaDiag, 0, sizeof (gRdnaDiag)); memset (gRdnaGrid, 0, sizeof (gRdnaGrid)); }
         }
       if (host && !rc) rc = rdnaTestModsHost (&S, tested, nTested, zFile != 0, res3, badLD, splitLD, cellStart, &cells, gRdnaDiag, &badMod);
       if (rc == -2)

@@ -262,3 +262,48 @@ def test_example_runs_like_modasm(golden_dir, tmp_path):
         assert open(str(tmp_path / ("YY-TEST" + n))).read() == g["YY"][n] and open(str(tmp_path / ("ZZ-TEST" + n))).read() == g["ZZ"][n]
     assert gzip.open(out + ".mod").read() == gzip.open(stem + "_X.mod").read()
     assert trs.readset_mask(gzip.open(out + ".readset").read()) == trs.readset_mask(gzip.open(stem + "_X.readset").read())
+
+
+# ---- -T past one partner tile, share and scan step: the sets of tests/rdna_designs.py ----
+
+def designed_run(name, tmp_path, want_z=True, batch=None):
+    """a fresh load of the design through the device against its checked restatement; returns (restatement, Diag, Grid)"""
+    from tests import rdna_designs as rd
+    rs = rd.load(name, tmp_path)
+    with mg.knobs(READSET_HOST=0, TESTMODS_BATCH=batch):
+        out = rd.compare(name, rs, tmp_path, 0, want_z)
+    trd.destroy(rs)
+    return out
+
+
+@pytest.mark.parametrize("want_z, batch", [(True, None), (False, None), (True, 1)])
+def test_designed_three_partner_tiles(want_z, batch, tmp_path):
+    """set A: nP = 8197, mgRdnaAccumKernel over blockIdx.y = 0 .. 2, the last tile of 5 ordinals; a tested mod with cells in tile 1 alone; one in tile 2
+    that is its own partner; nSplitLD and nBadLD of other mods in tiles 1 and 2; with the ZZ lines (Emit over 33 steps of 256) and without; one batch
+    and a batch per tested mod"""
+    r, diag, grid = designed_run("A", tmp_path, want_z, batch)
+    assert diag[0] == (3 if batch else 1)
+    assert grid == (3, 16, 16, max(r.len) + 1)
+
+
+@pytest.mark.parametrize("batch, share", [(1024, 1), (512, 2), (511, 4), (256, 4), (128, 8), (127, 16)])
+def test_designed_visit_shares(batch, share, tmp_path):
+    """set B: 1030 tested mods under MODGPU_TESTMODS_BATCH: the least share of the call is 1, 2, 4, 4, 8, 16 (mgRdnaAccumKernel's gridDim.z; with 1 a
+    wave walks several visits), the last, smaller batch has 16; every call gives the restatement's YY, ZZ and ModInfo, so all give the same"""
+    from tests import rdna_designs as rd
+    assert (batch, share) in rd.B_BATCHES
+    r, diag, grid = designed_run("B", tmp_path, True, batch)
+    assert diag[0] == rd.batches_b(batch)
+    assert grid == (1, share, 16, max(r.len) + 1)
+
+
+@pytest.mark.parametrize("name", ["C", "D", "E513", "E256", "E257", "F"])
+def test_designed_steps_of_256_and_64(name, tmp_path):
+    """set C: 600 partners, a tested mod with cells on both sides of an empty step of 256 and one with every cell (mgRdnaRuleKernel's stride,
+    mgRdnaEmitKernel's at += tot: the ZZ lines ascend in m); D: i's first occurrence at hits 0, 63, 64, 65, 127, 128, last, and twice in a read
+    (mgRdnaVisitKernel); E: count arrays of exactly 513, 256 and 257 cells with the rules reading cells 0, 255, 256, 257, 512 (mgRdnaSuffixKernel's
+    carry); F: dx = 65535 at hits 63, 64, 127 (mgRdnaPosKernel's carry)"""
+    for want_z in (True, False):
+        r, diag, grid = designed_run(name, tmp_path, want_z)
+        assert diag[0] == 1
+        assert grid == (1, 16, 16, max(r.len) + 1)

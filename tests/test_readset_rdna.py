@@ -26,6 +26,7 @@ TOPMASK, TOPBIT = 0x7fffffff, 0x80000000
 MS_REPEAT, MS_RDNA = 8, 0x20
 REF, CORE, VAR, MULTI = 1, 2, 4, 8
 NAMES = ["mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetTestModsRun", "mgReadsetRdnaPath"]
+HOOKS = ["mgReadsetRdnaDiag", "mgReadsetRdnaGrid"]
 
 
 class Refused(Exception):
@@ -64,6 +65,9 @@ class Rdna:
         self.run_no = 0
         self.out, self.yy, self.zz = [], {}, {}
         self.diag = None
+        # what the last -T saw, for the designed sets (tests/rdna_designs.py): the tested mods; per tested mod the extents of its start and end array,
+        # the cells of either that a visit counted in, its partners, and per visit (read, hit number of i's first occurrence in it, forward)
+        self.tested, self.ext, self.start_cells, self.end_cells, self.cell_mods, self.first = None, {}, {}, {}, {}, {}
 
     def n_copy(self):
         info = np.array(self.info, np.int64) & 3
@@ -166,8 +170,10 @@ class Rdna:
         res, bad_ld, split_ld = {}, [0] * self.m, [0] * self.m
         zz, visits, occ, big = [], 0, 0, [0, 0]
         cnt, mn, mx = np.zeros(self.m, np.int64), np.zeros(self.m, np.int64), np.zeros(self.m, np.int64)
+        self.tested, self.ext, self.start_cells, self.end_cells, self.cell_mods, self.first = tested, {}, {}, {}, {}, {}
         for i in tested:
             start, end = {}, {}
+            self.first[i] = []
             cnt[:] = 0; mn[:] = 1 << 40; mx[:] = -(1 << 40)
             # a read that holds i more than once is visited once per occurrence, every time from the FIRST occurrence: the same contribution each time
             rd, times = np.unique(np.array(self.inv[self.inv_start[i]:self.inv_start[i] + self.depth[i]], np.int64), return_counts=True)
@@ -181,12 +187,14 @@ class Rdna:
                 if o < 0:
                     raise Refused("len - x - w < 0")
                 fw = bool(self.fwd[h0 + f])
+                self.first[i] += [(r, f, fw)] * t
                 s, e = (x, o) if fw else (o, x)
                 start[s] = start.get(s, 0) + t; end[e] = end.get(e, 0) + t
                 d = self.pos[h0:h1] - x if fw else x - self.pos[h0:h1]
                 keep = chk[mods]; keep[f] = False
                 np.add.at(cnt, mods[keep], t); np.minimum.at(mn, mods[keep], d[keep]); np.maximum.at(mx, mods[keep], d[keep])
             cells = {int(m_): (int(cnt[m_]), int(mn[m_]), int(mx[m_])) for m_ in np.flatnonzero(cnt)}
+            self.cell_mods[i], self.start_cells[i], self.end_cells[i] = sorted(cells), sorted(start), sorted(end)
             def suffix(t):
                 ext = max(t) + 1
                 a = [0] * ext
@@ -196,6 +204,7 @@ class Rdna:
                     a[k_] += a[k_ + 1]
                 return a
             start, end = suffix(start), suffix(end)
+            self.ext[i] = (len(start), len(end))
             for y, arr in enumerate((start, end)):                     # arrayReCreate clears 20000 cells of an array that is there (array.c:103): stale cells from the second such mod on
                 big[y] += len(arr) > 20000
                 if big[y] > 1:
@@ -629,10 +638,29 @@ def test_names_in_header_library_and_binding():
     L = mg.lib()
     for n in NAMES:
         assert re.search(r"^int  %s \(" % n, header, re.M), n
-    assert re.search(r"^void mgReadsetRdnaDiag \(", header, re.M)
+    for n in HOOKS:
+        assert re.search(r"^void %s \(" % n, header, re.M), n
     assert re.search(r"^const MgModInfo \*mgReadsetModInfo \(", header, re.M) and re.search(r"^const U8 \*mgReadsetReadFlags \(", header, re.M)
-    for n in NAMES + ["mgReadsetRdnaDiag", "mgReadsetModInfo", "mgReadsetReadFlags"]:
+    for n in NAMES + HOOKS + ["mgReadsetModInfo", "mgReadsetReadFlags"]:
         assert n in mg.EXPORTS and hasattr(L, n), n
     assert [f[0] for f in mg.MgReadset._fields_][-2:] == ["bad", "contained"]          # the struct has no new field
-    for f in ("readset_ref_flag", "readset_ref_flag_hits", "readset_reset_bits", "readset_test_mods", "readset_mod_info", "readset_read_flags", "readset_rdna_diag"):
+    for f in ("readset_ref_flag", "readset_ref_flag_hits", "readset_reset_bits", "readset_test_mods", "readset_mod_info", "readset_read_flags", "readset_rdna_diag", "readset_rdna_grid"):
         assert callable(getattr(mg, f)), f
+
+
+DESIGNED = ["A", "B", "C", "D", "E513", "E256", "E257", "F"]
+
+
+@pytest.mark.parametrize("name", DESIGNED)
+def test_designed_sets_through_the_host_loops(name, tmp_path):
+    """the sets of tests/rdna_designs.py -- A three tiles of partners, B 1030 tested mods, C more than 256 partners, D i's first occurrence at the block
+    lines, E count arrays of exactly 256, 257 and 513 cells, F positions across dx = 65535 -- each not refused and with its properties asserted from
+    the restatement, then by rdnaTestModsHost: lines, YY, ZZ and state against the restatement, with and without the ZZ lines"""
+    from tests import rdna_designs as rd
+    assert sorted(DESIGNED) == sorted(rd.BUILDERS)
+    with host_loops():
+        for want_z in (True, False):
+            rs = rd.load(name, tmp_path)
+            r, diag, grid = rd.compare(name, rs, tmp_path, 1, want_z)
+            assert diag[0] == 1 and grid == (0, 0, 0, 0)              # nothing was launched
+            destroy(rs)
