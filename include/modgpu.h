@@ -637,6 +637,41 @@ Modset *mgModsetReadText (const char *filename) ;
 int     mgModsetReadTextPath (void) ;   /* test hook: what the calling thread's last mgModsetReadText did: 0 = parsed on the device, 1 = parsed on the host and inserted on the device, 2 = built on the host, -1 = it failed before it chose */
 int  mgFormatF2 (char *buf64, double x) ;	/* test hook: the "%.2f" of the Q / M lines as the library's parallel formatter writes it (glibc's rounding of the double's exact value, in integer arithmetic; snprintf itself for nan / inf / negative); returns the length */
 
+/* The reference's `composition` program (composition.c:32-121) on the device: a FASTA or FASTQ file's records, their lengths, its bases
+ * and qualities.  flags: MG_COMP_BASES (-b), MG_COMP_QUALS (-q), MG_COMP_LENGTHS (-l); -t's rusage lines are not provided.  The program's
+ * stdout goes to `out`, its "incomplete sequence record line N" to `err` (either may be 0), the counts into *res (may be 0).  The file's
+ * bytes -- plain, or inflated by the host if it is gzip, as the reference reads everything through gzread -- cross to the device in the
+ * device text parser's windows (MODGPU_TEXT_WINDOW_KB) and are counted there (mg_composition.hip); there is no host computation of the
+ * counts, and without a HIP device the call fails like every batch entry point.  FASTA: a record starts at a '>' that begins a line; of
+ * its sequence lines the letters ABCDGHKMNRSTVWY count as their upper case, '-' as itself, every other byte is dropped (seqio.c:49,322).
+ * FASTQ: four lines a record, the sequence line counted as it is, qualities as byte - 33.  lenMin follows composition.c:64: an empty record
+ * resets it (lengths 5, 0, 100 give 100).
+ *   Returns 0, or -1 with mgLastError () and nothing written to `out`:
+ *   - FASTQ that breaks a rule, with the reference's words: "no initial @ for FASTQ record line N", "missing + FASTQ line N", "qual not
+ *     same length as seq line N";
+ *   - a byte the reference would index a table out of bounds with -- 0x80 or above in a FASTA sequence line, or in a FASTQ sequence line
+ *     with MG_COMP_BASES; a quality byte below 33 or from 0x80 with MG_COMP_QUALS -- named by its file offset (without the flag that touches
+ *     the byte, the file is fine);
+ *   - MG_COMP_LENGTHS where lenMin < lenMax and every record is shorter than 4 bases: the reference divides by zero (composition.c:107).
+ *     *res is filled all the same;
+ *   - a record of 2^31 bases or more; an empty or unreadable file; text whose first byte is neither '>' nor '@' (binary, ONEcode and
+ *     BAM input are not read).
+ *   A last record the reference drops as unfinished (no final newline, a FASTA file that ends in a header line, a FASTQ file that ends
+ * inside a record) is dropped here, too: the message goes to `err`, the records before it are reported, the return is 0. */
+#define MG_COMP_BASES 1
+#define MG_COMP_QUALS 2
+#define MG_COMP_LENGTHS 4
+typedef struct {
+  int type ;                         /* 1 fasta, 2 fastq */
+  U64 nSeq, totLen, lenMin, lenMax ;
+  U64 base[256], qual[256] ;         /* zero where the flag was not set */
+  U32 nBins ; int *binCount ; U64 *binSum ;   /* -l: malloc'ed, [nBins], bin isqrt (100 len); 0 without the flag */
+} MgComposition ;
+int  mgCompositionFile (const char *filename, int flags, FILE *out, FILE *err, MgComposition *res) ;
+int  mgCompositionText (const char *text, U64 n, int flags, FILE *out, FILE *err, MgComposition *res) ;   /* the same on text in host memory: the file's bytes, already inflated */
+void mgCompositionFree (MgComposition *res) ;   /* the arrays; res itself is the caller's */
+void mgCompositionDiag (U64 out4[4]) ;           /* of the calling thread's last call: windows, tiles of 4 KiB, records that crossed a window edge, kernel launches */
+
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):
  *   mgSynthGenome: nBases iid-uniform bases, base g = splitmix64(seed ^ g*0x9E3779B97F4A7C15) >> 62
  *   mgSynthReads : read r = genome[start[r], start[r]+len[r]) reverse-complemented when

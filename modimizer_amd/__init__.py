@@ -88,6 +88,11 @@ class MgRep1Result(C.Structure):      # include/modgpu.h (modrep.c:272-489)
                 ("readI", C.POINTER(C.c_int)), ("hitStart", U64P), ("hitK", C.POINTER(C.c_int))]
 
 
+class MgComposition(C.Structure):     # include/modgpu.h (composition.c:32-121)
+    _fields_ = [("type", C.c_int), ("nSeq", C.c_uint64), ("totLen", C.c_uint64), ("lenMin", C.c_uint64), ("lenMax", C.c_uint64),
+                ("base", C.c_uint64 * 256), ("qual", C.c_uint64 * 256), ("nBins", C.c_uint32), ("binCount", C.POINTER(C.c_int)), ("binSum", U64P)]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -115,6 +120,7 @@ EXPORTS = [
     "mgReadsetRefFlagFile", "mgReadsetRefFlagHits", "mgReadsetResetBits", "mgReadsetTestMods", "mgReadsetModInfo", "mgReadsetReadFlags", "mgReadsetTestModsRun", "mgReadsetRdnaPath", "mgReadsetRdnaDiag", "mgReadsetRdnaGrid",
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
+    "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
@@ -279,6 +285,9 @@ def lib():
     sig("mgRep1ResultFree", None, RES1); sig("mgRepRunFinish1", i32, vp, vp, vp, RES1); sig("mgRepAnalyze1File", i32, RR, C.c_char_p, C.c_char_p, vp, vp, RES1)
     sig("mgRepAnalyze1Hits", i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, RES1); sig("mgRepCount2", i32, RR, vp, vp, i32, vp)
     sig("mgRepAnalyze2File", i32, RR, C.c_char_p, C.c_char_p, vp, vp); sig("mgRep1Diag", None, vp)
+    COMP = C.POINTER(MgComposition)
+    sig("mgCompositionFile", i32, C.c_char_p, i32, vp, vp, COMP); sig("mgCompositionText", i32, vp, u64, i32, vp, vp, COMP)
+    sig("mgCompositionFree", None, COMP); sig("mgCompositionDiag", None, vp)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -852,6 +861,51 @@ def rep_analyze2_file(ref, seq_path, mod_path, out_path):
     if rc:
         raise ModgpuError("mgRepAnalyze2File failed: " + lib().mgLastError().decode())
     return list(c)
+
+
+COMP_BASES, COMP_QUALS, COMP_LENGTHS = 1, 2, 4      # include/modgpu.h: composition's -b, -q, -l
+
+
+def _composition(call, what):
+    """run `call (out FILE *, err FILE *, result *)`; (stdout text, stderr text, the MgComposition as a dict of ints and numpy arrays)"""
+    import tempfile
+    res = MgComposition()
+    with tempfile.TemporaryDirectory(prefix="modgpu_comp_") as d:
+        po, pe = os.path.join(d, "out"), os.path.join(d, "err")
+        with CFile(po, "w") as fo, CFile(pe, "w") as fe:
+            rc = call(fo, fe, C.byref(res))
+        out, err = open(po, "rb").read(), open(pe, "rb").read()
+    def arr(ptr, count, dtype):
+        return np.ctypeslib.as_array(ptr, (count,)).astype(dtype, copy=True) if count and ptr else np.zeros(0, dtype)
+    r = dict(type=res.type, nSeq=res.nSeq, totLen=res.totLen, lenMin=res.lenMin, lenMax=res.lenMax,
+             base=np.array(res.base, np.uint64), qual=np.array(res.qual, np.uint64),
+             binCount=arr(res.binCount, res.nBins, np.int32), binSum=arr(res.binSum, res.nBins, np.uint64))
+    lib().mgCompositionFree(C.byref(res))
+    if rc:
+        e = ModgpuError(what + " failed: " + lib().mgLastError().decode())
+        e.out, e.err, e.result = out, err, r
+        raise e
+    return out.decode("latin-1"), err.decode("latin-1"), r
+
+
+def composition_file(path, flags=0):
+    """mgCompositionFile: the reference's `composition [-b] [-q] [-l] file` (flags: COMP_BASES | COMP_QUALS | COMP_LENGTHS) counted on the
+    device.  Returns (stdout text, stderr text, result dict: type, nSeq, totLen, lenMin, lenMax, base[256], qual[256], binCount, binSum);
+    raises ModgpuError with the library's message (its .out, .err and .result hold what the call left)."""
+    return _composition(lambda fo, fe, res: lib().mgCompositionFile(os.fsencode(path), flags, fo, fe, res), "mgCompositionFile")
+
+
+def composition_text(text, flags=0):
+    """mgCompositionText: the same on the file's bytes in memory (bytes or a uint8 array)"""
+    buf = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    return _composition(lambda fo, fe, res: lib().mgCompositionText(buf.ctypes.data if len(buf) else None, len(buf), flags, fo, fe, res), "mgCompositionText")
+
+
+def composition_diag():
+    """mgCompositionDiag: dict(windows, tiles, crossed, launches) of the calling thread's last composition call"""
+    v = (C.c_uint64 * 4)()
+    lib().mgCompositionDiag(v)
+    return dict(zip(("windows", "tiles", "crossed", "launches"), (int(x) for x in v)))
 
 
 def rep1_diag():

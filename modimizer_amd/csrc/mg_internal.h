@@ -185,6 +185,49 @@ MG_HIDDEN void mgSetErrorText (const char *msg);
 /* the file mover of the device text parser (mg_textgpu.hip), for the other reader of plain text (mg_settext.hip) */
 MG_HIDDEN int mgTextReadParallel (int fd, unsigned char *dst, size_t n, int64_t off);      /* [off, off + n) of the file into dst by the parser's team of threads; 0 = read */
 MG_HIDDEN size_t mgTextWindowBytes (size_t fileSize);      /* text per window: MODGPU_TEXT_WINDOW_KB, or the parser's default for a file of that size; whole tiles of 4 KiB */
+/* The parser's window loop for another consumer of FASTA / FASTQ text (mg_composition.hip): the text -- whatever `fill` produces: a plain
+   file by the parser's team of threads, an inflated stream, a block of host memory -- goes through the parser's own page-locked and device
+   window buffers, two of each, and `fn` launches its kernels on `stream` for every window in order while the next one is read and crosses
+   the link.  fill (src, dst, cap, off): up to cap bytes that follow byte off of the text into dst; the count, less than cap only at the
+   text's end, (size_t) -1 on a read error.  fn: 0, or non-zero to end the walk (the streamer then returns -1, the error is fn's).
+   sizeHint: the text's size where it is known (the window is the parser's for a file of that size; MODGPU_TEXT_WINDOW_KB comes first).
+   Returns 0 with every kernel of every window finished; *nWindows is set either way */
+typedef struct { const unsigned char *dText, *hText; size_t n; U64 off; U32 prevByte; U64 index; } MgTextWindow;      /* prevByte: the byte before the window, '\n' before the text's first */
+typedef size_t (*MgTextFillFn) (void *src, unsigned char *dst, size_t cap, U64 off);
+typedef int (*MgTextWindowFn) (void *ctx, const MgTextWindow *w, void *stream);
+MG_HIDDEN int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows);
+/* K1 of the FASTA parser for that consumer: tileEvent[t] = the code (txEvent below) of the last event of tile t of the window, 0: none */
+MG_HIDDEN int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64 textBase, U32 prevByte, U64 *dTileEvent, void *stream);
+#ifdef __HIPCC__
+/* the per-byte rules of the device text parser, for its kernels and those of the other consumer.  Both cut a window into tiles of
+   MG_TEXT_TILE bytes, one workgroup of 256 threads with one 16-byte load each (the files name their own thread count: tests/test_abi.py
+   resolves the workgroup primitives' THREADS through the file that calls them) */
+#define MG_TEXT_TILE 4096
+/* a thread's 16 bytes and the byte before them */
+static __device__ __forceinline__ void txLoad (const unsigned char *text, U64 n, U64 at, U32 prevByte, unsigned char *b, U32 *prev)
+{
+  uint4 v = make_uint4 (0, 0, 0, 0);
+  if (at + 16 <= n) v = *reinterpret_cast<const uint4 *> (text + at);
+  else { unsigned char t[16]; for (int j = 0 ; j < 16 ; ++j) t[j] = at + j < n ? text[at + j] : 0; __builtin_memcpy (&v, t, 16); }
+  __builtin_memcpy (b, &v, 16);
+  *prev = at ? text[at - 1] : prevByte;
+}
+/* the event code of byte i of the window (0: no event): newline -> even, record start -> odd; a later event has a larger code */
+static __device__ __forceinline__ U64 txEvent (U32 c, U32 prev, U64 filePos)
+{
+  if (c == '\n') return (filePos + 1) << 1;
+  if (c == '>' && prev == '\n') return ((filePos + 1) << 1) | 1;
+  return 0;
+}
+/* the newlines among a thread's bytes (FASTQ: the line a byte belongs to is the number of newlines before it) */
+static __device__ __forceinline__ U32 txNewlines (const unsigned char *b, U64 at, U64 n)
+{
+  U32 c = 0;
+#pragma unroll
+  for (int j = 0 ; j < 16 ; ++j) c += (at + j < n && b[j] == '\n') ? 1u : 0u;
+  return c;
+}
+#endif
 /* modutils -rt (mg_settext.hip): the `want` lines that follow byte bodyOff of the file parsed on the device against the strict grammar
    (modgpu.h), tokens of k bytes; 0 = all of them passed, the three device arrays (hipMalloc: mgDeviceFree) hold them; 1 = some line
    does not pass, or there are fewer (nothing is returned); -1 = error */

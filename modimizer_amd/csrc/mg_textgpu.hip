@@ -49,6 +49,8 @@
 #define TX_THREADS 256
 #define TX_PER     16                                   /* bytes per thread: one 16-byte load */
 #define TX_TILE    (TX_THREADS * TX_PER)                 /* 4 KiB of text per workgroup */
+static_assert (TX_TILE == MG_TEXT_TILE, "mg_internal.h states the tile");
+/* txLoad, txEvent and txNewlines: mg_internal.h (mg_composition.hip reads text by the same rules) */
 
 struct TxState {                                         /* device resident, carried from window to window */
   U64 lastEvent;        /* code of the last event of the text so far: bit 0 = it was a record start (we are in a header) */
@@ -65,24 +67,6 @@ __device__ __forceinline__ U32 txCode (U32 c)
   U32 code = 4;
   code = u == 'A' ? 0u : code; code = u == 'C' ? 1u : code; code = u == 'G' ? 2u : code; code = u == 'T' ? 3u : code; code = u == 'N' ? 0u : code;
   return code;
-}
-
-/* a thread's 16 bytes and the byte before them */
-__device__ __forceinline__ void txLoad (const unsigned char *text, U64 n, U64 at, U32 prevByte, unsigned char *b, U32 *prev)
-{
-  uint4 v = make_uint4 (0, 0, 0, 0);
-  if (at + 16 <= n) v = *reinterpret_cast<const uint4 *> (text + at);
-  else { unsigned char t[16]; for (int j = 0 ; j < 16 ; ++j) t[j] = at + j < n ? text[at + j] : 0; memcpy (&v, t, 16); }
-  memcpy (b, &v, 16);
-  *prev = at ? text[at - 1] : prevByte;
-}
-
-/* the event code of byte i of the window (0: no event): newline -> even, record start -> odd; a later event has a larger code */
-__device__ __forceinline__ U64 txEvent (U32 c, U32 prev, U64 filePos)
-{
-  if (c == '\n') return (filePos + 1) << 1;
-  if (c == '>' && prev == '\n') return ((filePos + 1) << 1) | 1;
-  return 0;
 }
 
 /* K1: the last event of every tile */
@@ -290,8 +274,7 @@ void mgTextNewlineKernel (const unsigned char *__restrict__ text, U64 n, U64 *__
   unsigned char b[16]; U32 prev = 0; U32 c = 0;
   if (at < n)
     { txLoad (text, n, at, 0, b, &prev);
-#pragma unroll
-      for (int j = 0 ; j < 16 ; ++j) c += (at + j < n && b[j] == '\n') ? 1u : 0u;
+      c = txNewlines (b, at, n);
     }
   const U32 t = mgBlockReduce<TX_THREADS, MgSum> (c, sRed);
   if (threadIdx.x == 0) tileNL[blockIdx.x] = t;
@@ -342,8 +325,7 @@ void mgTextFastqCountKernel (const unsigned char *__restrict__ text, U64 n, U32 
   unsigned char b[16]; U32 prev = 0; U32 nl = 0;
   if (at < n)
     { txLoad (text, n, at, prevByte, b, &prev);
-#pragma unroll
-      for (int j = 0 ; j < 16 ; ++j) nl += (at + j < n && b[j] == '\n') ? 1u : 0u;
+      nl = txNewlines (b, at, n);
     }
   const U64 line = tileLine[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nl, sScan);
   U32 nb = 0, nq = 0, ne = 0, bad = 0;
@@ -381,8 +363,7 @@ void mgTextFastqEmitKernel (const unsigned char *__restrict__ text, U64 n, U64 t
   unsigned char b[16]; U32 prev = 0; U32 nl = 0;
   if (at < n)
     { txLoad (text, n, at, prevByte, b, &prev);
-#pragma unroll
-      for (int j = 0 ; j < 16 ; ++j) nl += (at + j < n && b[j] == '\n') ? 1u : 0u;
+      nl = txNewlines (b, at, n);
     }
   const U64 line = tileLine[blockIdx.x] + mgBlockExclusive<TX_THREADS, MgSum> (nl, sScan);
   U32 nb = 0, nq = 0, ne = 0, bad = 0;
@@ -559,6 +540,57 @@ static int txHostThreads (void)
 /* the two for mg_settext.hip (mg_internal.h) */
 extern "C" int mgTextReadParallel (int fd, unsigned char *dst, size_t n, int64_t off) { return txReadParallel (fd, dst, n, (off_t) off, txHostThreads ()) ? 0 : -1; }
 extern "C" size_t mgTextWindowBytes (size_t fileSize) { return txWindowBytes (fileSize); }
+
+/* K1 for the other consumer of FASTA text (mg_internal.h) */
+extern "C" int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64 textBase, U32 prevByte, U64 *dTileEvent, void *stream)
+{
+  const U64 nTiles = (n + TX_TILE - 1) / TX_TILE;
+  hipLaunchKernelGGL (mgTextEventKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, (hipStream_t) stream, dText, (U64) n, textBase, prevByte, dTileEvent);
+  return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+/* the window loop for a consumer that keeps nothing per base (mg_internal.h): the parser's buffers, its window size and its overlap of read,
+   copy and kernels -- the window's copy is started as soon as it is read, its kernels are launched behind the copy's event, the next window
+   is read while they run -- without the batch accumulator */
+extern "C" int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows)
+{
+  if (nWindows) *nWindows = 0;
+  if (mgEnsureDevice ()) return -1;
+  int curDev = 0;
+  if (hipGetDevice (&curDev) != hipSuccess || curDev < 0 || curDev >= TX_MAXDEV) { (void) hipGetLastError (); mgSetError ("device text windows: no buffers are kept for this device"); return -1; }
+  TxBufs &t = gTxs[curDev];
+  std::lock_guard<std::mutex> g (t.lock);
+  const size_t window = txWindowBytes (sizeHint);
+  if (txReserve (t, window, 0, 0)) { mgSetError ("device text windows: allocation failed"); return -1; }
+  hipStream_t st = 0;
+  U64 off = 0, w = 0; U32 prevByte = '\n';
+  int rc = 0;
+  size_t nCur = fill (src, t.hPin[0], window, 0);
+  if (nCur == (size_t) -1) { mgSetError ("device text windows: read failed"); return -1; }
+  if (nCur && (hipMemcpyAsync (t.dText[0], t.hPin[0], nCur, hipMemcpyHostToDevice, t.copy) != hipSuccess || hipEventRecord (t.h2dDone[0], t.copy) != hipSuccess)) rc = -2;
+  while (nCur && !rc)
+    { const int cur = (int) (w & 1), oth = cur ^ 1;
+      if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { rc = -2; break; }
+      MgTextWindow win; win.dText = t.dText[cur]; win.hText = t.hPin[cur]; win.n = nCur; win.off = off; win.prevByte = prevByte; win.index = w;
+      if (fn (ctx, &win, (void *) st)) { rc = -1; break; }
+      prevByte = t.hPin[cur][nCur - 1];
+      /* the next window into the other page-locked buffer (whose last copy to the device must be over) and across the link at once: the other
+         device buffer is free, its window's kernels were waited for */
+      size_t nNext = 0;
+      if (nCur == window)
+        { if (w >= 1 && hipEventSynchronize (t.h2dDone[oth]) != hipSuccess) { rc = -2; break; }
+          nNext = fill (src, t.hPin[oth], window, off + nCur);
+          if (nNext == (size_t) -1) { mgSetError ("device text windows: read failed"); rc = -1; break; }
+          if (nNext && (hipMemcpyAsync (t.dText[oth], t.hPin[oth], nNext, hipMemcpyHostToDevice, t.copy) != hipSuccess
+                        || hipEventRecord (t.h2dDone[oth], t.copy) != hipSuccess)) { rc = -2; break; }
+        }
+      if (hipStreamSynchronize (st) != hipSuccess) { rc = -2; break; }
+      off += nCur; nCur = nNext; ++w;
+    }
+  if (rc) { (void) hipStreamSynchronize (t.copy); (void) hipStreamSynchronize (st); }      /* nothing of this call is left in flight over buffers the next one takes */
+  if (rc == -2) { mgSetError ("device text windows: HIP failure (%s)", hipGetErrorString (hipGetLastError ())); rc = -1; }
+  if (nWindows) *nWindows = w + (rc && nCur ? 1 : 0);
+  return rc;
+}
 
 struct TxSink {                                            /* what is done with a batch of complete records */
   int (*fn) (void *ctx, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads, const char *idBytes, const U64 *idOff, hipStream_t st);
