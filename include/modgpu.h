@@ -672,6 +672,45 @@ int  mgCompositionText (const char *text, U64 n, int flags, FILE *out, FILE *err
 void mgCompositionFree (MgComposition *res) ;   /* the arrays; res itself is the caller's */
 void mgCompositionDiag (U64 out4[4]) ;           /* of the calling thread's last call: windows, tiles of 4 KiB, records that crossed a window edge, kernel launches */
 
+/* The reference's `seqconvert -fa|-fq` (seqconvert.c) and `seqhoco` (seqhoco.c) on the device: a FASTA or FASTQ file rewritten as FASTA or
+ * FASTQ.  The text -- plain, or inflated by the host if it is gzip -- crosses to the device in the device text parser's windows, every byte
+ * is classified, compacted and re-emitted there (mg_seqconvert.hip), and the host writes what comes back; it computes nothing per byte.
+ * The text goes through twice: once to judge it (nothing is written before the whole of it is known to be acceptable, and the walk finds
+ * where an unfinished last record or seqhoco's stop begins), once to write it.
+ *   Header line (seqio.c:303-313): the id ends at the first white-space byte; if that is not the newline, the rest of the line is the
+ * description.  Written: '>' or '@', the id and -- only if the description is not empty -- one space and the description ("r1\tx" becomes
+ * "r1 x", "r2 " becomes "r2", a CRLF header loses its '\r' where that is the separator).
+ *   FASTA in: a record starts at a '>' that begins a line; of its sequence lines the letters ABCDGHKMNRSTVWY are written in upper case and
+ * '-' as itself, every other byte is dropped; one line a record.  FASTQ in: four lines a record, sequence and quality lines written as they
+ * are, the '+' line as "+".  FASTQ out of FASTA: the quality line is '!' for every base.  An empty record is written with empty lines.
+ *   MG_SEQ_HOCO: FASTA in keeps ACGTNacgtn only; within a record a kept byte is written iff it is the first or differs under toupper from
+ * the kept byte before it ("aAaA" -> "a"); no descriptions; the output is FASTA and ends before the first record whose kept length is 0
+ * (seqhoco.c:26).  The byte from beyond the sequence that the program appends to every line (seqhoco.c:29-30) is not written.
+ *   outName: "-" stdout, "-z" stdout gzipped, a name ending in .gz a gzip file (mgGzipOpenWrite).  Without MG_SEQ_FASTA / MG_SEQ_FASTQ /
+ * MG_SEQ_HOCO the type is the name's .fa / .fq suffix (before .gz), as in seqio.c:426-428.  The program's stderr chatter is not provided;
+ * its counters are in *res (may be 0).
+ *   Returns 0, or -1 with mgLastError (), nothing written to `out` and the output file removed -- whatever the failure, and also a file of
+ * that name that was there before the call and that the call never opened (the program would have truncated it when it opened its output):
+ *   - FASTQ that breaks a rule, in the reference's words (see mgCompositionFile);
+ *   - a byte from 0x80 in a FASTA sequence line; with MG_SEQ_HOCO and FASTQ in, a sequence byte outside ACGTNacgtn (the program indexes a
+ *     table out of bounds with either); a NUL byte in a header line (the program's strlen would cut the name there) -- named by file offset;
+ *   - a record of 2^31 bases or more; an empty or unreadable file; text that starts with neither '>' nor '@';
+ *   - both type flags; MG_SEQ_HOCO with MG_SEQ_FASTQ; no type from flags or name (the program would write its binary format, which its
+ *     own reader does not read back: seqio.c:573-581).
+ *   An unfinished last record is dropped, "incomplete sequence record line N" goes to `err`, the return is 0 (see mgCompositionFile). */
+#define MG_SEQ_FASTA 1
+#define MG_SEQ_FASTQ 2
+#define MG_SEQ_HOCO 4
+typedef struct {
+  int inType, outType ;                       /* 1 fasta, 2 fastq */
+  U64 nSeq, totSeqLen, maxSeqLen ;            /* of what was WRITTEN: seqconvert's "written N sequences ... total length ... max length" */
+  U64 totIdLen, totDescLen, maxIdLen, maxDescLen ;
+  U64 nSeqIn, totSeqLenIn ;                   /* complete records read / their bases after the input filter (differs under HOCO) */
+} MgSeqConvert ;
+int  mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) ;
+int  mgSeqConvertText (const char *text, U64 n, int flags, FILE *out, FILE *err, MgSeqConvert *res) ;   /* input already inflated, output to `out` */
+void mgSeqConvertDiag (U64 out4[4]) ;   /* calling thread's last call: windows, 4 KiB tiles, records that crossed a window edge, kernel launches */
+
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):
  *   mgSynthGenome: nBases iid-uniform bases, base g = splitmix64(seed ^ g*0x9E3779B97F4A7C15) >> 62
  *   mgSynthReads : read r = genome[start[r], start[r]+len[r]) reverse-complemented when

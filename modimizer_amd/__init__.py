@@ -93,6 +93,11 @@ class MgComposition(C.Structure):     # include/modgpu.h (composition.c:32-121)
                 ("base", C.c_uint64 * 256), ("qual", C.c_uint64 * 256), ("nBins", C.c_uint32), ("binCount", C.POINTER(C.c_int)), ("binSum", U64P)]
 
 
+class MgSeqConvert(C.Structure):      # include/modgpu.h (seqconvert.c, seqhoco.c)
+    _fields_ = [("inType", C.c_int), ("outType", C.c_int)] + [(n, C.c_uint64) for n in (
+        "nSeq", "totSeqLen", "maxSeqLen", "totIdLen", "totDescLen", "maxIdLen", "maxDescLen", "nSeqIn", "totSeqLenIn")]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -121,6 +126,7 @@ EXPORTS = [
     "mgRepRefCreate", "mgRepRefFromArrays", "mgRepRefDestroy", "mgRepRunBegin", "mgRepRunAdd", "mgRepRunFinish", "mgRepResultFree", "mgRepAnalyze3File", "mgRepPath",
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
+    "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
@@ -288,6 +294,8 @@ def lib():
     COMP = C.POINTER(MgComposition)
     sig("mgCompositionFile", i32, C.c_char_p, i32, vp, vp, COMP); sig("mgCompositionText", i32, vp, u64, i32, vp, vp, COMP)
     sig("mgCompositionFree", None, COMP); sig("mgCompositionDiag", None, vp)
+    CONV = C.POINTER(MgSeqConvert)
+    sig("mgSeqConvertFile", i32, C.c_char_p, C.c_char_p, i32, vp, CONV); sig("mgSeqConvertText", i32, vp, u64, i32, vp, vp, CONV); sig("mgSeqConvertDiag", None, vp)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -905,6 +913,55 @@ def composition_diag():
     """mgCompositionDiag: dict(windows, tiles, crossed, launches) of the calling thread's last composition call"""
     v = (C.c_uint64 * 4)()
     lib().mgCompositionDiag(v)
+    return dict(zip(("windows", "tiles", "crossed", "launches"), (int(x) for x in v)))
+
+
+SEQ_FASTA, SEQ_FASTQ, SEQ_HOCO = 1, 2, 4      # include/modgpu.h: seqconvert -fa, -fq; seqhoco
+
+
+def _seq_convert_result(res):
+    return {n: int(getattr(res, n)) for n, _ in MgSeqConvert._fields_}
+
+
+def seq_convert_file(in_path, out_path, flags=0):
+    """mgSeqConvertFile: the reference's `seqconvert -fa|-fq -o out in` (flags: SEQ_FASTA or SEQ_FASTQ; without one the type is out's .fa /
+    .fq suffix) or, with SEQ_HOCO, `seqhoco in` written to out, rewritten on the device.  Returns (stderr text, result dict); raises
+    ModgpuError with the library's message (its .err and .result hold what the call left)."""
+    import tempfile
+    res = MgSeqConvert()
+    with tempfile.TemporaryDirectory(prefix="modgpu_conv_") as d:
+        pe = os.path.join(d, "err")
+        with CFile(pe, "w") as fe:
+            rc = lib().mgSeqConvertFile(os.fsencode(in_path), os.fsencode(out_path), flags, fe, C.byref(res))
+        err = open(pe, "rb").read()
+    if rc:
+        e = ModgpuError("mgSeqConvertFile failed: " + lib().mgLastError().decode("latin-1"))
+        e.err, e.result = err, _seq_convert_result(res)
+        raise e
+    return err.decode("latin-1"), _seq_convert_result(res)
+
+
+def seq_convert_text(data, flags):
+    """mgSeqConvertText: the same on the file's bytes in memory (bytes or a uint8 array).  Returns (output bytes, stderr text, result dict)"""
+    import tempfile
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    res = MgSeqConvert()
+    with tempfile.TemporaryDirectory(prefix="modgpu_conv_") as d:
+        po, pe = os.path.join(d, "out"), os.path.join(d, "err")
+        with CFile(po, "w") as fo, CFile(pe, "w") as fe:
+            rc = lib().mgSeqConvertText(buf.ctypes.data if len(buf) else None, len(buf), flags, fo, fe, C.byref(res))
+        out, err = open(po, "rb").read(), open(pe, "rb").read()
+    if rc:
+        e = ModgpuError("mgSeqConvertText failed: " + lib().mgLastError().decode("latin-1"))
+        e.out, e.err, e.result = out, err, _seq_convert_result(res)
+        raise e
+    return out, err.decode("latin-1"), _seq_convert_result(res)
+
+
+def seq_convert_diag():
+    """mgSeqConvertDiag: dict(windows, tiles, crossed, launches) of the calling thread's last conversion"""
+    v = (C.c_uint64 * 4)()
+    lib().mgSeqConvertDiag(v)
     return dict(zip(("windows", "tiles", "crossed", "launches"), (int(x) for x in v)))
 
 

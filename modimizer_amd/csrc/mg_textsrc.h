@@ -1,0 +1,51 @@
+/* mg_textsrc.h — where the text of a walk over mgTextStreamWindows comes from (mg_composition.hip, mg_seqconvert.hip): the `src` and `fill` of that call */
+#ifndef MG_TEXTSRC_H
+#define MG_TEXTSRC_H
+#include <fcntl.h>
+#include <stdio.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include "mg_common.h"
+#include "mg_internal.h"
+
+/* where the text comes from: a plain file (the parser's team of readers), an inflated stream, host memory; at most `limit` bytes of it */
+struct CpSource {
+  const char *name = 0;
+  int fd = -1; FILE *fz = 0;
+  const unsigned char *mem = 0;
+  U64 size = 0;                     /* of the plain file / the memory; a guess for a stream */
+  U64 limit = ~(U64) 0;
+  bool stream () const { return fz != 0; }
+  int open (const char *filename)
+  { name = filename;
+    fd = ::open (filename, O_RDONLY);
+    if (fd < 0) { mgSetError ("failed to open sequence file %s", filename); return -1; }
+    struct stat sb; unsigned char magic[2] = { 0, 0 };
+    const bool regular = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode);
+    if (regular && sb.st_size == 0) { mgSetError ("sequence file %s unreadable or empty", filename); return -1; }
+    if (regular && pread (fd, magic, 2, 0) == 2 && !(magic[0] == 0x1f && magic[1] == 0x8b)) { size = (U64) sb.st_size; return 0; }
+    ::close (fd); fd = -1;                                    /* gzip (the reference reads everything through gzread, seqio.c:33-40): the host inflates, the device counts */
+    size = regular ? (U64) sb.st_size * 4 : (U64) 1 << 30;
+    return reopen ();
+  }
+  int reopen ()
+  { if (!name || fd >= 0) return 0;
+    if (fz) fclose (fz);
+    fz = mgFzOpen (name, "r");
+    if (!fz) { mgSetError ("failed to open sequence file %s", name); return -1; }
+    return 0;
+  }
+  void close () { if (fd >= 0) ::close (fd); if (fz) fclose (fz); fd = -1; fz = 0; }
+  static size_t fill (void *v, unsigned char *dst, size_t cap, U64 off)
+  { CpSource *s = (CpSource *) v;
+    if (off >= s->limit) return 0;
+    if (s->limit - off < cap) cap = (size_t) (s->limit - off);
+    if (s->fz) { const size_t g = fread (dst, 1, cap, s->fz); return g < cap && ferror (s->fz) ? (size_t) -1 : g; }
+    if (off >= s->size) return 0;
+    if (s->size - off < cap) cap = (size_t) (s->size - off);
+    if (s->mem) { memcpy (dst, s->mem + off, cap); return cap; }
+    return mgTextReadParallel (s->fd, dst, cap, (int64_t) off) ? (size_t) -1 : cap;
+  }
+};
+#endif
