@@ -711,6 +711,29 @@ int  mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE 
 int  mgSeqConvertText (const char *text, U64 n, int flags, FILE *out, FILE *err, MgSeqConvert *res) ;   /* input already inflated, output to `out` */
 void mgSeqConvertDiag (U64 out4[4]) ;   /* calling thread's last call: windows, 4 KiB tiles, records that crossed a window edge, kernel launches */
 
+/* Blocked gzip (BGZF: bgzip, htslib) inflated on the device.  A BGZF file is a row of gzip members of at most 64 KiB, compressed and not,
+ * each an independent raw-deflate stream with its own CRC-32 and length: one wave inflates one member (mg_inflate.hip).
+ *   mgInflateMembersDevice: n members of the device buffer dComp into the device buffer dOut.  members[] (host) names each one's deflate
+ * payload -- offset and length WITHOUT the gzip header and trailer -- its place in dOut, and the CRC-32 and length its trailer states.
+ * No slack is asked of either buffer: the decoder reads and writes single bytes inside [cOff, cOff + cLen) and [uOff, uOff + uLen) only.
+ * A member whose cLen or uLen exceeds 65536 or whose ranges leave compBytes / outBytes is refused with MG_ERR_ARG before anything is
+ * launched.  status[i] (host, may be 0): 0 ok, 1 input exhausted, 2 bad block type, 3 stored LEN/NLEN mismatch, 4 bad code lengths,
+ * 5 invalid symbol, 6 distance beyond the member's start, 7 output longer or shorter than stated, 8 CRC mismatch; *nBad the members whose
+ * status is not 0 (a bad member does not stop the others; what its range of dOut holds is undefined, nothing outside it is written).
+ * Returns when the launch is over (it waits for `stream`).
+ *   mgInflateMemberHost: the same decoder compiled for the host, one member on the calling thread -- a test hook, as mgIterScanHost is.
+ * stats8 (may be 0): deflate blocks stored / fixed / dynamic, longest literal/length code, longest distance, longest match, longest
+ * distance code, literal/length symbols.  Returns 0 (the verdict is *status), -1 on a null argument.
+ *   mgBgzfInflateFile: `bgzip -d`: the file's text to outName ("-": stdout).  0, or -1 with mgLastError () and no output file left;
+ * -2: not a BGZF file from its first byte to its last (nothing is written).
+ *   mgCompositionFile and mgSeqConvertFile take this path for a file that is BGZF from end to end (MODGPU_BGZF_HOST=1: never). */
+typedef struct { U64 cOff; U64 uOff; U32 cLen; U32 uLen; U32 crc; U32 pad; } MgGzMember;   /* deflate payload: offset and length without header and trailer */
+MgStatus mgInflateMembersDevice (const U8 *dComp, U64 compBytes, const MgGzMember *members /* host */, U32 n,
+                                 U8 *dOut, U64 outBytes, U32 *status /* host, [n]; may be 0 */, U32 *nBad, void *stream) ;
+void     mgInflateDiag (U64 out4[4]) ;   /* calling thread's last call: members inflated on the device, compressed bytes uploaded, text bytes produced, kernel launches */
+int      mgInflateMemberHost (const U8 *comp, U32 cLen, U8 *out, U32 uLen, U32 crc, U32 *status, U64 stats8[8]) ;
+int      mgBgzfInflateFile (const char *inName, const char *outName /* "-": stdout */, FILE *err) ;
+
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):
  *   mgSynthGenome: nBases iid-uniform bases, base g = splitmix64(seed ^ g*0x9E3779B97F4A7C15) >> 62
  *   mgSynthReads : read r = genome[start[r], start[r]+len[r]) reverse-complemented when

@@ -98,6 +98,10 @@ class MgSeqConvert(C.Structure):      # include/modgpu.h (seqconvert.c, seqhoco.
         "nSeq", "totSeqLen", "maxSeqLen", "totIdLen", "totDescLen", "maxIdLen", "maxDescLen", "nSeqIn", "totSeqLenIn")]
 
 
+class MgGzMember(C.Structure):        # include/modgpu.h: a gzip member's deflate payload (offset and length without header and trailer), where its text goes, what its trailer states
+    _fields_ = [("cOff", C.c_uint64), ("uOff", C.c_uint64), ("cLen", C.c_uint32), ("uLen", C.c_uint32), ("crc", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -127,6 +131,7 @@ EXPORTS = [
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
     "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
+    "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
@@ -296,6 +301,8 @@ def lib():
     sig("mgCompositionFree", None, COMP); sig("mgCompositionDiag", None, vp)
     CONV = C.POINTER(MgSeqConvert)
     sig("mgSeqConvertFile", i32, C.c_char_p, C.c_char_p, i32, vp, CONV); sig("mgSeqConvertText", i32, vp, u64, i32, vp, vp, CONV); sig("mgSeqConvertDiag", None, vp)
+    sig("mgInflateMembersDevice", i32, vp, u64, C.POINTER(MgGzMember), u32, vp, u64, vp, C.POINTER(u32), vp); sig("mgInflateDiag", None, vp)
+    sig("mgInflateMemberHost", i32, vp, u32, vp, u32, u32, C.POINTER(u32), vp); sig("mgBgzfInflateFile", i32, C.c_char_p, C.c_char_p, vp)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -963,6 +970,114 @@ def seq_convert_diag():
     v = (C.c_uint64 * 4)()
     lib().mgSeqConvertDiag(v)
     return dict(zip(("windows", "tiles", "crossed", "launches"), (int(x) for x in v)))
+
+
+INFLATE_STATUS = ("ok", "input exhausted", "bad block type", "stored LEN/NLEN mismatch", "bad code lengths", "invalid symbol",
+                  "distance beyond the start", "output longer or shorter than stated", "CRC mismatch")      # include/modgpu.h
+INFLATE_STATS = ("stored", "fixed", "dynamic", "litlen_bits", "distance", "match", "dist_bits", "symbols")
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # bgzip's end marker: an empty member
+
+
+def bgzf_member(payload, text_len, crc):
+    """one BGZF member around a raw-deflate payload: the gzip header with the 'BC' extra field (the member's size - 1), CRC-32 and length"""
+    import struct
+    if len(payload) + 26 > 65536:
+        raise ValueError("a BGZF member holds at most 65510 compressed bytes")
+    return b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(payload) + 25) + payload + struct.pack("<II", crc, text_len)
+
+
+def bgzf_bytes(data, block=65280, level=6, eof=True, threads=1):
+    """blocked gzip (BGZF) as bgzip writes it, from Python's zlib: members of `block` text bytes (65280 is bgzip's), then the empty end marker;
+    threads > 1: the members are deflated by that many threads (zlib releases the interpreter lock)"""
+    import zlib
+    data = memoryview(bytes(data) if not isinstance(data, (bytes, memoryview)) else data)
+
+    def one(i):
+        ch = bytes(data[i:i + block])
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        pay = c.compress(ch) + c.flush()
+        if len(pay) + 26 > 65536:                     # text that deflate cannot shrink: stored, as bgzip falls back to
+            c = zlib.compressobj(0, zlib.DEFLATED, -15)
+            pay = c.compress(ch) + c.flush()
+        return bgzf_member(pay, len(ch), zlib.crc32(ch))
+    starts = range(0, len(data), block)
+    if threads > 1:
+        from multiprocessing.pool import ThreadPool
+        with ThreadPool(threads) as pool:
+            out = pool.map(one, starts, chunksize=64)
+    else:
+        out = [one(i) for i in starts]
+    if eof:
+        out.append(BGZF_EOF)
+    return b"".join(out)
+
+
+def bgzf_members(blob):
+    """the members of a BGZF blob as mgInflateMembersDevice takes them: [(payload offset, payload length, text offset, text length, crc)]"""
+    import struct
+    out, at, u = [], 0, 0
+    while at < len(blob):
+        xlen, = struct.unpack_from("<H", blob, at + 10)
+        size = struct.unpack_from("<H", blob, at + 16)[0] + 1
+        crc, n = struct.unpack_from("<II", blob, at + size - 8)
+        out.append((at + 12 + xlen, size - 12 - xlen - 8, u, n, crc))
+        at += size; u += n
+    return out
+
+
+def inflate_member_host(payload, text_len, crc, guard=64):
+    """mgInflateMemberHost: one raw-deflate payload through the decoder's host compile.  Returns (status, text bytes, stats dict, guards intact):
+    the output range lies between `guard` bytes of 0xA5 on both sides, and so does a copy of the payload."""
+    payload = bytes(payload)
+    comp = np.full(len(payload) + 2 * guard, 0xA5, np.uint8)
+    comp[guard:guard + len(payload)] = np.frombuffer(payload, np.uint8)
+    out = np.full(text_len + 2 * guard, 0xA5, np.uint8)
+    st = C.c_uint32(99)
+    stats = (C.c_uint64 * 8)()
+    if lib().mgInflateMemberHost(comp.ctypes.data + guard, len(payload), out.ctypes.data + guard, text_len, crc, C.byref(st), stats):
+        raise ModgpuError("mgInflateMemberHost failed: " + lib().mgLastError().decode("latin-1"))
+    intact = bool((out[:guard] == 0xA5).all() and (out[guard + text_len:] == 0xA5).all())
+    return int(st.value), out[guard:guard + text_len].tobytes(), dict(zip(INFLATE_STATS, (int(x) for x in stats))), intact
+
+
+def inflate_members_device(comp, members, out_bytes, fill=0xA5):
+    """mgInflateMembersDevice: `comp` (bytes) to the device, the members [(cOff, cLen, uOff, uLen, crc)] inflated into a device buffer of out_bytes
+    bytes preset to `fill`.  Returns (the whole output buffer as a uint8 array, statuses as a uint32 array, nBad); raises ModgpuError on a refusal."""
+    comp = np.frombuffer(bytes(comp), np.uint8)
+    n = len(members)
+    tab = (MgGzMember * max(n, 1))()
+    for i, (c_off, c_len, u_off, u_len, crc) in enumerate(members):
+        tab[i] = MgGzMember(c_off, u_off, c_len, u_len, crc, 0)
+    d_comp, d_out = DeviceBuffer.from_numpy(comp), DeviceBuffer(max(out_bytes, 16))
+    try:
+        check(lib().mgMemsetD(d_out.ptr, fill, d_out.nbytes, None)); check(lib().mgStreamSynchronize(None))
+        status = np.full(max(n, 1), 99, np.uint32)
+        bad = C.c_uint32(0)
+        rc = lib().mgInflateMembersDevice(d_comp.ptr, len(comp), tab, n, d_out.ptr, out_bytes, status.ctypes.data, C.byref(bad), None)
+        if rc:
+            e = ModgpuError("mgInflateMembersDevice failed: " + lib().mgLastError().decode("latin-1"))
+            e.status = rc
+            raise e
+        return d_out.to_numpy(np.uint8, out_bytes), status[:n], int(bad.value)
+    finally:
+        d_comp.free(); d_out.free()
+
+
+def inflate_diag():
+    """mgInflateDiag: dict(members, uploaded, text, launches) of the calling thread's last call that could inflate on the device"""
+    v = (C.c_uint64 * 4)()
+    lib().mgInflateDiag(v)
+    return dict(zip(("members", "uploaded", "text", "launches"), (int(x) for x in v)))
+
+
+def bgzf_inflate_file(in_path, out_path):
+    """mgBgzfInflateFile: `bgzip -d` on the device.  True; False if the file is not BGZF from end to end (nothing is written); raises ModgpuError"""
+    rc = lib().mgBgzfInflateFile(os.fsencode(in_path), os.fsencode(out_path), None)
+    if rc == -2:
+        return False
+    if rc:
+        raise ModgpuError("mgBgzfInflateFile failed: " + lib().mgLastError().decode("latin-1"))
+    return True
 
 
 def rep1_diag():

@@ -500,7 +500,7 @@ struct CpPass {                                          /* one walk over the te
   { CpPass *p = (CpPass *) v;
     hipStream_t st = (hipStream_t) stream;
     if (!w->index)
-      { p->type = w->hText[0] == '>' ? 1 : w->hText[0] == '@' ? 2 : 0;
+      { p->type = w->first == '>' ? 1 : w->first == '@' ? 2 : 0;
         if (!p->type) { p->typeError = true; return -1; }
       }
     const U64 nTiles = (w->n + CP_TILE - 1) / CP_TILE;
@@ -512,7 +512,7 @@ struct CpPass {                                          /* one walk over the te
         hipLaunchKernelGGL (mgCompStateScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, p->dA, nTiles, p->dState);
         hipLaunchKernelGGL (mgCompFastaKernel, dim3 (grid), dim3 (CP_THREADS), 0, st, w->dText, (U64) w->n, w->off, w->prevByte, nTiles, p->dA,
                             p->dU, p->dV, p->dW, p->dMinE, p->dMinM, p->flags, p->bins, p->dState);
-        const int crossing = w->index && !(w->hText[0] == '>' && w->prevByte == '\n');
+        const int crossing = w->index && !(w->first == '>' && w->prevByte == '\n');
         hipLaunchKernelGGL (mgCompFastaStitchKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, nTiles, p->dU, p->dV, p->dW, p->dMinE, p->dMinM, p->dB, p->dC, crossing, p->bins, p->dState);
       }
     else
@@ -523,7 +523,7 @@ struct CpPass {                                          /* one walk over the te
         hipLaunchKernelGGL (mgCompFastqPairKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, nTiles, p->dMinE, p->dMinM, p->dState);
       }
     if (hipGetLastError () != hipSuccess) return mgFailedWith ("mgComposition: launch failed");
-    p->lastByte = w->hText[w->n - 1]; p->bytes = w->off + w->n;
+    p->lastByte = w->last; p->bytes = w->off + w->n;
     gCompDiag[1] += nTiles; gCompDiag[3] += 4;
     return 0;
   }
@@ -548,7 +548,7 @@ static int cpWalk (CpSource &src, int flags, int force, CpResult *out)
   if (hipMemcpy (p.dState, &out->st, sizeof (CpState), hipMemcpyHostToDevice) != hipSuccess) { scratch.fail (); return -1; }
   if (!src.stream () && p.growBins (src.size < src.limit ? src.size : src.limit)) return -1;
   U64 nWindows = 0;
-  const int rc = mgTextStreamWindows ((size_t) src.size, CpSource::fill, &src, CpPass::window, &p, &nWindows);
+  const int rc = src.walk ((size_t) src.size, CpSource::fill, CpPass::window, &p, &nWindows);
   gCompDiag[0] += nWindows;
   if (p.typeError) { mgSetError ("sequence file %s is neither FASTA nor FASTQ text", src.name ? src.name : "(text)"); return -1; }
   if (rc) return -1;
@@ -621,7 +621,7 @@ static void cpPrint (std::string &s, int flags, const MgComposition *r)
 static int cpCompose (CpSource &src, int flags, FILE *out, FILE *err, MgComposition *res)
 {
   typedef unsigned long long ull;
-  memset (gCompDiag, 0, sizeof (gCompDiag));
+  memset (gCompDiag, 0, sizeof (gCompDiag)); mgInflateDiagReset ();
   if (res) memset (res, 0, sizeof (*res));
   if (flags & ~(MG_COMP_BASES | MG_COMP_QUALS | MG_COMP_LENGTHS)) { mgSetError ("mgComposition: unknown flags %d", flags); return -1; }
   if (mgEnsureDevice ()) return -1;

@@ -192,10 +192,28 @@ MG_HIDDEN size_t mgTextWindowBytes (size_t fileSize);      /* text per window: M
    text's end, (size_t) -1 on a read error.  fn: 0, or non-zero to end the walk (the streamer then returns -1, the error is fn's).
    sizeHint: the text's size where it is known (the window is the parser's for a file of that size; MODGPU_TEXT_WINDOW_KB comes first).
    Returns 0 with every kernel of every window finished; *nWindows is set either way */
-typedef struct { const unsigned char *dText, *hText; size_t n; U64 off; U32 prevByte; U64 index; } MgTextWindow;      /* prevByte: the byte before the window, '\n' before the text's first */
+typedef struct { const unsigned char *dText, *hText; size_t n; U64 off; U32 prevByte; U64 index; U32 first, last; } MgTextWindow;      /* prevByte: the byte before the window, '\n' before the text's first; first, last: the window's own first and last byte; hText: the window in page-locked host memory, 0 from a device source */
 typedef size_t (*MgTextFillFn) (void *src, unsigned char *dst, size_t cap, U64 off);
 typedef int (*MgTextWindowFn) (void *ctx, const MgTextWindow *w, void *stream);
 MG_HIDDEN int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows);
+/* The same loop over a source that fills the window's DEVICE buffer (blocked gzip inflated on the device, mg_bgzfsrc.hip): no page-locked copy of the
+   window exists, the consumers read w->first and w->last.  dfill (src, dDst, cap, off, stream, &n, &more, &first, &last): up to cap bytes that follow byte
+   off into dDst by work on `stream` that is over when it returns; n may be short of cap anywhere, *more says whether text follows; 0, or -1 with the error set */
+typedef int (*MgTextDevFillFn) (void *src, unsigned char *dDst, size_t cap, U64 off, void *stream, size_t *n, int *more, U32 *first, U32 *last);
+MG_HIDDEN int mgTextStreamWindowsDev (size_t sizeHint, MgTextDevFillFn dfill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows);
+/* mg_inflate.hip for mg_bgzfsrc.hip: mgInflateMembersDevice with the caller's device scratch (mgInflateWorkBytes (n)), adding to the thread's mgInflateDiag */
+MG_HIDDEN MgStatus mgInflateRun (const U8 *dComp, U64 compBytes, const MgGzMember *members, U32 n, U8 *dOut, U64 outBytes, void *dWork, U32 *status, U32 *nBad, void *stream);
+MG_HIDDEN size_t mgInflateWorkBytes (U32 n);
+MG_HIDDEN void mgInflateDiagReset (void);
+MG_HIDDEN void mgInflateDiagUploaded (U64 bytes);
+/* A file that is blocked gzip from its first byte to its last as a source of text on the device (mg_bgzfsrc.hip).  Open: 0 and *out, -2 = not such a
+   file (no error is set: the caller reads it as any gzip), -1 = error.  fd stays the caller's.  Fill: the MgTextDevFillFn contract, below `limit` */
+typedef struct MgBgzfSrc MgBgzfSrc;
+MG_HIDDEN int mgBgzfSrcOpen (const char *name, int fd, U64 fileSize, MgBgzfSrc **out);
+MG_HIDDEN void mgBgzfSrcClose (MgBgzfSrc *s);
+MG_HIDDEN void mgBgzfSrcRewind (MgBgzfSrc *s);
+MG_HIDDEN U64 mgBgzfSrcTextBytes (const MgBgzfSrc *s);
+MG_HIDDEN int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
 /* K1 of the FASTA parser for that consumer: tileEvent[t] = the code (txEvent below) of the last event of tile t of the window, 0: none */
 MG_HIDDEN int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64 textBase, U32 prevByte, U64 *dTileEvent, void *stream);
 #ifdef __HIPCC__

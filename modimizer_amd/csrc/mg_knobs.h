@@ -42,6 +42,7 @@ typedef struct {
   long overlapCands;       /* MODGPU_OVERLAP_CANDS: candidates (entries of the inverse lists) per device batch of modasm's overlap passes; unset: from the free device memory */
   long testModsBatch;      /* MODGPU_TESTMODS_BATCH: tested mods per device batch of modasm -T (mgReadsetTestMods); unset: as many as half of the free device memory holds, 2 GiB at most */
   long overlapLds;        /* MODGPU_OVERLAP_LDS: entries of a query's mod table that a wave of the pair kernel stages in LDS (default 1024, at most 2048); a longer table is searched in HBM */
+  long bgzfHost;           /* MODGPU_BGZF_HOST: 1 = mgCompositionFile / mgSeqConvertFile inflate a blocked-gzip (BGZF) file on the host, as every other gzip, not on the device */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */
   /* development knobs */
@@ -59,6 +60,7 @@ typedef struct {
   long xferPieceKb;        /* MODGPU_XFER_PIECE_KB: dev, bytes per piece of the array transfers (default 4096) */
   long xferStreams;        /* MODGPU_XFER_STREAMS: dev, 0 = the array transfers' copies on the device's default stream instead of a stream per transfer thread */
   long xferThreads;        /* MODGPU_XFER_THREADS: host threads of the array transfers (mg_xfer.hip) */
+  long inflateNoCrc;       /* MODGPU_INFLATE_NOCRC: dev, 1 = the inflate kernel skips the CRC-32 (tools/inflate_probe.py measures what the check costs) */
   long seedTiming, uploadTiming, textTiming, parseTiming;   /* MODGPU_*_TIMING prints */
   long scanDebug, bucketDebug;                               /* only read by -DMG_ABLATE builds */
 } MgKnobs;

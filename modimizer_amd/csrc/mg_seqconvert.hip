@@ -633,14 +633,14 @@ struct SqPass {                                          /* one walk over the te
   { SqPass *p = (SqPass *) v;
     hipStream_t st = (hipStream_t) stream;
     if (!w->index)
-      { p->type = w->hText[0] == '>' ? 1 : w->hText[0] == '@' ? 2 : 0;
+      { p->type = w->first == '>' ? 1 : w->first == '@' ? 2 : 0;
         if (!p->type) { p->typeError = true; return -1; }
         p->g.fastq = p->type == 2;
       }
     const U64 nTiles = (w->n + SQ_TILE - 1) / SQ_TILE;
     if (nTiles > p->tilesCap) { mgSetError ("mgSeqConvert: a window of %llu tiles, room for %llu", (unsigned long long) nTiles, (unsigned long long) p->tilesCap); return -1; }
     const int cur = (int) (w->index & 1);
-    const int edge = !w->index ? 0 : (p->g.fastq ? w->prevByte == '\n' : w->hText[0] == '>' && w->prevByte == '\n') ? 1 : 2;
+    const int edge = !w->index ? 0 : (p->g.fastq ? w->prevByte == '\n' : w->first == '>' && w->prevByte == '\n') ? 1 : 2;
     if (p->ev[0][0]) { p->readEvents (); (void) hipEventRecord (p->ev[cur][0], st); }
     hipLaunchKernelGGL (mgSeqFnKernel, dim3 ((unsigned) nTiles), dim3 (SQ_THREADS), 0, st, w->dText, (U64) w->n, w->prevByte, p->g.fastq, p->T.fn, p->T.nl);
     hipLaunchKernelGGL (mgSeqStateScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, p->T, nTiles, p->g.fastq, edge, p->dState);
@@ -658,7 +658,7 @@ struct SqPass {                                          /* one walk over the te
       { if (p->pending != SQ_NONE && p->drain (p->pending)) return -1;
         p->pending = w->index;
       }
-    p->lastByte = w->hText[w->n - 1]; p->bytes = w->off + w->n;
+    p->lastByte = w->last; p->bytes = w->off + w->n;
     gSeqDiag[1] += nTiles;
     return 0;
   }
@@ -698,7 +698,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, SqState *S, int *ty
   struct timespec t0, t1; clock_gettime (CLOCK_MONOTONIC, &t0);
   if (mgKnobs ()->seedTiming == 1)
     for (int i = 0 ; i < 4 ; ++i) if (hipEventCreate (&p.ev[i >> 1][i & 1]) != hipSuccess) { (void) hipGetLastError (); p.ev[0][0] = 0; break; }
-  int rc = mgTextStreamWindows (hint, sqFill, &src, SqPass::window, &p, &nWindows);
+  int rc = src.walk (hint, sqFill, SqPass::window, &p, &nWindows);
   if (p.ev[0][0]) { if (!rc) p.readEvents (); gSeqMs[p.write ? 7 : 6] += p.msKernels; }
   for (int i = 0 ; i < 4 ; ++i) if (p.ev[i >> 1][i & 1]) (void) hipEventDestroy (p.ev[i >> 1][i & 1]);
   gSeqDiag[0] += nWindows;
@@ -738,7 +738,7 @@ struct SqSink {
 static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqConvert *res)
 {
   typedef unsigned long long ull;
-  memset (gSeqDiag, 0, sizeof (gSeqDiag)); memset (gSeqMs, 0, sizeof (gSeqMs));
+  memset (gSeqDiag, 0, sizeof (gSeqDiag)); memset (gSeqMs, 0, sizeof (gSeqMs)); mgInflateDiagReset ();
   if (mgEnsureDevice ()) return -1;
   SqCfg g = { 0, (flags & MG_SEQ_FASTQ) != 0, (flags & MG_SEQ_HOCO) != 0, 0 };
   SqState S; int type = 0; U32 lastByte = 0; U64 textEnd = 0;
@@ -845,5 +845,57 @@ extern "C" int mgSeqConvertFile (const char *inName, const char *outName, int fl
   if (src.open (inName)) { src.close (); return -1; }
   int rc = sqConvert (src, flags, sink, err, res);
   src.close ();
+  return sink.close (rc);
+}
+
+/* `bgzip -d`: a blocked-gzip file's text, inflated on the device (mg_bgzfsrc.hip), through the writer of the second walk above: window k + 1 is inflated
+   while window k crosses to a page-locked block and the block before that is written */
+extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE *err)
+{
+  (void) err;
+  mgInflateDiagReset ();
+  if (!inName || !outName) { mgSetError ("mgBgzfInflateFile: no file name"); return -1; }
+  const int fd = ::open (inName, O_RDONLY);
+  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
+  struct stat sb;
+  MgBgzfSrc *bz = 0;
+  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgBgzfSrcOpen (inName, fd, (U64) sb.st_size, &bz) : -2;
+  if (rc) { ::close (fd); return rc; }
+  SqSink sink; sink.name = outName; sink.toStdout = !strcmp (outName, "-");
+  const U64 text = mgBgzfSrcTextBytes (bz);
+  const size_t window = mgTextWindowBytes ((size_t) (text < SQ_WINDOW_HINT ? text : SQ_WINDOW_HINT));
+  MgDevScratch scratch ("mgBgzfInflateFile");
+  unsigned char *dBuf[2] = { 0, 0 };
+  hipStream_t inflate = 0, copy = 0;
+  SqWriter wr; bool wrOpen = false;
+  FILE *out = 0;
+  rc = -1;
+  do
+    { if (mgEnsureDevice ()) break;
+      if (scratch.get (&dBuf[0], window) || scratch.get (&dBuf[1], window)) break;
+      if (hipStreamCreateWithFlags (&inflate, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags (&copy, hipStreamNonBlocking) != hipSuccess) { scratch.fail (); break; }
+      if (!(out = sink.get ())) break;
+      wrOpen = true;
+      if (wr.open (out, window)) break;
+      SqWriter::Block *pending = 0;
+      U64 off = 0; int more = 1; bool bad = false;
+      for (U64 k = 0 ; more && !bad ; ++k)
+        { size_t n = 0; U32 first, last;
+          if (mgBgzfSrcFill (bz, dBuf[k & 1], window, off, ~(U64) 0, (void *) inflate, &n, &more, &first, &last)) { bad = true; break; }
+          if (pending) { if (hipStreamSynchronize (copy) != hipSuccess) { scratch.fail (); bad = true; pending->n = 0; } wr.submit (*pending); pending = 0; }
+          if (bad || !n) break;
+          SqWriter::Block &b = wr.acquire ();
+          b.n = n; b.spliceAt = 0; b.spliceCount = 0;
+          if (hipMemcpyAsync (b.p, dBuf[k & 1], n, hipMemcpyDeviceToHost, copy) != hipSuccess) { scratch.fail (); b.n = 0; wr.submit (b); bad = true; break; }
+          pending = &b; off += n;
+        }
+      if (pending) { if (hipStreamSynchronize (copy) != hipSuccess) { scratch.fail (); bad = true; pending->n = 0; } wr.submit (*pending); }
+      if (!bad) rc = 0;
+    }
+  while (0);
+  if (wrOpen && wr.close () && !rc) { mgSetError ("mgBgzfInflateFile: write failed"); rc = -1; }
+  if (inflate) { (void) hipStreamSynchronize (inflate); (void) hipStreamDestroy (inflate); }
+  if (copy) { (void) hipStreamSynchronize (copy); (void) hipStreamDestroy (copy); }
+  mgBgzfSrcClose (bz); ::close (fd);
   return sink.close (rc);
 }

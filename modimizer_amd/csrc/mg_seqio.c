@@ -143,22 +143,9 @@ static int threadCount (void);
  * as any other (which is what the reference does, seqio.c:33-40, one thread); here the members of a
  * stretch of the file are inflated by the pool, each straight to its place in the text window.
  * A member that is not a BGZF block hands the rest of the file to zlib's stream reader. */
+#include "mg_bgzf.h"
 typedef struct { size_t cOff, cLen, uOff, uLen; } BgBlock;
 typedef struct { const unsigned char *src; char *dst; const BgBlock *blocks; size_t n, next; int bad; } BgJob;
-
-static size_t bgzfBlockSize (const unsigned char *p, size_t avail, size_t *payloadOff)     /* 0: not a block header */
-{
-  if (avail < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return 0;
-  const size_t xlen = (size_t) p[10] | ((size_t) p[11] << 8);
-  if (avail < 12 + xlen) return 0;
-  for (size_t at = 12 ; at + 4 <= 12 + xlen ; )
-    { const size_t len = (size_t) p[at + 2] | ((size_t) p[at + 3] << 8);
-      if (p[at] == 'B' && p[at + 1] == 'C' && len == 2 && at + 6 <= 12 + xlen)
-        { *payloadOff = 12 + xlen; return ((size_t) p[at + 4] | ((size_t) p[at + 5] << 8)) + 1; }
-      at += 4 + len;
-    }
-  return 0;
-}
 
 static void *bgzfWorker (void *arg)
 {

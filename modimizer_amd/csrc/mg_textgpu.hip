@@ -551,7 +551,7 @@ extern "C" int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64
 /* the window loop for a consumer that keeps nothing per base (mg_internal.h): the parser's buffers, its window size and its overlap of read,
    copy and kernels -- the window's copy is started as soon as it is read, its kernels are launched behind the copy's event, the next window
    is read while they run -- without the batch accumulator */
-extern "C" int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows)
+static int txStreamWindows (size_t sizeHint, MgTextFillFn fill, MgTextDevFillFn dfill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows)
 {
   if (nWindows) *nWindows = 0;
   if (mgEnsureDevice ()) return -1;
@@ -564,33 +564,55 @@ extern "C" int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *sr
   hipStream_t st = 0;
   U64 off = 0, w = 0; U32 prevByte = '\n';
   int rc = 0;
-  size_t nCur = fill (src, t.hPin[0], window, 0);
-  if (nCur == (size_t) -1) { mgSetError ("device text windows: read failed"); return -1; }
-  if (nCur && (hipMemcpyAsync (t.dText[0], t.hPin[0], nCur, hipMemcpyHostToDevice, t.copy) != hipSuccess || hipEventRecord (t.h2dDone[0], t.copy) != hipSuccess)) rc = -2;
-  while (nCur && !rc)
+  /* the window at `at` into buffer i and on its way: a host source fills the page-locked buffer and the copy is started; a device source fills the device
+     buffer itself by work on the copy stream.  Either way h2dDone[i] is recorded behind it.  0, -1 (the error is set), -2 (HIP) */
+  struct Got { size_t n; int more; U32 first, last; };
+  auto load = [&] (int i, U64 at, Got *o) -> int
+    { o->n = 0; o->more = 0; o->first = o->last = 0;
+      if (dfill)
+        { if (dfill (src, t.dText[i], window, at, (void *) t.copy, &o->n, &o->more, &o->first, &o->last)) return -1; }
+      else
+        { o->n = fill (src, t.hPin[i], window, at);
+          if (o->n == (size_t) -1) { o->n = 0; mgSetError ("device text windows: read failed"); return -1; }
+          o->more = o->n == window;
+          if (o->n) { o->first = t.hPin[i][0]; o->last = t.hPin[i][o->n - 1]; }
+          if (o->n && hipMemcpyAsync (t.dText[i], t.hPin[i], o->n, hipMemcpyHostToDevice, t.copy) != hipSuccess) return -2;
+        }
+      if (o->n && hipEventRecord (t.h2dDone[i], t.copy) != hipSuccess) return -2;
+      return 0;
+    };
+  Got cur0, nxt;
+  rc = load (0, 0, &cur0);
+  if (rc == -1) return -1;
+  Got curG = cur0;
+  while (curG.n && !rc)
     { const int cur = (int) (w & 1), oth = cur ^ 1;
+      const size_t nCur = curG.n;
       if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { rc = -2; break; }
-      MgTextWindow win; win.dText = t.dText[cur]; win.hText = t.hPin[cur]; win.n = nCur; win.off = off; win.prevByte = prevByte; win.index = w;
+      MgTextWindow win; win.dText = t.dText[cur]; win.hText = dfill ? 0 : t.hPin[cur]; win.n = nCur; win.off = off; win.prevByte = prevByte; win.index = w;
+      win.first = curG.first; win.last = curG.last;
       if (fn (ctx, &win, (void *) st)) { rc = -1; break; }
-      prevByte = t.hPin[cur][nCur - 1];
+      prevByte = curG.last;
       /* the next window into the other page-locked buffer (whose last copy to the device must be over) and across the link at once: the other
          device buffer is free, its window's kernels were waited for */
-      size_t nNext = 0;
-      if (nCur == window)
+      nxt.n = 0; nxt.more = 0; nxt.first = nxt.last = 0;
+      if (curG.more)
         { if (w >= 1 && hipEventSynchronize (t.h2dDone[oth]) != hipSuccess) { rc = -2; break; }
-          nNext = fill (src, t.hPin[oth], window, off + nCur);
-          if (nNext == (size_t) -1) { mgSetError ("device text windows: read failed"); rc = -1; break; }
-          if (nNext && (hipMemcpyAsync (t.dText[oth], t.hPin[oth], nNext, hipMemcpyHostToDevice, t.copy) != hipSuccess
-                        || hipEventRecord (t.h2dDone[oth], t.copy) != hipSuccess)) { rc = -2; break; }
+          rc = load (oth, off + nCur, &nxt);
+          if (rc) break;
         }
       if (hipStreamSynchronize (st) != hipSuccess) { rc = -2; break; }
-      off += nCur; nCur = nNext; ++w;
+      off += nCur; curG = nxt; ++w;
     }
   if (rc) { (void) hipStreamSynchronize (t.copy); (void) hipStreamSynchronize (st); }      /* nothing of this call is left in flight over buffers the next one takes */
   if (rc == -2) { mgSetError ("device text windows: HIP failure (%s)", hipGetErrorString (hipGetLastError ())); rc = -1; }
-  if (nWindows) *nWindows = w + (rc && nCur ? 1 : 0);
+  if (nWindows) *nWindows = w + (rc && curG.n ? 1 : 0);
   return rc;
 }
+extern "C" int mgTextStreamWindows (size_t sizeHint, MgTextFillFn fill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows)
+{ return txStreamWindows (sizeHint, fill, 0, src, fn, ctx, nWindows); }
+extern "C" int mgTextStreamWindowsDev (size_t sizeHint, MgTextDevFillFn dfill, void *src, MgTextWindowFn fn, void *ctx, U64 *nWindows)
+{ return txStreamWindows (sizeHint, 0, dfill, src, fn, ctx, nWindows); }
 
 struct TxSink {                                            /* what is done with a batch of complete records */
   int (*fn) (void *ctx, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads, const char *idBytes, const U64 *idOff, hipStream_t st);
