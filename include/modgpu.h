@@ -734,6 +734,32 @@ void     mgInflateDiag (U64 out4[4]) ;   /* calling thread's last call: members 
 int      mgInflateMemberHost (const U8 *comp, U32 cLen, U8 *out, U32 uLen, U32 crc, U32 *status, U64 stats8[8]) ;
 int      mgBgzfInflateFile (const char *inName, const char *outName /* "-": stdout */, FILE *err) ;
 
+/* Blocked gzip (BGZF) deflated on the device: the writer's half.  Text is cut into blocks of at most 65280 bytes (bgzip's), each block becomes
+ * one complete BGZF member of at most 65536 bytes -- the 18-byte header with the 'BC' field, ONE raw-deflate block, CRC-32 and length -- and
+ * one workgroup deflates one block (mg_deflate.hip over mg_deflate_core.h): LZ77 with a one-candidate hash of the next 4 bytes, then the
+ * cheapest of a stored block, a dynamic-Huffman block of literals only and a dynamic-Huffman block with the matches, by their exact bit
+ * costs.  A member is a pure function of its block's bytes: the host compile of the core writes the same bytes as the kernel.
+ *   mgDeflateBlocksDevice: blocks[i] (host) names n ranges [uOff, uOff + uLen) of the device buffer dText; their members are written to
+ * dOut packed, in order, from dOut[0]; memberOff[i] (host, n + 1 entries) is where member i begins, memberOff[n] the bytes written, and
+ * nothing beyond that is written.  Refused with MG_ERR_ARG before anything is launched: uLen > 65280, a range that leaves textBytes,
+ * outBytes < 65536 * n.  Returns when `stream` is idle.
+ *   mgDeflateBlockHost: the same encoder compiled for the host, one block on the calling thread into out[0 .. 65536) -- a test hook.
+ * stats8 (may be 0): the kind written (0 stored, 1 literals only, 2 with matches), literals, matches, longest match, longest distance,
+ * longest literal/length code, longest distance code, payload bits.  Returns 0, -1 on a null argument or uLen > 65280.
+ *   mgBgzfDeflateFile: `bgzip`: any regular file to outName as BGZF with bgzip's 28-byte end-of-file member (an empty file gives that
+ * member alone).  0, or -1 with mgLastError () and no output file left.
+ *   mgSeqConvertFileBgzf: mgSeqConvertFile in every respect -- flags, the type from a .fa / .fq suffix (here before an optional .gz or
+ * .bgz), refusals and their words, *res, no file after a refusal, BGZF input inflated on the device -- but the second walk's output never
+ * crosses the link as text: it is deflated on the device and written as BGZF whatever the name's suffix.
+ *   MODGPU_BGZF_BLOCK: text bytes per member, 1 .. 65280 (default 65280; the tests cross block boundaries with small files). */
+typedef struct { U64 uOff; U32 uLen; U32 pad; } MgGzBlock;
+MgStatus mgDeflateBlocksDevice (const U8 *dText, U64 textBytes, const MgGzBlock *blocks /* host */, U32 n,
+                                U8 *dOut, U64 outBytes, U64 *memberOff /* host, [n + 1] */, void *stream) ;
+int      mgDeflateBlockHost (const U8 *text, U32 uLen, U8 *out /* 65536 */, U32 *outLen, U64 stats8[8]) ;
+void     mgDeflateDiag (U64 out4[4]) ;   /* calling thread's last call: blocks deflated on the device, text bytes in, file bytes out, kernel launches */
+int      mgBgzfDeflateFile (const char *inName, const char *outName, FILE *err) ;
+int      mgSeqConvertFileBgzf (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) ;
+
 /* Deterministic synthetic reads generated directly in HBM (not from the reference):
  *   mgSynthGenome: nBases iid-uniform bases, base g = splitmix64(seed ^ g*0x9E3779B97F4A7C15) >> 62
  *   mgSynthReads : read r = genome[start[r], start[r]+len[r]) reverse-complemented when

@@ -102,6 +102,10 @@ class MgGzMember(C.Structure):        # include/modgpu.h: a gzip member's deflat
     _fields_ = [("cOff", C.c_uint64), ("uOff", C.c_uint64), ("cLen", C.c_uint32), ("uLen", C.c_uint32), ("crc", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class MgGzBlock(C.Structure):         # include/modgpu.h: a block of text for the device's BGZF encoder: where it lies, its length (at most 65280)
+    _fields_ = [("uOff", C.c_uint64), ("uLen", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class MgSeqBatch(C.Structure):        # include/modgpu.h
     _fields_ = [("bases", C.POINTER(C.c_int8)), ("offsets", C.POINTER(C.c_int64)), ("names", C.POINTER(C.c_char_p)),
                 ("nSeq", C.c_int), ("total", C.c_int64), ("isFastq", C.c_int), ("basesCap", C.c_int64)]
@@ -132,6 +136,7 @@ EXPORTS = [
     "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
     "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
     "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile",
+    "mgDeflateBlocksDevice", "mgDeflateBlockHost", "mgDeflateDiag", "mgBgzfDeflateFile", "mgSeqConvertFileBgzf",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
@@ -303,6 +308,9 @@ def lib():
     sig("mgSeqConvertFile", i32, C.c_char_p, C.c_char_p, i32, vp, CONV); sig("mgSeqConvertText", i32, vp, u64, i32, vp, vp, CONV); sig("mgSeqConvertDiag", None, vp)
     sig("mgInflateMembersDevice", i32, vp, u64, C.POINTER(MgGzMember), u32, vp, u64, vp, C.POINTER(u32), vp); sig("mgInflateDiag", None, vp)
     sig("mgInflateMemberHost", i32, vp, u32, vp, u32, u32, C.POINTER(u32), vp); sig("mgBgzfInflateFile", i32, C.c_char_p, C.c_char_p, vp)
+    sig("mgDeflateBlocksDevice", i32, vp, u64, C.POINTER(MgGzBlock), u32, vp, u64, C.POINTER(u64), vp); sig("mgDeflateDiag", None, vp)
+    sig("mgDeflateBlockHost", i32, vp, u32, vp, C.POINTER(u32), vp); sig("mgBgzfDeflateFile", i32, C.c_char_p, C.c_char_p, vp)
+    sig("mgSeqConvertFileBgzf", i32, C.c_char_p, C.c_char_p, i32, vp, CONV)
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
@@ -1078,6 +1086,82 @@ def bgzf_inflate_file(in_path, out_path):
     if rc:
         raise ModgpuError("mgBgzfInflateFile failed: " + lib().mgLastError().decode("latin-1"))
     return True
+
+
+DEFLATE_STATS = ("kind", "literals", "matches", "match", "distance", "litlen_bits", "dist_bits", "bits")      # include/modgpu.h
+BGZF_BLOCK = 65280                                    # text bytes of a member, at most: bgzip's
+
+
+def deflate_block_host(text, guard=64):
+    """mgDeflateBlockHost: one block of at most 65280 bytes through the encoder's host compile.  Returns (member bytes, stats dict, guards intact):
+    the 65536-byte slot lies between `guard` bytes of 0xA5 on both sides, and so does a copy of the text."""
+    text = bytes(text)
+    src = np.full(len(text) + 2 * guard, 0xA5, np.uint8)
+    src[guard:guard + len(text)] = np.frombuffer(text, np.uint8)
+    keep = src.copy()
+    out = np.full(65536 + 2 * guard, 0xA5, np.uint8)
+    n = C.c_uint32(0)
+    stats = (C.c_uint64 * 8)()
+    if lib().mgDeflateBlockHost(src.ctypes.data + guard, len(text), out.ctypes.data + guard, C.byref(n), stats):
+        raise ModgpuError("mgDeflateBlockHost failed: " + lib().mgLastError().decode("latin-1"))
+    intact = bool((out[:guard] == 0xA5).all() and (out[guard + 65536:] == 0xA5).all() and (src == keep).all())
+    return out[guard:guard + int(n.value)].tobytes(), dict(zip(DEFLATE_STATS, (int(x) for x in stats))), intact
+
+
+def deflate_blocks_device(text, blocks, out_bytes=None, guard=4096, fill=0xA5):
+    """mgDeflateBlocksDevice: `text` (bytes) to the device, its ranges [(offset, length)] deflated into BGZF members that are packed from the first
+    byte of a device buffer of out_bytes bytes (default 65536 a block) with `guard` bytes preset to `fill` behind it.  Returns (the packed members as
+    bytes, memberOff as a list of n + 1, guard intact); raises ModgpuError (.status) on a refusal."""
+    data = np.frombuffer(bytes(text), np.uint8)
+    n = len(blocks)
+    out_bytes = 65536 * n if out_bytes is None else out_bytes
+    tab = (MgGzBlock * max(n, 1))()
+    for i, (off, length) in enumerate(blocks):
+        tab[i] = MgGzBlock(off, length, 0)
+    d_text, d_out = DeviceBuffer.from_numpy(data if len(data) else np.zeros(1, np.uint8)), DeviceBuffer(max(out_bytes, 16) + guard)
+    try:
+        check(lib().mgMemsetD(d_out.ptr, fill, d_out.nbytes, None)); check(lib().mgStreamSynchronize(None))
+        off = (C.c_uint64 * (n + 1))()
+        rc = lib().mgDeflateBlocksDevice(d_text.ptr, len(data), tab, n, d_out.ptr, out_bytes, off, None)
+        if rc:
+            e = ModgpuError("mgDeflateBlocksDevice failed: " + lib().mgLastError().decode("latin-1"))
+            e.status = rc
+            raise e
+        whole = d_out.to_numpy(np.uint8, d_out.nbytes)
+        end = int(off[n])
+        return whole[:end].tobytes(), [int(x) for x in off], bool((whole[end:] == fill).all())
+    finally:
+        d_text.free(); d_out.free()
+
+
+def deflate_diag():
+    """mgDeflateDiag: dict(blocks, text, file, launches) of the calling thread's last call that could deflate on the device"""
+    v = (C.c_uint64 * 4)()
+    lib().mgDeflateDiag(v)
+    return dict(zip(("blocks", "text", "file", "launches"), (int(x) for x in v)))
+
+
+def bgzf_deflate_file(in_path, out_path):
+    """mgBgzfDeflateFile: `bgzip` on the device: any regular file to out_path as BGZF (knobs(BGZF_BLOCK=n): n text bytes a member); raises ModgpuError"""
+    if lib().mgBgzfDeflateFile(os.fsencode(in_path), os.fsencode(out_path), None):
+        raise ModgpuError("mgBgzfDeflateFile failed: " + lib().mgLastError().decode("latin-1"))
+
+
+def seqconvert_file_bgzf(in_path, out_path, flags=0):
+    """mgSeqConvertFileBgzf: seq_convert_file with the output deflated on the device and written as BGZF, whatever out_path's suffix (the type may
+    come from a .fa / .fq before .gz or .bgz).  Returns (stderr text, result dict); raises ModgpuError as seq_convert_file does."""
+    import tempfile
+    res = MgSeqConvert()
+    with tempfile.TemporaryDirectory(prefix="modgpu_conv_") as d:
+        pe = os.path.join(d, "err")
+        with CFile(pe, "w") as fe:
+            rc = lib().mgSeqConvertFileBgzf(os.fsencode(in_path), os.fsencode(out_path), flags, fe, C.byref(res))
+        err = open(pe, "rb").read()
+    if rc:
+        e = ModgpuError("mgSeqConvertFileBgzf failed: " + lib().mgLastError().decode("latin-1"))
+        e.err, e.result = err, _seq_convert_result(res)
+        raise e
+    return err.decode("latin-1"), _seq_convert_result(res)
 
 
 def rep1_diag():

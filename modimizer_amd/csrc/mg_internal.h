@@ -214,6 +214,25 @@ MG_HIDDEN void mgBgzfSrcClose (MgBgzfSrc *s);
 MG_HIDDEN void mgBgzfSrcRewind (MgBgzfSrc *s);
 MG_HIDDEN U64 mgBgzfSrcTextBytes (const MgBgzfSrc *s);
 MG_HIDDEN int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
+/* mg_deflate.hip for mg_bgzfsink.hip: mgDeflateBlocksDevice on `stream` with device scratch that outlives the call (it only grows; Free drops it),
+   adding to the thread's mgDeflateDiag */
+typedef struct MgDeflateWork MgDeflateWork;
+MG_HIDDEN MgDeflateWork *mgDeflateWorkNew (void);
+MG_HIDDEN void mgDeflateWorkFree (MgDeflateWork *w);
+MG_HIDDEN MgStatus mgDeflateRun (MgDeflateWork *w, const U8 *dText, U64 textBytes, const MgGzBlock *blocks, U32 n, U8 *dOut, U64 outBytes, U64 *memberOff, void *stream);
+MG_HIDDEN void mgDeflateDiagReset (void);
+/* Text on the device as a blocked-gzip (BGZF) file (mg_bgzfsink.hip): what is appended is cut into blocks of MODGPU_BGZF_BLOCK bytes wherever the appends
+   end, whole blocks are deflated on the device (mg_deflate.hip) and their packed members handed to `emit` in file order -- a device range, or for the
+   end-of-file member host bytes -- of at most mgBgzfSinkEmitMax () bytes a call, and is done with them when it returns; the tail of less than a block stays on the device.  Close (flush = 1)
+   deflates the tail and emits the end-of-file member.  Every call: 0, or -1 with the error set (emit's own, if it was emit that failed) */
+typedef struct MgBgzfSink MgBgzfSink;
+typedef int (*MgBgzfEmitFn) (void *ctx, const unsigned char *src, size_t n, int onDevice, void *stream);
+MG_HIDDEN MgBgzfSink *mgBgzfSinkOpen (MgBgzfEmitFn emit, void *ctx, const char *what, U64 textHint);      /* textHint: about how much text will come: a short text gets a short row; 0 = no idea */
+MG_HIDDEN size_t mgBgzfSinkEmitMax (const MgBgzfSink *s);
+MG_HIDDEN int mgBgzfSinkAppendDevice (MgBgzfSink *s, const unsigned char *dSrc, size_t n);      /* (the bytes are there: their producer has been waited for) */
+MG_HIDDEN int mgBgzfSinkAppendRun (MgBgzfSink *s, int byte, U64 n);
+MG_HIDDEN int mgBgzfSinkAppendHost (MgBgzfSink *s, const void *p, size_t n);
+MG_HIDDEN int mgBgzfSinkClose (MgBgzfSink *s, int flush);
 /* K1 of the FASTA parser for that consumer: tileEvent[t] = the code (txEvent below) of the last event of tile t of the window, 0: none */
 MG_HIDDEN int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64 textBase, U32 prevByte, U64 *dTileEvent, void *stream);
 #ifdef __HIPCC__

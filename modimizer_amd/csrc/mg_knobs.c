@@ -37,7 +37,7 @@ static void readAll (void)
   { const char *c = e ? strchr (e, ',') : 0; k.hotChunk = c ? atol (c + 1) : MG_KNOB_UNSET; }
   k.noAvx2 = num ("MODGPU_NO_AVX2");               k.textHost = num ("MODGPU_TEXT_HOST");
   k.textWindowKb = num ("MODGPU_TEXT_WINDOW_KB");   k.bgzfHost = num ("MODGPU_BGZF_HOST");
-  k.inflateNoCrc = num ("MODGPU_INFLATE_NOCRC");
+  k.inflateNoCrc = num ("MODGPU_INFLATE_NOCRC");   k.bgzfBlock = num ("MODGPU_BGZF_BLOCK");
   k.fileBatchMbp = num ("MODGPU_FILE_BATCH_MBP");  k.fileBatchBases = num ("MODGPU_FILE_BATCH_BASES");
   k.queryHostChain = num ("MODGPU_QUERY_HOST_CHAIN");
   k.iterHostBelow = num ("MODGPU_ITER_HOST_BELOW");

@@ -601,7 +601,7 @@ struct SqPass {                                          /* one walk over the te
   int type = 0;
   size_t tilesCap = 0, outCap = 0;
   SqTiles T; SqState *dState = 0; SqWin *dWin = 0; unsigned char *dOut[2] = { 0, 0 };
-  SqWriter *wr = 0; hipStream_t copy = 0;
+  SqWriter *wr = 0; MgBgzfSink *bz = 0; hipStream_t copy = 0;      /* the window's output goes to one of the two: as text to the writer thread, or on the device into the BGZF sink */
   U64 pending = SQ_NONE;                                  /* the window whose output is still on the device */
   U32 lastByte = 0; U64 bytes = 0;
   double msCopy = 0, msWait = 0, msKernels = 0;
@@ -618,6 +618,14 @@ struct SqPass {                                          /* one walk over the te
     if (hipMemcpyAsync (&w, dWin + (k & 1), sizeof (w), hipMemcpyDeviceToHost, copy) != hipSuccess || hipStreamSynchronize (copy) != hipSuccess) return mgHipFail (hipGetLastError (), "mgSeqConvert"), -1;
     if (w.outBytes > outCap || (w.spliceCount && w.spliceAt > w.outBytes))
       { mgSetError ("mgSeqConvert: a window's output of %llu bytes, room for %llu", (unsigned long long) w.outBytes, (unsigned long long) outCap); return -1; }
+    if (bz)                                                /* the text stays on the device: the sink deflates it there (mg_bgzfsink.hip) */
+      { const U64 at = w.spliceCount ? w.spliceAt : w.outBytes;
+        clock_gettime (CLOCK_MONOTONIC, &t0);
+        const int rc = mgBgzfSinkAppendDevice (bz, dOut[k & 1], (size_t) at) || (w.spliceCount && mgBgzfSinkAppendRun (bz, '!', w.spliceCount))
+                       || mgBgzfSinkAppendDevice (bz, dOut[k & 1] + at, (size_t) (w.outBytes - at));
+        clock_gettime (CLOCK_MONOTONIC, &t1); msCopy += sqMs (t0, t1);
+        return rc ? -1 : 0;
+      }
     clock_gettime (CLOCK_MONOTONIC, &t0);
     SqWriter::Block &b = wr->acquire ();
     clock_gettime (CLOCK_MONOTONIC, &t1);
@@ -664,11 +672,11 @@ struct SqPass {                                          /* one walk over the te
   }
 };
 
-/* the text of `src` below src.limit through the kernels; the second walk writes to `out`.  0 / -1 */
-static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, SqState *S, int *type, U32 *lastByte, U64 *bytes)
+/* the text of `src` below src.limit through the kernels; the second walk writes to `out`, or appends to `bz`.  0 / -1 */
+static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, MgBgzfSink *bz, SqState *S, int *type, U32 *lastByte, U64 *bytes)
 {
   MgDevScratch scratch ("mgSeqConvert");
-  SqPass p; p.g = g; p.write = out != 0;
+  SqPass p; p.g = g; p.write = out != 0 || bz != 0; p.bz = bz;
   const size_t hint = (size_t) src.size < SQ_WINDOW_HINT ? (size_t) src.size : SQ_WINDOW_HINT, window = mgTextWindowBytes (hint);
   p.tilesCap = window / SQ_TILE + 2;
   U64 *block = 0;
@@ -691,7 +699,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, SqState *S, int *ty
     { p.outCap = sqOutCap (window, g.fastq != 0, g.outFastq != 0);
       if (scratch.get (&p.dOut[0], p.outCap) || scratch.get (&p.dOut[1], p.outCap)) return -1;
       if (hipStreamCreateWithFlags (&p.copy, hipStreamNonBlocking) != hipSuccess) { scratch.fail (); return -1; }
-      if (wr.open (out, p.outCap)) { wr.close (); (void) hipStreamDestroy (p.copy); return -1; }
+      if (!bz && wr.open (out, p.outCap)) { wr.close (); (void) hipStreamDestroy (p.copy); return -1; }
       p.wr = &wr;
     }
   U64 nWindows = 0;
@@ -704,7 +712,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, SqState *S, int *ty
   gSeqDiag[0] += nWindows;
   if (p.write)
     { if (!rc && p.pending != SQ_NONE && p.drain (p.pending)) rc = -1;
-      if (wr.close () && !rc) { mgSetError ("mgSeqConvert: write failed"); rc = -1; }
+      if (!bz && wr.close () && !rc) { mgSetError ("mgSeqConvert: write failed"); rc = -1; }
       (void) hipStreamDestroy (p.copy);
       gSeqMs[3] += p.msCopy; gSeqMs[4] += p.msWait; gSeqMs[5] += wr.msWrite;
     }
@@ -718,17 +726,53 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, SqState *S, int *ty
   return 0;
 }
 
-/* where the output goes: a FILE of the caller's, or a file that is opened once the text has been judged -- a refusal makes none */
+/* the BGZF sink's packed members: to a page-locked block of the writer thread's */
+static int sqBgzfEmit (void *ctx, const unsigned char *src, size_t n, int onDevice, void *stream)
+{
+  SqWriter *wr = (SqWriter *) ctx;
+  SqWriter::Block &b = wr->acquire ();
+  int rc = 0;
+  b.n = n; b.spliceAt = 0; b.spliceCount = 0;
+  if (!onDevice) memcpy (b.p, src, n);
+  else if (n && (hipMemcpyAsync (b.p, src, n, hipMemcpyDeviceToHost, (hipStream_t) stream) != hipSuccess || hipStreamSynchronize ((hipStream_t) stream) != hipSuccess))
+    { b.n = 0; rc = -1; mgHipFail (hipGetLastError (), "blocked gzip on the device"); }
+  wr->submit (b);
+  return rc;
+}
+
+/* a FILE as a BGZF file: the sink on the device and the writer thread behind it */
+struct SqBgzf {
+  SqWriter wr; MgBgzfSink *sink = 0; bool wrOpen = false;
+  int open (FILE *f, const char *what, U64 textHint)
+  { if (!(sink = mgBgzfSinkOpen (sqBgzfEmit, &wr, what, textHint))) return -1;
+    wrOpen = true;
+    return wr.open (f, mgBgzfSinkEmitMax (sink));
+  }
+  int close (int rc)                                       /* a call that failed leaves the file unfinished: it is removed */
+  { if (sink && mgBgzfSinkClose (sink, !rc) && !rc) rc = -1;
+    sink = 0;
+    if (wrOpen && wr.close () && !rc) { mgSetError ("%s", "blocked gzip on the device: write failed"); rc = -1; }
+    wrOpen = false;
+    return rc;
+  }
+};
+
+/* where the output goes: a FILE of the caller's, or a file that is opened once the text has been judged -- a refusal makes none.  The file is text, text
+   through mgGzipOpenWrite (gz), or BGZF deflated on the device (bgzf) */
 struct SqSink {
-  FILE *f = 0; const char *name = 0; bool gz = false, toStdout = false, opened = false;
+  FILE *f = 0; const char *name = 0; bool gz = false, toStdout = false, opened = false, bgzf = false;
+  SqBgzf bz; U64 textHint = 0;
   FILE *get ()
   { if (f || !name) return f;
     f = gz ? mgGzipOpenWrite (toStdout ? "/dev/stdout" : name) : toStdout ? fdopen (dup (1), "w") : fopen (name, "w");
     if (f) opened = true; else mgSetError ("failed to open output file %s", name);
+    if (f && bgzf && bz.open (f, "mgSeqConvert", textHint)) { (void) close (-1); return 0; }
     return f;
   }
+  MgBgzfSink *device () { return bgzf ? bz.sink : 0; }
   int close (int rc)                                       /* the file is the call's: closed; none is left if the call failed (nor one from an earlier call: the program would have truncated it) */
-  { if (opened && fclose (f) && !rc) { mgSetError ("failed to write output file %s", name); rc = -1; }
+  { if (bgzf) rc = bz.close (rc);
+    if (opened && fclose (f) && !rc) { mgSetError ("failed to write output file %s", name); rc = -1; }
     if (rc && name && !toStdout) (void) remove (name);
     if (opened) { f = 0; opened = false; }
     return rc;
@@ -743,7 +787,7 @@ static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqCo
   SqCfg g = { 0, (flags & MG_SEQ_FASTQ) != 0, (flags & MG_SEQ_HOCO) != 0, 0 };
   SqState S; int type = 0; U32 lastByte = 0; U64 textEnd = 0;
   /* the first walk: is the text acceptable, and where does what is written end */
-  if (sqWalk (src, g, 0, &S, &type, &lastByte, &textEnd)) return -1;
+  if (sqWalk (src, g, 0, 0, &S, &type, &lastByte, &textEnd)) return -1;
   const bool fastq = type == 2;
   const bool complete = fastq ? lastByte == '\n' && !(S.line & 3) : lastByte == '\n' && S.hdrEnd != textEnd;
   const U64 cut = fastq ? S.Bpos : S.Bpos - 1;            /* the byte after the last complete record (FASTQ) / where the text's last record starts (FASTA: its first byte is a start) */
@@ -774,21 +818,26 @@ static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqCo
   MgSeqConvert r; memset (&r, 0, sizeof (r));
   r.inType = type; r.outType = g.outFastq ? 2 : 1;
   /* the second walk: the records that are written */
+  sink.textHint = limit;                                   /* (a short text gets a short row in the BGZF sink) */
   FILE *out = sink.get ();
   if (!out) return -1;
   if (limit)
     { src.limit = limit;
       g.written = 1; g.fastq = fastq;                      /* (the output buffers are sized by it) */
-      if (src.reopen () || sqWalk (src, g, out, &S, &type, &lastByte, &textEnd)) return -1;
+      if (src.reopen () || sqWalk (src, g, sink.device () ? 0 : out, sink.device (), &S, &type, &lastByte, &textEnd)) return -1;
       U64 maxSeq = S.maxSeq, maxId = S.maxId, maxDesc = S.maxDesc;
       if (!fastq)                                           /* the record that the text's end ends: its two newlines, and its '!' */
         { const U64 len = S.V[SQ_K] - S.VB[SQ_K], id = S.V[SQ_I] - S.VB[SQ_I], desc = S.V[SQ_D] - S.VB[SQ_D];
           if (len > maxSeq) maxSeq = len;
           if (id > maxId) maxId = id;
           if (desc > maxDesc) maxDesc = desc;
-          bool ok = fputc ('\n', out) != EOF;
-          if (ok && g.outFastq) ok = fputs ("+\n", out) != EOF && SqWriter::bangs (out, len) && fputc ('\n', out) != EOF;
-          if (!ok) { mgSetError ("mgSeqConvert: write failed"); return -1; }
+          if (MgBgzfSink *bz = sink.device ())
+            { if (mgBgzfSinkAppendHost (bz, "\n", 1) || (g.outFastq && (mgBgzfSinkAppendHost (bz, "+\n", 2) || mgBgzfSinkAppendRun (bz, '!', len) || mgBgzfSinkAppendHost (bz, "\n", 1)))) return -1; }
+          else
+            { bool ok = fputc ('\n', out) != EOF;
+              if (ok && g.outFastq) ok = fputs ("+\n", out) != EOF && SqWriter::bangs (out, len) && fputc ('\n', out) != EOF;
+              if (!ok) { mgSetError ("mgSeqConvert: write failed"); return -1; }
+            }
         }
       r.nSeq = r.nSeqIn = S.nRec; r.totSeqLen = S.V[SQ_K]; r.maxSeqLen = maxSeq; r.totIdLen = S.V[SQ_I]; r.totDescLen = S.V[SQ_D]; r.maxIdLen = maxId; r.maxDescLen = maxDesc;
       r.totSeqLenIn = S.totFilt;
@@ -823,30 +872,35 @@ extern "C" int mgSeqConvertText (const char *text, U64 n, int flags, FILE *out, 
   return rc;
 }
 
-extern "C" int mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res)
+/* mgSeqConvertFile and mgSeqConvertFileBgzf: they differ in where the second walk's output goes, and in that the latter's type suffix may stand before .bgz too */
+static int sqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res, bool bgzf)
 {
   if (res) memset (res, 0, sizeof (*res));
   if (sqFlags (flags, "mgSeqConvertFile")) return -1;
   if (!inName || !outName) { mgSetError ("mgSeqConvertFile: no file name"); return -1; }
-  SqSink sink; sink.name = outName;
-  sink.toStdout = !strcmp (outName, "-") || !strcmp (outName, "-z");
+  SqSink sink; sink.name = outName; sink.bgzf = bgzf;
+  sink.toStdout = !strcmp (outName, "-") || (!bgzf && !strcmp (outName, "-z"));
   size_t len = strlen (outName);
-  sink.gz = !strcmp (outName, "-z") || (!sink.toStdout && len > 3 && !strcmp (outName + len - 3, ".gz"));
+  const bool gzName = !sink.toStdout && len > 3 && !strcmp (outName + len - 3, ".gz"), bgzName = bgzf && !sink.toStdout && len > 4 && !strcmp (outName + len - 4, ".bgz");
+  sink.gz = !bgzf && (!strcmp (outName, "-z") || gzName);
   if (!(flags & (MG_SEQ_FASTA | MG_SEQ_FASTQ | MG_SEQ_HOCO)))      /* seqio.c:426-428 */
-    { if (sink.gz && !sink.toStdout) len -= 3;
+    { if (gzName) len -= 3; else if (bgzName) len -= 4;
       if (!sink.toStdout && len > 3 && !strncmp (outName + len - 3, ".fa", 3)) flags |= MG_SEQ_FASTA;
       else if (!sink.toStdout && len > 3 && !strncmp (outName + len - 3, ".fq", 3)) flags |= MG_SEQ_FASTQ;
       else
-        { mgSetError ("mgSeqConvertFile: no output type from the flags or from a .fa / .fq%s suffix of %s (the program would write its binary format)", sink.gz ? " before .gz" : "", outName);
+        { mgSetError ("mgSeqConvertFile: no output type from the flags or from a .fa / .fq%s suffix of %s (the program would write its binary format)", sink.gz || gzName ? " before .gz" : bgzName ? " before .bgz" : "", outName);
           return -1;
         }
     }
   CpSource src;
   if (src.open (inName)) { src.close (); return -1; }
+  mgDeflateDiagReset ();
   int rc = sqConvert (src, flags, sink, err, res);
   src.close ();
   return sink.close (rc);
 }
+extern "C" int mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, false); }
+extern "C" int mgSeqConvertFileBgzf (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, true); }
 
 /* `bgzip -d`: a blocked-gzip file's text, inflated on the device (mg_bgzfsrc.hip), through the writer of the second walk above: window k + 1 is inflated
    while window k crosses to a page-locked block and the block before that is written */
@@ -897,5 +951,43 @@ extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE 
   if (inflate) { (void) hipStreamSynchronize (inflate); (void) hipStreamDestroy (inflate); }
   if (copy) { (void) hipStreamSynchronize (copy); (void) hipStreamDestroy (copy); }
   mgBgzfSrcClose (bz); ::close (fd);
+  return sink.close (rc);
+}
+
+/* `bgzip`: any regular file as BGZF.  The file is read by the parser's team of readers into page-locked pieces, a piece crosses the link as it is, and the
+   sink (mg_bgzfsink.hip) deflates it on the device; only the compressed file comes back, to the writer thread of the second walk above */
+#define SQ_BGZIP_PIECE ((size_t) 16 << 20)
+extern "C" int mgBgzfDeflateFile (const char *inName, const char *outName, FILE *err)
+{
+  (void) err;
+  mgDeflateDiagReset ();
+  if (!inName || !outName) { mgSetError ("mgBgzfDeflateFile: no file name"); return -1; }
+  const int fd = ::open (inName, O_RDONLY);
+  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
+  struct stat sb;
+  if (fstat (fd, &sb) || !S_ISREG (sb.st_mode)) { ::close (fd); mgSetError ("mgBgzfDeflateFile: %s is not a regular file", inName); return -1; }
+  const U64 size = (U64) sb.st_size;
+  const size_t piece = size < SQ_BGZIP_PIECE ? (size_t) size : SQ_BGZIP_PIECE;
+  SqSink sink; sink.name = outName; sink.toStdout = !strcmp (outName, "-"); sink.bgzf = true; sink.textHint = size ? size : 1;
+  MgDevScratch scratch ("mgBgzfDeflateFile");
+  unsigned char *dPiece = 0, *hPiece = 0;
+  int rc = -1;
+  do
+    { if (mgEnsureDevice ()) break;
+      if (piece && scratch.get (&dPiece, piece)) break;
+      if (piece && !(hPiece = (unsigned char *) mgPinnedAlloc (piece))) { mgSetError ("mgBgzfDeflateFile: no page-locked memory"); break; }
+      if (!sink.get ()) break;
+      bool bad = false;
+      for (U64 off = 0 ; off < size && !bad ; off += piece)
+        { const size_t n = size - off < piece ? (size_t) (size - off) : piece;
+          if (mgTextReadParallel (fd, hPiece, n, (int64_t) off)) { mgSetError ("failed to read file %s", inName); bad = true; }
+          else if (hipMemcpy (dPiece, hPiece, n, hipMemcpyHostToDevice) != hipSuccess) { scratch.fail (); bad = true; }
+          else if (mgBgzfSinkAppendDevice (sink.device (), dPiece, n)) bad = true;
+        }
+      if (!bad) rc = 0;
+    }
+  while (0);
+  mgPinnedFree (hPiece);
+  ::close (fd);
   return sink.close (rc);
 }
