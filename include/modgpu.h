@@ -550,11 +550,21 @@ void mgSeqReleaseBuffers (void) ;	/* the readers keep their two largest buffers 
 void mgReleaseBuffers (void) ;	/* everything the library caches between calls: the readers' buffers (mgSeqReleaseBuffers), the device buffers and pinned staging of the host-buffer entry points (mgAddSequenceBatch, mgUploadPack: they live on the device the last call ran on and are re-made by themselves when the caller moves to another one), the calling thread's iterator scratch (modRCiterator), the page-locked blocks and device arrays mgQueryFile leaves */
 /* Plain FASTA / FASTQ text parsed ON THE DEVICE (the host only moves the bytes: parallel pread into pinned memory, the text as it
  * is across PCIe, record starts / headers / bases found by small kernels per window): mgAddSequenceFile, mgReferenceFastaRead and
- * mgQueryFile take this path by themselves for plain text and use the reader above for gzip, a file that does not end in a
+ * mgQueryFile take this path by themselves for plain text and for blocked gzip (BGZF) from end to end -- inflated on the device into
+ * the same windows, MODGPU_BGZF_HOST=1: by the reader above -- and use the reader above for ordinary gzip, a file that does not end in a
  * newline, a FASTA file whose last line is a header, FASTQ that breaks a rule (from the first record not handed on).
  * This entry returns the parser's records as host arrays (bases 0..3 one per byte, offsets[nSeq + 1]; free () both): 0 = done,
  * -1 = error (mgLastError), -2 = not a file the device parser takes as a whole (nothing is returned). */
 int  mgTextParseFileDevice (const char *filename, char **bases, int64_t **offsets, int64_t *nSeq) ;
+/* test hook: the reader that takes a file up where the device parser hands it over -- from the record that starts at byte startOff of the
+ * file's TEXT (a file offset for plain text, the offset in the inflated text for blocked gzip), which is line startLine and record
+ * startSeq + 1 of the file; 0 for an offset at or past the text's end, for ordinary gzip, for a pipe */
+MgSeqReader *mgSeqOpenAt (const char *filename, U64 startOff, U64 startLine, U64 startSeq) ;
+/* of the calling thread's last file call (mgAddSequenceFile, mgAddSequenceFile10x, mgReferenceFastaRead, mgQueryFile, mgRefPaintFile,
+ * mgTextParseFileDevice ..): which parser took the file -- 0 the host parser from the start, 1 the device parser over plain text, 2 the
+ * device parser over blocked gzip inflated on the device --, windows parsed on the device, text bytes parsed on the device, the text
+ * offset handed to the host parser (0: none) */
+void mgTextFileDiag (U64 out4[4]) ;
 /* the callers' per-file loops: parsing of the next batch overlaps the GPU work on the current one */
 int  mgAddSequenceFile (Modset *ms, const char *filename, FILE *out) ;                        /* modutils.c:33-51 */
 int  mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FILE *out) ;   /* modmap.c:93-134 */

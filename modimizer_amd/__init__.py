@@ -137,7 +137,7 @@ EXPORTS = [
     "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
     "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile",
     "mgDeflateBlocksDevice", "mgDeflateBlockHost", "mgDeflateDiag", "mgBgzfDeflateFile", "mgSeqConvertFileBgzf",
-    "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
+    "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgSeqOpenAt", "mgTextFileDiag", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
     "mgAddSequenceFile10x", "mgAddSequenceBatch10x", "mgTrim10xDevice", "mgAdd10xDiag",
     "mgModsetSetCopy", "mgModsetSetCopyM", "mgModsetSetCopyPath", "mgModsetSummaryDevice",
@@ -314,6 +314,7 @@ def lib():
     sig("mgSeqOpen", vp, C.c_char_p); sig("mgSeqNextBatch", i32, vp, C.c_int64, C.POINTER(MgSeqBatch))
     sig("mgSeqBatchFree", None, C.POINTER(MgSeqBatch)); sig("mgSeqClose", None, vp); sig("mgSeqReleaseBuffers", None); sig("mgReleaseBuffers", None)
     sig("mgTextParseFileDevice", i32, C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64))
+    sig("mgSeqOpenAt", vp, C.c_char_p, u64, u64, u64); sig("mgTextFileDiag", None, vp)
     sig("mgAddSequenceFile", i32, MS, C.c_char_p, vp); sig("mgReferenceFastaRead", i32, vp, C.c_char_p, C.c_bool, vp)
     sig("mgQueryFile", i32, vp, C.c_char_p, vp)
     sig("mgReportDepths", i32, MS, C.POINTER(MS), i32, vp)
@@ -1076,6 +1077,14 @@ def inflate_diag():
     v = (C.c_uint64 * 4)()
     lib().mgInflateDiag(v)
     return dict(zip(("members", "uploaded", "text", "launches"), (int(x) for x in v)))
+
+
+def text_file_diag():
+    """mgTextFileDiag: dict(path, windows, text, handed_over) of the calling thread's last file call: path 0 = the host parser from the
+    start, 1 = the device parser over plain text, 2 = over blocked gzip inflated on the device"""
+    v = (C.c_uint64 * 4)()
+    lib().mgTextFileDiag(v)
+    return dict(zip(("path", "windows", "text", "handed_over"), (int(x) for x in v)))
 
 
 def bgzf_inflate_file(in_path, out_path):

@@ -13,9 +13,12 @@
  * carried on the device -- and moves to the front of the other staging buffer when more members are needed.  Members are taken in
  * batches whose compressed bytes, a contiguous stretch of the file with headers and trailers, are read by the parser's team of readers
  * (mgTextReadParallel) into page-locked memory in pieces of 16 MiB, one read while the one before is on the link, and uploaded once.  Where device memory allows, the compressed file STAYS on the device
- * for the call's second walk (seqconvert's, composition's re-walk up to a cut): that walk reads and uploads nothing.
+ * for the call's second walk (seqconvert's, composition's re-walk up to a cut): that walk reads and uploads nothing.  A caller that walks the
+ * file once (the text parser, mg_textgpu.hip) says so (mgBgzfSrcOneWalk): nothing stays then, the compressed bytes pass through a ring of
+ * look + 2 x 64 KiB, and the memory a resident file would take is the modset table's.
  * Everything runs on the stream the loop passes (its copy stream); the fill returns with the work over, the statuses checked and the
  * two bytes fetched, while the window before is still in its consumer's kernels. */
+#include <fcntl.h>
 #include <string.h>
 #include <unistd.h>
 #include <string>
@@ -37,6 +40,7 @@ struct MgBgzfSrc {
   unsigned char *dStage[2] = { 0, 0 }; size_t stageCap = 0; int p = 0; size_t at = 0, have = 0;
   size_t look = 0;                                       /* text the staging buffer is filled up to: several windows, so that a launch has members for every CU */
   unsigned char *dComp = 0; size_t compCap = 0; bool resident = false; U64 uploadedTo = 0;
+  bool oneWalk = false;                                  /* the caller walks the file once: the compressed bytes pass through a ring of look + 2 x 64 KiB, nothing stays */
   unsigned char *hComp[2] = { 0, 0 }; hipEvent_t up[2] = { 0, 0 }; size_t piece = 0; U64 pieces = 0;      /* the file crosses in pieces: one is read while the one before it is on the link */
   MgDevBuf<unsigned char> work; unsigned char *hEdge = 0;
   std::vector<MgGzMember> batch; std::vector<U32> status;
@@ -87,6 +91,70 @@ extern "C" int mgBgzfSrcOpen (const char *name, int fd, U64 fileSize, MgBgzfSrc 
 extern "C" void mgBgzfSrcClose (MgBgzfSrc *s) { if (s) { s->release (); delete s; } }
 extern "C" void mgBgzfSrcRewind (MgBgzfSrc *s) { s->m = 0; s->pos = 0; s->at = s->have = 0; }
 extern "C" U64 mgBgzfSrcTextBytes (const MgBgzfSrc *s) { return s->textBytes; }
+extern "C" void mgBgzfSrcOneWalk (MgBgzfSrc *s) { s->oneWalk = true; }      /* (before the first fill) */
+
+/* member m inflated on the host (the decoder's host compile) behind what `text` holds; 0, -2 = it does not inflate */
+static int bzHostMember (MgBgzfSrc *s, size_t m, std::vector<unsigned char> &comp, std::vector<unsigned char> &text)
+{
+  const MgGzMember &g = s->mem[m];
+  comp.resize (g.cLen);
+  if (pread (s->fd, comp.data (), g.cLen, (off_t) g.cOff) != (ssize_t) g.cLen) return -2;
+  const size_t at = text.size (); text.resize (at + g.uLen);
+  U32 status = 0;
+  if (mgInflateMemberHost (comp.data (), g.cLen, text.data () + at, g.uLen, g.crc, &status, 0) || status) return -2;
+  return 0;
+}
+/* what the text parser looks at before it starts, from the member table: the text's first byte, and its last min (cap, text) bytes into tail
+   (*tailN of them) -- the first non-empty member and the last non-empty ones, walking back until the tail is in hand, inflated on the host.
+   0, -2 = a member among them does not inflate (the caller leaves the file to the host reader, which reports it) */
+extern "C" int mgBgzfSrcEdges (MgBgzfSrc *s, unsigned char *first, unsigned char *tail, size_t cap, size_t *tailN)
+{
+  *tailN = 0; *first = 0;
+  if (!s->textBytes) return 0;
+  std::vector<unsigned char> comp, text, piece;
+  size_t m = 0;
+  while (!s->mem[m].uLen) ++m;
+  if (bzHostMember (s, m, comp, text)) return -2;
+  *first = text[0];
+  const size_t want = s->textBytes < cap ? (size_t) s->textBytes : cap;
+  text.clear ();
+  for (size_t k = s->mem.size () ; k-- > 0 && text.size () < want ; )
+    { if (!s->mem[k].uLen) continue;
+      piece.clear ();
+      if (bzHostMember (s, k, comp, piece)) return -2;
+      text.insert (text.begin (), piece.begin (), piece.end ());
+    }
+  memcpy (tail, text.data () + (text.size () - want), want);
+  *tailN = want;
+  return 0;
+}
+
+/* the first byte of a file's text: the file's own first byte, or for a file that starts with blocked-gzip members the first byte of the first
+   non-empty one, inflated on the host; -1: none to be had (for a caller that picks its path by the format's first letter: mg_callers.c) */
+extern "C" int mgTextFirstByte (const char *filename)
+{
+  const int fd = open (filename, O_RDONLY);
+  if (fd < 0) return -1;
+  std::vector<unsigned char> buf (BZ_MEMBER + 64), text;
+  int first = -1;
+  for (U64 at = 0 ; ; )
+    { const ssize_t g = pread (fd, buf.data (), buf.size (), (off_t) at);
+      if (g < 1) break;
+      size_t pay = 0;
+      const size_t size = g >= 18 ? bgzfBlockSize (buf.data (), (size_t) g, &pay) : 0;
+      if (!size) { if (!at) first = buf[0]; break; }        /* plain text (or something the host reader judges) */
+      if (size < pay + 8 + 2 || size > (size_t) g) break;
+      const U32 crc = bzLe32 (buf.data () + size - 8), uLen = bzLe32 (buf.data () + size - 4);
+      if (uLen > BZ_MEMBER) break;
+      if (!uLen) { at += size; continue; }
+      text.resize (uLen);
+      U32 status = 0;
+      if (!mgInflateMemberHost (buf.data () + pay, (U32) (size - pay - 8), text.data (), uLen, crc, &status, 0) && !status) first = text[0];
+      break;
+    }
+  close (fd);
+  return first;
+}
 
 static int bzReserve (MgBgzfSrc *s, size_t cap)
 {
@@ -96,7 +164,7 @@ static int bzReserve (MgBgzfSrc *s, size_t cap)
   size_t look = cap * 8 < BZ_LOOK_MAX ? cap * 8 : BZ_LOOK_MAX; if (look < cap) look = cap;
   const size_t stage = look + BZ_MEMBER;
   size_t freeB = 0;
-  if (s->fileSize <= BZ_RESIDENT_MAX && mgDevFreeBytes (&freeB) && s->fileSize <= freeB / 4) s->resident = true;
+  if (!s->oneWalk && s->fileSize <= BZ_RESIDENT_MAX && mgDevFreeBytes (&freeB) && s->fileSize <= freeB / 4) s->resident = true;
   s->compCap = s->resident ? (size_t) s->fileSize : look + 2 * BZ_MEMBER;
   s->piece = s->compCap < BZ_PIECE ? s->compCap : BZ_PIECE;
   if (hipMalloc ((void **) &s->dStage[0], stage) != hipSuccess || hipMalloc ((void **) &s->dStage[1], stage) != hipSuccess
@@ -180,6 +248,9 @@ extern "C" int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64
       || hipStreamSynchronize (st) != hipSuccess) return mgHipFail (hipGetLastError (), "blocked gzip on the device"), -1;
   *first = s->hEdge[0]; *last = s->hEdge[1];
   s->at += take; s->have -= take; s->pos += take;
+  /* one walk: the empty members behind the text's last byte (bgzip's end marker) are part of the file -- uploaded and checked as every other */
+  if (s->oneWalk && s->pos == s->textBytes)
+    while (s->m < s->mem.size ()) if (bzLoad (s, st)) { (void) hipStreamSynchronize (st); return -1; }
   *n = take; *more = s->pos < end;
   return 0;
 }

@@ -213,6 +213,10 @@ MG_HIDDEN int mgBgzfSrcOpen (const char *name, int fd, U64 fileSize, MgBgzfSrc *
 MG_HIDDEN void mgBgzfSrcClose (MgBgzfSrc *s);
 MG_HIDDEN void mgBgzfSrcRewind (MgBgzfSrc *s);
 MG_HIDDEN U64 mgBgzfSrcTextBytes (const MgBgzfSrc *s);
+MG_HIDDEN int mgTextFirstByte (const char *filename);      /* the first byte of the file's text, through blocked gzip if that is what the file starts with; -1: none */
+MG_HIDDEN void mgBgzfSrcOneWalk (MgBgzfSrc *s);      /* before the first fill: the file is walked once, so its compressed bytes do not stay on the device (no Rewind after it) */
+/* the text's first byte and its last min (cap, text) bytes, from the first and the last non-empty members inflated on the host; 0, -2 = one of them does not inflate */
+MG_HIDDEN int mgBgzfSrcEdges (MgBgzfSrc *s, unsigned char *first, unsigned char *tail, size_t cap, size_t *tailN);
 MG_HIDDEN int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
 /* mg_deflate.hip for mg_bgzfsink.hip: mgDeflateBlocksDevice on `stream` with device scratch that outlives the call (it only grows; Free drops it),
    adding to the thread's mgDeflateDiag */

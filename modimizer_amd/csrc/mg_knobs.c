@@ -39,6 +39,7 @@ static void readAll (void)
   k.textWindowKb = num ("MODGPU_TEXT_WINDOW_KB");   k.bgzfHost = num ("MODGPU_BGZF_HOST");
   k.inflateNoCrc = num ("MODGPU_INFLATE_NOCRC");   k.bgzfBlock = num ("MODGPU_BGZF_BLOCK");
   k.fileBatchMbp = num ("MODGPU_FILE_BATCH_MBP");  k.fileBatchBases = num ("MODGPU_FILE_BATCH_BASES");
+  k.textIdsDevice = num ("MODGPU_TEXT_IDS_DEVICE");
   k.queryHostChain = num ("MODGPU_QUERY_HOST_CHAIN");
   k.iterHostBelow = num ("MODGPU_ITER_HOST_BELOW");
   k.readsetHost = num ("MODGPU_READSET_HOST");

@@ -42,7 +42,9 @@ typedef struct {
   long overlapCands;       /* MODGPU_OVERLAP_CANDS: candidates (entries of the inverse lists) per device batch of modasm's overlap passes; unset: from the free device memory */
   long testModsBatch;      /* MODGPU_TESTMODS_BATCH: tested mods per device batch of modasm -T (mgReadsetTestMods); unset: as many as half of the free device memory holds, 2 GiB at most */
   long overlapLds;        /* MODGPU_OVERLAP_LDS: entries of a query's mod table that a wave of the pair kernel stages in LDS (default 1024, at most 2048); a longer table is searched in HBM */
-  long bgzfHost;           /* MODGPU_BGZF_HOST: 1 = mgCompositionFile / mgSeqConvertFile inflate a blocked-gzip (BGZF) file on the host, as every other gzip, not on the device */
+  long bgzfHost;           /* MODGPU_BGZF_HOST: 1 = a blocked-gzip (BGZF) file is inflated on the host, as every other gzip, not on the device: by mgCompositionFile / mgSeqConvertFile, and by the
+                              device text parser's callers (mgAddSequenceFile, mgReferenceFastaRead, mgQueryFile ..), which then read it with the host parser from the start */
+  long textIdsDevice;      /* MODGPU_TEXT_IDS_DEVICE: 1 = the record ids of a PLAIN file come from the id kernels too (blocked gzip: always), not from the host team over the page-locked window */
   long bgzfBlock;          /* MODGPU_BGZF_BLOCK: text bytes per member of the device's BGZF writer (mg_bgzfsink.hip), 1 .. 65280 (default and bgzip's: 65280) */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */

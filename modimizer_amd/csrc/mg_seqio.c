@@ -280,9 +280,31 @@ static size_t readParallel (MgSeqReader *r, char *dst, size_t n)
 
 static void closeInput (MgSeqReader *r) { if (r->gz) gzclose (r->gz); else close (r->fd); free (r->cbuf); r->cbuf = 0; }
 
-/* startOff / startLine / startSeq: a reader that takes a plain regular file up from a record that starts at byte startOff, which
-   is line startLine of the file and record startSeq + 1 (the device text parser hands a file over like this when it meets text
-   it leaves to this parser: mg_textgpu.hip); 0 / 1 / 0 for a whole file */
+/* blocked gzip: the member that holds byte textOff of the TEXT, by a walk over the members' headers (one pread a member: its trailer and the
+   next one's header lie side by side) that sums their ISIZE.  *fileOff: where that member starts in the file, *uOff: the text offset of its first
+   byte.  0 = found; -1 = the text ends at or before textOff, or a member on the way is not a block */
+static int bgzfSeekText (int fd, size_t textOff, size_t *fileOff, size_t *uOff)
+{
+  unsigned char buf[8 + 64];
+  size_t at = 0, text = 0;
+  ssize_t g = pread (fd, buf + 8, 64, 0);
+  for (;;)
+    { size_t pay = 0;
+      if (g < 18) return -1;
+      const size_t size = bgzfBlockSize (buf + 8, (size_t) g, &pay);
+      if (!size || size < pay + 8 + 2) return -1;
+      g = pread (fd, buf, sizeof (buf), (off_t) (at + size - 8));
+      if (g < 8) return -1;
+      const size_t uLen = (size_t) buf[4] | ((size_t) buf[5] << 8) | ((size_t) buf[6] << 16) | ((size_t) buf[7] << 24);
+      if (textOff < text + uLen) { *fileOff = at; *uOff = text; return 0; }
+      text += uLen; at += size; g -= 8;
+    }
+}
+
+/* startOff / startLine / startSeq: a reader that takes a regular file up from a record that starts at byte startOff of its TEXT -- a
+   file offset for plain text, the offset in the inflated text for blocked gzip -- which is line startLine of the file and record
+   startSeq + 1 (the device text parser hands a file over like this when it meets text it leaves to this parser: mg_textgpu.hip);
+   0 / 1 / 0 for a whole file */
 static MgSeqReader *seqOpenAt (const char *filename, size_t startOff, U64 startLine, U64 startSeq)
 {
   pthread_once (&convOnce, convInit);
@@ -308,12 +330,22 @@ static MgSeqReader *seqOpenAt (const char *filename, size_t startOff, U64 startL
   { struct stat st;                                              /* plain file: the window it will need is known */
     if (!gz && !bgzf && fstat (fd, &st) == 0 && S_ISREG (st.st_mode)) r->fileSize = (size_t) st.st_size;
   }
-  if (startOff)
+  size_t skip = 0;                                               /* blocked gzip: bytes of the first member read that lie before startOff */
+  if (startOff && bgzf)
+    { size_t uOff = 0;
+      if (bgzfSeekText (fd, startOff, &r->bgzfOff, &uOff)) { closeInput (r); free (r); bigFlush (); return 0; }
+      skip = startOff - uOff;
+    }
+  else if (startOff)
     { if (!r->fileSize || startOff >= r->fileSize || lseek (fd, (off_t) startOff, SEEK_SET) < 0) { closeInput (r); free (r); bigFlush (); return 0; }
       r->consumed = startOff;
     }
   r->buf = (char *) bigAlloc (r->cap);
   r->len = readSome (r, r->buf, r->cap);
+  if (skip)                                                      /* (whole members are read, the first of them holds byte startOff: len > skip) */
+    { if (r->len <= skip) r->len = 0;
+      else { memmove (r->buf, r->buf + skip, r->len - skip); r->len -= skip; }
+    }
   if (!r->len)
     { fprintf (stderr, "sequence file %s unreadable or empty\n", filename);   /* seqio.c:41-45 */
       closeInput (r); bigFree (r->buf, r->cap); free (r); bigFlush ();
@@ -332,6 +364,8 @@ static MgSeqReader *seqOpenAt (const char *filename, size_t startOff, U64 startL
 }
 
 MgSeqReader *mgSeqOpen (const char *filename) { return seqOpenAt (filename, 0, 1, 0); }
+MgSeqReader *mgSeqOpenAt (const char *filename, U64 startOff, U64 startLine, U64 startSeq)      /* test hook: the reader the device text parser's hand-over opens */
+{ return seqOpenAt (filename, (size_t) startOff, startLine, startSeq); }
 
 void mgSeqClose (MgSeqReader *r)
 {
@@ -1117,8 +1151,7 @@ int mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FI
 {
   { RefDevCtx c; c.ref = ref; c.isAdd = isAdd;
     U64 nSeq = 0, totLen = 0, resumeOff = 0, resumeLine = 1;
-    int first = -1;
-    { FILE *f = fopen (filename, "rb"); if (f) { first = fgetc (f); fclose (f); } }
+    const int first = mgTextFirstByte (filename);        /* (of the text: a blocked-gzip file is looked into) */
     if (first == '>')                                     /* (a FASTQ reference goes the host way: the hand-over in the middle of a file is not worth having here) */
       { const int rc = mgTextForEachBatchDevice (filename, refDeviceBatch, &c, 0, 0, &nSeq, &totLen, &resumeOff, &resumeLine);
         if (rc == -1) return -1;

@@ -25,12 +25,23 @@
  * it, line mod 4 says what the byte is; the format's rules are checked on the device and never judged there.
  *
  * Return codes of the parser (txParseFile, mgAddSequenceFileDevice, mgTextForEachBatchDevice): 0 = the whole file; -1 = error
- * (mgLastError); -2 = not a file for this path -- gzip / blocked gzip, a file whose last byte is not a newline (the reference reports
- * the unfinished record, seqio.c:213-217), a FASTA file whose last line is a header, anything that is not a regular file, no
- * device: the caller uses the host parser from the start; -3 = FASTQ text that breaks a rule, or ends inside a record, somewhere
- * after byte *resumeOff: the records before it have been handed on, the host parser continues from there (and says what the
- * reference says).  mgTextParseFileDevice (the test hook) maps -3 to -2 and hands nothing on.  Record ids (seqio.c:303-304) are
- * extracted for the callers that print them (mgReferenceFastaRead, mgQueryFile), not for mgAddSequenceFile (modutils.c:35 ignores them).
+ * (mgLastError); -2 = not a file for this path -- ordinary gzip (and whatever else mgBgzfSrcOpen declines: blocked gzip followed by a
+ * foreign member, mg_pgzip.c's 16 MiB members, a truncated block), text whose last byte is not a newline (the reference reports
+ * the unfinished record, seqio.c:213-217), FASTA text whose last line is a header, anything that is not a regular file, no
+ * device, MODGPU_TEXT_HOST=1, blocked gzip under MODGPU_BGZF_HOST=1: the caller uses the host parser from the start; -3 = FASTQ text
+ * that breaks a rule, or ends inside a record, somewhere after byte *resumeOff: the records before it have been handed on, the host
+ * parser continues from there (and says what the reference says).  mgTextParseFileDevice (the test hook) maps -3 to -2 and hands
+ * nothing on.  Record ids (seqio.c:303-304) are extracted for the callers that print them (mgReferenceFastaRead, mgQueryFile), not for
+ * mgAddSequenceFile (modutils.c:35 ignores them).
+ *
+ * A file that is blocked gzip (BGZF) from end to end is inflated on the device (mg_bgzfsrc.hip) straight into the window's device
+ * buffer and parsed by the same loops; the windows come from one source with two makers (TxSrc below).  For such a file
+ *   - `fileSize` in the loops is the TEXT's size (mgBgzfSrcTextBytes), and what the parser looks at before it starts -- first byte,
+ *     last byte, the last line -- comes from the first and the last members, inflated on the host (mgBgzfSrcEdges);
+ *   - event codes, recPos / endP and *resumeOff carry TEXT offsets (the host parser is opened at a text offset: mg_seqio.c seqOpenAt);
+ *   - prevByte comes from the source's `last` (no page-locked copy of the window exists), and the record ids from the id kernels
+ *     ("record ids on the device" below), not from the host team;
+ *   - a member that does not inflate in the middle of the file is -1, the message naming the member's file offset.
  */
 #include <fcntl.h>
 #include <pthread.h>
@@ -406,6 +417,8 @@ struct TxBufs {
   unsigned char *dBases = 0; size_t basesCap = 0;
   U64 *dRecOff = 0; size_t recCap = 0;
   U32 *dPacked = 0; size_t packedWords = 0;
+  MgDevBuf<U32> dIdLen, dIdLenT, dIdPlace; MgDevBuf<unsigned char> dIdBytes;      /* the id kernels: per header its id's length, that + 1 if it ends in the window, its place; the ids' bytes */
+  unsigned char *hIdBytes = 0; size_t hIdBytesCap = 0; U32 *hIdPlace = 0; size_t hIdPlaceCap = 0;      /* ... and where they land, page-locked */
   hipStream_t copy = 0;
   std::mutex lock;
   void release ()
@@ -413,6 +426,8 @@ struct TxBufs {
     if (hCounts) (void) hipHostFree (hCounts);
     if (hHdr) (void) hipHostFree (hHdr);
     hHdr = 0; dHdr = 0; hdrCap = 0;
+    dIdLen.drop (); dIdLenT.drop (); dIdPlace.drop (); dIdBytes.drop ();
+    mgPinnedFree (hIdBytes); mgPinnedFree (hIdPlace); hIdBytes = 0; hIdPlace = 0; hIdBytesCap = hIdPlaceCap = 0;
     (void) hipFree (dState); (void) hipFree (dOverflow); (void) hipFree (dTileEvent); (void) hipFree (dTileBaseOff); (void) hipFree (dTileStartOff);
     (void) hipFree (dTileBases); (void) hipFree (dTileStarts); (void) hipFree (dBases); (void) hipFree (dRecOff); (void) hipFree (dPacked);
     (void) hipFree (dTileOffQ); (void) hipFree (dTileQual); (void) hipFree (dTq); (void) hipFree (dEndQ); (void) hipFree (dEndP); (void) hipFree (dRecPos);
@@ -548,6 +563,42 @@ extern "C" int mgTextLaunchEventTiles (const unsigned char *dText, size_t n, U64
   hipLaunchKernelGGL (mgTextEventKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, (hipStream_t) stream, dText, (U64) n, textBase, prevByte, dTileEvent);
   return hipGetLastError () == hipSuccess ? 0 : -1;
 }
+/* ---- where a window's text comes from: ONE loader for the parser's two loops and for the window loop below ----
+ * A host source (fill) fills the page-locked buffer and the copy to the device is started; a device source (dfill) fills the device buffer itself by
+ * work on the copy stream.  Either way h2dDone[i] is recorded behind it.  Two makers for the parser: the plain file (its team of readers) and a
+ * blocked-gzip file inflated on the device (mg_bgzfsrc.hip). */
+struct TxSrc { MgTextFillFn fill = 0; MgTextDevFillFn dfill = 0; void *src = 0; };
+struct TxGot { size_t n; int more; U32 first, last; };   /* the window's bytes, whether text follows, its first and last byte */
+/* the window at `at` into buffer i and on its way.  0, -1 (the error is set), -2 (HIP) */
+static int txLoadWindow (TxBufs &t, const TxSrc &s, size_t window, int i, U64 at, TxGot *o)
+{
+  o->n = 0; o->more = 0; o->first = o->last = 0;
+  if (s.dfill)
+    { if (s.dfill (s.src, t.dText[i], window, at, (void *) t.copy, &o->n, &o->more, &o->first, &o->last)) return -1; }
+  else
+    { o->n = s.fill (s.src, t.hPin[i], window, at);
+      if (o->n == (size_t) -1) { o->n = 0; mgSetError ("device text windows: read failed"); return -1; }
+      o->more = o->n == window;
+      if (o->n) { o->first = t.hPin[i][0]; o->last = t.hPin[i][o->n - 1]; }
+      if (o->n && hipMemcpyAsync (t.dText[i], t.hPin[i], o->n, hipMemcpyHostToDevice, t.copy) != hipSuccess) return -2;
+    }
+  if (o->n && hipEventRecord (t.h2dDone[i], t.copy) != hipSuccess) return -2;
+  return 0;
+}
+struct TxPlain { int fd; U64 size; int nThreads; };
+static size_t txPlainFill (void *v, unsigned char *dst, size_t cap, U64 off)
+{
+  const TxPlain *p = (const TxPlain *) v;
+  if (off >= p->size) return 0;
+  if (p->size - off < cap) cap = (size_t) (p->size - off);
+  return txReadParallel (p->fd, dst, cap, (off_t) off, p->nThreads) ? cap : (size_t) -1;
+}
+static TxSrc txSrcPlain (TxPlain *p) { TxSrc s; s.fill = txPlainFill; s.src = p; return s; }
+struct TxBgzf { MgBgzfSrc *bz; U64 size; };              /* size: the text's */
+static int txBgzfFill (void *v, unsigned char *dDst, size_t cap, U64 off, void *stream, size_t *n, int *more, U32 *first, U32 *last)
+{ const TxBgzf *b = (const TxBgzf *) v; return mgBgzfSrcFill (b->bz, dDst, cap, off, b->size, stream, n, more, first, last); }
+static TxSrc txSrcBgzf (TxBgzf *b) { TxSrc s; s.dfill = txBgzfFill; s.src = b; return s; }
+
 /* the window loop for a consumer that keeps nothing per base (mg_internal.h): the parser's buffers, its window size and its overlap of read,
    copy and kernels -- the window's copy is started as soon as it is read, its kernels are launched behind the copy's event, the next window
    is read while they run -- without the batch accumulator */
@@ -564,27 +615,11 @@ static int txStreamWindows (size_t sizeHint, MgTextFillFn fill, MgTextDevFillFn 
   hipStream_t st = 0;
   U64 off = 0, w = 0; U32 prevByte = '\n';
   int rc = 0;
-  /* the window at `at` into buffer i and on its way: a host source fills the page-locked buffer and the copy is started; a device source fills the device
-     buffer itself by work on the copy stream.  Either way h2dDone[i] is recorded behind it.  0, -1 (the error is set), -2 (HIP) */
-  struct Got { size_t n; int more; U32 first, last; };
-  auto load = [&] (int i, U64 at, Got *o) -> int
-    { o->n = 0; o->more = 0; o->first = o->last = 0;
-      if (dfill)
-        { if (dfill (src, t.dText[i], window, at, (void *) t.copy, &o->n, &o->more, &o->first, &o->last)) return -1; }
-      else
-        { o->n = fill (src, t.hPin[i], window, at);
-          if (o->n == (size_t) -1) { o->n = 0; mgSetError ("device text windows: read failed"); return -1; }
-          o->more = o->n == window;
-          if (o->n) { o->first = t.hPin[i][0]; o->last = t.hPin[i][o->n - 1]; }
-          if (o->n && hipMemcpyAsync (t.dText[i], t.hPin[i], o->n, hipMemcpyHostToDevice, t.copy) != hipSuccess) return -2;
-        }
-      if (o->n && hipEventRecord (t.h2dDone[i], t.copy) != hipSuccess) return -2;
-      return 0;
-    };
-  Got cur0, nxt;
-  rc = load (0, 0, &cur0);
+  TxSrc s; s.fill = fill; s.dfill = dfill; s.src = src;
+  TxGot cur0, nxt;
+  rc = txLoadWindow (t, s, window, 0, 0, &cur0);
   if (rc == -1) return -1;
-  Got curG = cur0;
+  TxGot curG = cur0;
   while (curG.n && !rc)
     { const int cur = (int) (w & 1), oth = cur ^ 1;
       const size_t nCur = curG.n;
@@ -598,7 +633,7 @@ static int txStreamWindows (size_t sizeHint, MgTextFillFn fill, MgTextDevFillFn 
       nxt.n = 0; nxt.more = 0; nxt.first = nxt.last = 0;
       if (curG.more)
         { if (w >= 1 && hipEventSynchronize (t.h2dDone[oth]) != hipSuccess) { rc = -2; break; }
-          rc = load (oth, off + nCur, &nxt);
+          rc = txLoadWindow (t, s, window, oth, off + nCur, &nxt);
           if (rc) break;
         }
       if (hipStreamSynchronize (st) != hipSuccess) { rc = -2; break; }
@@ -630,7 +665,7 @@ struct TxSink {                                            /* what is done with 
 struct TxIds {
   std::vector<char> bytes; std::vector<U64> off;
   bool open = false; bool skipOne = false;                 /* the last id is not finished; its '@' is the next window's first byte */
-  double tLens = 0;                 /* (dev timing) */
+  double tLens = 0, tDev = 0;       /* (dev timing: the host team's two passes, the id kernels with their copies) */
   void clear () { bytes.clear (); off.clear (); open = false; skipOne = false; }
   void feed (const unsigned char *p, size_t n)
   { if (skipOne) { if (!n) return; ++p; --n; skipOne = false; }
@@ -737,39 +772,174 @@ static bool txHeadersLaunch (TxBufs &t, const U64 *dSrc, size_t n, hipStream_t s
   return hipGetLastError () == hipSuccess;
 }
 
-static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine);
+/* ---- record ids on the device ----
+ * For a window that has no page-locked copy (a device source), and for plain files under MODGPU_TEXT_IDS_DEVICE=1: the ids are cut out where
+ * the text is.  Entry g of a window is an id that starts at byte start (g): the byte after a header's first byte -- the emit kernels' recPos
+ * (FASTA) or endP + 1 (FASTQ) say where the headers are -- or, for the one explicit entry in front (nPre), the continuation of an id the
+ * window before left open (byte 0, or 1 when that header's first byte is this window's first: TxIds::skipOne) or the FASTQ header at the
+ * file's first byte.
+ *   lengths  the bytes from start up to the first C-locale white space (TxIds::space) or the window's end;
+ *   places   an exclusive sum of length + 1 (+ 0 for an id that does not end in the window) by mgGroupSumKernel (mg_prefix.h);
+ *   gather   the bytes and the 0 terminators into one compact buffer.
+ * Shape: SIXTEEN LANES an entry, four entries a wave.  Ids are a few to a few tens of bytes (a read name), rarely hundreds, and a window
+ * of short reads holds 4e5 of them, 300 bytes apart.  A lane per entry walking bytes makes every load instruction of a wave touch 64
+ * different cache lines for 64 bytes wanted and runs as many dependent loads as the id is long; a wave per entry takes one line a step but
+ * leaves three quarters of its lanes idle on the common id and needs 4e5 waves.  Sixteen lanes read 16 consecutive bytes a step (one
+ * line, seldom two), find the end with the group's 16 bits of one ballot, finish the common id in one to three steps, and in the gather
+ * write 16 consecutive bytes a step.  A 10 000-byte id costs its group 625 steps: rare, and it holds back one wave.
+ * No lane reads at or beyond byte n of the window: a position there counts as the end.  Only a window's last entry can be left open (an id
+ * ends before the next header starts); the gather kernel says so, and whether its header is the next window's first byte, in place[cnt]. */
+#define TX_ID_LANES 16
+#define TX_ID_THREADS 256
+__device__ __forceinline__ bool txSpace (U32 c) { return c == ' ' || (c >= 9 && c <= 13); }      /* TxIds::space */
+/* where entry g's id starts in the window: n or more = no byte of it is here */
+__device__ __forceinline__ U64 txIdStart (U32 g, U32 nPre, U64 preStart, const U64 *__restrict__ src, U64 add, U64 off)
+{ return g < nPre ? preStart : src[g - nPre] + add - off; }
+
+__global__ __launch_bounds__ (TX_ID_THREADS)
+void mgTextIdLenKernel (const unsigned char *__restrict__ text, U64 n, const U64 *__restrict__ src, U64 add, U64 off, U32 nPre, U64 preStart, U32 cnt,
+                        U32 *__restrict__ len, U32 *__restrict__ lenT)
+{
+  const U32 g = (blockIdx.x * TX_ID_THREADS + threadIdx.x) / TX_ID_LANES, l = threadIdx.x & (TX_ID_LANES - 1);
+  const U32 shift = (threadIdx.x & 63u) & ~(U32) (TX_ID_LANES - 1);      /* the group's bits in the wave's ballot */
+  const bool live = g < cnt;
+  const U64 start = live ? txIdStart (g, nPre, preStart, src, add, off) : n;
+  U64 p = start, end = start;
+  bool done = start >= n;                                  /* (uniform over the group, as everything below but q and sp) */
+  for (;;)
+    { bool sp = false;
+      if (!done) { const U64 q = p + l; sp = q >= n || txSpace (text[q]); }
+      const U64 b = __ballot (sp);
+      if (!done)
+        { const U32 m = (U32) (b >> shift) & 0xffffu;
+          if (m) { end = p + (U64) (__ffs (m) - 1); done = true; }
+          else p += TX_ID_LANES;
+        }
+      if (!__any (!done)) break;
+    }
+  if (live && l == 0)
+    { const U32 L = (U32) (end - start);                   /* end <= n where start < n; end == start otherwise */
+      len[g] = L; lenT[g] = L + (end < n ? 1u : 0u);
+    }
+}
+
+__global__ __launch_bounds__ (TX_ID_THREADS)
+void mgTextIdGatherKernel (const unsigned char *__restrict__ text, U64 n, const U64 *__restrict__ src, U64 add, U64 off, U32 nPre, U64 preStart, U32 cnt,
+                           const U32 *__restrict__ len, const U32 *__restrict__ lenT, U32 *place, unsigned char *__restrict__ out)
+{
+  const U32 g = (blockIdx.x * TX_ID_THREADS + threadIdx.x) / TX_ID_LANES, l = threadIdx.x & (TX_ID_LANES - 1);
+  if (g >= cnt) return;
+  const U64 start = txIdStart (g, nPre, preStart, src, add, off);
+  const U32 L = len[g], o = place[g];
+  const bool closed = lenT[g] > L;
+  for (U32 i = l ; i < L ; i += TX_ID_LANES) out[o + i] = text[start + i];      /* start + L <= n */
+  if (l == 0 && closed) out[o + L] = 0;
+  if (l == 0 && g == cnt - 1) place[cnt] = (closed ? 1u : 0u) | (start > n ? 2u : 0u);      /* the last entry: it ended here; its header is the next window's first byte */
+}
+
+/* the ids of a window through the kernels, appended to ids as TxIds::headers does from the page-locked window: dSrc[0 .. nSrc) + add - off are
+   the id starts in the window (dText, n bytes, the text's byte off first), headerAt0: a header at the window's byte 0 that dSrc does not
+   list (the FASTQ file's first).  The stream is waited for.  0 / -1 */
+static int txIdsDevice (TxBufs &t, TxIds &ids, const unsigned char *dText, size_t n, const U64 *dSrc, U64 add, U64 off, size_t nSrc, bool headerAt0, hipStream_t st)
+{
+  const bool cont = ids.open;                              /* the first entry continues the id the window before left open: no new id */
+  const U32 nPre = cont || headerAt0 ? 1u : 0u;
+  const U64 preStart = cont ? (ids.skipOne ? 1 : 0) : 1;
+  const size_t cnt = nSrc + nPre;
+  if (!cnt) return 0;
+  if ((U64) n + cnt >= 0xffffffffull) { mgSetError ("device text parser: a window of %zu bytes is too large for the id kernels", n); return -1; }
+  const double tA = mgNowS ();
+  if (t.dIdLen.reserve (cnt, cnt + cnt / 4 + 64, "record ids on the device") || t.dIdLenT.reserve (cnt, cnt + cnt / 4 + 64, "record ids on the device")
+      || t.dIdPlace.reserve (cnt + 2, cnt + cnt / 4 + 66, "record ids on the device")) return -1;
+  const unsigned grid = (unsigned) ((cnt * TX_ID_LANES + TX_ID_THREADS - 1) / TX_ID_THREADS);
+  U32 *hTotal = (U32 *) (t.hCounts + 6);                   /* page-locked: the scan's total lands where the host reads it */
+  hipLaunchKernelGGL (mgTextIdLenKernel, dim3 (grid), dim3 (TX_ID_THREADS), 0, st, dText, (U64) n, dSrc, add, off, nPre, preStart, (U32) cnt, t.dIdLen.p, t.dIdLenT.p);
+  hipLaunchKernelGGL ((mgGroupSumKernel<U32, U32>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dIdLenT.p, t.dIdPlace.p, (U32) cnt, hTotal);
+  if (hipGetLastError () != hipSuccess || hipStreamSynchronize (st) != hipSuccess) return mgHipFail (hipGetLastError (), "record ids on the device"), -1;
+  const size_t total = *hTotal, bytesCap = (total + 8) & ~(size_t) 7, placeBytes = ((cnt + 1) * 4 + 7) & ~(size_t) 7;
+  if (t.dIdBytes.reserve (bytesCap, bytesCap + bytesCap / 4, "record ids on the device")) return -1;
+  if (bytesCap > t.hIdBytesCap)
+    { mgPinnedFree (t.hIdBytes); t.hIdBytesCap = 0;
+      if (!(t.hIdBytes = (unsigned char *) mgPinnedAlloc (bytesCap + bytesCap / 4))) { mgSetError ("record ids on the device: no page-locked memory"); return -1; }
+      t.hIdBytesCap = bytesCap + bytesCap / 4;
+    }
+  if (placeBytes > t.hIdPlaceCap)
+    { mgPinnedFree (t.hIdPlace); t.hIdPlaceCap = 0;
+      if (!(t.hIdPlace = (U32 *) mgPinnedAlloc (placeBytes + placeBytes / 4))) { mgSetError ("record ids on the device: no page-locked memory"); return -1; }
+      t.hIdPlaceCap = placeBytes + placeBytes / 4;
+    }
+  hipLaunchKernelGGL (mgTextIdGatherKernel, dim3 (grid), dim3 (TX_ID_THREADS), 0, st, dText, (U64) n, dSrc, add, off, nPre, preStart, (U32) cnt,
+                      t.dIdLen.p, t.dIdLenT.p, t.dIdPlace.p, t.dIdBytes.p);
+  if (hipGetLastError () != hipSuccess) return mgHipFail (hipGetLastError (), "record ids on the device"), -1;
+  /* both land in page-locked memory by a kernel's stores, not by the copy engine, which is busy with the next window (mgCopyOutPinned) */
+  if (mgCopyOutPinned (t.hIdBytes, t.dIdBytes.p, bytesCap, (void *) st) != MG_OK || mgCopyOutPinned (t.hIdPlace, t.dIdPlace.p, placeBytes, (void *) st) != MG_OK) return -1;
+  const size_t base = ids.bytes.size (), skip = cont ? 1 : 0;
+  ids.bytes.insert (ids.bytes.end (), (const char *) t.hIdBytes, (const char *) t.hIdBytes + total);
+  size_t at = ids.off.size ();
+  ids.off.resize (at + cnt - skip);
+  for (size_t i = skip ; i < cnt ; ++i) ids.off[at++] = (U64) base + t.hIdPlace[i];
+  const U32 flags = t.hIdPlace[cnt];
+  ids.open = !(flags & 1u); ids.skipOne = (flags & 2u) != 0;
+  ids.tDev += mgNowS () - tA;
+  return 0;
+}
+
+static int txParseFastq (const TxSrc &src, size_t fileSize, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine);
+
+/* of the calling thread's last file call (mgTextFileDiag): which parser took it (0 the host's from the start, 1 this one over plain text, 2 this one over
+   blocked gzip inflated on the device), windows and text bytes parsed here, the text offset handed to the host parser */
+static thread_local U64 gTxDiag[4];
+extern "C" void mgTextFileDiag (U64 out4[4]) { memcpy (out4, gTxDiag, sizeof (gTxDiag)); }
 
 /* the file through the device parser; every batch of complete records goes to sink.  Returns 0, -1 (error: mgLastError), or -2
  * (not a file this path takes: the caller uses the host parser).  *nSeqOut / *totLenOut: records and bases of the file. */
 static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff = 0, U64 *resumeLine = 0)
 {
+  memset (gTxDiag, 0, sizeof (gTxDiag)); mgInflateDiagReset ();      /* the censuses are this call's */
   if (mgEnsureDevice ()) return -2;
   if (mgKnobs ()->textHost == 1) return -2;      /* test knob: the host parser */
-  int fd = open (filename, O_RDONLY);
-  if (fd < 0) return -2;
+  struct Input { int fd = -1; MgBgzfSrc *bz = 0; ~Input () { if (bz) mgBgzfSrcClose (bz); if (fd >= 0) close (fd); } } in;      /* closed on whichever return */
+  in.fd = open (filename, O_RDONLY);
+  if (in.fd < 0) return -2;
+  const int fd = in.fd;
   struct stat sb;
-  if (fstat (fd, &sb) || !S_ISREG (sb.st_mode) || sb.st_size < 2) { close (fd); return -2; }
-  const size_t fileSize = (size_t) sb.st_size;
-  unsigned char first = 0, lastc = 0;
-  if (pread (fd, &first, 1, 0) != 1 || pread (fd, &lastc, 1, (off_t) fileSize - 1) != 1 || (first != '>' && first != '@') || lastc != '\n') { close (fd); return -2; }
-  if (first == '>')                                       /* a FASTA file whose LAST line is a header: the reference reports the record as incomplete and does not
+  if (fstat (fd, &sb) || !S_ISREG (sb.st_mode) || sb.st_size < 2) return -2;
+  /* what is looked at before anything starts: the text's size, its first byte, its last bytes (4096, or all of it) -- preads of a plain file, the
+     first and the last members of blocked gzip inflated on the host */
+  size_t fileSize = (size_t) sb.st_size;
+  unsigned char first = 0, magic[2] = { 0, 0 }, tail[4096]; size_t tn = 0;
+  if (pread (fd, magic, 2, 0) != 2) return -2;
+  if (magic[0] == 0x1f && magic[1] == 0x8b)
+    { if (mgKnobs ()->bgzfHost == 1) return -2;           /* test knob: blocked gzip inflated on the host, as on every other path */
+      if (mgBgzfSrcOpen (filename, fd, (U64) sb.st_size, &in.bz)) return -2;      /* ordinary gzip, a foreign member, a truncated block ..: the host reader's */
+      mgBgzfSrcOneWalk (in.bz);                           /* (the compressed file does not stay on the device: that memory is the modset table's) */
+      fileSize = (size_t) mgBgzfSrcTextBytes (in.bz);
+      if (fileSize < 2 || mgBgzfSrcEdges (in.bz, &first, tail, sizeof (tail), &tn)) return -2;      /* (a member that does not inflate: the host parser reports it) */
+    }
+  else
+    { tn = fileSize < sizeof (tail) ? fileSize : sizeof (tail);
+      first = magic[0];
+      if (pread (fd, tail, tn, (off_t) (fileSize - tn)) != (ssize_t) tn) return -2;
+    }
+  if ((first != '>' && first != '@') || tail[tn - 1] != '\n') return -2;
+  if (first == '>')                                       /* FASTA text whose LAST line is a header: the reference reports the record as incomplete and does not
                                                              return it (seqio.c:213-217,314) -- left to the host parser, which says so with the line number */
-    { unsigned char tail[4096]; const size_t tn = fileSize < sizeof (tail) ? fileSize : sizeof (tail);
-      if (pread (fd, tail, tn, (off_t) (fileSize - tn)) != (ssize_t) tn) { close (fd); return -2; }
-      size_t i = tn - 1;                                   /* the final newline */
+    { size_t i = tn - 1;                                   /* the final newline */
       while (i > 0 && tail[i - 1] != '\n') --i;            /* start of the last line (or of the tail: a header longer than that is no record id line we want to judge here) */
-      if (tail[i] == '>' && (i > 0 || tn == fileSize)) { close (fd); return -2; }
+      if (tail[i] == '>' && (i > 0 || tn == fileSize)) return -2;
     }
 
   int curDev = 0;
-  if (hipGetDevice (&curDev) != hipSuccess || curDev < 0 || curDev >= TX_MAXDEV) { (void) hipGetLastError (); close (fd); return -2; }      /* (no room kept for that device: the host parser) */
+  if (hipGetDevice (&curDev) != hipSuccess || curDev < 0 || curDev >= TX_MAXDEV) { (void) hipGetLastError (); return -2; }      /* (no room kept for that device: the host parser) */
   TxBufs &t = gTxs[curDev];
   std::lock_guard<std::mutex> g (t.lock);
-  if (first == '@')
-    { const int rq = txParseFastq (fd, fileSize, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
-      close (fd);
-      return rq;
-    }
+  const int nThreads = txHostThreads ();
+  TxPlain plain; plain.fd = fd; plain.size = fileSize; plain.nThreads = nThreads;
+  TxBgzf bgzf; bgzf.bz = in.bz; bgzf.size = fileSize;
+  const TxSrc src = in.bz ? txSrcBgzf (&bgzf) : txSrcPlain (&plain);
+  const bool devIds = in.bz || mgKnobs ()->textIdsDevice == 1;      /* a device source has no page-locked window for the host team */
+  gTxDiag[0] = in.bz ? 2 : 1;
+  if (first == '@') return txParseFastq (src, fileSize, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
   const size_t window = txWindowBytes (fileSize);
   const U64 batch = txBatchBases (sink.batchBases), bigBatch = batch > txBatchBases (0) ? batch : txBatchBases (0);
   hipStream_t st = 0;
@@ -781,19 +951,19 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
     ck.lap (ck.reserve);
     TxState init; init.lastEvent = 0; init.accBases = 0; init.accRecs = 0;
     if (hipMemcpy (t.dState, &init, sizeof (init), hipMemcpyHostToDevice) != hipSuccess || hipMemset (t.dOverflow, 0, 4) != hipSuccess) break;
-    const int nThreads = txHostThreads ();
     TxIds ids; std::vector<U64> hdr;
     U64 accBases = 0, accRecs = 0;                          /* the accumulator as of the last synchronised window */
     size_t off = 0; int w = 0;
     U32 prevByte = '\n';
-    size_t nCur = fileSize < window ? fileSize : window;
+    TxGot got, nxt;
     ck.lap (ck.flush);
-    if (!txReadParallel (fd, t.hPin[0], nCur, 0, nThreads)) { mgSetError ("device text parser: read failed"); break; }
+    if (txLoadWindow (t, src, window, 0, 0, &got)) break;
     ck.lap (ck.read);
-    if (hipMemcpyAsync (t.dText[0], t.hPin[0], nCur, hipMemcpyHostToDevice, t.copy) != hipSuccess || hipEventRecord (t.h2dDone[0], t.copy) != hipSuccess) break;
     bool failed = false;
-    while (nCur)
+    while (got.n)
       { const int cur = w & 1, oth = cur ^ 1;
+        const size_t nCur = got.n;
+        ++gTxDiag[1]; gTxDiag[2] += nCur;
         /* the window crosses the link and is parsed ... */
         const U64 nTiles = (nCur + TX_TILE - 1) / TX_TILE;
         if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { failed = true; break; }      /* the window's copy was started as soon as it was read (copy stream) */
@@ -804,18 +974,16 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
         hipLaunchKernelGGL (mgTextOffsetScanKernel, dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, t.dTileBases, t.dTileStarts, nTiles, t.dTileBaseOff, t.dTileStartOff, t.dState, t.hCounts);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
         const U32 prevOfWindow = prevByte;
-        prevByte = t.hPin[cur][nCur - 1];
-        /* ... while the host reads the next one into the other pinned buffer (whose last copy to the device must be over) */
+        prevByte = got.last;
+        /* ... while the next one is loaded: read into the other pinned buffer (whose last copy to the device must be over) and across the link at once,
+           or inflated into the other device buffer, beside this window's kernels (that buffer is free: its window's kernels were waited for) */
         const size_t offNext = off + nCur;
-        size_t nNext = fileSize - offNext < window ? fileSize - offNext : window;
-        if (nNext)
+        nxt.n = 0; nxt.more = 0; nxt.first = nxt.last = 0;
+        if (got.more)
           { if (w >= 1 && hipEventSynchronize (t.h2dDone[oth]) != hipSuccess) { failed = true; break; }
             ck.lap (ck.flush);
-            if (!txReadParallel (fd, t.hPin[oth], nNext, (off_t) offNext, nThreads)) { mgSetError ("device text parser: read failed"); failed = true; break; }
+            if (txLoadWindow (t, src, window, oth, offNext, &nxt)) { failed = true; break; }
             ck.lap (ck.read);
-            /* across the link at once, beside this window's kernels (the other device buffer is free: its window's kernels were waited for) */
-            if (hipMemcpyAsync (t.dText[oth], t.hPin[oth], nNext, hipMemcpyHostToDevice, t.copy) != hipSuccess
-                || hipEventRecord (t.h2dDone[oth], t.copy) != hipSuccess) { failed = true; break; }
           }
         /* the counts are in: room for exactly what this window adds, then the bases and the offsets are written */
         if (hipStreamSynchronize (st) != hipSuccess) { failed = true; break; }
@@ -828,16 +996,18 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
                             t.dTileEvent, t.dTileBaseOff, t.dTileStartOff, t.dBases, (U64) t.basesCap, t.dRecOff, (U64) t.recCap, t.dOverflow,
                             sink.wantIds ? t.dRecPos : (U64 *) 0);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
-        if (sink.wantIds && !txHeadersLaunch (t, t.dRecPos + recsBefore, (size_t) (accRecs - recsBefore), st)) { failed = true; break; }
+        if (sink.wantIds && !devIds && !txHeadersLaunch (t, t.dRecPos + recsBefore, (size_t) (accRecs - recsBefore), st)) { failed = true; break; }
         if (hipStreamSynchronize (st) != hipSuccess) { failed = true; break; }
-        if (sink.wantIds)                                  /* the ids of the records that start in this window, while its text is in the pinned buffer */
+        if (sink.wantIds && devIds)                        /* the ids of the records that start in this window, by the id kernels where the text is */
+          { if (txIdsDevice (t, ids, t.dText[cur], nCur, t.dRecPos + recsBefore, 1, (U64) off, (size_t) (accRecs - recsBefore), false, st)) { failed = true; break; } }
+        else if (sink.wantIds)                             /* ... or by the host team, while the text is in the pinned buffer */
           { if (ids.open) ids.feed (t.hPin[cur], nCur);
             const U64 nNew = accRecs - recsBefore;
             hdr.assign (t.hHdr, t.hHdr + nNew);
             for (auto &h : hdr) h -= (U64) off;
             ids.headers (t.hPin[cur], nCur, hdr, nThreads);
           }
-        const bool eof = !nNext;
+        const bool eof = !nxt.n;
         if (eof || accBases >= bigBatch || (accBases >= batch && accRecs >= sink.batchRecs))
           { /* complete records: all of them at the end of the file, otherwise all but the one still open */
             U64 nRec = eof ? accRecs : accRecs - 1, total = accBases;
@@ -862,14 +1032,15 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
                   }
               }
           }
-        off = offNext; nCur = nNext; ++w;
+        off = offNext; got = nxt; ++w;
       }
     ck.lap (ck.flush);
     if (txTiming ()) fprintf (stderr, "  [device text] FASTA: reserve %.3f s, read %.3f, wait for the device %.3f, emit + flush + rest %.3f\n", ck.reserve, ck.read, ck.wait, ck.flush);
+    if (txTiming () && sink.wantIds) fprintf (stderr, "  [device text] ids: the team's two passes %.3f (%d threads), the id kernels %.3f\n", ids.tLens, nThreads, ids.tDev);
+    if (failed) { (void) hipStreamSynchronize (t.copy); (void) hipStreamSynchronize (st); }      /* nothing of this call is left in flight over buffers the next one takes */
     if (failed) { if (!mgLastError ()[0]) mgSetError ("device text parser: HIP failure (%s)", hipGetErrorString (hipGetLastError ())); break; }
     rc = 0;
   } while (0);
-  close (fd);
   if (nSeqOut) *nSeqOut = nSeq;
   if (totLenOut) *totLenOut = totLen;
   return rc;
@@ -878,7 +1049,7 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
 /* the FASTQ file through the device parser.  0 = the whole file; -1 = error; -3 = the text from byte *resumeOff on (a record start,
  * line *resumeLine) is left to the host parser: a rule of the format is broken somewhere after it, or the file ends in the middle of
  * a record -- the host parser then reports what the reference reports (seqio.c:213-217,326-339) */
-static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
+static int txParseFastq (const TxSrc &src, size_t fileSize, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
 {
   const size_t window = txWindowBytes (fileSize);
   const U64 batch = txBatchBases (sink.batchBases), bigBatch = batch > txBatchBases (0) ? batch : txBatchBases (0);
@@ -898,14 +1069,15 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
     U64 accBases = 0, accRecs = 0, accQual = 0;
     size_t off = 0; int w = 0;
     U32 prevByte = '\n';
-    size_t nCur = fileSize < window ? fileSize : window;
+    TxGot got, nxt;
     ck.lap (ck.flush);
-    if (!txReadParallel (fd, t.hPin[0], nCur, 0, nThreads)) { mgSetError ("device text parser: read failed"); break; }
+    if (txLoadWindow (t, src, window, 0, 0, &got)) break;
     ck.lap (ck.read);
-    if (hipMemcpyAsync (t.dText[0], t.hPin[0], nCur, hipMemcpyHostToDevice, t.copy) != hipSuccess || hipEventRecord (t.h2dDone[0], t.copy) != hipSuccess) break;
     bool failed = false, handOver = false;
-    while (nCur)
+    while (got.n)
       { const int cur = w & 1, oth = cur ^ 1;
+        const size_t nCur = got.n;
+        ++gTxDiag[1]; gTxDiag[2] += nCur;
         const U64 nTiles = (nCur + TX_TILE - 1) / TX_TILE;
         if (hipStreamWaitEvent (st, t.h2dDone[cur], 0) != hipSuccess) { failed = true; break; }      /* the window's copy was started as soon as it was read (copy stream) */
         hipLaunchKernelGGL (mgTextNewlineKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, t.dTileEvent);
@@ -916,17 +1088,14 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
                             t.dTileBaseOff, t.dTileOffQ, t.dTileStartOff, t.dTq, t.hCounts);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
         const U32 prevOfWindow = prevByte;
-        prevByte = t.hPin[cur][nCur - 1];
+        prevByte = got.last;
         const size_t offNext = off + nCur;
-        size_t nNext = fileSize - offNext < window ? fileSize - offNext : window;
-        if (nNext)
+        nxt.n = 0; nxt.more = 0; nxt.first = nxt.last = 0;
+        if (got.more)                                      /* the next window, beside this one's kernels (as in the FASTA loop) */
           { if (w >= 1 && hipEventSynchronize (t.h2dDone[oth]) != hipSuccess) { failed = true; break; }
             ck.lap (ck.flush);
-            if (!txReadParallel (fd, t.hPin[oth], nNext, (off_t) offNext, nThreads)) { mgSetError ("device text parser: read failed"); failed = true; break; }
+            if (txLoadWindow (t, src, window, oth, offNext, &nxt)) { failed = true; break; }
             ck.lap (ck.read);
-            /* across the link at once, beside this window's kernels (the other device buffer is free: its window's kernels were waited for) */
-            if (hipMemcpyAsync (t.dText[oth], t.hPin[oth], nNext, hipMemcpyHostToDevice, t.copy) != hipSuccess
-                || hipEventRecord (t.h2dDone[oth], t.copy) != hipSuccess) { failed = true; break; }
           }
         if (hipStreamSynchronize (st) != hipSuccess) { failed = true; break; }
         const U64 recsBefore = accRecs;
@@ -937,11 +1106,22 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
         hipLaunchKernelGGL (mgTextFastqEmitKernel, dim3 ((unsigned) nTiles), dim3 (TX_THREADS), 0, st, t.dText[cur], (U64) nCur, (U64) off, prevOfWindow, t.dTileEvent,
                             t.dTileBaseOff, t.dTileOffQ, t.dTileStartOff, t.dBases, (U64) t.basesCap, t.dRecOff, t.dEndQ, t.dEndP, (U64) t.recCap, t.dOverflow);
         if (hipGetLastError () != hipSuccess) { failed = true; break; }
-        if (sink.wantIds && !txHeadersLaunch (t, t.dEndP + recsBefore + 1, (size_t) (accRecs - recsBefore), st)) { failed = true; break; }
+        if (sink.wantIds && !devIds && !txHeadersLaunch (t, t.dEndP + recsBefore + 1, (size_t) (accRecs - recsBefore), st)) { failed = true; break; }
         if (hipStreamSynchronize (st) != hipSuccess) { failed = true; break; }
         const U64 nlCount = t.hCounts[3];
         bool bad = t.hCounts[4] != 0;
-        if (sink.wantIds && !bad)                         /* a header starts at the file's first byte and after every record's last newline */
+        if (sink.wantIds && !bad && devIds)               /* a header starts at the text's first byte and after every record's last newline: by the id kernels */
+          { ck.lap (ck.flush);
+            size_t nNew = (size_t) (accRecs - recsBefore);
+            if (nNew && !nxt.n)                            /* the text's last window: no header follows the text's last record */
+              { U64 lastEnd = 0;
+                if (hipMemcpy (&lastEnd, t.dEndP + accRecs, 8, hipMemcpyDeviceToHost) != hipSuccess) { failed = true; break; }
+                if (lastEnd + 1 >= (U64) fileSize) --nNew;
+              }
+            if (txIdsDevice (t, ids, t.dText[cur], nCur, t.dEndP + recsBefore + 1, 2, (U64) off, nNew, !off, st)) { failed = true; break; }
+            ck.lap (ck.ids);
+          }
+        else if (sink.wantIds && !bad)                    /* ... or by the host team over the page-locked window */
           { ck.lap (ck.flush);
             if (ids.open) ids.feed (t.hPin[cur], nCur);
             const U64 nNew = accRecs - recsBefore;
@@ -960,7 +1140,7 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
             bad = now.bad != 0;
           }
         U32 ov = 0; if (hipMemcpy (&ov, t.dOverflow, 4, hipMemcpyDeviceToHost) != hipSuccess || ov) { mgSetError ("device text parser: accumulator overflow"); failed = true; break; }
-        const bool eof = !nNext;
+        const bool eof = !nxt.n;
         U64 tail[3] = { 0, 0, 0 };                         /* bases, quality bytes, file position at the end of the last completed record */
         if (accRecs && (hipMemcpy (&tail[0], t.dRecOff + accRecs, 8, hipMemcpyDeviceToHost) != hipSuccess
                         || hipMemcpy (&tail[1], t.dEndQ + accRecs, 8, hipMemcpyDeviceToHost) != hipSuccess
@@ -983,11 +1163,12 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
                 accBases = carry; accQual -= tail[1]; accRecs = 0;
               }
           }
-        off = offNext; nCur = nNext; ++w;
+        off = offNext; got = nxt; ++w;
       }
     ck.lap (ck.flush);
     if (txTiming ()) fprintf (stderr, "  [device text] FASTQ: reserve %.3f s, read %.3f, wait for the device %.3f, record ids %.3f, pack + sink %.3f, emit + rest %.3f\n", ck.reserve, ck.read, ck.wait, ck.ids, ck.sink, ck.flush);
-    if (txTiming ()) fprintf (stderr, "  [device text] ids: the team's two passes %.3f (%d threads)\n", ids.tLens, nThreads);
+    if (txTiming ()) fprintf (stderr, "  [device text] ids: the team's two passes %.3f (%d threads), the id kernels %.3f\n", ids.tLens, nThreads, ids.tDev);
+    if (failed) { (void) hipStreamSynchronize (t.copy); (void) hipStreamSynchronize (st); }
     if (failed) { if (!mgLastError ()[0]) mgSetError ("device text parser: HIP failure (%s)", hipGetErrorString (hipGetLastError ())); break; }
     rc = handOver ? -3 : 0;
   } while (0);
@@ -995,6 +1176,7 @@ static int txParseFastq (int fd, size_t fileSize, TxBufs &t, const TxSink &sink,
   if (totLenOut) *totLenOut = totLen;
   if (resumeOff) *resumeOff = resume;
   if (resumeLine) *resumeLine = 4 * nSeq + 1;
+  if (rc == -3) gTxDiag[3] = resume;
   return rc;
 }
 
