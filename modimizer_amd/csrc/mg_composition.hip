@@ -1,7 +1,7 @@
 /* mg_composition.hip — the reference's `composition` program (composition.c:32-121 over seqIOopenRead (file, 0, true) / seqIOread,
  * seqio.c:30-73,234-346) on the device: how many records, how long, which bases, which qualities, the length bins of -l.
  *
- * The text goes through the device text parser's window loop (mgTextStreamWindows, mg_textgpu.hip) and is read by that parser's rules
+ * The text goes through the device text parser's window loop (mgTextStreamWindows, mg_textwin.hip) and is read by that parser's rules
  * (txLoad / txEvent / txNewlines, mg_internal.h); nothing is written per byte.  Four launches a window:
  *
  *   FASTA   A1  per tile of 4 KiB: the code of its last event (the parser's own K1);
@@ -199,12 +199,7 @@ void mgCompFastaKernel (const unsigned char *__restrict__ text, U64 n, U64 textB
     { const U64 at = (tile * CP_THREADS + threadIdx.x) * 16;
       unsigned char b[16]; U32 prev0 = 0;
       U64 last = 0;
-      if (at < n)
-        { txLoad (text, n, at, prevByte, b, &prev0);
-          U32 prev = prev0;
-#pragma unroll
-          for (int j = 0 ; j < 16 ; ++j) { if (at + j < n) { const U64 e = txEvent (b[j], prev, textBase + at + j); if (e) last = e; } prev = b[j]; }
-        }
+      if (at < n) { txLoad (text, n, at, prevByte, b, &prev0); last = txLastEvent (b, at, n, prev0, textBase + at); }
       const U64 excl = mgBlockExclusive<CP_THREADS, MgMax> (last, s64);
       const U64 in = excl > tileIn[tile] ? excl : tileIn[tile];
       /* the thread's kept bytes and starts: its place in the tile's two scans */

@@ -24,7 +24,7 @@ int  mgIterRequireDevice (void);                   /* 0 when a HIP device is usa
 void mgIterReleaseBuffers (void);                  /* the calling thread's iterator scratch (pinned buffers, stream) */
 /* the same for the minimizer iterator: *rec = malloc()ed {U64 hash[n]; U32 posF[n]} */
 int  mgIterMinScan (Seqhash *sh, const char *s, int len, U64 **rec, U64 *nOut);
-/* the file front end on the device (mg_textgpu.hip): plain FASTA / FASTQ text parsed by the GPU.  0 = done, -1 = error, -2 = not a
+/* the file front end on the device (mg_textgpu.hip; its windows, kernels and record ids: mg_textwin.hip, mg_textparse.hip, mg_textids.hip): plain FASTA / FASTQ text parsed by the GPU.  0 = done, -1 = error, -2 = not a
    file for this path (the host parser takes it), -3 = FASTQ text this parser leaves to the host parser from byte *resumeOff (a
    record start, line *resumeLine of the file; the counts are those of the records added so far) */
 int  mgAddSequenceFileDevice (Modset *ms, const char *filename, U64 *nSeq, U64 *totLen, U64 *totHash, U64 *resumeOff, U64 *resumeLine);
@@ -182,7 +182,7 @@ MG_HIDDEN int  mgRefPaintBatchDevice (Modset *ms, const U32 *dPacked, U64 totalB
                                       const char *idBytes, const U64 *idOff, MgTextOut *w, void **scratch);   /* modutils.c:262-270 over a device batch; 0 / -1 */
 MG_HIDDEN void mgRefPaintScratchFree (void *scratch);
 MG_HIDDEN void mgSetErrorText (const char *msg);
-/* the file mover of the device text parser (mg_textgpu.hip), for the other reader of plain text (mg_settext.hip) */
+/* the file mover of the device text parser (mg_textwin.hip), for the other reader of plain text (mg_settext.hip) */
 MG_HIDDEN int mgTextReadParallel (int fd, unsigned char *dst, size_t n, int64_t off);      /* [off, off + n) of the file into dst by the parser's team of threads; 0 = read */
 MG_HIDDEN size_t mgTextWindowBytes (size_t fileSize);      /* text per window: MODGPU_TEXT_WINDOW_KB, or the parser's default for a file of that size; whole tiles of 4 KiB */
 /* The parser's window loop for another consumer of FASTA / FASTQ text (mg_composition.hip): the text -- whatever `fill` produces: a plain
@@ -259,6 +259,14 @@ static __device__ __forceinline__ U64 txEvent (U32 c, U32 prev, U64 filePos)
   if (c == '\n') return (filePos + 1) << 1;
   if (c == '>' && prev == '\n') return ((filePos + 1) << 1) | 1;
   return 0;
+}
+/* the code of the last event among a thread's bytes, 0: none (prev: the byte before them; base: the text offset of b[0]) */
+static __device__ __forceinline__ U64 txLastEvent (const unsigned char *b, U64 at, U64 n, U32 prev, U64 base)
+{
+  U64 last = 0;
+#pragma unroll
+  for (int j = 0 ; j < 16 ; ++j) { if (at + j < n) { const U64 e = txEvent (b[j], prev, base + j); if (e) last = e; } prev = b[j]; }
+  return last;
 }
 /* the newlines among a thread's bytes (FASTQ: the line a byte belongs to is the number of newlines before it) */
 static __device__ __forceinline__ U32 txNewlines (const unsigned char *b, U64 at, U64 n)

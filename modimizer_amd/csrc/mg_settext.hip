@@ -1,7 +1,7 @@
 /* mg_settext.hip — modutils -rt (modutils.c:169-190) on the device: the lines of a set's text table parsed where the set is built.
  *
  * The host (mgModsetReadText, mg_callers.c) reads the header line, makes the set and hands over the rest of the file.  It comes here
- * as it is: parallel pread into one of two page-locked buffers (the file mover of mg_textgpu.hip), one copy across the link, and per
+ * as it is: parallel pread into one of two page-locked buffers (the file mover of mg_textwin.hip), one copy across the link, and per
  * window of text
  *
  *   lines   newlines counted per tile of 4 KiB, the counts scanned, the newline positions written in order (the same kernel twice);

@@ -1,4 +1,4 @@
-"""The FASTA front end ON THE DEVICE (mg_textgpu.hip) against the host parser (mg_seqio.c, itself pinned to the reference's
+"""The FASTA / FASTQ front end ON THE DEVICE (mg_textgpu.hip and, behind it, mg_textwin.hip, mg_textparse.hip, mg_textids.hip) against the host parser (mg_seqio.c, itself pinned to the reference's
 seqio.c by tests/test_seqio.py) and against what the reference program prints for the golden text files.
 
 mgAddSequenceFile takes the device parser by itself for plain FASTA text; MODGPU_TEXT_HOST=1 forces the host parser,
@@ -341,6 +341,84 @@ def test_query_file_device_parser_equals_host_parser(fmt, crlf, window_kb, batch
             L.mgReferenceDestroy(ref); L.modsetDestroy(ms)
     assert outs[0] == outs[1], [x for x in zip(outs[0].splitlines(), outs[1].splitlines()) if x[0] != x[1]][:3]
     assert outs[0].count(b"\nQ\t") >= n - 1 and outs[0].count(b"\nM\t") > 5
+
+
+# ---- the window walk's edges: texts of exactly 1, 2 and 3 windows, and a byte less and more ----
+EDGE_WINDOW_KB = 8                                           # two tiles a window
+EDGE_KNOBS = dict(TEXT_WINDOW_KB=EDGE_WINDOW_KB, FILE_BATCH_BASES=2000)      # a window holds more bases than that: a batch is cut at every window's end
+
+
+def _edge_text(fmt, size):
+    """`size` bytes of FASTA / FASTQ that end in a newline: a few dozen short records with awkward ids, so headers lie on both sides of
+    every window edge; the last record's sequence line (FASTQ: and its quality line) is padded to reach the size"""
+    rng = np.random.default_rng(size)
+    letters = np.frombuffer(b"ACGTacgtN", np.uint8)
+    mark = b">" if fmt == "fa" else b"@"
+
+    def record(core, tail, seq):
+        if fmt == "fa":
+            return mark + core + tail + b"\n" + b"".join(seq[j:j + 61] + b"\n" for j in range(0, len(seq), 61))
+        return mark + core + tail + b"\n" + seq + b"\n+\n" + b"I" * len(seq) + b"\n"
+
+    out, total = [], 0
+    for core, tail in _awkward_ids(rng, 400):
+        r = record(core, tail, letters[rng.integers(0, len(letters), int(rng.integers(100, 400)))].tobytes())
+        if total + len(r) + 200 > size:
+            break
+        out.append(r); total += len(r)
+    left = size - total                                      # 200 or more
+    if fmt == "fa":
+        out.append(b">last\n" + letters[rng.integers(0, len(letters), left - 7)].tobytes() + b"\n")      # one line, however long
+    else:
+        head = b"last" if left % 2 == 0 else b"lastx"      # sequence and quality line grow together: the header takes the odd byte
+        n = (left - len(head) - 6) // 2
+        out.append(record(head, b"", letters[rng.integers(0, len(letters), n)].tobytes()))
+    text = b"".join(out)
+    assert len(text) == size and text.endswith(b"\n") and 12 <= len(out) <= 120
+    return text
+
+
+@pytest.mark.parametrize("fmt", ["fa", "fq"])
+@pytest.mark.parametrize("size", [w * (EDGE_WINDOW_KB << 10) + d for w in (1, 2, 3) for d in (-1, 0, 1)])
+def test_window_walk_at_its_edges(fmt, size, golden_dir, tmp_path):
+    """Texts that end a byte before, at, and a byte after the end of the first, second and third window of 8 KiB, plain and as BGZF: the
+    records equal the host parser's, the record ids (the Q lines of mgQueryFile) equal the host parser's through the host team, through
+    the id kernels and from BGZF, and mgTextFileDiag counts ceil (bytes / window) windows.  At the exact multiples the plain source says
+    `more` and the next load returns nothing; three windows use a buffer for the second time."""
+    L = mg.lib()
+    text = _edge_text(fmt, size)
+    plain, blocked = str(tmp_path / ("t." + fmt)), str(tmp_path / ("t." + fmt + ".gz"))
+    open(plain, "wb").write(text)
+    open(blocked, "wb").write(mg.bgzf_bytes(text, block=1000))
+    windows = -(-size // (EDGE_WINDOW_KB << 10))
+    _, want = parse_file(plain, 1 << 40, 4)
+    for path, way in ((plain, 1), (blocked, 2)):
+        with mg.knobs(**EDGE_KNOBS):
+            rc, got = device_records(path)
+            diag = mg.text_file_diag()
+        assert rc == 0, L.mgLastError()
+        assert diag == dict(path=way, windows=windows, text=size, handed_over=0)
+        assert len(got) == len(want)
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a & 3, b & 3) if fmt == "fq" else np.array_equal(a, b), (path, i, len(a), len(b))
+    sh = mg.seqhashCreate(15, 8, 17); ms = mg.modsetCreate(sh, 20)
+    ref = L.mgReferenceCreate(ms, 1 << 26)
+    with mg.CFile(str(tmp_path / "ref.txt"), "w") as f:
+        assert L.mgReferenceFastaRead(ref, os.path.join(golden_dir, "ref.fa").encode(), True, f) == 0
+    outs = {}
+    for tag, path, way, kn in (("host", plain, 0, dict(TEXT_HOST=1, FILE_BATCH_BASES=2000)), ("team", plain, 1, EDGE_KNOBS),
+                               ("kernels", plain, 1, dict(TEXT_IDS_DEVICE=1, **EDGE_KNOBS)), ("bgzf", blocked, 2, EDGE_KNOBS)):
+        out = str(tmp_path / (tag + ".txt"))
+        with mg.knobs(**kn):
+            with mg.CFile(out, "w") as f:
+                assert L.mgQueryFile(ref, path.encode(), f) == 0, L.mgLastError()
+            diag = mg.text_file_diag()
+        assert diag["path"] == way and (not way or (diag["windows"], diag["text"]) == (windows, size)), (tag, diag)
+        outs[tag] = open(out, "rb").read()
+    L.mgReferenceDestroy(ref); L.modsetDestroy(ms)
+    assert sum(l.startswith(b"Q\t") for l in outs["host"].splitlines()) == len(want)
+    for tag in ("team", "kernels", "bgzf"):
+        assert outs[tag] == outs["host"], (tag, [x for x in zip(outs[tag].splitlines(), outs["host"].splitlines()) if x[0] != x[1]][:3])
 
 
 @pytest.mark.gpu

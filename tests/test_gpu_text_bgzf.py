@@ -1,4 +1,4 @@
-"""Blocked-gzip (BGZF) FASTA / FASTQ through the DEVICE text parser (mg_textgpu.hip over mg_bgzfsrc.hip): the file is inflated on the
+"""Blocked-gzip (BGZF) FASTA / FASTQ through the DEVICE text parser (mg_textgpu.hip and the mg_text*.hip files behind it, over mg_bgzfsrc.hip): the file is inflated on the
 device into the window buffers, parsed by the same kernels as plain text, its record ids cut out by the id kernels, and a FASTQ file
 that breaks a rule handed to the host parser at a TEXT offset.  Against the host parser on the plain text (records, ids), against the
 plain file and MODGPU_BGZF_HOST=1 (modsets), against MODGPU_TEXT_HOST=1 (the hand-over).  mgTextFileDiag says which way a file went,
