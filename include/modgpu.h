@@ -744,6 +744,24 @@ void     mgInflateDiag (U64 out4[4]) ;   /* calling thread's last call: members 
 int      mgInflateMemberHost (const U8 *comp, U32 cLen, U8 *out, U32 uLen, U32 crc, U32 *status, U64 stats8[8]) ;
 int      mgBgzfInflateFile (const char *inName, const char *outName /* "-": stdout */, FILE *err) ;
 
+/* Ordinary gzip (gzip, pigz, zlib: one member or several, no block table) inflated on the device (mg_gunzip.hip over mg_gunzip_core.h): block starts
+ * are found by testing bit offsets, chunks are decoded speculatively into 16-bit symbols, the chain of chunks is confirmed, the 32 KiB window is carried
+ * from chunk to chunk and the symbols are resolved into bytes; every member's CRC-32 and ISIZE are checked.
+ *   mgGzipInflateFile: `gzip -dc`: the file's text to outName ("-": stdout).  0, or -1 with mgLastError () and no output file left; -2: not a gzip
+ * file (or a first member with a 'BC' field, or more than the device keeps: nothing is written).
+ *   mgGunzipHost: the same pipeline compiled for the host, on the calling thread -- a test hook and the device's yardstick.  comp[0 .. n) is the gzip
+ * file, chunkBytes the compressed bytes per chunk (4096 at least), batchChunks the chunks per batch, symbolsPerChunk the room a chunk's symbols get
+ * before the retry.  *status: 0, the codes of mgInflateMembersDevice, 9 = a single chunk needs more than 2^28 symbols, 10 = not a gzip header where one
+ * must be (bytes behind a trailer included).  Nothing outside out[0 .. cap) is written; text longer than cap is status 7.  Returns 0 (the verdict is
+ * *status), -1 on a null argument or no memory.
+ *   mgGunzipDiag: the calling thread's last mgGzipInflateFile / mgCompositionFile / mgSeqConvertFile: chunks speculated, confirmed, discarded after a
+ * chain break, folded (no candidate), batches, members, capacity retries, kernel launches -- all 0 if the file did not take this path.  diag8 of
+ * mgGunzipHost counts the same.
+ *   mgCompositionFile and mgSeqConvertFile take this path for an ordinary gzip file of at least MODGPU_GZIP_MIN_KB (MODGPU_GZIP_HOST=1: never). */
+int      mgGzipInflateFile (const char *inName, const char *outName /* "-": stdout */, FILE *err) ;
+int      mgGunzipHost (const U8 *comp, U64 n, U32 chunkBytes, U32 batchChunks, U32 symbolsPerChunk, U8 *out, U64 cap, U64 *outLen, U32 *status, U64 diag8[8]) ;
+void     mgGunzipDiag (U64 out8[8]) ;
+
 /* Blocked gzip (BGZF) deflated on the device: the writer's half.  Text is cut into blocks of at most 65280 bytes (bgzip's), each block becomes
  * one complete BGZF member of at most 65536 bytes -- the 18-byte header with the 'BC' field, ONE raw-deflate block, CRC-32 and length -- and
  * one workgroup deflates one block (mg_deflate.hip over mg_deflate_core.h): LZ77 with a one-candidate hash of the next 4 bytes, then the

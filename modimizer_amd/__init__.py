@@ -135,7 +135,7 @@ EXPORTS = [
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
     "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
-    "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile",
+    "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile", "mgGzipInflateFile", "mgGunzipHost", "mgGunzipDiag",
     "mgDeflateBlocksDevice", "mgDeflateBlockHost", "mgDeflateDiag", "mgBgzfDeflateFile", "mgSeqConvertFileBgzf",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgSeqOpenAt", "mgTextFileDiag", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
@@ -308,6 +308,8 @@ def lib():
     sig("mgSeqConvertFile", i32, C.c_char_p, C.c_char_p, i32, vp, CONV); sig("mgSeqConvertText", i32, vp, u64, i32, vp, vp, CONV); sig("mgSeqConvertDiag", None, vp)
     sig("mgInflateMembersDevice", i32, vp, u64, C.POINTER(MgGzMember), u32, vp, u64, vp, C.POINTER(u32), vp); sig("mgInflateDiag", None, vp)
     sig("mgInflateMemberHost", i32, vp, u32, vp, u32, u32, C.POINTER(u32), vp); sig("mgBgzfInflateFile", i32, C.c_char_p, C.c_char_p, vp)
+    sig("mgGzipInflateFile", i32, C.c_char_p, C.c_char_p, vp); sig("mgGunzipDiag", None, vp)
+    sig("mgGunzipHost", i32, vp, u64, u32, u32, u32, vp, u64, C.POINTER(u64), C.POINTER(u32), vp)
     sig("mgDeflateBlocksDevice", i32, vp, u64, C.POINTER(MgGzBlock), u32, vp, u64, C.POINTER(u64), vp); sig("mgDeflateDiag", None, vp)
     sig("mgDeflateBlockHost", i32, vp, u32, vp, C.POINTER(u32), vp); sig("mgBgzfDeflateFile", i32, C.c_char_p, C.c_char_p, vp)
     sig("mgSeqConvertFileBgzf", i32, C.c_char_p, C.c_char_p, i32, vp, CONV)
@@ -1094,6 +1096,43 @@ def bgzf_inflate_file(in_path, out_path):
         return False
     if rc:
         raise ModgpuError("mgBgzfInflateFile failed: " + lib().mgLastError().decode("latin-1"))
+    return True
+
+
+GUNZIP_STATUS = INFLATE_STATUS + ("a chunk of more than 2^28 symbols", "not a gzip header")
+GUNZIP_DIAG = ("speculated", "confirmed", "discarded", "folded", "batches", "members", "retries", "launches")      # include/modgpu.h
+
+
+def gunzip_host(blob, chunk_bytes, batch_chunks, symbols_per_chunk, cap, guard=64):
+    """mgGunzipHost: a gzip file's bytes through the host compile of the device's pipeline.  Returns (status, text bytes, diag dict, guards intact):
+    the output range of `cap` bytes lies between `guard` bytes of 0xA5 on both sides, and so does a copy of the file."""
+    blob = bytes(blob)
+    comp = np.full(len(blob) + 2 * guard, 0xA5, np.uint8)
+    comp[guard:guard + len(blob)] = np.frombuffer(blob, np.uint8)
+    out = np.full(cap + 2 * guard, 0xA5, np.uint8)
+    st, n = C.c_uint32(99), C.c_uint64(0)
+    diag = (C.c_uint64 * 8)()
+    if lib().mgGunzipHost(comp.ctypes.data + guard, len(blob), chunk_bytes, batch_chunks, symbols_per_chunk, out.ctypes.data + guard, cap, C.byref(n), C.byref(st), diag):
+        raise ModgpuError("mgGunzipHost failed: " + lib().mgLastError().decode("latin-1"))
+    intact = bool((out[:guard] == 0xA5).all() and (out[guard + cap:] == 0xA5).all())
+    return int(st.value), out[guard:guard + int(n.value)].tobytes(), dict(zip(GUNZIP_DIAG, (int(x) for x in diag))), intact
+
+
+def gunzip_diag():
+    """mgGunzipDiag: dict(speculated, confirmed, discarded, folded, batches, members, retries, launches) of the calling thread's last call that could
+    inflate ordinary gzip on the device"""
+    v = (C.c_uint64 * 8)()
+    lib().mgGunzipDiag(v)
+    return dict(zip(GUNZIP_DIAG, (int(x) for x in v)))
+
+
+def gzip_inflate_file(in_path, out_path):
+    """mgGzipInflateFile: `gzip -dc` on the device.  True; False if the file is not ordinary gzip (nothing is written); raises ModgpuError"""
+    rc = lib().mgGzipInflateFile(os.fsencode(in_path), os.fsencode(out_path), None)
+    if rc == -2:
+        return False
+    if rc:
+        raise ModgpuError("mgGzipInflateFile failed: " + lib().mgLastError().decode("latin-1"))
     return True
 
 

@@ -616,7 +616,7 @@ static void cpPrint (std::string &s, int flags, const MgComposition *r)
 static int cpCompose (CpSource &src, int flags, FILE *out, FILE *err, MgComposition *res)
 {
   typedef unsigned long long ull;
-  memset (gCompDiag, 0, sizeof (gCompDiag)); mgInflateDiagReset ();
+  memset (gCompDiag, 0, sizeof (gCompDiag)); mgInflateDiagReset (); mgGunzipDiagReset ();
   if (res) memset (res, 0, sizeof (*res));
   if (flags & ~(MG_COMP_BASES | MG_COMP_QUALS | MG_COMP_LENGTHS)) { mgSetError ("mgComposition: unknown flags %d", flags); return -1; }
   if (mgEnsureDevice ()) return -1;

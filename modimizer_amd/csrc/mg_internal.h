@@ -218,6 +218,23 @@ MG_HIDDEN void mgBgzfSrcOneWalk (MgBgzfSrc *s);      /* before the first fill: t
 /* the text's first byte and its last min (cap, text) bytes, from the first and the last non-empty members inflated on the host; 0, -2 = one of them does not inflate */
 MG_HIDDEN int mgBgzfSrcEdges (MgBgzfSrc *s, unsigned char *first, unsigned char *tail, size_t cap, size_t *tailN);
 MG_HIDDEN int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
+/* mg_gunzip.hip: an ordinary gzip stream whose compressed bytes dComp[0 .. n) are on the device, inflated batch by batch (mg_gunzip_core.h); fd: the same
+   file, for the headers and trailers the host looks at.  Next: the stream's next text (*dText, *n bytes, the stream's until the next call) by work on
+   `stream` that is over when it returns, adding to the thread's mgGunzipDiag; 0, or -1 with the error set (*status and *errOff: a wrong stream) */
+typedef struct MgGunzipDev MgGunzipDev;
+MG_HIDDEN int mgGunzipDevOpen (const U8 *dComp, U64 n, int fd, U32 chunkBytes, U32 batchChunks, U32 symbolsPerChunk, MgGunzipDev **out);
+MG_HIDDEN void mgGunzipDevClose (MgGunzipDev *g);
+MG_HIDDEN void mgGunzipDevRewind (MgGunzipDev *g);
+MG_HIDDEN int mgGunzipDevNext (MgGunzipDev *g, void *stream, const U8 **dText, size_t *n, int *done, U32 *status, U64 *errOff);
+MG_HIDDEN void mgGunzipDiagReset (void);
+/* An ordinary gzip file as a source of text on the device (mg_gzipsrc.hip), with the contract of MgBgzfSrc.  Open: -2 = not a file for this path (not
+   gzip, a 'BC' first member, smaller than MODGPU_GZIP_MIN_KB, MODGPU_GZIP_HOST=1 -- `any`: the last two are not asked -- or more than the device holds) */
+typedef struct MgGzipSrc MgGzipSrc;
+MG_HIDDEN int mgGzipSrcOpen (const char *name, int fd, U64 fileSize, int any, MgGzipSrc **out);
+MG_HIDDEN void mgGzipSrcClose (MgGzipSrc *s);
+MG_HIDDEN void mgGzipSrcRewind (MgGzipSrc *s);
+MG_HIDDEN U64 mgGzipSrcSizeHint (const MgGzipSrc *s);
+MG_HIDDEN int mgGzipSrcFill (MgGzipSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
 /* mg_deflate.hip for mg_bgzfsink.hip: mgDeflateBlocksDevice on `stream` with device scratch that outlives the call (it only grows; Free drops it),
    adding to the thread's mgDeflateDiag */
 typedef struct MgDeflateWork MgDeflateWork;

@@ -38,6 +38,9 @@ static void readAll (void)
   k.noAvx2 = num ("MODGPU_NO_AVX2");               k.textHost = num ("MODGPU_TEXT_HOST");
   k.textWindowKb = num ("MODGPU_TEXT_WINDOW_KB");   k.bgzfHost = num ("MODGPU_BGZF_HOST");
   k.inflateNoCrc = num ("MODGPU_INFLATE_NOCRC");   k.bgzfBlock = num ("MODGPU_BGZF_BLOCK");
+  k.gzipHost = num ("MODGPU_GZIP_HOST");           k.gzipChunkKb = num ("MODGPU_GZIP_CHUNK_KB");
+  k.gzipBatch = num ("MODGPU_GZIP_BATCH");         k.gzipRatio = num ("MODGPU_GZIP_RATIO");
+  k.gzipMinKb = num ("MODGPU_GZIP_MIN_KB");
   k.fileBatchMbp = num ("MODGPU_FILE_BATCH_MBP");  k.fileBatchBases = num ("MODGPU_FILE_BATCH_BASES");
   k.textIdsDevice = num ("MODGPU_TEXT_IDS_DEVICE");
   k.queryHostChain = num ("MODGPU_QUERY_HOST_CHAIN");

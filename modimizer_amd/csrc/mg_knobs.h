@@ -45,6 +45,11 @@ typedef struct {
   long bgzfHost;           /* MODGPU_BGZF_HOST: 1 = a blocked-gzip (BGZF) file is inflated on the host, as every other gzip, not on the device: by mgCompositionFile / mgSeqConvertFile, and by the
                               device text parser's callers (mgAddSequenceFile, mgReferenceFastaRead, mgQueryFile ..), which then read it with the host parser from the start */
   long textIdsDevice;      /* MODGPU_TEXT_IDS_DEVICE: 1 = the record ids of a PLAIN file come from the id kernels too (blocked gzip: always), not from the host team over the page-locked window */
+  long gzipHost;           /* MODGPU_GZIP_HOST: 1 = an ordinary gzip file is inflated by the host's zlib stream, as before the device learned to (mg_gzipsrc.hip) */
+  long gzipChunkKb;        /* MODGPU_GZIP_CHUNK_KB: compressed KiB per chunk of the device's gzip inflate (4 at least; default 64) */
+  long gzipBatch;          /* MODGPU_GZIP_BATCH: chunks per batch (default 4096, less where device memory is short) */
+  long gzipRatio;          /* MODGPU_GZIP_RATIO: symbols a chunk may write, in multiples of its compressed bytes: the guess of guess-and-retry (unset: from the file's ISIZE) */
+  long gzipMinKb;          /* MODGPU_GZIP_MIN_KB: the smallest ordinary gzip file (compressed KiB) mgCompositionFile / mgSeqConvertFile inflate on the device (default 16384; 0: every one) */
   long bgzfBlock;          /* MODGPU_BGZF_BLOCK: text bytes per member of the device's BGZF writer (mg_bgzfsink.hip), 1 .. 65280 (default and bgzip's: 65280) */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */

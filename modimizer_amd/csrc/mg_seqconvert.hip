@@ -782,7 +782,7 @@ struct SqSink {
 static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqConvert *res)
 {
   typedef unsigned long long ull;
-  memset (gSeqDiag, 0, sizeof (gSeqDiag)); memset (gSeqMs, 0, sizeof (gSeqMs)); mgInflateDiagReset ();
+  memset (gSeqDiag, 0, sizeof (gSeqDiag)); memset (gSeqMs, 0, sizeof (gSeqMs)); mgInflateDiagReset (); mgGunzipDiagReset ();
   if (mgEnsureDevice ()) return -1;
   SqCfg g = { 0, (flags & MG_SEQ_FASTQ) != 0, (flags & MG_SEQ_HOCO) != 0, 0 };
   SqState S; int type = 0; U32 lastByte = 0; U64 textEnd = 0;
@@ -902,28 +902,18 @@ static int sqConvertFile (const char *inName, const char *outName, int flags, FI
 extern "C" int mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, false); }
 extern "C" int mgSeqConvertFileBgzf (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, true); }
 
-/* `bgzip -d`: a blocked-gzip file's text, inflated on the device (mg_bgzfsrc.hip), through the writer of the second walk above: window k + 1 is inflated
-   while window k crosses to a page-locked block and the block before that is written */
-extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE *err)
+/* `bgzip -d` and `gzip -dc`: a compressed file's text, inflated on the device (mg_bgzfsrc.hip, mg_gzipsrc.hip), through the writer of the second walk above:
+   window k + 1 is inflated while window k crosses to a page-locked block and the block before that is written.  fill: the source's, with the window loop's contract */
+template <class Fill> static int sqInflateFile (const char *what, U64 textHint, const char *outName, Fill fill)
 {
-  (void) err;
-  mgInflateDiagReset ();
-  if (!inName || !outName) { mgSetError ("mgBgzfInflateFile: no file name"); return -1; }
-  const int fd = ::open (inName, O_RDONLY);
-  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
-  struct stat sb;
-  MgBgzfSrc *bz = 0;
-  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgBgzfSrcOpen (inName, fd, (U64) sb.st_size, &bz) : -2;
-  if (rc) { ::close (fd); return rc; }
   SqSink sink; sink.name = outName; sink.toStdout = !strcmp (outName, "-");
-  const U64 text = mgBgzfSrcTextBytes (bz);
-  const size_t window = mgTextWindowBytes ((size_t) (text < SQ_WINDOW_HINT ? text : SQ_WINDOW_HINT));
-  MgDevScratch scratch ("mgBgzfInflateFile");
+  const size_t window = mgTextWindowBytes ((size_t) (textHint < SQ_WINDOW_HINT ? textHint : SQ_WINDOW_HINT));
+  MgDevScratch scratch (what);
   unsigned char *dBuf[2] = { 0, 0 };
   hipStream_t inflate = 0, copy = 0;
   SqWriter wr; bool wrOpen = false;
   FILE *out = 0;
-  rc = -1;
+  int rc = -1;
   do
     { if (mgEnsureDevice ()) break;
       if (scratch.get (&dBuf[0], window) || scratch.get (&dBuf[1], window)) break;
@@ -935,7 +925,7 @@ extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE 
       U64 off = 0; int more = 1; bool bad = false;
       for (U64 k = 0 ; more && !bad ; ++k)
         { size_t n = 0; U32 first, last;
-          if (mgBgzfSrcFill (bz, dBuf[k & 1], window, off, ~(U64) 0, (void *) inflate, &n, &more, &first, &last)) { bad = true; break; }
+          if (fill (dBuf[k & 1], window, off, (void *) inflate, &n, &more, &first, &last)) { bad = true; break; }
           if (pending) { if (hipStreamSynchronize (copy) != hipSuccess) { scratch.fail (); bad = true; pending->n = 0; } wr.submit (*pending); pending = 0; }
           if (bad || !n) break;
           SqWriter::Block &b = wr.acquire ();
@@ -947,11 +937,43 @@ extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE 
       if (!bad) rc = 0;
     }
   while (0);
-  if (wrOpen && wr.close () && !rc) { mgSetError ("mgBgzfInflateFile: write failed"); rc = -1; }
+  if (wrOpen && wr.close () && !rc) { mgSetError ("%s: write failed", what); rc = -1; }
   if (inflate) { (void) hipStreamSynchronize (inflate); (void) hipStreamDestroy (inflate); }
   if (copy) { (void) hipStreamSynchronize (copy); (void) hipStreamDestroy (copy); }
-  mgBgzfSrcClose (bz); ::close (fd);
   return sink.close (rc);
+}
+extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE *err)
+{
+  (void) err;
+  mgInflateDiagReset ();
+  if (!inName || !outName) { mgSetError ("mgBgzfInflateFile: no file name"); return -1; }
+  const int fd = ::open (inName, O_RDONLY);
+  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
+  struct stat sb;
+  MgBgzfSrc *bz = 0;
+  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgBgzfSrcOpen (inName, fd, (U64) sb.st_size, &bz) : -2;
+  if (rc) { ::close (fd); return rc; }
+  rc = sqInflateFile ("mgBgzfInflateFile", mgBgzfSrcTextBytes (bz), outName, [&] (unsigned char *d, size_t cap, U64 off, void *st, size_t *n, int *more, U32 *first, U32 *last)
+                      { return mgBgzfSrcFill (bz, d, cap, off, ~(U64) 0, st, n, more, first, last); });
+  mgBgzfSrcClose (bz); ::close (fd);
+  return rc;
+}
+/* `gzip -dc`: 0, -2 = not ordinary gzip (or more than the device keeps; nothing is written), -1 with mgLastError () and no output file left.  Any size is taken */
+extern "C" int mgGzipInflateFile (const char *inName, const char *outName, FILE *err)
+{
+  (void) err;
+  mgInflateDiagReset (); mgGunzipDiagReset ();
+  if (!inName || !outName) { mgSetError ("mgGzipInflateFile: no file name"); return -1; }
+  const int fd = ::open (inName, O_RDONLY);
+  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
+  struct stat sb;
+  MgGzipSrc *gz = 0;
+  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgGzipSrcOpen (inName, fd, (U64) sb.st_size, 1, &gz) : -2;
+  if (rc) { ::close (fd); return rc; }
+  rc = sqInflateFile ("mgGzipInflateFile", mgGzipSrcSizeHint (gz), outName, [&] (unsigned char *d, size_t cap, U64 off, void *st, size_t *n, int *more, U32 *first, U32 *last)
+                      { return mgGzipSrcFill (gz, d, cap, off, ~(U64) 0, st, n, more, first, last); });
+  mgGzipSrcClose (gz); ::close (fd);
+  return rc;
 }
 
 /* `bgzip`: any regular file as BGZF.  The file is read by the parser's team of readers into page-locked pieces, a piece crosses the link as it is, and the
