@@ -202,6 +202,10 @@ MgStatus mgTableDiag (Modset *ms, U64 *out9) ;
  * and out18 (host) holds: [2 * mode + where] launches of the batch scan, where = 1 when positions or read ids were asked for and 0
  * for the k-mers alone; [12 + mode] launches of the per-read iterator's kernel. */
 MgStatus mgScanDiag (U64 *out18) ;
+/* Where the bucketed add's value writer has run (tests, diagnostics): launches since the process started, out2 (host): [0] on the set's own
+ * stream, behind the add's merge kernel and beside whatever the caller starts next, [1] on the caller's stream inside the add
+ * (MODGPU_VALUE_ASYNC: 0 always there, 1 never, unset: off the caller's stream for mgAddReadsDevice).  Nothing resets them: take differences. */
+MgStatus mgValueWriterDiag (U64 *out2) ;
 
 /* modutils.c:53-63 on the device: dHist[65536] (U64) += histogram of depth[1..max], where depth is
  * the host depth at last sync plus pending device counts, saturated at 65535. */
@@ -213,7 +217,11 @@ MgStatus modsetDepthHistogramDevice (Modset *ms, U64 *dHist65536, void *stream) 
  *   mgQueryReadsDevice = the lookup loop of queryProcess (modmap.c:197-206): seeds (index,pos)
  *                        per read incl. misses.
  * nHash receives the number of modimizers.  Scratch is taken from an internal per-modset arena
- * that grows on demand. */
+ * that grows on demand (two of them, used in turn, when a set takes one mgAddReadsDevice after
+ * another: the last step of an add -- writing the set's value[] on the device -- runs on a stream
+ * of the library's own and may still be running when the call returns, beside whatever the caller
+ * starts next; every call of this library that looks at the values waits for it, and a device-wide
+ * synchronize covers it.  MODGPU_VALUE_ASYNC=0 keeps that step inside the call). */
 MgStatus mgAddReadsDevice (Modset *ms, const U32 *dPacked, U64 totalBases,
                            const U64 *dReadOffsets, U32 nReads, U64 *nHash, void *stream) ;
 MgStatus mgQueryReadsDevice (Modset *ms, const U32 *dPacked, U64 totalBases,

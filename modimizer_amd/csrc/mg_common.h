@@ -49,7 +49,7 @@ enum MgKernelId {
   MG_K_PAINT_ITEMS, MG_K_DEPTH_GUARD, MG_K_DEPTH_GATHER, MG_K_TEXT_LEN, MG_K_TEXT_SCAN, MG_K_TEXT_WRITE,
   MG_K_SETTEXT_LINES, MG_K_SETTEXT_SCAN, MG_K_SETTEXT_PARSE, MG_K_SETTEXT_LAST,
   MG_K_OVL_ACTIVE, MG_K_OVL_EMIT, MG_K_OVL_SORT, MG_K_OVL_RUNS, MG_K_OVL_PAIR,
-  MG_K_TRIM_OFFSETS, MG_K_TRIM_GATHER, MG_K_SETCOPY, MG_K_COPY_TALLY, MG_K_COUNT
+  MG_K_TRIM_OFFSETS, MG_K_TRIM_GATHER, MG_K_SETCOPY, MG_K_COPY_TALLY, MG_K_RANK_RECORD, MG_K_COUNT
 };
 void mgProfBegin (int id, hipStream_t st);
 void mgProfEnd (int id, hipStream_t st);
@@ -309,9 +309,14 @@ MgStatus mgTableClean (MgTable *t, hipStream_t st);                      /* zero
 void     mgTableForget (MgTable *t, hipStream_t st);                     /* all buckets empty again (no memset of the slots) */
 size_t   mgTableAddScratchBytes (const MgTable *t, U64 n);
 bool     mgTableUseBuckets (const MgTable *t, U64 n);
+/* Where the bucketed leg of mgTableAdd may run its value writer instead of on the caller's stream: `merged` is recorded on the caller's stream behind
+   the merge kernel, `stream` waits for it and runs the writer, `done` is recorded behind the writer.  launched (out): that happened -- then the
+   batch's k-mers (dKmer or the segments) and the add's scratch must stay as they are until `done` has completed, and so must value[]. */
+struct MgValueAside { hipStream_t stream; hipEvent_t merged, done; bool launched; };
 MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *scratch, hipStream_t st,
                      const MgHistReq *counted = 0,    /* counted: first-pass digit counts of exactly these n k-mers, if for this geometry */
-                     const MgSegSrc *segSrc = 0);     /* != 0 (and dKmer 0): the k-mers still sit in the scan's segments; only if mgTableAddTakesSegments */
+                     const MgSegSrc *segSrc = 0,      /* != 0 (and dKmer 0): the k-mers still sit in the scan's segments; only if mgTableAddTakesSegments */
+                     MgValueAside *aside = 0);
 bool     mgTableAddTakesSegments (const MgTable *t, U64 n, const MgHistReq *counted);
 MgStatus mgTableMarkOccupied (MgTable *t, const U64 *dKmer, U64 n, hipStream_t st);
 MgStatus mgTableFind (MgTable *t, const U64 *dKmer, U64 n, U32 *dIndexOut, hipStream_t st);

@@ -31,6 +31,7 @@ static void readAll (void)
   k.rankSliceShift = num ("MODGPU_RANK_SLICE_SHIFT");
   k.flagPolarity = num ("MODGPU_FLAG_POLARITY");   k.mergeSlots = num ("MODGPU_MERGE_SLOTS");
   k.mergePlace = num ("MODGPU_MERGE_PLACE");
+  k.valueAsync = num ("MODGPU_VALUE_ASYNC");
   k.bucketR = num ("MODGPU_BUCKET_R");             k.bucketT = num ("MODGPU_BUCKET_T");
   e = getenv ("MODGPU_HOT_SPLIT");
   k.hotSplit = e && *e ? atol (e) : MG_KNOB_UNSET;

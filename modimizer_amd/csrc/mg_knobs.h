@@ -33,6 +33,9 @@ typedef struct {
                               unset = by prefix scan where the expected lists fit the kernel's spill-free instance (mgTableAdd) */
   long bucketR, bucketT;   /* MODGPU_BUCKET_R / MODGPU_BUCKET_T: slots per bucket / threads of the bucket kernels */
   long hotSplit, hotChunk; /* MODGPU_HOT_SPLIT="split[,chunk]": occurrences above which a bucket is reduced chunk-wise first */
+  long valueAsync;         /* MODGPU_VALUE_ASYNC: 0 = a bucketed add writes value[] on the caller's stream, before its rank lookups; 1 = on the set's own stream behind the merge
+                              kernel, whatever the entry point (one that cannot leave the batch's k-mers alone afterwards waits for the writer before it returns);
+                              unset = on that stream for mgAddReadsDevice, whose batch stays in the set's scratch (mgAddBatch) */
   long noAvx2;             /* MODGPU_NO_AVX2: 1 = portable packer / parser loops */
   long textHost;           /* MODGPU_TEXT_HOST: 1 = the host parser for every file */
   long textWindowKb;       /* MODGPU_TEXT_WINDOW_KB: text per window of the device parser */

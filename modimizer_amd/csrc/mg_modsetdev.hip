@@ -22,10 +22,58 @@ extern "C" { volatile int mgLiveDeviceModsets = 0; }
 MgDev *mgDevLookup (const Modset *ms)
 { std::lock_guard<std::mutex> g (gRegLock); auto it = gReg.find (ms); return it == gReg.end () ? 0 : it->second; }
 
+/* ---- the pending value writer (MgDev.valueStream): its one owner ---- */
+MgStatus mgValueSettle (MgDev *d, hipStream_t st, int how, int slot)
+{
+  for (int i = 0 ; i < 2 ; ++i)
+    { if (!d->valuePending[i] || (slot >= 0 && i != slot)) continue;
+      if (how == MG_SETTLE_HOST) { MG_HIP (hipEventSynchronize (d->valueDone[i])); d->valuePending[i] = false; }
+      else MG_HIP (hipStreamWaitEvent (st, d->valueDone[i], 0));
+    }
+  return MG_OK;
+}
+MgStatus mgArenaOpen (MgDev *d, int slot, size_t need)
+{
+  MgStatus s = mgValueSettle (d, 0, MG_SETTLE_HOST, slot); if (s) return s;
+  MgArena &ar = mgArenaOf (d, slot);
+  if ((s = ar.reserve (need))) return s;
+  ar.reset ();
+  return MG_OK;
+}
+/* An add whose writer was left running in arena `slot` expects the set's next add in the other arena: that one is allocated now, in the call
+   that allocated the first (the first add of a set, where every other allocation of the set is made too), not in the next call -- which then
+   allocates and frees nothing, as it never did: a set's second add is as fast as its tenth.  The price is the second arena for a set that
+   turns out to take one add only.  Failing to get it is not this call's failure, and leaves no error sentence: the next add
+   asks once more and otherwise makes do with one arena (mgAddReadsDevice). */
+void mgArenaTwin (MgDev *d, int slot)
+{
+  MgArena &ar = mgArenaOf (d, slot), &other = mgArenaOf (d, slot ^ 1);
+  if (other.bytes >= ar.used || d->valuePending[slot ^ 1] || d->slotBusy[slot ^ 1]) return;
+  (void) other.tryReserve (ar.used);
+}
+/* the writer's stream and events, made on first use */
+static MgStatus mgValueStream (MgDev *d)
+{
+  if (d->valueStream) return MG_OK;
+  /* Highest priority: the runtime hands out its few hardware queues per priority, and a stream of the default priority may be given the caller's
+     own queue -- the writer then runs behind the caller's next kernels, not beside them.  (Not the lowest: DESIGN_EXPERIMENTS.md section R item 5.)
+     Between the writer and the caller's own kernels the priority decides nothing: the writer's few workgroups are resident before the caller's
+     next kernel arrives */
+  int lo = 0, hi = 0; (void) hipDeviceGetStreamPriorityRange (&lo, &hi);
+  MG_HIP (hipStreamCreateWithPriority (&d->valueStream, hipStreamNonBlocking, hi));
+  for (int i = 0 ; i < 2 ; ++i) MG_HIP (hipEventCreateWithFlags (&d->valueDone[i], hipEventDisableTiming));
+  MG_HIP (hipEventCreateWithFlags (&d->merged, hipEventDisableTiming));
+  return MG_OK;
+}
+
 static void mgDevFree (MgDev *d)
 {
   if (!d) return;
   MgOnDevice here (d->device);
+  (void) mgValueSettle (d, 0, MG_SETTLE_HOST);         /* (a writer still reads an arena and writes value[]) */
+  if (d->valueStream) { (void) hipStreamSynchronize (d->valueStream); (void) hipStreamDestroy (d->valueStream); }
+  for (int i = 0 ; i < 2 ; ++i) if (d->valueDone[i]) (void) hipEventDestroy (d->valueDone[i]);
+  if (d->merged) (void) hipEventDestroy (d->merged);
   if (d->hPin) (void) hipHostFree (d->hPin);
   if (d->built)
     { (void) hipFree (d->t.slots); (void) hipFree (d->t.value); (void) hipFree (d->t.occ); (void) hipFree (d->t.find8);
@@ -64,6 +112,7 @@ MgStatus mgDevRefuseInFlight (const MgDev *d)
 static MgStatus mgDevBuild (Modset *ms, MgDev *d, hipStream_t st)
 {
   MgTable &t = d->t;
+  { MgStatus s0 = mgValueSettle (d, st, MG_SETTLE_HOST); if (s0) return s0; }      /* (a new MgDev has none pending) */
   if (ms->tableBits < 20 || ms->tableBits > 32)
     { mgSetError ("device modset supports table bits 20..32 (got %d)", ms->tableBits); return MG_ERR_ARG; }
   memset (&t, 0, sizeof (t));
@@ -115,6 +164,7 @@ MgStatus mgDevGet (Modset *ms, MgDev **out, hipStream_t st)
     { /* the host appended entries through the scalar API (modsetIndexFind isAdd): mirror them */
       U32 first = d->t.max + 1, last = ms->max;
       if (last >= (ms->tableSize >> 2)) { mgSetError ("modset max %u beyond table capacity", last); return MG_ERR_CAPACITY; }
+      if ((s = mgValueSettle (d, st, MG_SETTLE_STREAM))) return s;      /* the copies below go behind the last add's values */
       MG_HIP (hipMemcpyAsync (d->t.value + first, ms->value + first, (size_t) (last - first + 1) * sizeof (U64), hipMemcpyHostToDevice, st));
       MG_HIP (hipMemcpyAsync (d->t.baseDepth + first, ms->depth + first, (size_t) (last - first + 1) * sizeof (U16), hipMemcpyHostToDevice, st));
       d->t.baseZero = false;
@@ -185,8 +235,7 @@ static MgStatus mgFoldCounts (MgDev *d, hipStream_t st, Modset *host = 0)
   MgTable &t = d->t;
   if (!t.max) return MG_OK;
   if (!t.pendingDepth) return MG_OK;                   /* nothing has counted since the last fold */
-  MgStatus s = d->arena.reserve (mgAl256 ((size_t) t.max * sizeof (U16)) + 4096); if (s) return s;      /* (no call is using the arena while a whole-set pass runs) */
-  d->arena.reset ();
+  MgStatus s = mgArenaOpen (d, 0, mgAl256 ((size_t) t.max * sizeof (U16)) + 4096); if (s) return s;      /* (no call is using the arena while a whole-set pass runs) */
   U16 *dDelta = (U16 *) d->arena.take ((size_t) t.max * sizeof (U16));
   s = mgTableExportDepth (&t, dDelta, st);
   MG_HIP (hipStreamSynchronize (st));
@@ -202,6 +251,7 @@ static int mgMergeDeviceCore (Modset *ms1, MgDev *d, const U64 *dV2, const U16 *
   MgTable &t = d->t;
   const U32 max1 = t.max;
   const char *const sorry = "device merge failed";
+  if (mgValueSettle (d, st, MG_SETTLE_HOST)) return mgFailedWith (sorry);      /* value[] is read below by the transfer team's own streams */
   MgDevScratch scratch ("device merge");
   U8 *dI1; U32 *dIdx;
   const size_t cap1 = (size_t) max1 + n2 + 2;
@@ -209,7 +259,7 @@ static int mgMergeDeviceCore (Modset *ms1, MgDev *d, const U64 *dV2, const U16 *
   if (hipMemset (dI1, 0, cap1) || hipDeviceSynchronize ()) return mgFailedWith (sorry);
   if (mgXferH2D (dI1, ms1->info, (size_t) max1 + 1)) return mgFailedWith (sorry);
   /* ms2's values in ms2 index order: existing ones are found, new ones get max1+1, max1+2, ... (modset.c:120) */
-  MgStatus as = mgAddBatch (ms1, d, dV2, n2, dIdx, 0, false, st);
+  MgStatus as = mgAddBatch (ms1, d, dV2, n2, dIdx, 0, -1, st);
   if (as == MG_ERR_CAPACITY) { fprintf (stderr, "FATAL ERROR: %s\n", mgLastError ()); exit (-1); }
   if (as) return mgFailedWith (sorry);
   t.baseZero = false; t.liveHistValid = false;
@@ -259,6 +309,7 @@ extern "C" int mgHookPruneDevice (Modset *ms, int lo, int hi)
   MgDev *d; if (mgDevGet (ms, &d, st)) return -1;
   MgTable &t = d->t;
   const U32 n = t.max;
+  if (mgValueSettle (d, st, MG_SETTLE_HOST)) return -1;      /* value[] is compacted, then rewritten, on the default stream and by plain copies */
   if (mgFoldCounts (d, st)) return -1;
   /* values of device-only entries must reach the host before the arrays are rewritten?  No: the
      survivors are compacted on the device and copied back as a whole. */
@@ -324,20 +375,32 @@ U64 mgAddChunkSize (void)
   return v;
 }
 
+/* asideSlot >= 0: the value writer may go onto the set's own stream; the batch and the scratch are in that arena and stay there */
 static MgStatus mgAddChunk (Modset *ms, MgDev *d, const U64 *dKmer, U64 n, U32 *dIndexOut, int withDepth,
-                            void *scratch, hipStream_t st, const MgHistReq *counted = 0, const MgSegSrc *segSrc = 0)
+                            void *scratch, hipStream_t st, const MgHistReq *counted = 0, const MgSegSrc *segSrc = 0, int asideSlot = -1)
 {
   MgTable &t = d->t;
   MgStatus s;
   MG_HIP (hipMemsetAsync (t.counters, 0, 16, st));
-  if ((s = mgTableAdd (&t, dKmer, n, withDepth, scratch, st, counted, segSrc))) return s;
+  MgValueAside aside = {};
+  if (asideSlot >= 0)
+    { if ((s = mgValueStream (d))) return s;
+      if ((s = mgValueSettle (d, 0, MG_SETTLE_HOST, asideSlot))) return s;      /* (its event is recorded anew) */
+      aside.stream = d->valueStream; aside.merged = d->merged; aside.done = d->valueDone[asideSlot];
+    }
+  else if ((s = mgValueSettle (d, st, MG_SETTLE_STREAM))) return s;              /* this add writes value[] on the caller's stream (either leg): behind the last add's writer */
+  s = mgTableAdd (&t, dKmer, n, withDepth, scratch, st, counted, segSrc, asideSlot >= 0 ? &aside : 0);
+  if (aside.launched) { d->valuePending[asideSlot] = true; d->valueLast = asideSlot; }
+  if (s) return s;
   volatile U64 *c = d->hPin;
   MG_HIP (hipMemcpyAsync (d->hPin, t.counters, 16, hipMemcpyDeviceToHost, st));
   MG_HIP (hipStreamSynchronize (st));
   U64 newMax = (U64) t.max + c[0];
   if (c[1] || newMax >= t.size)
     { /* modset.c:58 */
-      /* what the add had written by then goes out of the table again: the set answers as before the call, whichever lookup path is asked */
+      /* what the add had written by then goes out of the table again: the set answers as before the call, whichever lookup path is asked.
+         (The refused add's values are beyond max and nobody's; its writer is waited for because the caller is about to hear that the call is over) */
+      if ((s = mgValueSettle (d, st, MG_SETTLE_HOST))) return s;
       if ((s = mgTableRollback (&t, st))) return s;
       mgSetError ("hashTableSize %u is too small for %llu", t.size, (unsigned long long) newMax);
       return MG_ERR_CAPACITY;
@@ -349,30 +412,35 @@ static MgStatus mgAddChunk (Modset *ms, MgDev *d, const U64 *dKmer, U64 n, U32 *
   return MG_OK;
 }
 
-/* arenaLive: dKmer itself lives in d->arena (mgAddReadsDevice), so the arena must not be reset
- * or reallocated; the caller reserved room for the temporaries taken here. */
+/* liveSlot >= 0: dKmer (or the segments) lives in that arena (mgAddReadsDevice), so the arena must not be reset or reallocated; the caller
+ * reserved room for the temporaries taken here.  The value writer leaves the caller's stream where the knob says so (mg_knobs.h), for a batch
+ * of one chunk; where the k-mers are the caller's own it is waited for before the call returns. */
 MgStatus mgAddBatch (Modset *ms, MgDev *d, const U64 *dKmer, U64 n, U32 *dIndexOut, int withDepth,
-                     bool arenaLive, hipStream_t st, const MgHistReq *counted, const MgSegSrc *segSrc)
+                     int liveSlot, hipStream_t st, const MgHistReq *counted, const MgSegSrc *segSrc, bool asideByDefault)
 {
   if (!n) return MG_OK;
   MgStatus s = mgDevRefuseInFlight (d); if (s) return s;
   U64 chunk = n < MG_ADD_CHUNK ? n : MG_ADD_CHUNK;
   if ((s = mgTableEnsure (&d->t, chunk, st))) return s;
   size_t need = mgTableAddScratchBytes (&d->t, chunk) + 4096;
-  if (!arenaLive)
-    { if ((s = d->arena.reserve (need))) return s;
-      d->arena.reset ();
-    }
-  else if (d->arena.bytes - d->arena.used < need)
+  const int slot = liveSlot >= 0 ? liveSlot : 0;
+  MgArena &ar = mgArenaOf (d, slot);
+  if (liveSlot < 0) { if ((s = mgArenaOpen (d, 0, need))) return s; }
+  else if (ar.bytes - ar.used < need)
     { mgSetError ("internal: arena too small for insert temporaries"); return MG_ERR_NOMEM; }
-  void *scratch = d->arena.take (mgTableAddScratchBytes (&d->t, chunk));
+  void *scratch = ar.take (mgTableAddScratchBytes (&d->t, chunk));
+  const long va = mgKnobs ()->valueAsync;
+  /* (only the bucketed leg has a writer to move.  The direct leg writes value[] on the caller's stream, and mgAddChunk makes that stream wait for
+     whatever an earlier add left running: after a clear that writer stores to the very entries this add assigns) */
+  const bool aside = n <= chunk && mgTableUseBuckets (&d->t, chunk) && (va == MG_KNOB_UNSET ? asideByDefault : va == 1);
   for (U64 off = 0 ; off < n && !s ; off += chunk)
     { U64 m = n - off < chunk ? n - off : chunk;
       if (off) s = mgTableEnsure (&d->t, m, st);
       if (!s) s = mgAddChunk (ms, d, dKmer + off, m, dIndexOut ? dIndexOut + off : 0, withDepth, scratch, st,
                               (counted && n <= chunk) ? counted : 0,       /* the counts cover the whole batch */
-                              n <= chunk ? segSrc : 0);
+                              n <= chunk ? segSrc : 0, aside ? slot : -1);
     }
+  if (aside && liveSlot < 0) { MgStatus w = mgValueSettle (d, st, MG_SETTLE_HOST, slot); if (!s) s = w; }      /* dKmer is the caller's again when this returns */
   return s;
 }
 
@@ -380,7 +448,7 @@ extern "C" MgStatus modsetAddBatchDevice (Modset *ms, const U64 *dKmer, U64 n, U
 {
   hipStream_t st = (hipStream_t) stream;
   MgDev *d; MgStatus s = mgDevGet (ms, &d, st); if (s) return s;
-  return mgAddBatch (ms, d, dKmer, n, dIndexOut, withDepth, false, st);
+  return mgAddBatch (ms, d, dKmer, n, dIndexOut, withDepth, -1, st);
 }
 
 extern "C" MgStatus modsetFindBatchDevice (Modset *ms, const U64 *dKmer, U64 n, U32 *dIndexOut, void *stream)
@@ -408,6 +476,7 @@ extern "C" MgStatus modsetSyncToHost (Modset *ms, int wantIndex)
   hipStream_t st = 0;
   MgStatus s;
   MG_HIP (hipDeviceSynchronize ());
+  if ((s = mgValueSettle (d, st, MG_SETTLE_HOST))) return s;
   if (d->ticketsOut && (t.pendingDepth || (wantIndex && d->hostIndexMax < t.max)))
     { mgSetError ("a query batch of this modset is in flight (its scratch is what a sync would use)"); return MG_ERR_ARG; }
   if (t.max > t.syncedMax)
@@ -418,8 +487,7 @@ extern "C" MgStatus modsetSyncToHost (Modset *ms, int wantIndex)
   ms->max = t.max;
   if ((s = mgFoldCounts (d, st, ms))) return s;
   if (wantIndex && d->hostIndexMax < t.max)
-    { if ((s = d->arena.reserve (mgAl256 (ms->tableSize * sizeof (U32)) + 4096))) return s;
-      d->arena.reset ();
+    { if ((s = mgArenaOpen (d, 0, mgAl256 (ms->tableSize * sizeof (U32)) + 4096))) return s;
       U32 *dIndex = (U32 *) d->arena.take (ms->tableSize * sizeof (U32));
       if ((s = mgTableReplayIndex (&t, mgMakeParams (ms->hasher), ms->tableBits, dIndex, st))) return s;
       MG_HIP (hipStreamSynchronize (st));
@@ -450,7 +518,7 @@ extern "C" int mgHookDeviceView (Modset *ms, const U64 **dValue1, const U16 **dD
   MgDev *d = mgDevLookup (ms);
   if (!d || !d->built || d->ticketsOut) return -1;
   if (mgDevOnCallersGpu (d, true)) return -1;      /* (a sender stages from the host then) */
-  if (hipDeviceSynchronize () != hipSuccess || mgFoldCounts (d, 0, ms)) return -1;
+  if (hipDeviceSynchronize () != hipSuccess || mgValueSettle (d, 0, MG_SETTLE_HOST) || mgFoldCounts (d, 0, ms)) return -1;
   *dValue1 = d->t.value + 1; *dDepth1 = d->t.baseDepth + 1; *max = d->t.max;
   return 0;
 }
@@ -503,6 +571,7 @@ MgStatus mgModsetTableForPass (Modset *ms, MgTable **t)
   if (!d->built) return MG_OK;
   if ((s = mgDevRefuseInFlight (d))) return s;
   MG_HIP (hipDeviceSynchronize ());
+  if ((s = mgValueSettle (d, 0, MG_SETTLE_HOST))) return s;
   ms->max = d->t.max;
   *t = &d->t;
   return MG_OK;

@@ -13,7 +13,6 @@ struct MgScanBufs { U64 *kmer; U32 *posF; U32 *rid; void *work; U64 *count; U64 
  * took longer than the scan itself) */
 struct MgScanReq { const Seqhash *sh; const U32 *dPacked; U64 totalBases; const U64 *dReadOffsets; U32 nReads; bool wantPos; size_t extraPerSurvivor;
                    U32 *outPosF, *outRid; U64 outCap; bool lazy; };
-static inline MgArena &mgArenaOf (MgDev *d, int slot) { return slot ? d->arena2 : d->arena; }
 static inline U64 *mgCountPin (MgDev *d, int slot) { return d->hPin + 8 + 8 * slot; }
 
 /* launch: buffers out of the slot's arena for `cap` modimizers, the scan, its counters on their way to the slot's pinned words.  No
@@ -32,8 +31,7 @@ static MgStatus mgScanStart (MgDev *d, int slot, const MgScanReq &q, U64 cap, Mg
   const size_t need = mgAl256 (cap * perS) + 4 * 4096 + 512 * MG_HIST_STRIDE * 4 + mgAl256 (mgScanWorkBytes (q.totalBases, q.nReads, cap))
                       + (q.extraPerSurvivor ? mgTableAddScratchBytes (&d->t, cap < MG_ADD_CHUNK ? cap : MG_ADD_CHUNK) + 8192 : 0) + 8 * 256
                       + (lookupHist ? mgTableFindPartScratchBytes (cap) + 8192 : 0) + (lookup2 ? mgTableFindPart2ScratchBytes (cap) + 8192 : 0);
-  MgStatus s = ar.reserve (need); if (s) return s;
-  ar.reset ();
+  MgStatus s = mgArenaOpen (d, slot, need); if (s) return s;      /* (a value writer still reading that arena is waited for: the callers pick the other one where they can) */
   b->cap = cap;
   b->kmer = (U64 *) ar.take (cap * 8);
   const bool direct = q.wantPos && q.outPosF && q.outRid && q.outCap >= cap;
@@ -83,7 +81,7 @@ static MgStatus mgScanRounds (MgDev *d, int slot, const MgScanReq &q, U64 cap, M
 static MgStatus mgScanIntoArena (MgDev *d, const Seqhash *sh, const U32 *dPacked, U64 totalBases,
                                  const U64 *dReadOffsets, U32 nReads, bool wantPos, size_t extraPerSurvivor,
                                  MgScanBufs *b, U64 *nOut, hipStream_t st,
-                                 U32 *outPosF = 0, U32 *outRid = 0, U64 outCap = 0, bool lazy = false)
+                                 U32 *outPosF = 0, U32 *outRid = 0, U64 outCap = 0, bool lazy = false, int slot = 0)
 {
   MgStatus s = mgDevRefuseInFlight (d); if (s) return s;
   MgScanReq q = { sh, dPacked, totalBases, dReadOffsets, nReads, wantPos, extraPerSurvivor, outPosF, outRid, outCap, lazy };
@@ -94,7 +92,7 @@ static MgStatus mgScanIntoArena (MgDev *d, const Seqhash *sh, const U32 *dPacked
       if (expect > MG_ADD_CHUNK) expect = MG_ADD_CHUNK;
       if ((s = mgTableEnsure (&d->t, expect, st))) return s;
     }
-  return mgScanRounds (d, 0, q, mgSurvivorGuess (sh, totalBases), b, nOut, st);
+  return mgScanRounds (d, slot, q, mgSurvivorGuess (sh, totalBases), b, nOut, st);
 }
 
 extern "C" MgStatus mgAddReadsDevice (Modset *ms, const U32 *dPacked, U64 totalBases,
@@ -109,17 +107,33 @@ extern "C" MgStatus mgAddReadsDevice (Modset *ms, const U32 *dPacked, U64 totalB
   /* pos / isF / read are not needed by addSequence (modutils.c:24 passes 0 for isF and ignores pos) */
   /* the dense k-mer array is only made if the insert turns out to need it (a small batch, the table regrown): a large
      batch's first partition pass and index assignment read the scan's segments */
-  if ((s = mgScanIntoArena (d, ms->hasher, dPacked, totalBases, dReadOffsets, nReads, false, 4, &b, &n, st, 0, 0, 0, true))) return s;
+  /* the value writer of the add before this one may still be reading its batch out of one arena: this batch goes into the other, and the writer
+     runs beside this scan (mgTableAdd).  The arenas take turns whether or not that writer has finished -- no event is asked -- so which add pays
+     for the second arena's allocation does not depend on the host's timing; the writer that last read the arena taken here, two adds ago, is
+     waited for (mgArenaOpen) and has long finished.  No query ticket holds an arena here: mgScanIntoArena refuses the call while one is out */
+  int slot = d->valuePending[d->valueLast] ? d->valueLast ^ 1 : 0;
+  if (d->valuePending[slot ^ 1] && mgArenaOf (d, slot).bytes < mgArenaOf (d, slot ^ 1).used)
+    { /* the arena whose turn it is was never made as large as the other (mgArenaTwin found no room): once more, and where the device still has none
+         this add waits for the pending writer and takes that one's arena, as every add did when a set had one */
+      if ((s = mgValueSettle (d, 0, MG_SETTLE_HOST, slot))) return s;
+      if (!mgArenaOf (d, slot).tryReserve (mgArenaOf (d, slot ^ 1).used)) slot ^= 1;
+    }
+  if ((s = mgScanIntoArena (d, ms->hasher, dPacked, totalBases, dReadOffsets, nReads, false, 4, &b, &n, st, 0, 0, 0, true, slot))) return s;
   if (nHash) *nHash = n;
   if (!n) return MG_OK;
   if (b.lazy)
     { const U64 chunk = n < MG_ADD_CHUNK ? n : MG_ADD_CHUNK;
       if ((s = mgTableEnsure (&d->t, chunk, st))) return s;
       if (n <= MG_ADD_CHUNK && mgTableAddTakesSegments (&d->t, n, &b.counted))
-        return mgAddBatch (ms, d, 0, n, 0, 1, true, st, &b.counted, &b.seg);
+        { s = mgAddBatch (ms, d, 0, n, 0, 1, slot, st, &b.counted, &b.seg, true);
+          if (!s && d->valuePending[slot]) mgArenaTwin (d, slot);
+          return s;
+        }
       if ((s = mgLaunchSegCompact (b.seg, b.kmer, b.cap, b.count, st))) return s;
     }
-  return mgAddBatch (ms, d, b.kmer, n, 0, 1, true, st, &b.counted);
+  s = mgAddBatch (ms, d, b.kmer, n, 0, 1, slot, st, &b.counted, 0, true);
+  if (!s && d->valuePending[slot]) mgArenaTwin (d, slot);
+  return s;
 }
 
 /* the seeds of a scanned batch of n modimizers into the caller's arrays of `capacity` entries: their index[] -- ms given: inserted without
@@ -130,7 +144,7 @@ static MgStatus mgSeedsOfScanned (Modset *ms, MgDev *d, MgScanBufs &b, U64 n, U3
   if (n > capacity)
     { mgSetError ("%llu seeds exceed the caller's capacity %llu", (unsigned long long) n, (unsigned long long) capacity); return MG_ERR_CAPACITY; }
   MgStatus s;
-  if (ms) s = mgAddBatch (ms, d, b.kmer, n, dSeedIndex, 0, true, st, &b.counted);
+  if (ms) s = mgAddBatch (ms, d, b.kmer, n, dSeedIndex, 0, 0, st, &b.counted);
   else if (b.lazy && b.findScratch && mgTableFindTakesPartition (&d->t, n, &b.counted))
     s = mgTableFindPartitioned (&d->t, b.seg, n, &b.counted, dSeedIndex, b.kmer, b.findScratch, st, b.findScratch2);     /* (b.kmer: the dense array a lazy scan leaves unused) */
   else s = b.lazy ? mgTableFindSegments (&d->t, b.seg, n, dSeedIndex, st) : mgTableFind (&d->t, b.kmer, n, dSeedIndex, st);
@@ -241,7 +255,8 @@ extern "C" MgStatus mgQueryReadsDeviceAsync (Modset *ms, const U32 *dPacked, U64
       for (int i = 0 ; i < 2 ; ++i) MG_HIP (hipEventCreateWithFlags (&d->scanned[i], hipEventDisableTiming));
       MG_HIP (hipEventCreateWithFlags (&d->inputReady, hipEventDisableTiming));
     }
-  const int slot = d->slotBusy[d->nextSlot] ? d->nextSlot ^ 1 : d->nextSlot;
+  int slot = d->slotBusy[d->nextSlot] ? d->nextSlot ^ 1 : d->nextSlot;
+  if (d->valuePending[slot] && !d->slotBusy[slot ^ 1] && !d->valuePending[slot ^ 1]) slot ^= 1;      /* an arena a value writer may still read counts as busy (else mgScanStart waits for the writer) */
   MgQueryTicket *t = new MgQueryTicket ();
   t->ms = ms; t->d = d; t->slot = slot; t->dSeedIndex = dSeedIndex; t->dSeedPosF = dSeedPosF; t->dSeedRead = dSeedRead; t->capacity = capacity;
   t->q = MgScanReq { ms->hasher, dPacked, totalBases, dReadOffsets, nReads, true, 0, dSeedPosF, dSeedRead, capacity, true };

@@ -85,7 +85,7 @@ static const char *gKernelNames[MG_K_COUNT] = {
   "mgPaintItemsKernel", "mgDepthGuardKernel", "mgDepthGatherKernel", "mgTextLenKernel", "mgTextScanKernel", "mgTextWriteKernel",
   "mgSetTextLinesKernel", "mgSetTextScanKernel", "mgSetTextParseKernel", "mgSetTextLastKernel",
   "mgOvElem..TableKernels", "mgOvEmitKernel", "overlap sorts", "mgOvHead..PairInitKernels", "mgOvPairKernel",
-  "mgTrimSkip+OffsetsKernel", "mgTrimGatherKernel", "mgSetCopyKernel", "mgCopyTallyKernel" };
+  "mgTrimSkip+OffsetsKernel", "mgTrimGatherKernel", "mgSetCopyKernel", "mgCopyTallyKernel", "mgRankRecordKernel" };
 #define MG_PROF_POOL 8192
 struct MgProfRec { int id; hipEvent_t a, b; };
 static struct {

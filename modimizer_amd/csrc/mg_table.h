@@ -39,7 +39,7 @@ __device__ __forceinline__ bool mgLiveEntry (const uint4 &v, U32 keepMax) { retu
 
 /* counters[]: 0 = new entries this call, 1 = bucket overflow flag */
 
-/* the rank record mgRankAssignKernel leaves per row of 64 ordinals: the row's flags and the number of flags before it */
+/* the rank record mgRankRecordKernel (mgTablePrune: mgRankAssignKernel) leaves per row of 64 ordinals: the row's flags and the number of flags before it */
 struct __attribute__ ((aligned (16))) MgRankGrp { U64 bits; U32 rank; U32 pad; };   /* per 64 ordinals */
 
 /* ---- k-mers read from the scan's segments (MgSegSrc) instead of a dense array ---------------------------------

@@ -40,6 +40,7 @@
  * 3b and 4 are mg_bucket.hip, every lookup is mg_find.hip; what they share is mg_table.h (internal to these files).  A kernel is
  * defined, launched and given its attributes in one file only.
  */
+#include <atomic>
 #include "mg_table.h"
 
 /* ======================================================================================== */
@@ -132,12 +133,13 @@ void mgRankCountKernel (const unsigned char *__restrict__ flags, U64 n, U64 rows
 }
 
 /* pass B: every flagged ordinal o gets index baseMax+1+rank(o); value[index] = kmer[o].
- * DIRECT: also store the index in the slot.  BUCKETED: record, per row of 64 ordinals, the flag
- * bitmap and the number of flags before the row, for mgRankLookupKernel's rank(o) lookups. */
+ * DIRECT: also store the index in the slot.  Otherwise (mgTablePrune): record, per row of 64 ordinals, the flag
+ * bitmap and the number of flags before the row, for the pass that moves the survivors' depths.
+ * The bucketed leg of mgTableAdd does the two halves apart: mgRankRecordKernel, then mgValueWriteKernel. */
 #define MG_RANK_ROWS 8
-template <bool DIRECT, bool SEG>
+template <bool DIRECT>
 __global__ __launch_bounds__ (256)
-void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__restrict__ kmer, const MgSegSrc src, const MgSubSeg *__restrict__ subSeg,
+void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__restrict__ kmer,
                          U64 n, U64 rowsPerUnit,
                          const U64 *__restrict__ unitBase, U32 baseMax, U32 size,
                          U64 *__restrict__ value, MgSlot *__restrict__ slots, const U32 *__restrict__ slotId,
@@ -152,13 +154,9 @@ void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__r
   if (row >= rEnd) return;
   U64 run = unitBase[unit];
   const U64 below = ((U64) 1 << lane) - 1;
-  MgSegCursor cur; cur.w = 0; cur.s0 = 0; cur.s1 = 0;
-  if (SEG) { mgSegCursorFrom (subSeg, row * 64 / MG_PART_SUB, &cur); mgSegCursorSeek (src, &cur, row * 64); }
-  /* MG_RANK_ROWS rows per step: the loads of all four are in flight before the first ballot */
+  /* MG_RANK_ROWS rows per step: the loads of all of them are in flight before the first ballot */
   for ( ; row < rEnd ; row += MG_RANK_ROWS)
     { bool f[MG_RANK_ROWS]; U64 km[MG_RANK_ROWS]; U32 fl[MG_RANK_ROWS];
-      /* all the flag loads first, then all the k-mer loads, then the first use: with the segment walk's (uniform)
-         branches between them the compiler otherwise waits for each row's flags -- and everything older -- in turn */
 #pragma unroll
       for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
         { const U64 o = (row + j) * 64 + lane;
@@ -169,16 +167,7 @@ void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__r
       for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
         { const U64 o = (row + j) * 64 + lane;
           const bool in = (row + j < rEnd) && (o < n);
-          if (SEG)
-            { km[j] = 0;
-              if ((row + j) * 64 < n && row + j < rEnd)                      /* uniform */
-                { const U64 o0 = (row + j) * 64, last = o0 + 63 < n ? o0 + 63 : n - 1;
-                  mgSegCursorSeek (src, &cur, o0);
-                  const U64 *at = mgSegAddr (src, cur, o, last);
-                  if (in) km[j] = __builtin_nontemporal_load (at);
-                }
-            }
-          else km[j] = in ? __builtin_nontemporal_load (&kmer[o]) : 0;
+          km[j] = in ? __builtin_nontemporal_load (&kmer[o]) : 0;
         }
 #pragma unroll
       for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
@@ -202,6 +191,104 @@ void mgRankAssignKernel (const unsigned char *__restrict__ flags, const U64 *__r
                 }
             }
           run += (U32) __popcll (bits);
+        }
+    }
+}
+
+/* bit j of the result = bit 0 of byte j of q's 16 bytes (the multiplication gathers a word's four flag bits: no two of its partial products meet) */
+__device__ __forceinline__ U32 mgFlagBits16 (const uint4 &q)
+{
+#define MG_NIB(w) ((((w) & 0x01010101u) * 0x00204081u >> 21) & 0xfu)
+  return MG_NIB (q.x) | MG_NIB (q.y) << 4 | MG_NIB (q.z) << 8 | MG_NIB (q.w) << 12;
+#undef MG_NIB
+}
+
+/* The bucketed leg's first half: the rank records alone, grp[row] = {the row's flags, the number of flags before the row} -- all that the
+   rank lookups and the merge kernel need of the index assignment.  Same units as the count kernel; a lane takes a row, its 64 flag bytes in
+   four 16-byte loads (flags is 16-byte aligned: mgTableAdd), so a wave does 64 rows a step with one scan and one store of 64 records. */
+__global__ __launch_bounds__ (256)
+void mgRankRecordKernel (const unsigned char *__restrict__ flags, U64 n, U64 rowsPerUnit, const U64 *__restrict__ unitBase, MgRankGrp *__restrict__ grp)
+{
+  MG_BUILD_PRIO ();
+  const int lane = threadIdx.x & 63;
+  const U64 unit = (U64) blockIdx.x * 4 + (U32) __builtin_amdgcn_readfirstlane ((int) (threadIdx.x >> 6));
+  const U64 nRows = (n + 63) / 64;
+  U64 row = unit * rowsPerUnit, rEnd = row + rowsPerUnit;
+  if (rEnd > nRows) rEnd = nRows;
+  if (row >= rEnd) return;
+  U32 run = (U32) unitBase[unit];
+  for ( ; row < rEnd ; row += 64)
+    { const U64 r = row + lane;
+      const bool in = r < rEnd;
+      uint4 q[4] = {};
+      if (in)
+        { const uint4 *p = reinterpret_cast<const uint4 *> (flags + r * 64);
+#pragma unroll
+          for (int i = 0 ; i < 4 ; ++i) q[i] = p[i];
+        }
+      U64 bits = 0;
+#pragma unroll
+      for (int i = 0 ; i < 4 ; ++i) bits |= (U64) mgFlagBits16 (q[i]) << (16 * i);
+      if (in && (r + 1) * 64 > n) bits &= ((U64) 1 << (n - r * 64)) - 1;      /* the last row of all: the bytes behind flags[n - 1] are nobody's */
+      const U32 c = (U32) __popcll (bits), inc = mgWaveInclusiveSum (c);
+      if (in) { MgRankGrp g; g.bits = bits; g.rank = run + inc - c; g.pad = 0; grp[r] = g; }
+      run += (U32) __builtin_amdgcn_readlane ((int) inc, 63);
+    }
+}
+
+/* The second half: value[baseMax + 1 + rank (o)] = kmer[o] for every flagged ordinal o, from the rank records -- a stream of k-mers in (dense,
+   or SEG: still in the scan's segments) and values out that nothing later in the add reads, so it may run on a stream of its own beside the
+   NEXT batch's scan (mgTableAdd).  For that it takes no LDS and few waves: the grid is whatever the launch says, the rows are cut into one
+   contiguous piece per wave (rowsPerWave, a multiple of MG_RANK_ROWS), walked with MG_RANK_ROWS rows' loads in flight. */
+template <bool SEG>
+__global__ __launch_bounds__ (256)
+void mgValueWriteKernel (const MgRankGrp *__restrict__ grp, const U64 *__restrict__ kmer, const MgSegSrc src, const MgSubSeg *__restrict__ subSeg,
+                         U64 n, U64 rowsPerWave, U32 baseMax, U32 size, U64 *__restrict__ value)
+{
+  const int lane = threadIdx.x & 63;
+  const U64 wave = (U64) blockIdx.x * 4 + (U32) __builtin_amdgcn_readfirstlane ((int) (threadIdx.x >> 6));
+  const U64 nRows = (n + 63) / 64;
+  U64 row = wave * rowsPerWave, rEnd = row + rowsPerWave;
+  if (rEnd > nRows) rEnd = nRows;
+  if (row >= rEnd) return;
+  const U64 below = ((U64) 1 << lane) - 1;
+  MgSegCursor cur; cur.w = 0; cur.s0 = 0; cur.s1 = 0;
+  if (SEG) { mgSegCursorFrom (subSeg, row * 64 / MG_PART_SUB, &cur); mgSegCursorSeek (src, &cur, row * 64); }
+  for ( ; row < rEnd ; row += MG_RANK_ROWS)
+    { U64 km[MG_RANK_ROWS]; U64 bits[MG_RANK_ROWS]; U32 rank[MG_RANK_ROWS];
+      /* all the record loads first (uniform), then all the k-mer loads, then the first use: with the segment walk's (uniform)
+         branches between them the compiler otherwise waits for each row's loads -- and everything older -- in turn */
+#pragma unroll
+      for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
+        { const MgRankGrp g = grp[row + j < rEnd ? row + j : row];
+          bits[j] = g.bits; rank[j] = g.rank;
+        }
+#pragma unroll
+      for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
+        { const U64 o = (row + j) * 64 + lane;
+          const bool in = (row + j < rEnd) && (o < n);
+          if (SEG)
+            { km[j] = 0;
+              if (row + j < rEnd)                                            /* uniform (and then (row + j) * 64 < n) */
+                { const U64 o0 = (row + j) * 64, last = o0 + 63 < n ? o0 + 63 : n - 1;
+                  mgSegCursorSeek (src, &cur, o0);
+                  const U64 *at = mgSegAddr (src, cur, o, last);
+                  if (in) km[j] = __builtin_nontemporal_load (at);
+                }
+            }
+          else km[j] = in ? __builtin_nontemporal_load (&kmer[o]) : 0;
+        }
+      /* every load has landed before the first store goes out: with loads and stores both in flight the counter
+         cannot tell them apart, and each row's store would wait for the stores of the rows before it */
+#pragma unroll
+      for (int j = 0 ; j < MG_RANK_ROWS ; ++j) asm volatile ("" : "+v" (km[j]));
+#pragma unroll
+      for (int j = 0 ; j < MG_RANK_ROWS ; ++j)
+        { if (row + j >= rEnd) break;
+          if ((bits[j] >> lane) & 1)                                         /* (a row's flags beyond n are 0) */
+            { const U64 idx = (U64) baseMax + 1 + rank[j] + (U32) __popcll (bits[j] & below);
+              if (idx < size) __builtin_nontemporal_store (km[j], &value[idx]);
+            }
         }
     }
 }
@@ -847,24 +934,36 @@ static void mgAddPlan (const MgTable *t, U64 n, bool wasEmpty, MgAddPlan *p)
   p->tighten = tighten; p->tightPct = tightPct;
 }
 
-/* The ordered count of flags[] and what it gives, for both legs of mgTableAdd: every flagged ordinal gets index t->max + 1 + its rank and its k-mer goes to
-   value[index]; counters[0] = the number of flags.  slotId != 0: the direct leg, the index goes into the k-mer's slot too; otherwise a rank record per row of
-   64 ordinals is left in grp[] for the rank lookups.  segSrc != 0: the k-mers still sit in the scan's segments (subSeg: their cursors). */
-static MgStatus mgAssignIndices (MgTable *t, const unsigned char *flags, const U64 *dKmer, const MgSegSrc *segSrc, const MgSubSeg *subSeg, U64 n,
-                                 U64 *unitCount, U64 *unitBase, const U32 *slotId, MgRankGrp *grp, hipStream_t st)
+/* The ordered count of flags[], for both legs of mgTableAdd: unitBase[] = the number of flags before every rank unit, counters[0] = the number of flags */
+static MgStatus mgCountFlags (MgTable *t, const unsigned char *flags, U64 n, U64 *unitCount, U64 *unitBase, U32 *nBlocks, U64 *rows, hipStream_t st)
 {
-  const MgSegSrc noSrc = {};
-  U32 nBlocks; const U64 rows = mgRankRowsPerUnit (n, &nBlocks);
-  MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nBlocks), dim3 (256), 0, st, flags, n, rows, unitCount);
-  MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, unitCount, unitBase, nBlocks * 4, t->counters);
-#define MG_ASSIGN(DIRECT, SEG, KMER, SRC, SUB) MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<DIRECT, SEG>), dim3 (nBlocks), dim3 (256), 0, st, \
-                                                          flags, KMER, SRC, SUB, n, rows, unitBase, t->max, t->size, t->value, t->slots, slotId, grp)
-  if (slotId) MG_ASSIGN (true, false, dKmer, noSrc, (const MgSubSeg *) 0);
-  else if (segSrc) MG_ASSIGN (false, true, (const U64 *) 0, *segSrc, subSeg);
-  else MG_ASSIGN (false, false, dKmer, noSrc, (const MgSubSeg *) 0);
-#undef MG_ASSIGN
+  *rows = mgRankRowsPerUnit (n, nBlocks);
+  MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (*nBlocks), dim3 (256), 0, st, flags, n, *rows, unitCount);
+  MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, unitCount, unitBase, *nBlocks * 4, t->counters);
   return MG_OK;
 }
+
+/* The value writer of the bucketed leg (mgValueWriteKernel) on st: value[t->max + 1 + rank] = the k-mer of every flagged ordinal, from the rank records.
+   waves: how many take the rows between them -- MG_VALUE_WAVES_ASIDE beside another kernel, MG_VALUE_WAVES_ALONE with the device to itself.
+   segSrc != 0: the k-mers still sit in the scan's segments (subSeg: their cursors). */
+#ifndef MG_VALUE_WAVES_ASIDE
+#define MG_VALUE_WAVES_ASIDE 2048u   /* two waves a SIMD: what the next batch's scan leaves free */
+#endif
+#define MG_VALUE_WAVES_ALONE 8192u   /* as many as the rank units of the kernel this one was cut from */
+static std::atomic<U64> gValueWriters[2];      /* launches since the process started: off the caller's stream, on it (mgValueWriterDiag) */
+static MgStatus mgWriteValues (MgTable *t, const MgRankGrp *grp, const U64 *dKmer, const MgSegSrc *segSrc, const MgSubSeg *subSeg, U64 n, U32 waves, hipStream_t st)
+{
+  const MgSegSrc noSrc = {};
+  const U64 nRows = (n + 63) / 64;
+  U64 per = (nRows + waves - 1) / waves;
+  per = (per + MG_RANK_ROWS - 1) / MG_RANK_ROWS * MG_RANK_ROWS;
+  const U32 nBlocks = (U32) (((nRows + per - 1) / per + 3) / 4);
+  if (segSrc) MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgValueWriteKernel<true>), dim3 (nBlocks), dim3 (256), 0, st, grp, (const U64 *) 0, *segSrc, subSeg, n, per, t->max, t->size, t->value);
+  else MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgValueWriteKernel<false>), dim3 (nBlocks), dim3 (256), 0, st, grp, dKmer, noSrc, (const MgSubSeg *) 0, n, per, t->max, t->size, t->value);
+  MG_HIP (hipGetLastError ());
+  return MG_OK;
+}
+extern "C" MgStatus mgValueWriterDiag (U64 *out2) { for (int i = 0 ; i < 2 ; ++i) out2[i] = gValueWriters[i].load (std::memory_order_relaxed); return MG_OK; }
 
 /* The tightening of an add into an empty table (mgAddPlan), between the dedup kernel and the merge: the entries and the fullest bucket's are counted -- the stream
    is waited for -- and R comes down to what they need at load tightPct.  *fullest: the fullest bucket's entries, unless a bucket overflowed. */
@@ -902,9 +1001,11 @@ size_t mgTableAddScratchBytes (const MgTable *t, U64 n)
 
 /* insert a batch (ordinal order = array order); counters[0] = number of new entries afterwards */
 MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *scratch, hipStream_t st,
-                     const MgHistReq *counted, const MgSegSrc *segSrc)
+                     const MgHistReq *counted, const MgSegSrc *segSrc, MgValueAside *aside)
 {
+  if (aside) aside->launched = false;
   if (!n) return MG_OK;
+  if ((uintptr_t) scratch & 255) { mgSetError ("internal: the insert's scratch is not 256-byte aligned"); return MG_ERR_ARG; }      /* (mgRankRecordKernel reads flags[] 16 bytes at a time) */
   if (segSrc && !mgTableAddTakesSegments (t, n, counted)) { mgSetError ("internal: this insert needs the dense k-mers"); return MG_ERR_ARG; }
   t->liveHistValid = false;                          /* set again below if this add is the set's only one */
   if (withDepth) t->pendingDepth = true;
@@ -920,10 +1021,15 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
 
   if (!mgTableUseBuckets (t, n))
     { U32 *slotId = (U32 *) wb;
+      if (aside) { mgSetError ("internal: the direct insert has no value writer to run aside"); return MG_ERR_ARG; }      /* (it writes value[] on st: the caller decides by mgTableUseBuckets too, and orders st itself) */
       { MgStatus cs = mgTableClean (t, st); if (cs) return cs; }
       MG_LAUNCH (MG_K_TABLE_INSERT, st, mgTableInsertKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, t->slots, g, dKmer, n, slotId, withDepth, t->counters);
       MG_LAUNCH (MG_K_TABLE_FLAG, st, mgDirectFlagKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, t->slots, slotId, n, flags);
-      { MgStatus as = mgAssignIndices (t, flags, dKmer, (const MgSegSrc *) 0, (const MgSubSeg *) 0, n, blockCount, blockBase, slotId, grp, st); if (as) return as; }
+      { U32 nBlocks; U64 rows;
+        MgStatus as = mgCountFlags (t, flags, n, blockCount, blockBase, &nBlocks, &rows, st); if (as) return as;
+        MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<true>), dim3 (nBlocks), dim3 (256), 0, st,
+                   flags, dKmer, n, rows, blockBase, t->max, t->size, t->value, t->slots, slotId, grp);
+      }
       MG_HIP (hipGetLastError ());
       /* occ[] is kept exact only by the bucketed path and the loader; the direct path marks buckets non-empty */
       return mgTableMarkOccupied (t, dKmer, n, st);
@@ -1013,10 +1119,26 @@ MgStatus mgTableAdd (MgTable *t, const U64 *dKmer, U64 n, int withDepth, void *s
     { if ((s = mgAddTighten (t, plan.tightPct, uniqCount, &fullest, st))) return s;
       if (t->R != a.g.R) { a.g = mgGeomOf (t); lds = mgMergeLdsBytes (t->R); }
     }
-  if ((s = mgAssignIndices (t, flags, dKmer, segSrc, subSeg, n, blockCount, blockBase, (const U32 *) 0, grp, st))) return s;
+  /* index assignment in two halves.  The rank records are all the rest of the add needs; value[] is read by nobody before the caller looks at the
+     set, so with `aside` its writer -- a plain stream over 2 GB -- goes behind the merge kernel onto a stream of its own, where it runs beside
+     whatever the caller starts next: the scan of the next batch, which leaves the memory path idle.  (Beside the lookups or the merge of this add
+     it cost more than it hid: they want the memory path themselves.) */
+  { U32 nBlocks; U64 rows;
+    if ((s = mgCountFlags (t, flags, n, blockCount, blockBase, &nBlocks, &rows, st))) return s;
+    MG_LAUNCH (MG_K_RANK_RECORD, st, mgRankRecordKernel, dim3 (nBlocks), dim3 (256), 0, st, flags, n, rows, blockBase, grp);
+  }
+  if (!aside && (s = mgWriteValues (t, grp, dKmer, segSrc, subSeg, n, MG_VALUE_WAVES_ALONE, st))) return s;
   if ((s = mgRankLookup (a, st))) return s;
   if ((s = mgBucketMerge (a, fullest, bThreads, bGrid, perBlock, lds, st))) return s;
   MG_HIP (hipGetLastError ());
+  if (aside)
+    { MG_HIP (hipEventRecord (aside->merged, st));
+      MG_HIP (hipStreamWaitEvent (aside->stream, aside->merged, 0));
+      if ((s = mgWriteValues (t, grp, dKmer, segSrc, subSeg, n, MG_VALUE_WAVES_ASIDE, aside->stream))) return s;
+      MG_HIP (hipEventRecord (aside->done, aside->stream));
+      aside->launched = true;
+    }
+  gValueWriters[aside ? 0 : 1].fetch_add (1, std::memory_order_relaxed);
   return MG_OK;
 }
 
@@ -1239,9 +1361,8 @@ MgStatus mgTablePrune (MgTable *t, const U8 *dInfo, int lo, int hi, U64 *dNewVal
   MG_LAUNCH (MG_K_RANK_COUNT, st, mgRankCountKernel, dim3 (nBlocks), dim3 (256), 0, st, keep, (U64) n, rows, unitCount);
   MG_LAUNCH (MG_K_RANK_SCAN, st, (mgGroupSumKernel<U64, U64>), dim3 (1), dim3 (MG_GROUP_THREADS), 0, st, unitCount, unitBase, nBlocks * 4, t->counters);
   /* value[i+1] of survivor i -> newValue[1 + rank]: the assign kernel with "kmer" = value + 1, base 0 */
-  const MgSegSrc noSrc = {};
-  MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false, false>), dim3 (nBlocks), dim3 (256), 0, st,
-             keep, t->value + 1, noSrc, (const MgSubSeg *) 0, (U64) n, rows, unitBase, 0u, 0xffffffffu, dNewValue, t->slots, (const U32 *) 0, grp);
+  MG_LAUNCH (MG_K_TABLE_ASSIGN, st, (mgRankAssignKernel<false>), dim3 (nBlocks), dim3 (256), 0, st,
+             keep, t->value + 1, (U64) n, rows, unitBase, 0u, 0xffffffffu, dNewValue, t->slots, (const U32 *) 0, grp);
   MG_LAUNCH (MG_K_TABLE_EXPORT, st, mgPruneMoveKernel, dim3 (mgGridWide (n)), dim3 (256), 0, st, keep, grp, n, t->baseDepth, dInfo, dNewDepth, dNewInfo);
   MG_HIP (hipGetLastError ());
   return MG_OK;

@@ -89,7 +89,10 @@ BUILD_KNOBS = [{}, {}, {"TABLE_PATH": "bucket"}, {"TABLE_PATH": "direct"}, {"TAB
                # the merge kernel's placement by prefix scan (the default) off, and forced on at loads and bucket sizes where buckets run over their end
                {"TABLE_PATH": "bucket", "MERGE_PLACE": 0}, {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "TIGHT_LOAD": 85},
                {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "BUCKET_R": 256, "BUCKET_T": 256, "TABLE_LOAD": 85, "TIGHT_LOAD": 0},
-               {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "MERGE_SLOTS": 0, "FLAG_POLARITY": 1}]
+               {"TABLE_PATH": "bucket", "MERGE_PLACE": 1, "MERGE_SLOTS": 0, "FLAG_POLARITY": 1},
+               # the value writer kept on the caller's stream, and forced off it (the default for these batches) with either k-mer source
+               {"TABLE_PATH": "bucket", "VALUE_ASYNC": 0}, {"TABLE_PATH": "bucket", "VALUE_ASYNC": 1}, {"TABLE_PATH": "bucket", "VALUE_ASYNC": 1, "NO_SEGMENT_INPUT": 1},
+               {"TABLE_PATH": "bucket", "VALUE_ASYNC": 1, "MERGE_SLOTS": 1, "FLAG_POLARITY": 0}]
 
 
 def trial_build(rng, k, w, sd):
