@@ -12,7 +12,7 @@
  * window is a device-to-device copy out of it; what a window leaves over stays there -- the tail is
  * carried on the device -- and moves to the front of the other staging buffer when more members are needed.  Members are taken in
  * batches whose compressed bytes, a contiguous stretch of the file with headers and trailers, are read by the parser's team of readers
- * (mgTextReadParallel) into page-locked memory in pieces of 16 MiB, one read while the one before is on the link, and uploaded once.  Where device memory allows, the compressed file STAYS on the device
+ * into page-locked pieces, one read while the one before is on the link (MgDevFile, mg_devfile.h), and uploaded once.  Where device memory allows, the compressed file STAYS on the device
  * for the call's second walk (seqconvert's, composition's re-walk up to a cut): that walk reads and uploads nothing.  A caller that walks the
  * file once (the text parser, mg_textgpu.hip) says so (mgBgzfSrcOneWalk): nothing stays then, the compressed bytes pass through a ring of
  * look + 2 x 64 KiB, and the memory a resident file would take is the modset table's.
@@ -25,12 +25,11 @@
 #include <vector>
 #include "mg_common.h"
 #include "mg_internal.h"
+#include "mg_devfile.h"
 #include "mg_bgzf.h"
 
 #define BZ_MEMBER 65536u                                 /* the most a member inflates to, and the most it occupies in the file */
 #define BZ_LOOK_MAX ((size_t) 256 << 20)                 /* text inflated ahead of the windows: eight windows, this much at most (a window if it is larger) */
-#define BZ_PIECE ((size_t) 16 << 20)                     /* compressed bytes per read and upload */
-#define BZ_RESIDENT_MAX ((U64) 8 << 30)                  /* the compressed file stays on the device up to this size, and only in a quarter of the free memory */
 
 struct MgBgzfSrc {
   std::string name; int fd = -1; U64 fileSize = 0, textBytes = 0;
@@ -41,15 +40,14 @@ struct MgBgzfSrc {
   size_t look = 0;                                       /* text the staging buffer is filled up to: several windows, so that a launch has members for every CU */
   unsigned char *dComp = 0; size_t compCap = 0; bool resident = false; U64 uploadedTo = 0;
   bool oneWalk = false;                                  /* the caller walks the file once: the compressed bytes pass through a ring of look + 2 x 64 KiB, nothing stays */
-  unsigned char *hComp[2] = { 0, 0 }; hipEvent_t up[2] = { 0, 0 }; size_t piece = 0; U64 pieces = 0;      /* the file crosses in pieces: one is read while the one before it is on the link */
-  MgDevBuf<unsigned char> work; unsigned char *hEdge = 0;
+  MgDevFile file;                                        /* the file crosses in pieces: one is read while the one before it is on the link */
+  MgDevBuf<unsigned char> work; MgFillEdge edge;
   std::vector<MgGzMember> batch; std::vector<U32> status;
   size_t m = 0; U64 pos = 0;                             /* the next member to inflate; the text handed out so far */
   void release ()
   { for (int i = 0 ; i < 2 ; ++i) { (void) hipFree (dStage[i]); dStage[i] = 0; }
-    for (int i = 0 ; i < 2 ; ++i) { mgPinnedFree (hComp[i]); hComp[i] = 0; if (up[i]) (void) hipEventDestroy (up[i]); up[i] = 0; }
-    (void) hipFree (dComp); dComp = 0; mgPinnedFree (hEdge); hEdge = 0; work.drop ();
-    stageCap = compCap = look = piece = 0; pieces = 0; resident = false; uploadedTo = 0;
+    (void) hipFree (dComp); dComp = 0; file.release (); edge.release (); work.drop ();
+    stageCap = compCap = look = 0; resident = false; uploadedTo = 0;
   }
 };
 
@@ -164,16 +162,14 @@ static int bzReserve (MgBgzfSrc *s, size_t cap)
   size_t look = cap * 8 < BZ_LOOK_MAX ? cap * 8 : BZ_LOOK_MAX; if (look < cap) look = cap;
   const size_t stage = look + BZ_MEMBER;
   size_t freeB = 0;
-  if (!s->oneWalk && s->fileSize <= BZ_RESIDENT_MAX && mgDevFreeBytes (&freeB) && s->fileSize <= freeB / 4) s->resident = true;
+  s->resident = !s->oneWalk && mgFileStays (s->fileSize, &freeB);
   s->compCap = s->resident ? (size_t) s->fileSize : look + 2 * BZ_MEMBER;
-  s->piece = s->compCap < BZ_PIECE ? s->compCap : BZ_PIECE;
   if (hipMalloc ((void **) &s->dStage[0], stage) != hipSuccess || hipMalloc ((void **) &s->dStage[1], stage) != hipSuccess
-      || hipMalloc ((void **) &s->dComp, s->compCap) != hipSuccess
-      || hipEventCreateWithFlags (&s->up[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags (&s->up[1], hipEventDisableTiming) != hipSuccess)
+      || hipMalloc ((void **) &s->dComp, s->compCap) != hipSuccess)
     { mgHipFail (hipGetLastError (), "blocked gzip on the device"); s->release (); return -1; }
-  s->hComp[0] = (unsigned char *) mgPinnedAlloc (s->piece); s->hComp[1] = (unsigned char *) mgPinnedAlloc (s->piece); s->hEdge = (unsigned char *) mgPinnedAlloc (64);
-  if (!s->hComp[0] || !s->hComp[1] || !s->hEdge) { mgSetError ("blocked gzip %s: no page-locked memory", s->name.c_str ()); s->release (); return -1; }
-  s->stageCap = stage; s->look = look; s->p = 0; s->at = s->have = 0; s->uploadedTo = 0; s->pieces = 0;
+  const int rc = s->file.reserve (s->compCap, "blocked gzip on the device");
+  if (rc || !s->edge.ready ()) { if (rc != -1) mgSetError ("blocked gzip %s: no page-locked memory", s->name.c_str ()); s->release (); return -1; }
+  s->stageCap = stage; s->look = look; s->p = 0; s->at = s->have = 0; s->uploadedTo = 0;
   return 0;
 }
 
@@ -195,14 +191,8 @@ static int bzLoad (MgBgzfSrc *s, hipStream_t st)
   { const U64 from = s->resident && s->uploadedTo > a ? s->uploadedTo : a;      /* (resident: what an earlier walk brought stays) */
     if (from < b)
       { const size_t n = (size_t) (b - from);
-        for (size_t done = 0 ; done < n ; done += s->piece, ++s->pieces)
-          { const int k = (int) (s->pieces & 1);
-            const size_t part = n - done < s->piece ? n - done : s->piece;
-            if (s->pieces >= 2 && hipEventSynchronize (s->up[k]) != hipSuccess) return mgHipFail (hipGetLastError (), "blocked gzip on the device"), -1;
-            if (mgTextReadParallel (s->fd, s->hComp[k], part, (int64_t) (from + done))) { mgSetError ("failed to read sequence file %s", s->name.c_str ()); return -1; }
-            if (hipMemcpyAsync (s->dComp + (from + done - base), s->hComp[k], part, hipMemcpyHostToDevice, st) != hipSuccess
-                || hipEventRecord (s->up[k], st) != hipSuccess) return mgHipFail (hipGetLastError (), "blocked gzip on the device"), -1;
-          }
+        const int rc = s->file.upload (s->fd, from, n, s->dComp + (from - base), st, "blocked gzip on the device");
+        if (rc) { if (rc == -2) mgSetError ("failed to read sequence file %s", s->name.c_str ()); return -1; }
         mgInflateDiagUploaded (n);
         if (s->resident) s->uploadedTo = b;
       }
@@ -233,20 +223,17 @@ extern "C" int mgBgzfSrcFill (MgBgzfSrc *s, unsigned char *dDst, size_t cap, U64
 {
   hipStream_t st = (hipStream_t) stream;
   *n = 0; *more = 0; *first = *last = 0;
-  if (off != s->pos) { mgSetError ("blocked gzip %s: byte %llu asked for at byte %llu", s->name.c_str (), (unsigned long long) off, (unsigned long long) s->pos); return -1; }
   const U64 end = limit < s->textBytes ? limit : s->textBytes;
-  if (off >= end || !cap) return 0;
-  const size_t want = end - off < cap ? (size_t) (end - off) : cap;
+  size_t want = 0;
+  if (mgFillWant ("blocked gzip", s->name.c_str (), off, s->pos, end, cap, &want)) return -1;
+  if (!want) return 0;
   if (bzReserve (s, cap)) return -1;
   while (s->have < want && s->m < s->mem.size ()) if (bzLoad (s, st)) { (void) hipStreamSynchronize (st); return -1; }
   const size_t take = s->have < want ? s->have : want;
   if (!take) return 0;
   const unsigned char *src = s->dStage[s->p] + s->at;
-  if (hipMemcpyAsync (dDst, src, take, hipMemcpyDeviceToDevice, st) != hipSuccess
-      || hipMemcpyAsync (s->hEdge, src, 1, hipMemcpyDeviceToHost, st) != hipSuccess
-      || hipMemcpyAsync (s->hEdge + 1, src + take - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess
-      || hipStreamSynchronize (st) != hipSuccess) return mgHipFail (hipGetLastError (), "blocked gzip on the device"), -1;
-  *first = s->hEdge[0]; *last = s->hEdge[1];
+  if (hipMemcpyAsync (dDst, src, take, hipMemcpyDeviceToDevice, st) != hipSuccess) return mgHipFail (hipGetLastError (), "blocked gzip on the device"), -1;
+  if (s->edge.fetch ("blocked gzip", src, take, st, first, last)) return -1;
   s->at += take; s->have -= take; s->pos += take;
   /* one walk: the empty members behind the text's last byte (bgzip's end marker) are part of the file -- uploaded and checked as every other */
   if (s->oneWalk && s->pos == s->textBytes)

@@ -1,6 +1,6 @@
 /* mg_gunzip_core.h — ordinary gzip (RFC 1952: one deflate stream a member, no block table) inflated in parallel, written once for host and device.
  *
- * It sits beside mg_inflate_core.h and uses its bit reader, mgiBuild, mgiDecode, mgiBlockCodes and the CRC slice and combine arithmetic.  No zlib, no
+ * It sits beside mg_inflate_core.h and uses its bit reader, mgiBuild, mgiDecode, mgiBlockCodes, mgiStoredHeader, mgiLength, mgiDistance and the CRC slice and combine arithmetic.  No zlib, no
  * allocation, plain C that is also C++ / HIP: mg_gunzip.hip compiles the stages for gfx950 and the whole of it for the host (mgGunzipHost);
  * tools/gunzip_host_check.c includes nothing else.
  *
@@ -162,12 +162,8 @@ MGI_HD uint32_t mgzChunkDecode (const uint8_t *comp, uint64_t n, uint64_t start,
     { if (!mgiBits (b, 1, &last) || !mgiBits (b, 2, &type)) { st = MGI_INPUT; break; }
       if (type == 3) { st = MGI_BLOCKTYPE; break; }
       if (type == 0)
-        { uint32_t len, nlen, i;
-          b->buf >>= b->cnt & 7; b->cnt -= b->cnt & 7;
-          if (!mgiBits (b, 16, &len) || !mgiBits (b, 16, &nlen)) { st = MGI_INPUT; break; }
-          if ((len ^ 0xffffu) != nlen) { st = MGI_STORED; break; }
-          b->pos -= b->cnt >> 3; b->cnt = 0; b->buf = 0; b->ahave = 0;
-          if (len > b->n - b->pos) { st = MGI_INPUT; break; }
+        { uint32_t len, i;
+          { const int h = mgiStoredHeader (b); if (h < 0) { st = (uint32_t) -h; break; } len = (uint32_t) h; }
           if (len > cap - o) { st = MGZ_CAPACITY; break; }
           for (i = 0 ; i < len ; ++i) out[o + i] = b->in[b->pos + i];
           o += len; b->pos += len;
@@ -178,21 +174,13 @@ MGI_HD uint32_t mgzChunkDecode (const uint8_t *comp, uint64_t n, uint64_t start,
       if (st) break;
       for (;;)
         { int s = mgiDecode (b, T->lfast, MGI_LBITS, T->lcount, T->lsym);
-          uint32_t len, dist, extra, v = 0, i;
+          uint32_t len, dist, i;
           if (s < 0) { st = s == -2 ? MGI_INPUT : MGI_SYMBOL; break; }
           if (s < 256) { if (o >= cap) { st = MGZ_CAPACITY; break; } out[o++] = (uint16_t) s; continue; }
           if (s == 256) break;
-          if (s > 285) { st = MGI_SYMBOL; break; }
-          if (s < 265) { len = (uint32_t) s - 254; extra = 0; }
-          else if (s == 285) { len = 258; extra = 0; }
-          else { extra = ((uint32_t) s - 261) >> 2; len = 3 + ((4 + (((uint32_t) s - 261) & 3)) << extra); }
-          if (extra) { if (!mgiBits (b, extra, &v)) { st = MGI_INPUT; break; } len += v; }
-          s = mgiDecode (b, T->dfast, MGI_DBITS, T->dcount, T->dsym);
-          if (s < 0) { st = s == -2 ? MGI_INPUT : MGI_SYMBOL; break; }
-          if (s > 29) { st = MGI_SYMBOL; break; }
-          if (s < 4) { dist = (uint32_t) s + 1; extra = 0; }
-          else { extra = ((uint32_t) s >> 1) - 1; dist = 1 + ((2 + ((uint32_t) s & 1)) << extra); }
-          if (extra) { if (!mgiBits (b, extra, &v)) { st = MGI_INPUT; break; } dist += v; }
+          st = mgiLength (b, s, &len);
+          if (!st) st = mgiDistance (b, T, &dist);
+          if (st) break;
           if (dist > o && known != ~(uint32_t) 0 && dist - o > known) { st = MGI_DISTANCE; break; }
           if (len > cap - o) { st = MGZ_CAPACITY; break; }
           /* the copy, by the thread that wrote what it reads.  A place before the chunk's output is a marker: window place 32768 - (dist - o) + i; a

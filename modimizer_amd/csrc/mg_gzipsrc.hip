@@ -3,8 +3,8 @@
  *
  * Which files (mgGzipSrcOpen).  A regular file that begins 1f 8b 08, whose first member carries no 'BC' extra subfield (a file that is nearly BGZF keeps the
  * path it has), that is at least MODGPU_GZIP_MIN_KB in size and not more than the device keeps: the compressed file is uploaded ONCE -- read by the parser's
- * team of readers (mgTextReadParallel) into page-locked pieces of 16 MiB, one read while the piece before is on the link -- and STAYS on the device, by the
- * rule of BZ_RESIDENT_MAX (8 GiB, a quarter of the free memory), so the call's second walk reads and uploads nothing.  A larger file is the host's, as before.
+ * team of readers into page-locked pieces, one read while the piece before is on the link (MgDevFile, mg_devfile.h) -- and STAYS on the device, by the
+ * rule of mgFileStays (8 GiB, a quarter of the free memory), so the call's second walk reads and uploads nothing.  A larger file is the host's, as before.
  *
  * Filling a window (mgGzipSrcFill).  The stream (mg_gunzip.hip) inflates a batch of chunks ahead of the windows into its own staging; a window is device-to-
  * device copies out of it, what a window leaves over stays there for the next one.  The text's length is not known before its last batch, so a full window
@@ -17,10 +17,9 @@
 #include <string>
 #include "mg_common.h"
 #include "mg_internal.h"
+#include "mg_devfile.h"
 #include "mg_gunzip_core.h"
 
-#define GS_PIECE ((size_t) 16 << 20)
-#define GS_RESIDENT_MAX ((U64) 8 << 30)
 #define GS_CHUNK_KB 64                                   /* the defaults are measured: DESIGN.md, "Ordinary gzip inflated on the device" */
 #define GS_BATCH 4096
 #define GS_MIN_KB 16384                                  /* below it one chunk's serial decode (about 0.1 s) is more than the host's whole inflate */
@@ -33,7 +32,7 @@ struct MgGzipSrc {
   MgGunzipDev *g = 0;
   const U8 *text = 0; size_t have = 0; int done = 0;
   U64 pos = 0;
-  unsigned char *hEdge = 0;
+  MgFillEdge edge;
 };
 
 static U64 gsMinBytes (void)
@@ -47,14 +46,14 @@ extern "C" int mgGzipSrcOpen (const char *name, int fd, U64 fileSize, int any, M
   *out = 0;
   const MgKnobs *kn = mgKnobs ();
   if (!any && (kn->gzipHost == 1 || fileSize < gsMinBytes ())) return -2;
-  if (fileSize < 18 || fileSize > GS_RESIDENT_MAX) return -2;
+  if (fileSize < 18 || fileSize > MG_FILE_RESIDENT_MAX) return -2;
   std::string head ((size_t) (fileSize < 70000 ? fileSize : 70000), '\0');
   if (pread (fd, &head[0], head.size (), 0) != (ssize_t) head.size ()) return -2;
   uint64_t len = 0; int bc = 0;
   if (mgzHeader ((const uint8_t *) head.data (), head.size (), &len, &bc) == 2 || bc) return -2;
   if (mgEnsureDevice () != MG_OK) return -1;
   size_t freeB = 0;
-  if (!mgDevFreeBytes (&freeB) || fileSize > freeB / 4) return -2;
+  if (!mgFileStays (fileSize, &freeB)) return -2;
   MgGzipSrc *s = new MgGzipSrc; s->name = name ? name : ""; s->fd = fd; s->fileSize = fileSize;
   unsigned char t[4] = { 0, 0, 0, 0 };
   (void) ! pread (fd, t, 4, (off_t) (fileSize - 4));
@@ -75,7 +74,7 @@ extern "C" int mgGzipSrcOpen (const char *name, int fd, U64 fileSize, int any, M
 extern "C" void mgGzipSrcClose (MgGzipSrc *s)
 {
   if (!s) return;
-  mgGunzipDevClose (s->g); (void) hipFree (s->dComp); mgPinnedFree (s->hEdge);
+  mgGunzipDevClose (s->g); (void) hipFree (s->dComp); s->edge.release ();
   delete s;
 }
 extern "C" void mgGzipSrcRewind (MgGzipSrc *s) { s->pos = 0; s->have = 0; s->text = 0; s->done = 0; if (s->g) mgGunzipDevRewind (s->g); }
@@ -85,32 +84,18 @@ extern "C" U64 mgGzipSrcSizeHint (const MgGzipSrc *s) { return s->hint; }
 static int gsUpload (MgGzipSrc *s, hipStream_t st)
 {
   const char *what = "gzip on the device";
-  const size_t piece = s->fileSize < GS_PIECE ? (size_t) s->fileSize : GS_PIECE;
-  unsigned char *h[2] = { (unsigned char *) mgPinnedAlloc (piece), (unsigned char *) mgPinnedAlloc (piece) };
-  hipEvent_t up[2] = { 0, 0 };
-  int rc = -1;
-  do
-    { if (!h[0] || !h[1] || !(s->hEdge = (unsigned char *) mgPinnedAlloc (64))) { mgSetError ("gzip %s: no page-locked memory", s->name.c_str ()); break; }
-      if (hipMalloc ((void **) &s->dComp, (size_t) s->fileSize) != hipSuccess || hipEventCreateWithFlags (&up[0], hipEventDisableTiming) != hipSuccess
-          || hipEventCreateWithFlags (&up[1], hipEventDisableTiming) != hipSuccess) { mgHipFail (hipGetLastError (), what); break; }
-      bool bad = false;
-      U64 k = 0;
-      for (U64 done = 0 ; done < s->fileSize && !bad ; done += piece, ++k)
-        { const size_t part = s->fileSize - done < piece ? (size_t) (s->fileSize - done) : piece;
-          if (k >= 2 && hipEventSynchronize (up[k & 1]) != hipSuccess) { mgHipFail (hipGetLastError (), what); bad = true; break; }
-          if (mgTextReadParallel (s->fd, h[k & 1], part, (int64_t) done)) { mgSetError ("failed to read sequence file %s", s->name.c_str ()); bad = true; break; }
-          if (hipMemcpyAsync (s->dComp + done, h[k & 1], part, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord (up[k & 1], st) != hipSuccess)
-            { mgHipFail (hipGetLastError (), what); bad = true; }
-        }
-      if (hipStreamSynchronize (st) != hipSuccess && !bad) { mgHipFail (hipGetLastError (), what); bad = true; }
-      if (bad) break;
-      mgInflateDiagUploaded (s->fileSize);
-      if (mgGunzipDevOpen (s->dComp, s->fileSize, s->fd, s->chunkBytes, s->batch, s->spc, &s->g)) break;
-      s->uploaded = true; rc = 0;
-    }
-  while (0);
-  for (int i = 0 ; i < 2 ; ++i) { mgPinnedFree (h[i]); if (up[i]) (void) hipEventDestroy (up[i]); }
-  return rc;
+  MgDevFile file;
+  int rc = file.reserve ((size_t) s->fileSize, what);
+  if (rc == -2 || (!rc && !s->edge.ready ())) { mgSetError ("gzip %s: no page-locked memory", s->name.c_str ()); rc = -1; }
+  if (!rc && hipMalloc ((void **) &s->dComp, (size_t) s->fileSize) != hipSuccess) { mgHipFail (hipGetLastError (), what); rc = -1; }
+  if (!rc && (rc = file.upload (s->fd, 0, (size_t) s->fileSize, s->dComp, st, what)) == -2) mgSetError ("failed to read sequence file %s", s->name.c_str ());
+  if (hipStreamSynchronize (st) != hipSuccess && !rc) { mgHipFail (hipGetLastError (), what); rc = -1; }
+  file.release ();
+  if (rc) return -1;
+  mgInflateDiagUploaded (s->fileSize);
+  if (mgGunzipDevOpen (s->dComp, s->fileSize, s->fd, s->chunkBytes, s->batch, s->spc, &s->g)) return -1;
+  s->uploaded = true;
+  return 0;
 }
 
 /* text into the staging if it is empty and the stream has more; 0 / -1 */
@@ -129,9 +114,9 @@ extern "C" int mgGzipSrcFill (MgGzipSrc *s, unsigned char *dDst, size_t cap, U64
 {
   hipStream_t st = (hipStream_t) stream;
   *n = 0; *more = 0; *first = *last = 0;
-  if (off != s->pos) { mgSetError ("gzip %s: byte %llu asked for at byte %llu", s->name.c_str (), (unsigned long long) off, (unsigned long long) s->pos); return -1; }
-  if (off >= limit || !cap) return 0;
-  const size_t want = limit - off < cap ? (size_t) (limit - off) : cap;
+  size_t want = 0;
+  if (mgFillWant ("gzip", s->name.c_str (), off, s->pos, limit, cap, &want)) return -1;
+  if (!want) return 0;
   if (!s->uploaded && gsUpload (s, st)) return -1;
   size_t got = 0;
   while (got < want)
@@ -143,10 +128,7 @@ extern "C" int mgGzipSrcFill (MgGzipSrc *s, unsigned char *dDst, size_t cap, U64
     }
   if (!got) return 0;
   if (got == want && off + got < limit && gsAhead (s, st)) { (void) hipStreamSynchronize (st); return -1; }      /* does text follow? */
-  if (hipMemcpyAsync (s->hEdge, dDst, 1, hipMemcpyDeviceToHost, st) != hipSuccess
-      || hipMemcpyAsync (s->hEdge + 1, dDst + got - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess
-      || hipStreamSynchronize (st) != hipSuccess) return mgHipFail (hipGetLastError (), "gzip on the device"), -1;
-  *first = s->hEdge[0]; *last = s->hEdge[1];
+  if (s->edge.fetch ("gzip", dDst, got, st, first, last)) return -1;
   s->pos += got;
   *n = got; *more = s->have > 0 && s->pos < limit;
   return 0;

@@ -206,6 +206,47 @@ MGI_HD uint32_t mgiBlockCodes (MgInfBits *b, uint32_t type, MgInfTables *T, uint
   return MGI_OK;
 }
 
+/* A stored block's header (RFC 1951 3.2.4): to the byte boundary, LEN and its complement, and the whole bytes that were loaded ahead go back, so that the
+   reader holds no bits and in[pos] is the first payload byte.  Returns LEN, which the input holds -- the caller copies the bytes, moves pos past them and
+   primes the reader again -- or minus a status */
+MGI_HD int mgiStoredHeader (MgInfBits *b)
+{
+  uint32_t len, nlen;
+  b->buf >>= b->cnt & 7; b->cnt -= b->cnt & 7;
+  if (!mgiBits (b, 16, &len) || !mgiBits (b, 16, &nlen)) return -MGI_INPUT;
+  if ((len ^ 0xffffu) != nlen) return -MGI_STORED;
+  b->pos -= b->cnt >> 3; b->cnt = 0; b->buf = 0; b->ahave = 0;
+  return len > b->n - b->pos ? -MGI_INPUT : (int) len;
+}
+
+/* A match (RFC 1951 3.2.5), in two steps.  mgiLength: the literal/length symbol s > 256 that was just decoded and its extra bits into *len (3 .. 258);
+   mgiDistance: the distance symbol behind it and its extra bits into *dist (1 .. 32768).  A status each; whether they fit is the caller's to say */
+MGI_HD uint32_t mgiLength (MgInfBits *b, int s, uint32_t *len)
+{
+  uint32_t extra, v = 0;
+  if (s > 285) return MGI_SYMBOL;
+  /* 257 .. 264 no extra bits, then four codes to each number of extra bits, 285 is 258 */
+  if (s < 265) { *len = (uint32_t) s - 254; return MGI_OK; }
+  if (s == 285) { *len = 258; return MGI_OK; }
+  extra = ((uint32_t) s - 261) >> 2; *len = 3 + ((4 + (((uint32_t) s - 261) & 3)) << extra);
+  if (!mgiBits (b, extra, &v)) return MGI_INPUT;
+  *len += v;
+  return MGI_OK;
+}
+MGI_HD uint32_t mgiDistance (MgInfBits *b, const MgInfTables *T, uint32_t *dist)
+{
+  uint32_t extra, v = 0;
+  const int s = mgiDecode (b, T->dfast, MGI_DBITS, T->dcount, T->dsym);
+  if (s < 0) return s == -2 ? MGI_INPUT : MGI_SYMBOL;
+  if (s > 29) return MGI_SYMBOL;
+  /* 0 .. 3 no extra bits, then two codes to each number of extra bits */
+  if (s < 4) { *dist = (uint32_t) s + 1; return MGI_OK; }
+  extra = ((uint32_t) s >> 1) - 1; *dist = 1 + ((2 + ((uint32_t) s & 1)) << extra);
+  if (!mgiBits (b, extra, &v)) return MGI_INPUT;
+  *dist += v;
+  return MGI_OK;
+}
+
 /* One member: comp[0 .. cLen) inflated into out[0 .. uLen).  Returns MGI_OK .. MGI_OUTPUT; the CRC is the caller's (mgInfCrcSlice).
    stats: 0, or 8 counters that are raised, not cleared. */
 MGI_HD uint32_t mgInfInflate (const uint8_t *comp, uint32_t cLen, uint8_t *out, uint32_t uLen, MgInfTables *T, uint64_t *stats)
@@ -218,13 +259,9 @@ MGI_HD uint32_t mgInfInflate (const uint8_t *comp, uint32_t cLen, uint8_t *out, 
     { if (!mgiBits (b, 1, &last) || !mgiBits (b, 2, &type)) return MGI_INPUT;
       if (type == 3) return MGI_BLOCKTYPE;
       if (type == 0)
-        { uint32_t len, nlen, i;
+        { uint32_t len, i;
           MGI_STAT_ADD (MGI_ST_STORED);
-          b->buf >>= b->cnt & 7; b->cnt -= b->cnt & 7;           /* to the byte boundary */
-          if (!mgiBits (b, 16, &len) || !mgiBits (b, 16, &nlen)) return MGI_INPUT;
-          if ((len ^ 0xffffu) != nlen) return MGI_STORED;
-          b->pos -= b->cnt >> 3; b->cnt = 0; b->buf = 0; b->ahave = 0;      /* whole bytes that were loaded ahead go back */
-          if (len > b->n - b->pos) return MGI_INPUT;
+          { const int h = mgiStoredHeader (b); if (h < 0) return (uint32_t) -h; len = (uint32_t) h; }
           if (len > uLen - o) return MGI_OUTPUT;
           for (i = 0 ; i < len ; ++i) out[o + i] = b->in[b->pos + i];
           o += len; b->pos += len;
@@ -235,24 +272,12 @@ MGI_HD uint32_t mgInfInflate (const uint8_t *comp, uint32_t cLen, uint8_t *out, 
       { const uint32_t st = mgiBlockCodes (b, type, T, stats); if (st) return st; }
       for (;;)
         { int s = mgiDecode (b, T->lfast, MGI_LBITS, T->lcount, T->lsym);
-          uint32_t len, dist, extra, v = 0, i;
+          uint32_t len, dist, i;
           if (s < 0) return s == -2 ? MGI_INPUT : MGI_SYMBOL;
           MGI_STAT_ADD (MGI_ST_SYMBOLS);
           if (s < 256) { if (o >= uLen) return MGI_OUTPUT; out[o++] = (uint8_t) s; continue; }
           if (s == 256) break;
-          if (s > 285) return MGI_SYMBOL;
-          /* lengths 3 .. 258 (RFC 1951 3.2.5): 257 .. 264 no extra bits, then four codes to each number of extra bits, 285 is 258 */
-          if (s < 265) { len = (uint32_t) s - 254; extra = 0; }
-          else if (s == 285) { len = 258; extra = 0; }
-          else { extra = ((uint32_t) s - 261) >> 2; len = 3 + ((4 + (((uint32_t) s - 261) & 3)) << extra); }
-          if (extra) { if (!mgiBits (b, extra, &v)) return MGI_INPUT; len += v; }
-          s = mgiDecode (b, T->dfast, MGI_DBITS, T->dcount, T->dsym);
-          if (s < 0) return s == -2 ? MGI_INPUT : MGI_SYMBOL;
-          if (s > 29) return MGI_SYMBOL;
-          /* distances 1 .. 32768: 0 .. 3 no extra bits, then two codes to each number of extra bits */
-          if (s < 4) { dist = (uint32_t) s + 1; extra = 0; }
-          else { extra = ((uint32_t) s >> 1) - 1; dist = 1 + ((2 + ((uint32_t) s & 1)) << extra); }
-          if (extra) { if (!mgiBits (b, extra, &v)) return MGI_INPUT; dist += v; }
+          { uint32_t st = mgiLength (b, s, &len); if (!st) st = mgiDistance (b, T, &dist); if (st) return st; }
           if (dist > o) return MGI_DISTANCE;
           if (len > uLen - o) return MGI_OUTPUT;
           MGI_STAT_MAX (MGI_ST_DIST, dist); MGI_STAT_MAX (MGI_ST_MATCH, len);

@@ -58,7 +58,8 @@ static void readAll (void)
   k.packThreads = num ("MODGPU_PACK_THREADS");     k.parseThreads = num ("MODGPU_PARSE_THREADS");
   k.xferThreads = num ("MODGPU_XFER_THREADS");       k.gzipThreads = num ("MODGPU_GZIP_THREADS");
   k.xferPieceKb = num ("MODGPU_XFER_PIECE_KB");      k.xferStreams = num ("MODGPU_XFER_STREAMS");
-  k.seedTiming = num ("MODGPU_SEED_TIMING");       k.uploadTiming = num ("MODGPU_UPLOAD_TIMING");
+  k.filePieceKb = num ("MODGPU_FILE_PIECE_KB");
+  k.seedTiming = num ("MODGPU_SEED_TIMING");      k.uploadTiming = num ("MODGPU_UPLOAD_TIMING");
   k.textTiming = num ("MODGPU_TEXT_TIMING");       k.parseTiming = getenv ("MODGPU_PARSE_TIMING") ? 1 : MG_KNOB_UNSET;
   k.scanDebug = num ("MODGPU_SCAN_DEBUG");         k.bucketDebug = num ("MODGPU_BUCKET_DEBUG");
   gKnobs = k;

@@ -69,7 +69,8 @@ typedef struct {
   long parseThreads;       /* MODGPU_PARSE_THREADS */
   long gzipThreads;        /* MODGPU_GZIP_THREADS: threads that deflate the members of a .mod / .ref / .readset file (mg_pgzip.c) */
   long xferPieceKb;        /* MODGPU_XFER_PIECE_KB: dev, bytes per piece of the array transfers (default 4096) */
-  long xferStreams;        /* MODGPU_XFER_STREAMS: dev, 0 = the array transfers' copies on the device's default stream instead of a stream per transfer thread */
+  long filePieceKb;        /* MODGPU_FILE_PIECE_KB: dev, KiB per page-locked piece in which a file's bytes cross to the device (mg_devfile.h; 4 at least, default 16384): tests cross pieces with files of a few KiB */
+  long xferStreams;       /* MODGPU_XFER_STREAMS: dev, 0 = the array transfers' copies on the device's default stream instead of a stream per transfer thread */
   long xferThreads;        /* MODGPU_XFER_THREADS: host threads of the array transfers (mg_xfer.hip) */
   long inflateNoCrc;       /* MODGPU_INFLATE_NOCRC: dev, 1 = the inflate kernel skips the CRC-32 (tools/inflate_probe.py measures what the check costs) */
   long seedTiming, uploadTiming, textTiming, parseTiming;   /* MODGPU_*_TIMING prints */

@@ -30,16 +30,10 @@
  * written when a single walk found out).  Nothing is written before that is known; the second walk (F S M X W) sees only the text that is
  * written, which ends in a complete record.  Window i's output is copied out on a stream of its own while window i + 1 is in the kernels, and
  * written by a thread of its own. */
-#include <condition_variable>
-#include <mutex>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <thread>
-#include <time.h>
 #include "mg_prefix.h"
 #include "mg_internal.h"
 #include "mg_textsrc.h"
+#include "mg_textsink.h"
 
 #define SQ_THREADS 256
 #define SQ_WAVES   (SQ_THREADS / 64)
@@ -515,85 +509,18 @@ void mgSeqStitchKernel (SqTiles T, U64 nTiles, SqCfg g, SqWin *win, SqState *st)
 static thread_local U64 gSeqDiag[4];                     /* windows, tiles, records across a window edge, kernel launches */
 extern "C" void mgSeqConvertDiag (U64 out4[4]) { memcpy (out4, gSeqDiag, sizeof (gSeqDiag)); }
 static thread_local double gSeqMs[8];                    /* (MODGPU_SEED_TIMING=1) the first walk, the second; of both: reading; of the second: device -> page-locked copies, waiting for a block, the writer; the kernels of the first walk, of the second (between events on their stream) */
-/* The window for this path: a quarter of the parser's largest.  The output buffers are up to three windows each, two on the device and two page-locked,
-   made per call; the kernels and the link do not gain from more than this */
-#define SQ_WINDOW_HINT ((size_t) 32 << 20)
 /* The most output bytes n bytes of text can become (+ 16).  Every byte gives at most one, but: a record start gives the newline that ends the record before it
    and its own marker, while the newline in front of it gave one too if it ended a HEADER line -- a record without a sequence line grows by one byte, and
    there are at most (n + 1) / 2 starts in n bytes; the first byte of a description gives the space as well, where the separator (which gives nothing) may be
    the window before's last byte.  FASTA -> FASTQ: a start gives "\n+\n", the '!' run, "\n@": with s starts at most n - 2 s + 1 bytes are bases, each itself
    and its '!', so 2 n + 2 s + 1 <= 3 n + 2.  FASTQ in: a line gives at most its bytes */
 static size_t sqOutCap (size_t n, bool fastqIn, bool fastqOut) { return (fastqIn ? n : fastqOut ? 3 * n : n + n / 2) + 16; }
-static double sqMs (const struct timespec &a, const struct timespec &b) { return (b.tv_sec - a.tv_sec) * 1e3 + (b.tv_nsec - a.tv_nsec) * 1e-6; }
 static size_t sqFill (void *src, unsigned char *dst, size_t cap, U64 off)      /* CpSource::fill, timed */
 { struct timespec t0, t1; clock_gettime (CLOCK_MONOTONIC, &t0);
   const size_t got = CpSource::fill (src, dst, cap, off);
-  clock_gettime (CLOCK_MONOTONIC, &t1); gSeqMs[2] += sqMs (t0, t1);
+  clock_gettime (CLOCK_MONOTONIC, &t1); gSeqMs[2] += tsMs (t0, t1);
   return got;
 }
-
-/* the windows' output, written in order behind the caller: two page-locked blocks, one being filled while the other is written */
-struct SqWriter {
-  FILE *out = 0;
-  std::thread th; std::mutex mu; std::condition_variable cv;
-  struct Block { unsigned char *p = 0; bool pinned = false; size_t n = 0; U64 spliceAt = 0, spliceCount = 0; int state = 0; } blk[2];      /* state: 0 free, 1 being filled, 2 to be written */
-  U64 head = 0, tail = 0; bool closing = false, err = false, started = false;
-  double msWrite = 0;
-  int open (FILE *f, size_t cap)
-  { out = f;
-    for (int i = 0 ; i < 2 ; ++i)
-      { blk[i].p = (unsigned char *) mgPinnedAlloc (cap); blk[i].pinned = blk[i].p != 0;
-        if (!blk[i].p) blk[i].p = (unsigned char *) malloc (cap ? cap : 16);
-        if (!blk[i].p) { mgSetError ("mgSeqConvert: out of memory"); return -1; }
-      }
-    try { th = std::thread (&SqWriter::run, this); started = true; } catch (...) { started = false; }      /* (no thread: every block is written on the spot) */
-    return 0;
-  }
-  static bool bangs (FILE *f, U64 n)                     /* n times '!' */
-  { char run[1 << 16];
-    memset (run, '!', n < sizeof (run) ? (size_t) n : sizeof (run));
-    while (n) { const size_t k = n < sizeof (run) ? (size_t) n : sizeof (run); if (fwrite (run, 1, k, f) != k) return false; n -= k; }
-    return true;
-  }
-  void write (Block &b)
-  { struct timespec t0, t1; clock_gettime (CLOCK_MONOTONIC, &t0);
-    const size_t at = b.spliceCount ? (size_t) b.spliceAt : b.n;
-    bool ok = fwrite (b.p, 1, at, out) == at;
-    if (ok && b.spliceCount) ok = bangs (out, b.spliceCount) && fwrite (b.p + at, 1, b.n - at, out) == b.n - at;
-    clock_gettime (CLOCK_MONOTONIC, &t1);
-    msWrite += sqMs (t0, t1);
-    if (!ok) err = true;
-  }
-  void run ()
-  { std::unique_lock<std::mutex> lk (mu);
-    for (;;)
-      { Block &b = blk[head & 1];
-        cv.wait (lk, [&] { return b.state == 2 || closing; });
-        if (b.state != 2) return;
-        lk.unlock (); write (b); lk.lock ();
-        b.state = 0; ++head;
-        cv.notify_all ();
-      }
-  }
-  Block &acquire ()
-  { std::unique_lock<std::mutex> lk (mu);
-    Block &b = blk[tail & 1];
-    cv.wait (lk, [&] { return b.state == 0; });
-    b.state = 1;
-    return b;
-  }
-  void submit (Block &b)
-  { if (!started) { write (b); b.state = 0; ++tail; ++head; return; }
-    std::lock_guard<std::mutex> lk (mu);
-    b.state = 2; ++tail;
-    cv.notify_all ();
-  }
-  int close ()
-  { if (started) { { std::lock_guard<std::mutex> lk (mu); closing = true; cv.notify_all (); } th.join (); started = false; }
-    for (int i = 0 ; i < 2 ; ++i) { if (blk[i].pinned) mgPinnedFree (blk[i].p); else free (blk[i].p); blk[i].p = 0; }
-    return err ? -1 : 0;
-  }
-};
 
 struct SqPass {                                          /* one walk over the text */
   SqCfg g = { 0, 0, 0, 0 };
@@ -601,7 +528,7 @@ struct SqPass {                                          /* one walk over the te
   int type = 0;
   size_t tilesCap = 0, outCap = 0;
   SqTiles T; SqState *dState = 0; SqWin *dWin = 0; unsigned char *dOut[2] = { 0, 0 };
-  SqWriter *wr = 0; MgBgzfSink *bz = 0; hipStream_t copy = 0;      /* the window's output goes to one of the two: as text to the writer thread, or on the device into the BGZF sink */
+  TsWriter *wr = 0; MgBgzfSink *bz = 0; hipStream_t copy = 0;      /* the window's output goes to one of the two: as text to the writer thread, or on the device into the BGZF sink */
   U64 pending = SQ_NONE;                                  /* the window whose output is still on the device */
   U32 lastByte = 0; U64 bytes = 0;
   double msCopy = 0, msWait = 0, msKernels = 0;
@@ -623,16 +550,16 @@ struct SqPass {                                          /* one walk over the te
         clock_gettime (CLOCK_MONOTONIC, &t0);
         const int rc = mgBgzfSinkAppendDevice (bz, dOut[k & 1], (size_t) at) || (w.spliceCount && mgBgzfSinkAppendRun (bz, '!', w.spliceCount))
                        || mgBgzfSinkAppendDevice (bz, dOut[k & 1] + at, (size_t) (w.outBytes - at));
-        clock_gettime (CLOCK_MONOTONIC, &t1); msCopy += sqMs (t0, t1);
+        clock_gettime (CLOCK_MONOTONIC, &t1); msCopy += tsMs (t0, t1);
         return rc ? -1 : 0;
       }
     clock_gettime (CLOCK_MONOTONIC, &t0);
-    SqWriter::Block &b = wr->acquire ();
+    TsWriter::Block &b = wr->acquire ();
     clock_gettime (CLOCK_MONOTONIC, &t1);
     if (w.outBytes && (hipMemcpyAsync (b.p, dOut[k & 1], w.outBytes, hipMemcpyDeviceToHost, copy) != hipSuccess || hipStreamSynchronize (copy) != hipSuccess))
       { b.n = 0; b.spliceCount = 0; wr->submit (b); return mgHipFail (hipGetLastError (), "mgSeqConvert"), -1; }
     clock_gettime (CLOCK_MONOTONIC, &t2);
-    msWait += sqMs (t0, t1); msCopy += sqMs (t1, t2);
+    msWait += tsMs (t0, t1); msCopy += tsMs (t1, t2);
     b.n = (size_t) w.outBytes; b.spliceAt = w.spliceAt; b.spliceCount = w.spliceCount;
     wr->submit (b);
     return 0;
@@ -677,7 +604,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, MgBgzfSink *bz, SqS
 {
   MgDevScratch scratch ("mgSeqConvert");
   SqPass p; p.g = g; p.write = out != 0 || bz != 0; p.bz = bz;
-  const size_t hint = (size_t) src.size < SQ_WINDOW_HINT ? (size_t) src.size : SQ_WINDOW_HINT, window = mgTextWindowBytes (hint);
+  const size_t hint = (size_t) src.size < TS_WINDOW_HINT ? (size_t) src.size : TS_WINDOW_HINT, window = mgTextWindowBytes (hint);
   p.tilesCap = window / SQ_TILE + 2;
   U64 *block = 0;
   if (scratch.get (&p.dState, 1) || scratch.get (&p.dWin, 2) || scratch.get (&block, (size_t) SQ_TILE_ARRAYS * p.tilesCap)) return -1;
@@ -694,7 +621,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, MgBgzfSink *bz, SqS
   memset (S, 0, sizeof (*S));
   S->errLine = S->errOff = S->badOff = S->nulOff = S->badLine = S->stopStart = S->stopEnd = SQ_NONE;
   if (hipMemcpy (p.dState, S, sizeof (*S), hipMemcpyHostToDevice) != hipSuccess) { scratch.fail (); return -1; }
-  SqWriter wr;
+  TsWriter wr;
   if (p.write)
     { p.outCap = sqOutCap (window, g.fastq != 0, g.outFastq != 0);
       if (scratch.get (&p.dOut[0], p.outCap) || scratch.get (&p.dOut[1], p.outCap)) return -1;
@@ -716,7 +643,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, MgBgzfSink *bz, SqS
       (void) hipStreamDestroy (p.copy);
       gSeqMs[3] += p.msCopy; gSeqMs[4] += p.msWait; gSeqMs[5] += wr.msWrite;
     }
-  clock_gettime (CLOCK_MONOTONIC, &t1); gSeqMs[p.write ? 1 : 0] += sqMs (t0, t1);
+  clock_gettime (CLOCK_MONOTONIC, &t1); gSeqMs[p.write ? 1 : 0] += tsMs (t0, t1);
   if (p.typeError) { mgSetError ("sequence file %s is neither FASTA nor FASTQ text", src.name ? src.name : "(text)"); return -1; }
   if (rc) return -1;
   if (!nWindows) { mgSetError ("sequence file %s unreadable or empty", src.name ? src.name : "(text)"); return -1; }
@@ -726,60 +653,7 @@ static int sqWalk (CpSource &src, const SqCfg &g, FILE *out, MgBgzfSink *bz, SqS
   return 0;
 }
 
-/* the BGZF sink's packed members: to a page-locked block of the writer thread's */
-static int sqBgzfEmit (void *ctx, const unsigned char *src, size_t n, int onDevice, void *stream)
-{
-  SqWriter *wr = (SqWriter *) ctx;
-  SqWriter::Block &b = wr->acquire ();
-  int rc = 0;
-  b.n = n; b.spliceAt = 0; b.spliceCount = 0;
-  if (!onDevice) memcpy (b.p, src, n);
-  else if (n && (hipMemcpyAsync (b.p, src, n, hipMemcpyDeviceToHost, (hipStream_t) stream) != hipSuccess || hipStreamSynchronize ((hipStream_t) stream) != hipSuccess))
-    { b.n = 0; rc = -1; mgHipFail (hipGetLastError (), "blocked gzip on the device"); }
-  wr->submit (b);
-  return rc;
-}
-
-/* a FILE as a BGZF file: the sink on the device and the writer thread behind it */
-struct SqBgzf {
-  SqWriter wr; MgBgzfSink *sink = 0; bool wrOpen = false;
-  int open (FILE *f, const char *what, U64 textHint)
-  { if (!(sink = mgBgzfSinkOpen (sqBgzfEmit, &wr, what, textHint))) return -1;
-    wrOpen = true;
-    return wr.open (f, mgBgzfSinkEmitMax (sink));
-  }
-  int close (int rc)                                       /* a call that failed leaves the file unfinished: it is removed */
-  { if (sink && mgBgzfSinkClose (sink, !rc) && !rc) rc = -1;
-    sink = 0;
-    if (wrOpen && wr.close () && !rc) { mgSetError ("%s", "blocked gzip on the device: write failed"); rc = -1; }
-    wrOpen = false;
-    return rc;
-  }
-};
-
-/* where the output goes: a FILE of the caller's, or a file that is opened once the text has been judged -- a refusal makes none.  The file is text, text
-   through mgGzipOpenWrite (gz), or BGZF deflated on the device (bgzf) */
-struct SqSink {
-  FILE *f = 0; const char *name = 0; bool gz = false, toStdout = false, opened = false, bgzf = false;
-  SqBgzf bz; U64 textHint = 0;
-  FILE *get ()
-  { if (f || !name) return f;
-    f = gz ? mgGzipOpenWrite (toStdout ? "/dev/stdout" : name) : toStdout ? fdopen (dup (1), "w") : fopen (name, "w");
-    if (f) opened = true; else mgSetError ("failed to open output file %s", name);
-    if (f && bgzf && bz.open (f, "mgSeqConvert", textHint)) { (void) close (-1); return 0; }
-    return f;
-  }
-  MgBgzfSink *device () { return bgzf ? bz.sink : 0; }
-  int close (int rc)                                       /* the file is the call's: closed; none is left if the call failed (nor one from an earlier call: the program would have truncated it) */
-  { if (bgzf) rc = bz.close (rc);
-    if (opened && fclose (f) && !rc) { mgSetError ("failed to write output file %s", name); rc = -1; }
-    if (rc && name && !toStdout) (void) remove (name);
-    if (opened) { f = 0; opened = false; }
-    return rc;
-  }
-};
-
-static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqConvert *res)
+static int sqConvert (CpSource &src, int flags, TsSink &sink, FILE *err, MgSeqConvert *res)
 {
   typedef unsigned long long ull;
   memset (gSeqDiag, 0, sizeof (gSeqDiag)); memset (gSeqMs, 0, sizeof (gSeqMs)); mgInflateDiagReset (); mgGunzipDiagReset ();
@@ -835,7 +709,7 @@ static int sqConvert (CpSource &src, int flags, SqSink &sink, FILE *err, MgSeqCo
             { if (mgBgzfSinkAppendHost (bz, "\n", 1) || (g.outFastq && (mgBgzfSinkAppendHost (bz, "+\n", 2) || mgBgzfSinkAppendRun (bz, '!', len) || mgBgzfSinkAppendHost (bz, "\n", 1)))) return -1; }
           else
             { bool ok = fputc ('\n', out) != EOF;
-              if (ok && g.outFastq) ok = fputs ("+\n", out) != EOF && SqWriter::bangs (out, len) && fputc ('\n', out) != EOF;
+              if (ok && g.outFastq) ok = fputs ("+\n", out) != EOF && TsWriter::bangs (out, len) && fputc ('\n', out) != EOF;
               if (!ok) { mgSetError ("mgSeqConvert: write failed"); return -1; }
             }
         }
@@ -866,7 +740,7 @@ extern "C" int mgSeqConvertText (const char *text, U64 n, int flags, FILE *out, 
   if (!out) { mgSetError ("mgSeqConvertText: no output"); return -1; }
   if (!text || !n) { mgSetError ("sequence text unreadable or empty"); return -1; }
   CpSource src; src.mem = (const unsigned char *) text; src.size = n;
-  SqSink sink; sink.f = out;
+  TsSink sink; sink.f = out;
   const int rc = sqConvert (src, flags, sink, err, res);
   if (!rc && fflush (out)) { mgSetError ("mgSeqConvertText: write failed"); return -1; }
   return rc;
@@ -878,7 +752,7 @@ static int sqConvertFile (const char *inName, const char *outName, int flags, FI
   if (res) memset (res, 0, sizeof (*res));
   if (sqFlags (flags, "mgSeqConvertFile")) return -1;
   if (!inName || !outName) { mgSetError ("mgSeqConvertFile: no file name"); return -1; }
-  SqSink sink; sink.name = outName; sink.bgzf = bgzf;
+  TsSink sink; sink.name = outName; sink.bgzf = bgzf;
   sink.toStdout = !strcmp (outName, "-") || (!bgzf && !strcmp (outName, "-z"));
   size_t len = strlen (outName);
   const bool gzName = !sink.toStdout && len > 3 && !strcmp (outName + len - 3, ".gz"), bgzName = bgzf && !sink.toStdout && len > 4 && !strcmp (outName + len - 4, ".bgz");
@@ -901,115 +775,3 @@ static int sqConvertFile (const char *inName, const char *outName, int flags, FI
 }
 extern "C" int mgSeqConvertFile (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, false); }
 extern "C" int mgSeqConvertFileBgzf (const char *inName, const char *outName, int flags, FILE *err, MgSeqConvert *res) { return sqConvertFile (inName, outName, flags, err, res, true); }
-
-/* `bgzip -d` and `gzip -dc`: a compressed file's text, inflated on the device (mg_bgzfsrc.hip, mg_gzipsrc.hip), through the writer of the second walk above:
-   window k + 1 is inflated while window k crosses to a page-locked block and the block before that is written.  fill: the source's, with the window loop's contract */
-template <class Fill> static int sqInflateFile (const char *what, U64 textHint, const char *outName, Fill fill)
-{
-  SqSink sink; sink.name = outName; sink.toStdout = !strcmp (outName, "-");
-  const size_t window = mgTextWindowBytes ((size_t) (textHint < SQ_WINDOW_HINT ? textHint : SQ_WINDOW_HINT));
-  MgDevScratch scratch (what);
-  unsigned char *dBuf[2] = { 0, 0 };
-  hipStream_t inflate = 0, copy = 0;
-  SqWriter wr; bool wrOpen = false;
-  FILE *out = 0;
-  int rc = -1;
-  do
-    { if (mgEnsureDevice ()) break;
-      if (scratch.get (&dBuf[0], window) || scratch.get (&dBuf[1], window)) break;
-      if (hipStreamCreateWithFlags (&inflate, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags (&copy, hipStreamNonBlocking) != hipSuccess) { scratch.fail (); break; }
-      if (!(out = sink.get ())) break;
-      wrOpen = true;
-      if (wr.open (out, window)) break;
-      SqWriter::Block *pending = 0;
-      U64 off = 0; int more = 1; bool bad = false;
-      for (U64 k = 0 ; more && !bad ; ++k)
-        { size_t n = 0; U32 first, last;
-          if (fill (dBuf[k & 1], window, off, (void *) inflate, &n, &more, &first, &last)) { bad = true; break; }
-          if (pending) { if (hipStreamSynchronize (copy) != hipSuccess) { scratch.fail (); bad = true; pending->n = 0; } wr.submit (*pending); pending = 0; }
-          if (bad || !n) break;
-          SqWriter::Block &b = wr.acquire ();
-          b.n = n; b.spliceAt = 0; b.spliceCount = 0;
-          if (hipMemcpyAsync (b.p, dBuf[k & 1], n, hipMemcpyDeviceToHost, copy) != hipSuccess) { scratch.fail (); b.n = 0; wr.submit (b); bad = true; break; }
-          pending = &b; off += n;
-        }
-      if (pending) { if (hipStreamSynchronize (copy) != hipSuccess) { scratch.fail (); bad = true; pending->n = 0; } wr.submit (*pending); }
-      if (!bad) rc = 0;
-    }
-  while (0);
-  if (wrOpen && wr.close () && !rc) { mgSetError ("%s: write failed", what); rc = -1; }
-  if (inflate) { (void) hipStreamSynchronize (inflate); (void) hipStreamDestroy (inflate); }
-  if (copy) { (void) hipStreamSynchronize (copy); (void) hipStreamDestroy (copy); }
-  return sink.close (rc);
-}
-extern "C" int mgBgzfInflateFile (const char *inName, const char *outName, FILE *err)
-{
-  (void) err;
-  mgInflateDiagReset ();
-  if (!inName || !outName) { mgSetError ("mgBgzfInflateFile: no file name"); return -1; }
-  const int fd = ::open (inName, O_RDONLY);
-  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
-  struct stat sb;
-  MgBgzfSrc *bz = 0;
-  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgBgzfSrcOpen (inName, fd, (U64) sb.st_size, &bz) : -2;
-  if (rc) { ::close (fd); return rc; }
-  rc = sqInflateFile ("mgBgzfInflateFile", mgBgzfSrcTextBytes (bz), outName, [&] (unsigned char *d, size_t cap, U64 off, void *st, size_t *n, int *more, U32 *first, U32 *last)
-                      { return mgBgzfSrcFill (bz, d, cap, off, ~(U64) 0, st, n, more, first, last); });
-  mgBgzfSrcClose (bz); ::close (fd);
-  return rc;
-}
-/* `gzip -dc`: 0, -2 = not ordinary gzip (or more than the device keeps; nothing is written), -1 with mgLastError () and no output file left.  Any size is taken */
-extern "C" int mgGzipInflateFile (const char *inName, const char *outName, FILE *err)
-{
-  (void) err;
-  mgInflateDiagReset (); mgGunzipDiagReset ();
-  if (!inName || !outName) { mgSetError ("mgGzipInflateFile: no file name"); return -1; }
-  const int fd = ::open (inName, O_RDONLY);
-  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
-  struct stat sb;
-  MgGzipSrc *gz = 0;
-  int rc = fstat (fd, &sb) == 0 && S_ISREG (sb.st_mode) && sb.st_size > 0 ? mgGzipSrcOpen (inName, fd, (U64) sb.st_size, 1, &gz) : -2;
-  if (rc) { ::close (fd); return rc; }
-  rc = sqInflateFile ("mgGzipInflateFile", mgGzipSrcSizeHint (gz), outName, [&] (unsigned char *d, size_t cap, U64 off, void *st, size_t *n, int *more, U32 *first, U32 *last)
-                      { return mgGzipSrcFill (gz, d, cap, off, ~(U64) 0, st, n, more, first, last); });
-  mgGzipSrcClose (gz); ::close (fd);
-  return rc;
-}
-
-/* `bgzip`: any regular file as BGZF.  The file is read by the parser's team of readers into page-locked pieces, a piece crosses the link as it is, and the
-   sink (mg_bgzfsink.hip) deflates it on the device; only the compressed file comes back, to the writer thread of the second walk above */
-#define SQ_BGZIP_PIECE ((size_t) 16 << 20)
-extern "C" int mgBgzfDeflateFile (const char *inName, const char *outName, FILE *err)
-{
-  (void) err;
-  mgDeflateDiagReset ();
-  if (!inName || !outName) { mgSetError ("mgBgzfDeflateFile: no file name"); return -1; }
-  const int fd = ::open (inName, O_RDONLY);
-  if (fd < 0) { mgSetError ("failed to open file %s", inName); return -1; }
-  struct stat sb;
-  if (fstat (fd, &sb) || !S_ISREG (sb.st_mode)) { ::close (fd); mgSetError ("mgBgzfDeflateFile: %s is not a regular file", inName); return -1; }
-  const U64 size = (U64) sb.st_size;
-  const size_t piece = size < SQ_BGZIP_PIECE ? (size_t) size : SQ_BGZIP_PIECE;
-  SqSink sink; sink.name = outName; sink.toStdout = !strcmp (outName, "-"); sink.bgzf = true; sink.textHint = size ? size : 1;
-  MgDevScratch scratch ("mgBgzfDeflateFile");
-  unsigned char *dPiece = 0, *hPiece = 0;
-  int rc = -1;
-  do
-    { if (mgEnsureDevice ()) break;
-      if (piece && scratch.get (&dPiece, piece)) break;
-      if (piece && !(hPiece = (unsigned char *) mgPinnedAlloc (piece))) { mgSetError ("mgBgzfDeflateFile: no page-locked memory"); break; }
-      if (!sink.get ()) break;
-      bool bad = false;
-      for (U64 off = 0 ; off < size && !bad ; off += piece)
-        { const size_t n = size - off < piece ? (size_t) (size - off) : piece;
-          if (mgTextReadParallel (fd, hPiece, n, (int64_t) off)) { mgSetError ("failed to read file %s", inName); bad = true; }
-          else if (hipMemcpy (dPiece, hPiece, n, hipMemcpyHostToDevice) != hipSuccess) { scratch.fail (); bad = true; }
-          else if (mgBgzfSinkAppendDevice (sink.device (), dPiece, n)) bad = true;
-        }
-      if (!bad) rc = 0;
-    }
-  while (0);
-  mgPinnedFree (hPiece);
-  ::close (fd);
-  return sink.close (rc);
-}

@@ -1,4 +1,4 @@
-/* mg_textsrc.h — where the text of a walk over mgTextStreamWindows comes from (mg_composition.hip, mg_seqconvert.hip): the `src` and `fill` of that call */
+/* mg_textsrc.h — where the text of a walk over mgTextStreamWindows comes from (mg_composition.hip, mg_seqconvert.hip; mg_filecodec.hip for its two device sources): the `src` and `fill` of that call */
 #ifndef MG_TEXTSRC_H
 #define MG_TEXTSRC_H
 #include <fcntl.h>
