@@ -128,7 +128,7 @@ extern "C" int mgBgzfSrcEdges (MgBgzfSrc *s, unsigned char *first, unsigned char
 }
 
 /* the first byte of a file's text: the file's own first byte, or for a file that starts with blocked-gzip members the first byte of the first
-   non-empty one, inflated on the host; -1: none to be had (for a caller that picks its path by the format's first letter: mg_callers.c) */
+   non-empty one, inflated on the host; -1: none to be had (for a caller that picks its path by the format's first letter: mg_seqfiles.c) */
 extern "C" int mgTextFirstByte (const char *filename)
 {
   const int fd = open (filename, O_RDONLY);

@@ -129,7 +129,7 @@ __device__ __forceinline__ void mgChainBegin (MgChainState &st, U32 ns)
 
 /* a LANE per read.  (A wave per long read -- 64 records a fetch, the walk on wave-uniform values -- was built and measured: no
    faster.  What a batch's chaining costs is the serial walk of its LONGEST read, 3000 dependent steps of ~0.15 us for 200 kb,
-   however the steps are issued; the file entry point therefore makes few, large batches of long reads: mg_seqio.c.) */
+   however the steps are issued; the file entry point therefore makes few, large batches of long reads: mg_seqfiles.c.) */
 #define MG_CHAIN_AHEAD 16
 __global__ __launch_bounds__ (256)
 void mgChainKernel (const uint4 *__restrict__ rec, const U32 *__restrict__ seedPos,

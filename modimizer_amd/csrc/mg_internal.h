@@ -4,6 +4,8 @@
 #define MG_INTERNAL_H
 #include "modgpu.h"
 #include "mg_knobs.h"
+#include <stdlib.h>
+#include <time.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -35,9 +37,9 @@ int  mgTextParseFileDevice (const char *filename, char **basesOut, int64_t **off
    offsets) with its ids (id r = idBytes + idOff[r], 0-terminated: seqio.c:303-304) to fn; a non-zero return of fn ends the file */
 typedef int (*MgTextBatchFn) (void *ctx, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads, const char *idBytes, const U64 *idOff, void *stream);
 int  mgTextForEachBatchDevice (const char *filename, MgTextBatchFn fn, void *ctx, U64 batchBases, U64 batchRecs, U64 *nSeq, U64 *totLen, U64 *resumeOff, U64 *resumeLine);   /* a batch is handed on (at a window's end) once it holds batchBases bases (0: the default, 1 Gbp) and batchRecs records, or the default's bases whatever the records */
-/* the device halves of the modmap callers (mg_callers.c): a batch that is already on the device */
+/* the device halves of the modmap callers (mg_query.c, mg_reference.c): a batch that is already on the device */
 int  mgQueryProcessDevice (MgReference *ref, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, int nReads, const char **names, FILE *out);
-/* mgQueryFile's batches: Push runs the device half now, one writer thread formats and writes the lines, in order, behind it */
+/* mgQueryFile's batches (mg_queryout.c): Push runs the device half now, a formatter and a writer thread put the lines out, in order, behind it */
 typedef struct MgQueryPipe MgQueryPipe;
 MgQueryPipe *mgQueryPipeOpen (MgReference *ref, FILE *out);
 int  mgQueryPipePush (MgQueryPipe *p, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, int nReads, const char *idBytes, const U64 *idOff);
@@ -45,13 +47,23 @@ void mgQueryPipeClose (MgQueryPipe *p);                    /* returns when every
 int  mgReferenceAddDevice (MgReference *ref, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, int nSeq, const char **names, bool isAdd);
 void mgReferenceFinish (MgReference *ref, U64 totLen, bool isAdd, FILE *out);
 void mgTextReleaseBuffers (void);
-/* shared by the caller mirrors (mg_callers.c, the read set's files): not exported */
+/* shared by the caller mirrors (mg_callers.c and the files split off it, the read set's files): not exported */
 #define MG_HIDDEN __attribute__ ((visibility ("hidden")))
+static inline void mgFatal (const char *what) { fprintf (stderr, "FATAL ERROR: %s: %s\n", what, mgLastError ()); exit (-1); }
+static inline double mgMsBetween (const struct timespec *a, const struct timespec *b)      /* milliseconds from *a to *b */
+{ return (b->tv_sec - a->tv_sec) * 1e3 + (b->tv_nsec - a->tv_nsec) * 1e-6; }
+/* the ids of a device batch (id r = idBytes + idOff[r]) as the pointer array the callers take, into p[0 .. n) */
+static inline void mgIdPointers (const char **p, const char *idBytes, const U64 *idOff, size_t n)
+{ for (size_t i = 0 ; i < n ; ++i) p[i] = idBytes + idOff[i]; }
 typedef struct { void *dPacked, *dOff; U64 total; U32 nReads; } MgDevBatch;     /* host bytes -> 2-bit words in HBM */
 /* a file through the device text parser (devFn per batch: batchBases, batchRecs as mgTextForEachBatchDevice takes them), and where that one leaves it
    (-2, -3 above) through the host parser, from the start or from the record it stopped at: hostFn per batch, 0: every host batch is uploaded and handed
    to devFn with its ids.  Returns what the last leg returned */
 MG_HIDDEN int mgSeqWalkFile (const char *filename, MgTextBatchFn devFn, int (*hostFn) (MgSeqBatch *, void *), void *ctx, U64 batchBases, U64 batchRecs, U64 *nSeq, U64 *totLen);
+/* the host parser's batch loop (mg_seqio.c) for the file entry points (mg_seqfiles.c): every batch of the file through fn, the next one parsed while fn
+   works on this one; from a record that starts at byte startOff of the text, line startLine, record startSeq + 1 (0 / 1 / 0: the whole file).  -1: no such
+   file for this parser, else what fn returned last */
+MG_HIDDEN int mgSeqForEachBatchFrom (const char *filename, size_t startOff, U64 startLine, U64 startSeq, int (*fn) (MgSeqBatch *, void *), void *ctx);
 MG_HIDDEN void mgBatchUpload (MgDevBatch *b, const char *bases, const int64_t *offsets, int nReads);
 MG_HIDDEN void mgBatchFree (MgDevBatch *b);
 MG_HIDDEN FILE *mgTagOpen (const char *root, const char *tag, const char *mode);
@@ -80,6 +92,12 @@ typedef struct { U32 pos0, posN, id0, off0, offN; int n1, n2; U32 span; } MgChai
 MG_HIDDEN int  mgChainQueryDevice (const MgReference *ref, const U32 *dPacked, U64 totalBases, const U64 *dReadOffsets, U32 nReads,
                                    MgChainQ *hQ, MgChainM **hMOut, U32 maxM, int hQPinned);
 MG_HIDDEN void mgChainForget (const MgReference *ref);
+#define MG_QUERY_MAXM 16                               /* "M" blocks of a read that the chain kernel keeps; a read with more takes the long way (mg_query.c) */
+/* the "Q" / "M" lines of a batch whose tallies and blocks are on the host (mg_queryout.c): formatted by a team of threads and written to out, in order;
+   *msFormat, *msWrite are added to.  Returns the team's size */
+MG_HIDDEN int  mgQueryLinesOut (const MgReference *ref, const MgChainQ *q, const MgChainM *m, const int64_t *offsets, int nReads, const char **names, FILE *out,
+                                double *msFormat, double *msWrite);
+MG_HIDDEN int  mgQueryVerbose (void);                  /* modmap's -v (mgSetVerbose, mg_query.c): every batch takes the long way */
 /* the Reference built on the device (mg_refpack.hip): a batch's seeds appended (modmap.c:110-117), then copy classes + referencePack (modmap.c:125-129,74-91) into the caller's arrays */
 MG_HIDDEN MgStatus mgRefBuildAppend (MgReference *ref, const U32 *dIx, const U32 *dPosF, const U32 *dRid, U64 n, U32 idBase, U32 *appended);
 MG_HIDDEN int mgRefPackedTallies (MgReference *ref, U32 tallies[3]);      /* 1: packed on the device, nothing added since */
@@ -88,7 +106,7 @@ MG_HIDDEN void *mgPinnedAlloc (size_t bytes);          /* page-locked host memor
 MG_HIDDEN void mgPinnedFree (void *p);
 MG_HIDDEN MgStatus mgCopyOutPinned (void *dstPinned, const void *srcDev, size_t bytes, void *stream);   /* device -> page-locked block by a kernel (not the copy engine), waited for */
 MG_HIDDEN void mgChainReleaseBuffers (void);
-MG_HIDDEN void mgQueryReleaseBuffers (void);           /* the query path's cached buffers: page-locked blocks (mg_callers.c), device arrays (mg_chain.hip) */
+MG_HIDDEN void mgQueryReleaseBuffers (void);           /* the query path's cached buffers: page-locked blocks and line buffers (mg_queryout.c), device arrays (mg_chain.hip) */
 MG_HIDDEN void mgChainScratchKeep (int on);      /* 1: the query's device arrays stay allocated between batches; 0: ends that (and frees them) */
 /* a hit of a read: its mod, bit 31 set for forward orientation (modasm.c:22) */
 #define MG_TOPBIT  0x80000000u
@@ -173,7 +191,7 @@ MG_HIDDEN int mgRdnaN200Device (const MgRsView *v, const U8 *hQual, int *hN200, 
 MG_HIDDEN int mgRdnaTestModsDevice (const MgRsView *S, const U32 *tested, U32 nTested, const U32 *partner, U32 nPartner, U32 batch, int wantCells,
                                     int *res3, int *badLD, int *splitLD, U64 *cellStart, MgLdCell **cells, U64 diag[4], U32 grid[4], U32 *badMod);
 MG_HIDDEN MgStatus mgModsetAdoptDepthDevice (Modset *ms, const U16 *dDepth16);      /* the device table's depth copy = dDepth16[0 .. max] (mg_modsetdev.hip) */
-/* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_callers.c) */
+/* modutils' reports (mg_report.hip): text formatted on the device, copied out and written in order by a writer thread (mg_textout.c) */
 typedef struct MgTextOut MgTextOut;
 MG_HIDDEN MgTextOut *mgTextOutOpen (FILE *out);
 MG_HIDDEN int  mgTextOutFromDevice (MgTextOut *w, const void *dSrc, size_t bytes);   /* copied into page-locked blocks now, written behind the caller, in order */

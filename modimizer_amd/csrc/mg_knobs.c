@@ -86,6 +86,16 @@ static void cpuBudgetOnce (void)
 }
 int mgCpuBudget (void) { pthread_once (&gCpuOnce, cpuBudgetOnce); return gCpuBudget; }
 
+void mgTeamRun (int n, void *(*fn) (void *), void *arg, size_t stride)
+{
+  pthread_t th[32]; int started[32];
+  if (n > 32) n = 32;
+  for (int i = 1 ; i < n ; ++i) started[i] = pthread_create (&th[i], 0, fn, (char *) arg + (size_t) i * stride) == 0;
+  fn (arg);
+  for (int i = 1 ; i < n ; ++i) if (!started[i]) fn ((char *) arg + (size_t) i * stride);
+  for (int i = 1 ; i < n ; ++i) if (started[i]) pthread_join (th[i], 0);
+}
+
 /* arrays of hundreds of megabytes that a transfer from the device writes end to end: with 4 KiB pages that is a page fault per
    4 KiB (a million for a 4 GiB index[]), with transparent huge pages one per 2 MiB.  A hint, not a requirement (the kernel's THP
    mode decides); the memory stays what malloc () returned, free ()-able as the reference's callers free it. */

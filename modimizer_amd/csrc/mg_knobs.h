@@ -82,6 +82,11 @@ void mgReloadKnobs (void);
    number the host-side thread teams size themselves by (worked out once) */
 int mgCpuBudget (void);
 #include <stddef.h>
+/* a team of n threads (32 at most) over fn: thread i gets (char *) arg + i * stride -- stride 0: one shared job the threads take work from.
+   Share 0 runs on the caller, and so does the share of a thread that could not be started (for a shared job: one more worker that finds
+   nothing left); returns when all are done.  A larger n is cut to 32: with a stride the shares past 32 would not run, so such a caller
+   asks for 32 at most.  Not exported */
+__attribute__ ((visibility ("hidden"))) void mgTeamRun (int n, void *(*fn) (void *), void *arg, size_t stride);
 void mgHugeHint (void *p, size_t n);      /* madvise (MADV_HUGEPAGE) on the whole pages of a large malloc ()ed block */
 void *mgAllocBig (size_t n);              /* malloc () + that hint */
 #ifdef __cplusplus

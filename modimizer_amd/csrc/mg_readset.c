@@ -19,9 +19,6 @@
 static double rsNowMs (void) { struct timespec t; clock_gettime (CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 #define RS_LAP(what) do { if (lapOn) { const double q_ = rsNowMs (); fprintf (stderr, "readset: %s %.2f ms\n", what, q_ - lap); lap = q_; } } while (0)      /* dev: MODGPU_SEED_TIMING=1 */
 
-static void fatal (const char *what)
-{ fprintf (stderr, "FATAL ERROR: %s: %s\n", what, mgLastError ()); exit (-1); }
-
 MgReadset *mgReadsetCreate (Modset *ms)                            /* modasm.c:90-98 */
 {
   if (ms->max >= TOPBIT) { fprintf (stderr, "FATAL ERROR: too many entries in modset\n"); exit (-1); }   /* modasm.c:1562 */
@@ -68,12 +65,12 @@ static void reserveReads (MgReadset *rs, int more)
 static U32 *gDepthAccum (MgReadset *rs)
 {
   U32 *d = 0;
-  if (mgReadsetDevBegin (rs, rs->ms->max, &d)) fatal ("read set on the device");
+  if (mgReadsetDevBegin (rs, rs->ms->max, &d)) mgFatal ("read set on the device");
   return d;
 }
 static U32 *readsetBegin (MgReadset *rs)
 {
-  if (modsetSyncToHost (rs->ms, 0)) fatal ("modsetSyncToHost");
+  if (modsetSyncToHost (rs->ms, 0)) mgFatal ("modsetSyncToHost");
   return gDepthAccum (rs);
 }
 
@@ -85,12 +82,12 @@ static void readsetAddBatchDevice (MgReadset *rs, U32 *dDepth, const void *dPack
   const int lapOn = mgKnobs ()->seedTiming == 1; double lap = lapOn ? rsNowMs () : 0;
   reserveReads (rs, nReads);
   int64_t *offsets = (int64_t *) malloc (((size_t) nReads + 1) * sizeof (int64_t));
-  if (mgMemcpyD2H (offsets, dOff, ((size_t) nReads + 1) * 8, 0)) fatal ("D2H");
+  if (mgMemcpyD2H (offsets, dOff, ((size_t) nReads + 1) * 8, 0)) mgFatal ("D2H");
   /* scan, lookup, hit lists, distances and counts on the device (mg_chain.hip) */
   U64 *hStart = (U64 *) malloc (((size_t) nReads + 1) * sizeof (U64));
   U32 *hMiss = (U32 *) malloc (((size_t) nReads + 1) * sizeof (U32));
   U32 *dHit = 0; U16 *dDx = 0;
-  if (mgReadsetSeedsDevice (ms, (const U32 *) dPacked, total, (const U64 *) dOff, (U32) nReads, hStart, hMiss, &dHit, &dDx, dDepth)) fatal ("read scan");
+  if (mgReadsetSeedsDevice (ms, (const U32 *) dPacked, total, (const U64 *) dOff, (U32) nReads, hStart, hMiss, &dHit, &dDx, dDepth)) mgFatal ("read scan");
   const U64 n = hStart[nReads];
   RS_LAP ("batch: scan + lookups + hit lists");
   if (rs->totHit + n + 1 > rs->capHit)
@@ -100,7 +97,7 @@ static void readsetAddBatchDevice (MgReadset *rs, U32 *dDepth, const void *dPack
       if (!rs->hit || !rs->dx) { fprintf (stderr, "FATAL ERROR: out of memory\n"); exit (-1); }
       mgHugeHint (rs->hit, rs->capHit * sizeof (U32)); mgHugeHint (rs->dx, rs->capHit * sizeof (U16));      /* the lists arrive into fresh pages: one fault per 2 MiB, not per 4 KiB */
     }
-  if (n && (mgCopyD2HBig (rs->hit + rs->totHit, dHit, (size_t) n * sizeof (U32)) || mgCopyD2HBig (rs->dx + rs->totHit, dDx, (size_t) n * sizeof (U16)))) fatal ("hit lists");
+  if (n && (mgCopyD2HBig (rs->hit + rs->totHit, dHit, (size_t) n * sizeof (U32)) || mgCopyD2HBig (rs->dx + rs->totHit, dDx, (size_t) n * sizeof (U16)))) mgFatal ("hit lists");
   RS_LAP ("batch: hit lists to the host");
   mgReadsetDevAppendHits (rs, dHit, n);              /* (the inverse lists are made from them on the device when the file is done) */
   mgDeviceFree (dHit); mgDeviceFree (dDx);
@@ -160,7 +157,7 @@ static void readsetFinish (MgReadset *rs, U64 hitsBefore)
   mgHugeHint (rs->invStart, ((size_t) ms->max + 2) * sizeof (U64));
   MgRsView v; mgRsViewOf (rs, &v);
   if (mgReadsetFinishDevice (rs, ms, &v, ms->depth, rs->invStart, &rs->invSpace, (int *) rs->nCopy))
-    fatal ("read set on the device");                  /* (the device table's depth copy was set there too) */
+    mgFatal ("read set on the device");                  /* (the device table's depth copy was set there too) */
 }
 
 int mgReadsetRead (MgReadset *rs, const char *bases, const int64_t *offsets, int nReads)

@@ -11,7 +11,7 @@
  * gathered from the folded view of each set (host depth plus pending device counts, saturated: mgHookDeviceView), and the text itself
  * is made here, by one formatter that serves both reports.  It takes a chunk of at most MG_TEXT_CHUNK lines in three passes: every
  * line's length (one workgroup sums 1024 of them), an exclusive scan of the workgroup sums, and the bytes, each line written by one
- * lane at its offset.  A chunk's text is copied into page-locked blocks and written, in order, by a writer thread (mg_callers.c) while
+ * lane at its offset.  A chunk's text is copied into page-locked blocks and written, in order, by a writer thread (mg_textout.c) while
  * the device goes on with the next chunk, so the memory a report takes does not grow with the set.
  *
  * Integer to text: digit counts by comparisons, decimal digits by a multiply-high with the reciprocal of 10 (exact for every 32-bit

@@ -134,9 +134,6 @@ static int threadCount (void)
   return (int) n;
 }
 
-static void runPool (int n, void *(*fn) (void *), void *arg);
-static int threadCount (void);
-
 /* ---- blocked gzip (BGZF: bgzip, htslib) ----
  * A gzip file made of members of at most 64 KiB, each carrying its compressed length in a 'BC' extra
  * field and, like every gzip member, its CRC and uncompressed length at its end.  zlib reads such a file
@@ -221,7 +218,7 @@ static size_t bgzfRead (MgSeqReader *r, char *dst, size_t room)
         { BgJob j; j.src = c; j.dst = dst; j.blocks = blocks; j.n = n; j.next = 0; j.bad = 0;
           int nt = r->nThreads > 0 ? r->nThreads : threadCount ();
           if ((size_t) nt > n / 16 + 1) nt = (int) (n / 16 + 1);
-          runPool (nt, bgzfWorker, &j);
+          mgTeamRun (nt, bgzfWorker, &j, 0);
           if (j.bad) { fprintf (stderr, "FATAL ERROR: corrupt BGZF block near file offset %zu\n", r->bgzfOff); exit (-1); }
         }
       free (blocks);
@@ -268,11 +265,8 @@ static void *readWorker (void *arg)
 static size_t readParallel (MgSeqReader *r, char *dst, size_t n)
 {
   ReadJob j; j.fd = r->fd; j.dst = dst; j.fileOff = r->consumed; j.n = n; j.slice = (size_t) 8 << 20; j.next = 0; j.got = 0;
-  pthread_t th[32]; int started[32];
   int nt = r->nThreads; if ((size_t) nt > n / j.slice + 1) nt = (int) (n / j.slice + 1);
-  for (int i = 1 ; i < nt ; ++i) started[i] = pthread_create (&th[i], 0, readWorker, &j) == 0;
-  readWorker (&j);
-  for (int i = 1 ; i < nt ; ++i) if (started[i]) pthread_join (th[i], 0);
+  mgTeamRun (nt, readWorker, &j, 0);
   r->consumed += j.got;
   (void) lseek (r->fd, (off_t) r->consumed, SEEK_SET);
   return j.got;
@@ -453,11 +447,7 @@ static size_t findFastaStarts (MgSeqReader *r, size_t **startsOut)
   StartJob j; j.buf = r->buf; j.lo = r->pos; j.hi = r->len; j.slice = (size_t) 4 << 20; j.next = 0;
   j.nSlices = (j.hi - j.lo + j.slice - 1) / j.slice;
   j.found = (size_t **) calloc (j.nSlices + 1, sizeof (size_t *)); j.nFound = (size_t *) calloc (j.nSlices + 1, sizeof (size_t));
-  pthread_t th[32]; int started[32];
-  int nt = r->nThreads < (int) j.nSlices ? r->nThreads : (int) j.nSlices; if (nt < 1) nt = 1;
-  for (int i = 1 ; i < nt ; ++i) started[i] = pthread_create (&th[i], 0, startWorker, &j) == 0;
-  startWorker (&j);
-  for (int i = 1 ; i < nt ; ++i) if (started[i]) pthread_join (th[i], 0);
+  mgTeamRun (r->nThreads < (int) j.nSlices ? r->nThreads : (int) j.nSlices, startWorker, &j, 0);
   size_t n = 0;
   for (size_t k = 0 ; k < j.nSlices ; ++k) n += j.nFound[k];
   size_t *starts = (size_t *) malloc ((n + 1) * sizeof (size_t)), at = 0;
@@ -518,15 +508,6 @@ static int cutFastq (MgSeqReader *r, size_t at, RawRec *rec, U64 line)
  * consecutive lines, so every record can be delimited and checked on its own.  FASTA: the record
  * starts are known (findFastaStarts), a record runs up to the next start.  What the pool cannot
  * decide (the last, possibly unfinished, record of the window) is left to cutFasta / cutFastq. */
-static void runPool (int n, void *(*fn) (void *), void *arg)
-{
-  pthread_t th[32]; int started[32];
-  if (n > 32) n = 32;
-  for (int i = 1 ; i < n ; ++i) started[i] = pthread_create (&th[i], 0, fn, arg) == 0;
-  fn (arg);
-  for (int i = 1 ; i < n ; ++i) if (started[i]) pthread_join (th[i], 0);
-}
-
 typedef struct { const char *buf; size_t lo, hi, slice, nSlices, next; U32 **found; size_t *nFound, *prefix; } LineJob;
 static void *lineWorker (void *arg)
 {
@@ -632,7 +613,7 @@ static size_t cutByPool (MgSeqReader *r, int64_t maxBases, const size_t *starts,
       lj.nSlices = (lj.hi - lj.lo + lj.slice - 1) / lj.slice;
       lj.found = (U32 **) calloc (lj.nSlices, sizeof (U32 *)); lj.nFound = (size_t *) calloc (lj.nSlices, sizeof (size_t));
       lj.prefix = (size_t *) calloc (lj.nSlices + 1, sizeof (size_t));
-      runPool (r->nThreads < (int) lj.nSlices ? r->nThreads : (int) lj.nSlices, lineWorker, &lj);
+      mgTeamRun (r->nThreads < (int) lj.nSlices ? r->nThreads : (int) lj.nSlices, lineWorker, &lj, 0);
       for (size_t k = 0 ; k < lj.nSlices ; ++k) lj.prefix[k + 1] = lj.prefix[k] + lj.nFound[k];
       cj.lines = &lj; cj.nCand = lj.prefix[lj.nSlices] / 4;
     }
@@ -646,7 +627,7 @@ static size_t cutByPool (MgSeqReader *r, int64_t maxBases, const size_t *starts,
     { RawRec *cand = (RawRec *) malloc (cj.nCand * sizeof (RawRec));
       cj.recs = cand; cj.grain = cj.nCand / ((size_t) r->nThreads * 16) + 1;
       pthread_mutex_init (&cj.mu, 0);
-      runPool (r->nThreads, cutWorker, &cj);
+      mgTeamRun (r->nThreads, cutWorker, &cj, 0);
       pthread_mutex_destroy (&cj.mu);
       while (taken < cj.nCand && (int64_t) *rawSeq < maxBases)
         { if (taken == cj.errRec)
@@ -823,14 +804,7 @@ static void runJob (Job *j, int nThreads)
 {
   j->next = 0;
   j->grain = j->nUnits / ((size_t) nThreads * 16) + 1;
-  if (nThreads > 1 && j->nUnits > 1)
-    { pthread_t th[32]; int started[32];
-      int n = nThreads < (int) j->nUnits ? nThreads : (int) j->nUnits;
-      for (int i = 1 ; i < n ; ++i) started[i] = pthread_create (&th[i], 0, worker, j) == 0;
-      worker (j);
-      for (int i = 1 ; i < n ; ++i) if (started[i]) pthread_join (th[i], 0);
-    }
-  else worker (j);
+  mgTeamRun ((size_t) nThreads < j->nUnits ? nThreads : (int) j->nUnits, worker, j, 0);
 }
 
 /* ---- per-record bookkeeping by the pool ---- */
@@ -948,7 +922,7 @@ int mgSeqNextBatch (MgSeqReader *r, int64_t maxBases, MgSeqBatch *out)
   if (nRec < 4096) bk.nRuns = 1;
   bk.run = (BookRun *) calloc (bk.nRuns + 1, sizeof (BookRun));
   const int bookThreads = bk.nRuns > 1 ? r->nThreads : 1;
-  bk.phase = 0; bk.next = 0; runPool (bookThreads, bookWorker, &bk);
+  bk.phase = 0; bk.next = 0; mgTeamRun (bookThreads, bookWorker, &bk, 0);
   size_t nUnits = 0, nameBytes = 0;
   for (size_t c = 0 ; c < bk.nRuns ; ++c)
     { size_t nu = bk.run[c].units, nb = bk.run[c].nameBytes;
@@ -962,19 +936,19 @@ int mgSeqNextBatch (MgSeqReader *r, int64_t maxBases, MgSeqBatch *out)
   size_t *unitDst = (size_t *) malloc ((nUnits ? nUnits : 1) * sizeof (size_t));
   bk.units = units; bk.names = out->names; bk.offsets = out->offsets; bk.unitDst = unitDst;
   bk.nameArena = (char *) malloc (nameBytes ? nameBytes : 1);    /* one block for all ids (names[0] is its start), filled by the pool with the bases */
-  bk.phase = 1; bk.next = 0; runPool (bookThreads, bookWorker, &bk);
+  bk.phase = 1; bk.next = 0; mgTeamRun (bookThreads, bookWorker, &bk, 0);
   Job j; memset (&j, 0, sizeof (j));
   j.raw = r->buf; j.units = units; j.nUnits = nUnits; j.isFastq = r->isFastq;
   j.phase = 0;
   if (!r->isFastq) runJob (&j, r->nThreads);                     /* a FASTQ line keeps every byte: nothing to count */
   TIMING (2, "count");
 
-  bk.phase = 2; bk.next = 0; runPool (bookThreads, bookWorker, &bk);
+  bk.phase = 2; bk.next = 0; mgTeamRun (bookThreads, bookWorker, &bk, 0);
   size_t total = 0;
   for (size_t c = 0 ; c < bk.nRuns ; ++c)
     { size_t nb = bk.run[c].bases; bk.run[c].bases = total; total += nb; line += bk.run[c].lines; }
   if (!r->isFastq) line += nRec;                                 /* the header lines */
-  bk.phase = 3; bk.next = 0; runPool (bookThreads, bookWorker, &bk);
+  bk.phase = 3; bk.next = 0; mgTeamRun (bookThreads, bookWorker, &bk, 0);
   free (bk.run);
   out->offsets[nRec] = (int64_t) total;
   out->total = (int64_t) total;
@@ -999,7 +973,7 @@ void mgSeqBatchFree (MgSeqBatch *b)
   memset (b, 0, sizeof (*b));
 }
 
-/* ---- the callers' file loops ---- */
+/* ---- the batch loop of the callers' file loops (mg_seqfiles.c) ---- */
 
 typedef struct { MgSeqReader *r; int64_t maxBases; MgSeqBatch batch; int n; } Prefetch;
 static void *prefetchMain (void *arg) { Prefetch *p = (Prefetch *) arg; p->n = mgSeqNextBatch (p->r, p->maxBases, &p->batch); return 0; }
@@ -1013,7 +987,7 @@ static int64_t batchBases (void)
 }
 
 /* every batch of the file through fn, the next batch being parsed while fn works on this one */
-static int forEachBatchFrom (const char *filename, size_t startOff, U64 startLine, U64 startSeq, int (*fn) (MgSeqBatch *, void *), void *ctx)
+int mgSeqForEachBatchFrom (const char *filename, size_t startOff, U64 startLine, U64 startSeq, int (*fn) (MgSeqBatch *, void *), void *ctx)
 {
   MgSeqReader *r = seqOpenAt (filename, startOff, startLine, startSeq);
   if (!r) return -1;
@@ -1035,194 +1009,4 @@ static int forEachBatchFrom (const char *filename, size_t startOff, U64 startLin
   if (p.n > 0) mgSeqBatchFree (&p.batch);
   mgSeqClose (r);
   return rc;
-}
-
-static int forEachBatch (const char *filename, int (*fn) (MgSeqBatch *, void *), void *ctx)
-{ return forEachBatchFrom (filename, 0, 1, 0, fn, ctx); }
-
-/* a host parser's batch for a callback that takes device batches: uploaded, its ids as one block and their offsets in it (the ids share one block:
-   mgSeqBatchFree) */
-typedef struct { MgTextBatchFn devFn; void *ctx; } WalkUpload;
-static int walkUploadBatch (MgSeqBatch *b, void *v)
-{
-  WalkUpload *u = (WalkUpload *) v;
-  if (b->nSeq <= 0) return 0;
-  U64 *idOff = (U64 *) malloc ((size_t) b->nSeq * 8);
-  if (!idOff) return -1;
-  for (int r = 0 ; r < b->nSeq ; ++r) idOff[r] = (U64) (b->names[r] - b->names[0]);
-  MgDevBatch d; mgBatchUpload (&d, b->bases, b->offsets, b->nSeq);
-  const int rc = u->devFn (u->ctx, (const U32 *) d.dPacked, d.total, (const U64 *) d.dOff, (U32) b->nSeq, b->names[0], idOff, 0);
-  mgBatchFree (&d);
-  free (idOff);
-  return rc;
-}
-
-/* plain FASTA / FASTQ text is parsed on the device (mg_textgpu.hip) and goes to devFn batch by batch; gzip, a last line without its newline (-2): the host
-   parser over the whole file; FASTQ that breaks a rule (-3): the host parser from the first record the device parser has not handed on.  hostFn takes the
-   host parser's batches, 0: each is uploaded and goes to devFn */
-int mgSeqWalkFile (const char *filename, MgTextBatchFn devFn, int (*hostFn) (MgSeqBatch *, void *), void *ctx, U64 batchBases, U64 batchRecs, U64 *nSeq, U64 *totLen)
-{
-  WalkUpload u; u.devFn = devFn; u.ctx = ctx;
-  void *hostCtx = hostFn ? ctx : (void *) &u;
-  if (!hostFn) hostFn = walkUploadBatch;
-  U64 resumeOff = 0, resumeLine = 1;
-  int rc = mgTextForEachBatchDevice (filename, devFn, ctx, batchBases, batchRecs, nSeq, totLen, &resumeOff, &resumeLine);
-  if (rc == -2) rc = forEachBatch (filename, hostFn, hostCtx);
-  else if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, *nSeq, hostFn, hostCtx);
-  return rc;
-}
-
-typedef struct { Modset *ms; U64 nSeq, totLen, totHash; } AddCtx;
-static int addBatch (MgSeqBatch *b, void *v)
-{
-  AddCtx *c = (AddCtx *) v;
-  int64_t h = mgAddSequenceBatch (c->ms, b->bases, b->offsets, b->nSeq);
-  if (h < 0) return -1;
-  c->nSeq += (U64) b->nSeq; c->totLen += (U64) b->total; c->totHash += (U64) h;
-  return 0;
-}
-
-int mgAddSequenceFile (Modset *ms, const char *filename, FILE *out)            /* modutils.c:33-51 */
-{
-  AddCtx c; memset (&c, 0, sizeof (c)); c.ms = ms;
-  /* plain FASTA / FASTQ text: the device parses it (mg_textgpu.hip), the host only moves the bytes; everything else -- gzip, a
-     last line without its newline -- through the host parser below */
-  U64 resumeOff = 0, resumeLine = 1;
-  int rc = mgAddSequenceFileDevice (ms, filename, &c.nSeq, &c.totLen, &c.totHash, &resumeOff, &resumeLine);
-  if (rc == -1) return -1;
-  if (rc == -2) rc = forEachBatch (filename, addBatch, &c);
-  else if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, c.nSeq, addBatch, &c);   /* the device parser met FASTQ text it leaves to this one (a record that breaks the rules, an unfinished one): from the first record it has not added */
-  if (rc) return rc;
-  fprintf (out, "added %llu sequences total length %llu total hashes %llu, new max %u\n",
-           (unsigned long long) c.nSeq, (unsigned long long) c.totLen, (unsigned long long) c.totHash, ms->max);
-  return 0;
-}
-
-/* the host parser's legs of a 10x file: the batch's records go on from the file's count, so the odd ones stay the odd ones */
-static int addBatch10x (MgSeqBatch *b, void *v)
-{
-  AddCtx *c = (AddCtx *) v;
-  mgAdd10xDiagHostLeg ();
-  int64_t h = mgAddSequenceBatch10x (c->ms, b->bases, b->offsets, b->nSeq, c->nSeq + 1);
-  if (h < 0) return -1;
-  c->nSeq += (U64) b->nSeq; c->totLen += (U64) b->total; c->totHash += (U64) h;
-  return 0;
-}
-
-int mgAddSequenceFile10x (Modset *ms, const char *filename, FILE *out)         /* modutils.c:33-51 with is10x */
-{
-  AddCtx c; memset (&c, 0, sizeof (c)); c.ms = ms;
-  mgAdd10xDiagReset ();
-  /* as mgAddSequenceFile: plain text through the device parser, whose batches are trimmed where they lie; gzip, a last line without its
-     newline and the rest of a FASTQ file that breaks a rule through the host parser, trimmed once they are uploaded */
-  U64 resumeOff = 0, resumeLine = 1;
-  int rc = mgAddSequenceFile10xDevice (ms, filename, &c.nSeq, &c.totLen, &c.totHash, &resumeOff, &resumeLine);
-  if (rc == -1) return -1;
-  if (rc == -2) rc = forEachBatch (filename, addBatch10x, &c);
-  else if (rc == -3) rc = forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, c.nSeq, addBatch10x, &c);
-  if (rc) return rc;
-  fprintf (out, "added %llu sequences total length %llu total hashes %llu, new max %u\n",
-           (unsigned long long) c.nSeq, (unsigned long long) c.totLen, (unsigned long long) c.totHash, ms->max);
-  return 0;
-}
-
-/* the ids of a device batch as the pointer array the callers take */
-static const char **idPointers (const char *idBytes, const U64 *idOff, U32 n)
-{
-  const char **p = (const char **) malloc (((size_t) n + 1) * sizeof (char *));
-  for (U32 i = 0 ; i < n ; ++i) p[i] = idBytes + idOff[i];
-  return p;
-}
-
-typedef struct { MgReference *ref; bool isAdd; } RefDevCtx;
-static int refDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *idBytes, const U64 *idOff, void *stream)
-{
-  RefDevCtx *c = (RefDevCtx *) v; (void) stream;
-  const char **names = idPointers (idBytes, idOff, nReads);
-  int rc = mgReferenceAddDevice (c->ref, dPacked, total, dOff, (int) nReads, names, c->isAdd);
-  free (names);
-  return rc;
-}
-
-/* modmap reads the whole reference before it classifies and packs (modmap.c:93-134), and its report
- * lines are per file.  Plain FASTA text is parsed on the device (mg_textgpu.hip), batch by batch -- first-occurrence
- * indices do not depend on where a stream is cut -- everything else by the host parser as one batch holding every record */
-int mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FILE *out)
-{
-  { RefDevCtx c; c.ref = ref; c.isAdd = isAdd;
-    U64 nSeq = 0, totLen = 0, resumeOff = 0, resumeLine = 1;
-    const int first = mgTextFirstByte (filename);        /* (of the text: a blocked-gzip file is looked into) */
-    if (first == '>')                                     /* (a FASTQ reference goes the host way: the hand-over in the middle of a file is not worth having here) */
-      { const int rc = mgTextForEachBatchDevice (filename, refDeviceBatch, &c, 0, 0, &nSeq, &totLen, &resumeOff, &resumeLine);
-        if (rc == -1) return -1;
-        if (rc == 0) { mgReferenceFinish (ref, totLen, isAdd, out); return 0; }
-      }
-  }
-  MgSeqReader *r = mgSeqOpen (filename);
-  if (!r) { fprintf (stderr, "FATAL ERROR: failed to read reference sequence file %s\n", filename); exit (-1); }   /* modmap.c:99 */
-  MgSeqBatch b;
-  int n = mgSeqNextBatch (r, INT64_MAX, &b);
-  int rc = mgReferenceRead (ref, b.bases, b.offsets, n, (const char **) b.names, isAdd, out);
-  mgSeqBatchFree (&b);
-  mgSeqClose (r);
-  return rc;
-}
-
-typedef struct { MgReference *ref; FILE *out; } QueryCtx;
-static int queryBatch (MgSeqBatch *b, void *v)
-{ QueryCtx *c = (QueryCtx *) v; return mgQueryProcess (c->ref, b->bases, b->offsets, b->nSeq, (const char **) b->names, c->out); }
-
-static int queryDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *idBytes, const U64 *idOff, void *stream)
-{ (void) stream; return mgQueryPipePush ((MgQueryPipe *) v, dPacked, total, dOff, (int) nReads, idBytes, idOff); }
-
-/* short reads: a query batch per window of the file (128 MiB of text; a batch is handed on at the first window's end at which it holds
-   this many bases and records): the lines of one batch are formatted and written while the next one is read, parsed and queried.
-   Long reads (few lines): batches of the default size, 1 Gbp -- the chaining of a batch (mg_chain.hip) takes as long as the serial
-   walk of its longest read, whatever else it holds: 38 batches of 134 Mbp spent 17 ms there per 5 Gbp */
-#define MG_QUERY_FILE_BATCH 32000000ull
-#define MG_QUERY_FILE_BATCH_RECS 200000ull
-
-int mgQueryFile (MgReference *ref, const char *filename, FILE *out)            /* modmap.c:188-196 */
-{
-  QueryCtx c; c.ref = ref; c.out = out;
-  /* plain FASTA / FASTQ text: parsed on the device, the batches stay there (no 1-byte-per-base upload); gzip, a last line without
-     its newline, FASTQ that breaks a rule: the host parser (from the first record the device parser has not handed on) */
-  U64 nSeq = 0, totLen = 0, resumeOff = 0, resumeLine = 1;
-  MgQueryPipe *pipe = mgQueryPipeOpen (ref, out);
-  int rc = mgTextForEachBatchDevice (filename, queryDeviceBatch, pipe, MG_QUERY_FILE_BATCH, MG_QUERY_FILE_BATCH_RECS, &nSeq, &totLen, &resumeOff, &resumeLine);
-  mgQueryPipeClose (pipe);                                 /* every line of the device parser's batches is out */
-  if (rc == 0 || rc == -1) return rc;
-  if (rc == -3) return forEachBatchFrom (filename, (size_t) resumeOff, resumeLine, nSeq, queryBatch, &c);
-  rc = forEachBatch (filename, queryBatch, &c);
-  if (rc == -1 && access (filename, R_OK)) { fprintf (stderr, "FATAL ERROR: failed to read query sequence file %s\n", filename); exit (-1); }   /* modmap.c:196 */
-  return rc;
-}
-
-/* modutils.c:260-273 ("-P"): plain FASTA / FASTQ text is parsed on the device and each batch painted there (mg_report.hip), its text
-   written behind the next batch by the writer thread; gzip, a last line without its newline, FASTQ that breaks a rule: the host parser
-   (from the first record the device parser has not handed on), each of its batches uploaded and painted the same way */
-typedef struct { Modset *ms; MgTextOut *w; void *scratch; } PaintCtx;
-static int paintDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dOff, U32 nReads, const char *idBytes, const U64 *idOff, void *stream)
-{ PaintCtx *c = (PaintCtx *) v; (void) stream; return mgRefPaintBatchDevice (c->ms, dPacked, total, dOff, nReads, idBytes, idOff, c->w, &c->scratch); }
-#define MG_PAINT_FILE_BATCH 128000000ull
-
-int mgRefPaintFile (Modset *ms, const char *filename, FILE *out)
-{
-  char msg[600];
-  if (!ms || !filename || !out) { mgSetErrorText ("mgRefPaintFile: invalid arguments"); return -1; }
-  { FILE *f = fopen (filename, "r");
-    if (!f) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); return -1; }    /* modutils.c:262 */
-    fclose (f);
-  }
-  if (mgIterRequireDevice ()) return -1;
-  { MgSeqReader *r = mgSeqOpen (filename);                  /* (what the host parser cannot take -- and so the device parser neither: the reference's seqIOopenRead fails) */
-    if (!r) { snprintf (msg, sizeof (msg), "failed to open ref seq file %s", filename); mgSetErrorText (msg); return -1; }
-    mgSeqClose (r);
-  }
-  PaintCtx c; c.ms = ms; c.w = mgTextOutOpen (out); c.scratch = 0;
-  U64 nSeq = 0, totLen = 0;
-  int rc = mgSeqWalkFile (filename, paintDeviceBatch, 0, &c, MG_PAINT_FILE_BATCH, 1, &nSeq, &totLen);
-  if (mgTextOutClose (c.w) && !rc) { mgSetErrorText ("mgRefPaintFile: write failed"); rc = -1; }
-  mgRefPaintScratchFree (c.scratch);
-  return rc ? -1 : 0;
 }

@@ -1,6 +1,6 @@
 /* mg_settext.hip — modutils -rt (modutils.c:169-190) on the device: the lines of a set's text table parsed where the set is built.
  *
- * The host (mgModsetReadText, mg_callers.c) reads the header line, makes the set and hands over the rest of the file.  It comes here
+ * The host (mgModsetReadText, mg_modsettext.c) reads the header line, makes the set and hands over the rest of the file.  It comes here
  * as it is: parallel pread into one of two page-locked buffers (the file mover of mg_textwin.hip), one copy across the link, and per
  * window of text
  *
@@ -13,7 +13,7 @@
  * Everything a window's kernels need from the one before (lines done, bytes carried, the flag) is in a small state block on the
  * device, so the host enqueues window after window without waiting and reads the state once, at the end of the file.  A line that does
  * not fit the carry area (128 bytes; a line of the grammar has at most 66) raises the flag.  A file that raises it is parsed again on
- * the host by the reference's own fscanf format (mg_callers.c): the device takes the regular file, the host the irregular one.
+ * the host by the reference's own fscanf format (mg_modsettext.c): the device takes the regular file, the host the irregular one.
  *
  * Then the set: modsetAddBatchDevice gives every line its index in order of first occurrence, as modsetIndexFind (.., true) line after
  * line does; the reference assigns depth[index] and info[index] on every line, so the LAST line of a k-mer wins: an atomicMax of the

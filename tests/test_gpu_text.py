@@ -424,7 +424,7 @@ def test_window_walk_at_its_edges(fmt, size, golden_dir, tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["w", "a"])
 def test_query_lines_written_by_the_team_at_their_places(mode, golden_dir, tmp_path):
-    """A batch of many reads is formatted by a team of threads, piece by piece, and the pieces are written in order (mg_callers.c
+    """A batch of many reads is formatted by a team of threads, piece by piece, and the pieces are written in order (mg_queryout.c
     queryFormatLines / queryWritePieces) around whatever the caller puts into the same FILE before and after -- a file opened for
     writing or for appending.  Against the single-thread output (MODGPU_PARSE_THREADS=1), through the device parser (a batch per
     window, formatter and writer threads behind it) and the host parser."""

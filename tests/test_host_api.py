@@ -185,7 +185,7 @@ def test_pack_host_matches_the_word_layout():
 
 
 def test_format_f2_equals_printf():
-    """the parallel formatter of the Q / M lines (mg_callers.c fmtF2) against printf ("%.2f") itself: every ratio a / b the lines
+    """the parallel formatter of the Q / M lines (mg_queryout.c fmtF2) against printf ("%.2f") itself: every ratio a / b the lines
     can hold for small a, b (ties like 1/8 = 0.125 -> 0.12, 3/8 -> 0.38, and 0.005-neighbours such as 1/200), random ratios,
     values beyond 1, and the non-finite cases (0/0 -> -nan or nan as glibc prints it, x/0 -> inf)"""
     import ctypes as C
