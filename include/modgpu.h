@@ -202,6 +202,15 @@ MgStatus mgTableDiag (Modset *ms, U64 *out9) ;
  * and out18 (host) holds: [2 * mode + where] launches of the batch scan, where = 1 when positions or read ids were asked for and 0
  * for the k-mers alone; [12 + mode] launches of the per-read iterator's kernel. */
 MgStatus mgScanDiag (U64 *out18) ;
+/* Which threshold test the low-bits filter (mode 2 above) has run with (tests, diagnostics): launches since the process started, batch
+ * scan and iterator alike, counted where the instance is chosen, out2 (host): [0] with four starts' top bytes packed into one register
+ * and tested together (d <= 256; MODGPU_SCAN_PACKED_TEST=0 turns it off), [1] with every start compared on its own.  Their sum is what
+ * mgScanDiag counts for mode 2.  Nothing resets them: take differences. */
+MgStatus mgScanTailDiag (U64 *out2) ;
+/* The packed test itself, on the host (tests): bit 8j + 7 of the result is set when byte j of acc is below N, for nRep = 0x01010101 * N,
+ * 1 <= N <= 32 -- and for a byte equal to N directly above a flagged byte, which the filter, a superset test, may pass.  The line the
+ * kernel compiles (csrc/mg_packedtest.h). */
+U32 mgScanBytesBelow (U32 acc, U32 nRep) ;
 /* Where the bucketed add's value writer has run (tests, diagnostics): launches since the process started, out2 (host): [0] on the set's own
  * stream, behind the add's merge kernel and beside whatever the caller starts next, [1] on the caller's stream inside the add
  * (MODGPU_VALUE_ASYNC: 0 always there, 1 never, unset: off the caller's stream for mgAddReadsDevice).  Nothing resets them: take differences. */

@@ -122,7 +122,7 @@ EXPORTS = [
     "mgPackedWords", "mgPackHost", "mgPackDevice", "mgUnpackDevice", "mgUploadPack",
     "mgScanWorkBytes", "seqhashScanBatchDevice", "seqhashScanBatch", "seqhashMinimizerBatchDevice", "seqhashMinimizerBatch",
     "modsetAddBatchDevice", "modsetFindBatchDevice", "modsetSyncToHost", "mgXferThreadCount", "mgXferDiag", "mgCopyD2HBig", "mgCopyH2DBig", "mgModsetDeviceRelease",
-    "mgModsetHostChanged", "modsetDepthHistogramDevice", "mgTableCheckLayout", "mgTableDiag", "mgScanDiag", "mgValueWriterDiag", "mgAddReadsDevice", "mgQueryReadsDevice", "mgQueryReadsDeviceAsync", "mgQueryReadsDeviceWait",
+    "mgModsetHostChanged", "modsetDepthHistogramDevice", "mgTableCheckLayout", "mgTableDiag", "mgScanDiag", "mgScanTailDiag", "mgScanBytesBelow", "mgValueWriterDiag", "mgAddReadsDevice", "mgQueryReadsDevice", "mgQueryReadsDeviceAsync", "mgQueryReadsDeviceWait",
     "mgAddSequenceBatch", "mgDepthHistogram", "mgSynthGenome", "mgSynthReads",
     "mgInsertReadsDevice", "mgAddSequences", "mgModsetWriteText", "mgReferenceCreate", "mgReferenceDestroy",
     "mgReferenceRead", "mgQueryProcess", "mgReferenceWrite", "mgGzipOpenWrite", "mgFzOpen", "mgGzipOpenRead", "mgReferenceLoad",
@@ -270,7 +270,7 @@ def lib():
     sig("modsetFindBatchDevice", i32, MS, vp, u64, vp, vp)
     sig("modsetSyncToHost", i32, MS, i32); sig("mgXferThreadCount", i32); sig("mgXferDiag", None, U64P); sig("mgCopyD2HBig", i32, vp, vp, C.c_size_t); sig("mgCopyH2DBig", i32, vp, vp, C.c_size_t); sig("mgModsetDeviceRelease", i32, MS)
     sig("mgModsetHostChanged", None, MS)
-    sig("modsetDepthHistogramDevice", i32, MS, vp, vp); sig("mgTableCheckLayout", i32, MS, U64P); sig("mgTableDiag", i32, MS, U64P); sig("mgScanDiag", i32, U64P); sig("mgValueWriterDiag", i32, U64P)
+    sig("modsetDepthHistogramDevice", i32, MS, vp, vp); sig("mgTableCheckLayout", i32, MS, U64P); sig("mgTableDiag", i32, MS, U64P); sig("mgScanDiag", i32, U64P); sig("mgScanTailDiag", i32, U64P); sig("mgScanBytesBelow", u32, u32, u32); sig("mgValueWriterDiag", i32, U64P)
     sig("mgAddReadsDevice", i32, MS, vp, u64, vp, u32, U64P, vp)
     sig("mgQueryReadsDevice", i32, MS, vp, u64, vp, u32, vp, vp, vp, u64, U64P, vp)
     sig("mgQueryReadsDeviceAsync", i32, MS, vp, u64, vp, u32, vp, vp, vp, u64, C.POINTER(vp), vp); sig("mgQueryReadsDeviceWait", i32, vp, U64P, vp)

@@ -24,6 +24,8 @@ typedef struct {
   long minTile;            /* MODGPU_MIN_TILE: dev, positions per tile of the minimizer scan (default 512) */
   long minTiled;           /* MODGPU_MIN_TILED: 0 = the minimizer scan walks every window one link at a time (the path of windows wider than 256) */
   long scanDiv64;          /* MODGPU_SCAN_DIV64: 1 = the exact modes test divisibility in 64-bit arithmetic whatever k and d */
+  long scanPackedTest;     /* MODGPU_SCAN_PACKED_TEST: 0 = the filter mode tests every start's threshold on its own (compare + add-with-carry); 1 or unset: four starts packed
+                              into one register where the test reads the top byte alone (d <= 256) */
   long scanHist;           /* MODGPU_SCAN_HIST: 0 = the compaction kernel counts the first partition digit */
   long noSegmentInput;     /* MODGPU_NO_SEGMENT_INPUT: 1 = the build always gets a dense copy */
   long rankSliceShift;     /* MODGPU_RANK_SLICE_SHIFT */

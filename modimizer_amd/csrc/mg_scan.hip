@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include "mg_prefix.h"
+#include "mg_packedtest.h"
 
 /* ---------------------------------------------------------------------------------------- */
 /* K1: bytes 0..3 -> 2-bit packed words (first base in the top bits)                          */
@@ -128,6 +129,7 @@ struct MgScanArgs {
   U64 *segKmer; U32 *segPosF; U32 *segRead;        /* [nWorkers * segCap] */
   U64 *blockCount;       /* [nWorkers] true number of modimizers each worker found */
   U32 fS, thresh;        /* fast path: factor1 << (32-B), 2^(32-m) */
+  U32 nRep;              /* its packed test (d <= 256): 2^(8-m) in every byte (mg_packedtest.h) */
   U32 *histCount;        /* != 0: count the modimizers per coarse digit of their table bucket (what the first partition pass of the modset build sorts by) */
   int histKbits, histHiB;   /* the digit = top histHiB bits of mgMixK (kmer, histKbits); histKbits >= 24 */
 #ifdef MG_ABLATE
@@ -192,7 +194,7 @@ __device__ __forceinline__ U64 mgKmerAt (const U32 *sWords, U32 q, int sh1)
 
 #define MG_MODE_ANY   0      /* any d: exact test in phase A via modular inverse */
 #define MG_MODE_POW2  1      /* d = 2^m: exact test in phase A via a mask */
-#define MG_MODE_FAST  2      /* d = 2^m, shift1+m <= 32, k >= 17: low-bits filter in phase A */
+#define MG_MODE_FAST  2      /* d = 2^m, shift1+m <= 32, k >= 17: low-bits filter in phase A (two instances: the threshold test of four starts packed into one register, m <= 8, or per start) */
 #define MG_MODE_ODD   3      /* odd d (the reference's default w = 31): the exact test is the inverse's product alone */
 #define MG_MODE_ODD32 4      /* odd d < 2^15 and k <= 20 (the reference's defaults k = 19, w = 31): that test in 32-bit arithmetic (mgDivisibleOdd32) */
 #define MG_MODE_ANY32 5      /* d = odd 2^s with the ODD PART below 2^15 (d itself up to 32767 2^16), k <= 20: low s bits zero and the 32-bit test on the rest (mgDivisibleAny32) */
@@ -211,6 +213,21 @@ __device__ __forceinline__ U64 mgKmerAt (const U32 *sWords, U32 q, int sh1)
 #define MG_WAVE_SYNC() do { __builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier (); \
                             __builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
+/* the FAST filter's packed test, one start: byte j of acc = top byte of min (hf, xr * fS) -- the min the filter pays for anyway, told by SDWA byte
+ * selects to read its operands' top bytes and to write one byte lane of acc, the others kept (j = 0 clears them: acc needs no initial value).
+ * gfx940-family hardware does not forward a partly written register to the next instruction: a VALU instruction that reads acc -- the next
+ * start's min, which keeps acc's other bytes, or the detect -- must not be the one directly behind this min.  Hence the reverse strand's multiply
+ * INSIDE the statement, in front of the min (two statements on one acc always have it between their mins), and a wait state behind the last. */
+#define MG_SDWA_TOP_MIN(J, UNUSED) "v_mul_lo_u32 %1, %3, %4\n\tv_min_u32_sdwa %0, %2, %1 dst_sel:BYTE_" #J " dst_unused:" UNUSED " src0_sel:BYTE_3 src1_sel:BYTE_3"
+__device__ __forceinline__ void mgTopByteMin (U32 &acc, const U32 hf, const U32 xr, const U32 fS, const int j)       /* j: a constant once unrolled */
+{
+  U32 hr;
+  if (j == 0)      asm (MG_SDWA_TOP_MIN (0, "UNUSED_PAD")      : "=&v" (acc), "=&v" (hr) : "v" (hf), "v" (xr), "s" (fS));
+  else if (j == 1) asm (MG_SDWA_TOP_MIN (1, "UNUSED_PRESERVE") : "+v" (acc), "=&v" (hr) : "v" (hf), "v" (xr), "s" (fS));
+  else if (j == 2) asm (MG_SDWA_TOP_MIN (2, "UNUSED_PRESERVE") : "+v" (acc), "=&v" (hr) : "v" (hf), "v" (xr), "s" (fS));
+  else             asm (MG_SDWA_TOP_MIN (3, "UNUSED_PRESERVE") "\n\ts_nop 0" : "+v" (acc), "=&v" (hr) : "v" (hf), "v" (xr), "s" (fS));
+}
+
 /* One templated kernel; every WAVEFRONT is an independent worker.
  *
  * A worker owns a contiguous range of tiles (4096 k-mer starts each: 64 lanes x 64 starts) and its own
@@ -226,9 +243,15 @@ __device__ __forceinline__ U64 mgKmerAt (const U32 *sWords, U32 q, int sh1)
  *                      last 16 bases of the forward k-mer and the first 16 bases, reverse-
  *                      complemented, of the reverse one.  With fS = factor1 << (32-B):
  *                      candidate  <=>  min (winF*fS, winR*fS) mod 2^32 < 2^(32-m)
- *                      (one v_alignbit + one 32-bit multiply per strand, a min, a compare into VCC and an
- *                      add-with-carry that shifts the bit into the mask): a superset of the modimizers,
- *                      about 2/d of the starts.
+ *                      (one v_alignbit + one 32-bit multiply per strand and a min; then the threshold): a superset
+ *                      of the modimizers, about 2/d of the starts.  The threshold, up to d = 256: it reads the top byte
+ *                      of the min alone, so the min writes that byte into one of four byte lanes of an accumulator
+ *                      (mgTopByteMin) and four starts share one "which bytes are below 2^(8-m)" (mgBytesBelow,
+ *                      mg_packedtest.h: a subtract and a three-way and), shifted into the mask in the starts' own order
+ *                      -- now and then with an extra candidate where a borrow ran into a byte equal to the threshold,
+ *                      which phase C tests exactly like every other.  Above d = 256 (and under
+ *                      MODGPU_SCAN_PACKED_TEST=0): a compare into VCC and an add-with-carry that shifts the bit into
+ *                      the mask, per start.
  * Phase B  a DPP prefix sum over the lanes' candidate counts orders the candidates; they are listed,
  *          in order, in the wavefront's LDS list (rounds of MG_CAND_CAP).
  * Phase C  dense: one lane per candidate recomputes both full hashes from the tile in LDS, picks the
@@ -257,7 +280,7 @@ __device__ __forceinline__ void mgScanHistDone (const MgScanArgs &a, U32 *sHist,
 /* the work of one worker (wavefront): its tiles, its segment; returns the number of modimizers it found (uniform).
  * SINGLE: the batch is one read [0, totalBases) (the per-read iterator facade): no per-tile metadata array, every tile's
  * first read is read 0. */
-template <int MODE, bool SINGLE, bool WHERE>        /* WHERE: pos / read of the modimizers are wanted, not the k-mers alone (the modset build) */
+template <int MODE, bool SINGLE, bool WHERE, bool PACKED>        /* WHERE: pos / read of the modimizers are wanted, not the k-mers alone (the modset build); PACKED: FAST with the threshold test of four starts in one register (d <= 256) */
 __device__ __forceinline__ U64 mgScanWorker (const MgScanArgs &a, const U64 worker, const int lane,
                                              U32 (*sWordsW)[MG_TILE_WORDS + 8], unsigned short *sCand, U64 *sOff, U32 *sHist)
 {
@@ -346,26 +369,56 @@ __device__ __forceinline__ U64 mgScanWorker (const MgScanArgs &a, const U64 work
           fw[5] = w[5] << c2;
 #pragma unroll
           for (int j = 0 ; j < 6 ; ++j) rw[j] = mgRevComp16 (w[j]);
-          const U32 fS = a.fS, thresh = a.thresh;
-          U32 acc = 0, candLo = 0;
+          const U32 fS = a.fS;
+          if (PACKED)
+            { /* the threshold reads the top byte of the min alone (m <= 8): start s of a 32-start half goes to byte s >> 3 of accumulator s & 7, and
+                 four starts share one "which bytes are below 2^(8-m)" (mgBytesBelow: a sub and a three-way and).  Its flags sit at bit 7 of each
+                 byte: shifted down by 7 - g they are the mask's bits 8j + g, the starts' own order.  Everything is unrolled, every shift a
+                 constant: the starts are computed accumulator by accumulator, one accumulator live. */
+              U32 nRep = a.nRep;
+              asm ("" : "+v" (nRep));                              /* in a vector register: the detect's other constant takes a scalar one, and the kernel has none to spare */
+              U32 m2[2];
 #pragma unroll
-          for (int chunk = 0 ; chunk < 4 ; ++chunk)
-            { const U32 f0 = fw[0], f1w = fw[1], r0 = rw[0], r1 = rw[1];
-              fw[0] = fw[1]; fw[1] = fw[2]; fw[2] = fw[3]; fw[3] = fw[4]; fw[4] = fw[5];
-              rw[0] = rw[1]; rw[1] = rw[2]; rw[2] = rw[3]; rw[3] = rw[4]; rw[4] = rw[5];
+              for (int half = 0 ; half < 2 ; ++half)
+                { U32 M = 0;
 #pragma unroll
-              for (int tt = 0 ; tt < 16 ; ++tt)
-                { U32 xf = __funnelshift_l (f1w, f0, 2 * tt);     /* window, first base on top */
-                  U32 xr = __funnelshift_r (r0, r1, 2 * tt);      /* reverse-complemented window */
-                  U32 hf = xf * fS, hr = xr * fS;
-                  U32 mn = hf < hr ? hf : hr;
-                  /* acc = 2*acc + (mn < thresh): compare into vcc, add-with-carry of acc to itself */
-                  asm ("v_cmp_gt_u32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-                       : "+v" (acc) : "s" (thresh), "v" (mn) : "vcc");
+                  for (int g = 0 ; g < 8 ; ++g)
+                    { U32 acc;
+#pragma unroll
+                      for (int j = 0 ; j < 4 ; ++j)
+                        { const int s = 32 * half + 8 * j + g, c = s >> 4, tt = s & 15;
+                          const U32 xf = __funnelshift_l (fw[c + 1], fw[c], 2 * tt);     /* window, first base on top */
+                          const U32 xr = __funnelshift_r (rw[c], rw[c + 1], 2 * tt);     /* reverse-complemented window */
+                          mgTopByteMin (acc, xf * fS, xr, fS, j);
+                        }
+                      M |= mgBytesBelow (acc, nRep) >> (7 - g);
+                    }
+                  m2[half] = M;
                 }
-              if (chunk == 1) { candLo = acc; acc = 0; }
+              cand = ((U64) m2[1] << 32) | m2[0];
             }
-          cand = ((U64) __brev (acc) << 32) | __brev (candLo);
+          else
+            { const U32 thresh = a.thresh;
+              U32 acc = 0, candLo = 0;
+#pragma unroll
+              for (int chunk = 0 ; chunk < 4 ; ++chunk)
+                { const U32 f0 = fw[0], f1w = fw[1], r0 = rw[0], r1 = rw[1];
+                  fw[0] = fw[1]; fw[1] = fw[2]; fw[2] = fw[3]; fw[3] = fw[4]; fw[4] = fw[5];
+                  rw[0] = rw[1]; rw[1] = rw[2]; rw[2] = rw[3]; rw[3] = rw[4]; rw[4] = rw[5];
+#pragma unroll
+                  for (int tt = 0 ; tt < 16 ; ++tt)
+                    { U32 xf = __funnelshift_l (f1w, f0, 2 * tt);     /* window, first base on top */
+                      U32 xr = __funnelshift_r (r0, r1, 2 * tt);      /* reverse-complemented window */
+                      U32 hf = xf * fS, hr = xr * fS;
+                      U32 mn = hf < hr ? hf : hr;
+                      /* acc = 2*acc + (mn < thresh): compare into vcc, add-with-carry of acc to itself */
+                      asm ("v_cmp_gt_u32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
+                           : "+v" (acc) : "s" (thresh), "v" (mn) : "vcc");
+                    }
+                  if (chunk == 1) { candLo = acc; acc = 0; }
+                }
+              cand = ((U64) __brev (acc) << 32) | __brev (candLo);
+            }
         }
       else
         { /* exact modes: both k-mers of every start straight out of the lane's six words (96 bases: its 64 starts and
@@ -551,7 +604,7 @@ __device__ __forceinline__ U64 mgScanWorker (const MgScanArgs &a, const U64 work
   return found;
 }
 
-template <int MODE, bool WHERE>
+template <int MODE, bool WHERE, bool PACKED>
 __global__ __launch_bounds__ (MG_SCAN_THREADS)
 void mgScanKernel (const MgScanArgs a)
 {
@@ -569,7 +622,7 @@ void mgScanKernel (const MgScanArgs a)
       __syncthreads ();
     }
   if (worker >= a.nWorkers) { if (a.histCount) mgScanHistDone (a, sHist, &sDone, lane); return; }
-  const U64 found = mgScanWorker<MODE, false, WHERE> (a, worker, lane, sWordsAll[wave], sCandAll[wave], sOffAll[wave], sHist);
+  const U64 found = mgScanWorker<MODE, false, WHERE, PACKED> (a, worker, lane, sWordsAll[wave], sCandAll[wave], sOffAll[wave], sHist);
   if (lane == 0) a.blockCount[worker] = found;
   if (a.histCount) mgScanHistDone (a, sHist, &sDone, lane);
 }
@@ -583,7 +636,7 @@ void mgScanKernel (const MgScanArgs a)
 #define MG_ITER_MAX_TILES 64
 struct MgIterOut { U64 *out; U64 capEntries; volatile U64 *flag; U64 seq; };
 
-template <int MODE>
+template <int MODE, bool PACKED>
 __global__ __launch_bounds__ (MG_ITER_WAVES * 64)
 void mgIterScanKernel (const MgScanArgs a, const MgIterOut o)
 {
@@ -594,7 +647,7 @@ void mgIterScanKernel (const MgScanArgs a, const MgIterOut o)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane ((int) (threadIdx.x >> 6));
   U64 found = 0;
-  if ((U64) wave < a.nWorkers) found = mgScanWorker<MODE, true, true> (a, (U64) wave, lane, sWordsAll[wave], sCandAll[wave], sOffAll[wave], (U32 *) 0);
+  if ((U64) wave < a.nWorkers) found = mgScanWorker<MODE, true, true, PACKED> (a, (U64) wave, lane, sWordsAll[wave], sCandAll[wave], sOffAll[wave], (U32 *) 0);
   if (lane == 0) sFound[wave] = found;
   __syncthreads ();                                   /* the segments (global memory, written by this workgroup) and the counts are in */
   U64 before = 0, total = 0;
@@ -817,18 +870,32 @@ extern "C" MgStatus mgScanDiag (U64 *out18)
   return MG_OK;
 }
 
-/* which phase-A mode a hasher gets; sets the filter's constants in *a */
+/* the FAST launches among them, batch scan and iterator, by the threshold test of the instance that was chosen (mgScanTailDiag): [0] packed, [1] per start */
+static std::atomic<U64> gScanTails[2];
+#define MG_TAIL_COUNTED(packed) gScanTails[(packed) ? 0 : 1].fetch_add (1, std::memory_order_relaxed)
+
+extern "C" MgStatus mgScanTailDiag (U64 *out2)
+{
+  for (int i = 0 ; i < 2 ; ++i) out2[i] = gScanTails[i].load (std::memory_order_relaxed);
+  return MG_OK;
+}
+
+extern "C" U32 mgScanBytesBelow (U32 acc, U32 nRep) { return mgBytesBelow (acc, nRep); }
+
+/* which phase-A mode a hasher gets; sets the filter's constants in *a (nRep != 0: the packed test) */
 static int mgScanMode (const MgHashParams &p, MgScanArgs *a)
 {
   const bool pow2 = (p.dOddInv == 1 && p.dOddLim == ~0ull);
   const int B = p.shift1 + p.dShift;
   const int forceGeneric = mgKnobs ()->scanGeneric == 1;       /* test knob */
-  a->fS = 0; a->thresh = 0;
+  a->fS = 0; a->thresh = 0; a->nRep = 0;
   /* the filter passes 2/d of the starts to the exact evaluation: from d = 8 up that beats computing both full
      hashes everywhere (measured at k=31: d=4 1.80 ms/Gbp exact vs 2.29 filtered) */
   if (pow2 && p.dShift >= 3 && B <= 32 && p.k >= 17 && !forceGeneric)
     { a->fS = (U32) (p.factor1 << (32 - B));
       a->thresh = (U32) 1 << (32 - p.dShift);
+      /* up to d = 256 the threshold is a whole number of top bytes: four starts' tests in one register (test knob: 0 = every start on its own) */
+      if (p.dShift <= 8 && mgKnobs ()->scanPackedTest != 0) a->nRep = mgBytesBelowRep (p.dShift);
       return MG_MODE_FAST;
     }
   if (pow2) return MG_MODE_POW2;
@@ -861,7 +928,7 @@ MgStatus mgLaunchScanRange (const MgHashParams &p, const U32 *dPacked, U64 total
   a.tileBegin = tile0; a.tileLimit = tile1;
   a.tilesPerWorker = g.tilesPerBlock; a.nWorkers = g.nBlocks; a.segCap = g.segCap;
   a.segKmer = segKmer; a.segPosF = dPosF ? segPosF : 0; a.segRead = dReadId ? segRead : 0; a.blockCount = blockCount;
-  a.fS = 0; a.thresh = 0;
+  a.fS = 0; a.thresh = 0; a.nRep = 0;
   /* the first partition digit, counted by the scan itself when the table hash allows it (2k >= 24); otherwise by the compaction kernel */
   int hHiB = 0, hLoB = 0;
   if (hist && hist->binCount)
@@ -877,12 +944,15 @@ MgStatus mgLaunchScanRange (const MgHashParams &p, const U32 *dPacked, U64 total
   const unsigned grid = (g.nBlocks + MG_WAVES - 1) / MG_WAVES;
   const int mode = mgScanMode (p, &a);
   const bool where = a.segPosF || a.segRead;
-#define MG_SCAN_LAUNCH(M) do { if (where) { MG_SCAN_COUNTED (2 * (M) + 1); MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, true>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } \
-                               else       { MG_SCAN_COUNTED (2 * (M));     MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, false>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } } while (0)
-  if (mode == MG_MODE_FAST) MG_SCAN_LAUNCH (MG_MODE_FAST); else if (mode == MG_MODE_POW2) MG_SCAN_LAUNCH (MG_MODE_POW2);
+#define MG_SCAN_LAUNCH_P(M, P) do { if (where) { MG_SCAN_COUNTED (2 * (M) + 1); MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, true, P>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } \
+                                    else       { MG_SCAN_COUNTED (2 * (M));     MG_LAUNCH (MG_K_SCAN, st, (mgScanKernel<M, false, P>), dim3 (grid), dim3 (MG_SCAN_THREADS), 0, st, a); } } while (0)
+#define MG_SCAN_LAUNCH(M) MG_SCAN_LAUNCH_P (M, false)
+  if (mode == MG_MODE_FAST) { MG_TAIL_COUNTED (a.nRep); if (a.nRep) MG_SCAN_LAUNCH_P (MG_MODE_FAST, true); else MG_SCAN_LAUNCH (MG_MODE_FAST); }
+  else if (mode == MG_MODE_POW2) MG_SCAN_LAUNCH (MG_MODE_POW2);
   else if (mode == MG_MODE_ODD) MG_SCAN_LAUNCH (MG_MODE_ODD); else if (mode == MG_MODE_ODD32) MG_SCAN_LAUNCH (MG_MODE_ODD32);
   else if (mode == MG_MODE_ANY32) MG_SCAN_LAUNCH (MG_MODE_ANY32); else MG_SCAN_LAUNCH (MG_MODE_ANY);
 #undef MG_SCAN_LAUNCH
+#undef MG_SCAN_LAUNCH_P
   MG_HIP (hipGetLastError ());
   MG_LAUNCH (MG_K_SEG_SCAN, st, mgSegScanKernel, dim3 (1), dim3 (1024), 0, st, blockCount, g.nBlocks, g.segCap, capacity, segStart, dCount);
   MG_HIP (hipGetLastError ());
@@ -950,11 +1020,14 @@ MgStatus mgLaunchIterScan (const MgHashParams &p, const U32 *dPacked, U64 totalB
 #endif
   MgIterOut o; o.out = out; o.capEntries = capEntries; o.flag = flag; o.seq = seq;
   const int mode = mgScanMode (p, &a);
-#define MG_ITER_LAUNCH(M) do { MG_SCAN_COUNTED (2 * MG_MODE_COUNT + (M)); hipLaunchKernelGGL (mgIterScanKernel<M>, dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o); } while (0)
-  if (mode == MG_MODE_FAST) MG_ITER_LAUNCH (MG_MODE_FAST); else if (mode == MG_MODE_POW2) MG_ITER_LAUNCH (MG_MODE_POW2);
+#define MG_ITER_LAUNCH_P(M, P) do { MG_SCAN_COUNTED (2 * MG_MODE_COUNT + (M)); hipLaunchKernelGGL ((mgIterScanKernel<M, P>), dim3 (1), dim3 (MG_ITER_WAVES * 64), 0, st, a, o); } while (0)
+#define MG_ITER_LAUNCH(M) MG_ITER_LAUNCH_P (M, false)
+  if (mode == MG_MODE_FAST) { MG_TAIL_COUNTED (a.nRep); if (a.nRep) MG_ITER_LAUNCH_P (MG_MODE_FAST, true); else MG_ITER_LAUNCH (MG_MODE_FAST); }
+  else if (mode == MG_MODE_POW2) MG_ITER_LAUNCH (MG_MODE_POW2);
   else if (mode == MG_MODE_ODD) MG_ITER_LAUNCH (MG_MODE_ODD); else if (mode == MG_MODE_ODD32) MG_ITER_LAUNCH (MG_MODE_ODD32);
   else if (mode == MG_MODE_ANY32) MG_ITER_LAUNCH (MG_MODE_ANY32); else MG_ITER_LAUNCH (MG_MODE_ANY);
 #undef MG_ITER_LAUNCH
+#undef MG_ITER_LAUNCH_P
   MG_HIP (hipGetLastError ());
   return MG_OK;
 }
