@@ -1,5 +1,6 @@
 /* mg_bucket.hip — the one-workgroup-per-bucket kernels of the device modset table's bucketed build (mg_table.hip, steps 2, 3b and 4):
- * oversize buckets reduced chunk by chunk (mgHot*), dedup, rank lookups, merge; and their launches, which mgTableAdd calls in that order.
+ * oversize buckets reduced chunk by chunk (mgHot*), dedup, rank lookups, merge; and their launches, which mgTableAdd (mg_tableadd.hip) calls in that order, the ordered flag count
+ * (step 3, mg_rank.hip) between the dedup and the lookups.
  * MgBucketArgs, mgLdsClaim and the kernels' constants: mg_table.h. */
 #include "mg_table.h"
 

@@ -263,7 +263,8 @@ MgStatus mgLaunchIterScan (const MgHashParams &p, const U32 *dPacked, U64 totalB
 MgStatus mgLaunchMinimizers (const MgHashParams &p, U32 w, const U32 *dPacked, const U64 *dReadOffsets, U32 nReads,
                              U64 *dHash, U32 *dPosF, U64 *dReadStart, U64 capacity, U64 *totalOut, hipStream_t st);
 
-/* device modset table: NB = 2^log2NB buckets of R slots; see mg_table.hip */
+/* device modset table: NB = 2^log2NB buckets of R slots; see mg_table.hip (layout, life cycle; the adds: mg_tableadd.hip; the lookups: mg_find.hip;
+   the whole-set passes: mg_tableset.hip) */
 struct MgSlot { U64 key; U32 ord; U32 cnt; };      /* 16 bytes; key = kmer+1, 0 = empty */
 struct MgTable {
   MgSlot *slots; U64 nSlots;      /* nSlots = NB x R: what the table USES of its allocation */
@@ -284,13 +285,13 @@ struct MgTable {
                           made: 4 = buckets the merge kernel laid out by prefix scan, 5 = those of them that ran over their end */
   bool pendingDepth;   /* an add with depth counting ran since the counts were last folded into baseDepth / the host's depth[] */
   bool dirty;          /* buckets with occ == 0 hold undefined bytes (never zeroed): see mgTableClean */
-  U64 *find8;          /* the partitioned lookups' copy of the table, 8 bytes a slot: (key's bits below the bucket id + 1) << 31 | index, 0 = empty (mg_table.hip
+  U64 *find8;          /* the partitioned lookups' copy of the table, 8 bytes a slot: (key's bits below the bucket id + 1) << 31 | index, 0 = empty (mg_find.hip
                           mgTableFind8); made when a lookup batch finds it missing or stale, the table itself being 16 bytes a slot with the counts */
   U64 find8Cap;        /* slots allocated for it */
   U64 find8Version, version;      /* version: bumped by whatever changes a slot's key or index (add, load, rehash, clear); find8 is the copy of find8Version */
   bool empty;          /* nothing has been put into the table since it was made or forgotten (every occ[] is zero): its geometry is free to change */
   U64 *pin;            /* four page-locked host words for small read-backs in the middle of an add (mgDevBuild): 0-2 the tightening's, 3 the overflow flag of a load or a change of geometry */
-  int newPct;          /* new entries per 100 modimizers in the last bucketed add (a hint for the next one: mg_table.hip, markDup) */
+  int newPct;          /* new entries per 100 modimizers in the last bucketed add (a hint for the next one: mg_tableadd.hip mgAddPlan, markDup) */
   int loadPct;         /* slots are provided for entries * 100 / loadPct (0: 60).  A set that is only being built and counted
                           (mgAddReadsDevice) takes 75: its size is set from the OCCURRENCES of a batch, an upper bound of
                           the new entries, and the bucket images are the largest stream of the build; before lookups the

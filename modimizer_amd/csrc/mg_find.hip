@@ -1,5 +1,5 @@
 /* mg_find.hip — K3: lookups in the device modset table (mg_table.hip: layout).  Direct probes in ordinal order, dense or from the scan's
- * segments; and the partitioned lookups, which send the batch through the build's partition passes (mg_part.hip) first. */
+ * segments; and the partitioned lookups, which send the batch through the build's partition passes (mg_part.hip) first.  The builds are mg_tableadd.hip. */
 #include "mg_table.h"
 
 /* ---- the read-only probe walk: every lookup kernel's ----

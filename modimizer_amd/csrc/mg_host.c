@@ -5,7 +5,7 @@
  * What differs is where the work happens:
  *   - modRCiterator runs ONE GPU scan over the read (mg_scan.hip) and modRCnext replays it;
  *   - the Modset host arrays are a mirror: batch inserts/lookups run on the device table
- *     (mg_table.hip, mg_find.hip) and the mgHook* calls below bring the host arrays up to date before any
+ *     (mg_table.hip, mg_tableadd.hip, mg_find.hip) and the mgHook* calls below bring the host arrays up to date before any
  *     function here reads them.
  * Scalar modsetIndexFind works on the host arrays, as the transparent struct demands (callers
  * index ms->value/depth/info themselves: modutils.c:26, modmap.c:126-129).

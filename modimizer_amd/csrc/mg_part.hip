@@ -1,5 +1,5 @@
 /* mg_part.hip — the radix partition of the device modset table (mg_table.hip, "bucketed", step 1): a batch's (k-mer, ordinal)
- * elements sorted by bucket id in one or two streaming passes.  mgTableAdd runs both passes; the partitioned lookups (mg_find.hip) run
+ * elements sorted by bucket id in one or two streaming passes.  mgTableAdd (mg_tableadd.hip) runs both passes; the partitioned lookups (mg_find.hip) run
  * the same passes and have the scatter kernel note where every sub-chunk's runs went.  Formats and arguments: mg_table.h. */
 #include "mg_table.h"
 

@@ -1,6 +1,7 @@
-/* mg_table.h — what the files of the device modset table share: mg_table.hip (layout, direct build, life cycle, mgTableAdd, whole-set
- * passes), mg_part.hip (radix partition), mg_bucket.hip (one workgroup per bucket: dedup, merge, rank lookups) and mg_find.hip (lookups).
- * Internal to those four; the library's interface to the table is in mg_common.h.
+/* mg_table.h — what the files of the device modset table share: mg_table.hip (layout, life cycle), mg_tableadd.hip (mgTableAdd: direct
+ * build, plan, scratch, launches), mg_rank.hip (ordered flag count), mg_tableset.hip (whole-set passes), mg_part.hip (radix partition),
+ * mg_bucket.hip (one workgroup per bucket: dedup, merge, rank lookups) and mg_find.hip (lookups).
+ * Internal to those seven; the library's interface to the table is in mg_common.h.
  *
  * One file per kernel: a kernel or kernel template is defined in exactly one .hip file, and every launch of it and every
  * hipFuncSetAttribute on it is in that file.  This header holds no kernel and nothing that instantiates one -- otherwise two objects
@@ -39,7 +40,7 @@ __device__ __forceinline__ bool mgLiveEntry (const uint4 &v, U32 keepMax) { retu
 
 /* counters[]: 0 = new entries this call, 1 = bucket overflow flag */
 
-/* the rank record mgRankRecordKernel (mgTablePrune: mgRankAssignKernel) leaves per row of 64 ordinals: the row's flags and the number of flags before it */
+/* the rank record mgRankRecordKernel (mgTablePrune: mgRankAssignKernel; both mg_rank.hip) leaves per row of 64 ordinals: the row's flags and the number of flags before it */
 struct __attribute__ ((aligned (16))) MgRankGrp { U64 bits; U32 rank; U32 pad; };   /* per 64 ordinals */
 
 /* ---- k-mers read from the scan's segments (MgSegSrc) instead of a dense array ---------------------------------
@@ -241,8 +242,23 @@ MgStatus mgRankLookup (const MgBucketArgs &a, hipStream_t st);
 MgStatus mgBucketMerge (const MgBucketArgs &a, U64 fullest, unsigned threads, unsigned grid, U32 perBlock, size_t lds, hipStream_t st);   /* fullest: the longest list a bucket may have */
 
 /* ---- host side ---- */
+#define MG_TABLE_HIDDEN __attribute__ ((visibility ("hidden")))      /* shared by these files, not one of the library's names */
 static inline unsigned mgGridWide (U64 n) { return mgGrid (n, 256, 16384); }      /* the table's kernels take up to 16384 workgroups */
 static inline MgGeom mgGeomOf (const MgTable *t) { MgGeom g; g.R = t->R; g.log2NB = t->log2NB; g.kbits = t->kbits; return g; }
+static inline void mgTableSetGeom (MgTable *t, int log2NB, U32 R) { t->log2NB = log2NB; t->R = R; t->nSlots = (U64) R << log2NB; }
+/* the next array of a scratch layout: count elements of T at base + *at, *at moved behind them to the next 256-byte boundary.  base 0: 0, the
+   layout is only measured */
+template <class T> static inline T *mgCarve (void *base, size_t *at, U64 count)
+{ T *p = base ? reinterpret_cast<T *> ((char *) base + *at) : 0; *at += mgAl256 (count * sizeof (T)); return p; }
+
+/* ---- the ordered flag count (mg_rank.hip): n flags in, their number in counters[0], an index for every flagged ordinal ---- */
+struct MgRankBufs { unsigned char *flags; U64 *unitCount, *unitBase; MgRankGrp *grp; };      /* [n] the flags; per rank unit: its flags, the flags before it; per 64 ordinals: the rank record */
+MG_TABLE_HIDDEN size_t mgRankCarve (void *base, U64 n, MgRankBufs *r);      /* the buffers at base (256-byte aligned) for n flags; returns their bytes.  base 0: only that */
+MG_TABLE_HIDDEN MgStatus mgRankCount (MgTable *t, const MgRankBufs &r, U64 n, hipStream_t st);      /* r.flags -> r.unitBase, counters[0] */
+MG_TABLE_HIDDEN MgStatus mgRankRecord (const MgRankBufs &r, U64 n, hipStream_t st);                /* -> r.grp */
+MG_TABLE_HIDDEN MgStatus mgRankAssignDirect (MgTable *t, const MgRankBufs &r, const U64 *dKmer, const U32 *slotId, U64 n, hipStream_t st);   /* -> value[], the slots' indices */
+MG_TABLE_HIDDEN MgStatus mgRankAssignPrune (MgTable *t, const MgRankBufs &r, U64 n, U64 *dNewValue, hipStream_t st);                          /* -> dNewValue[], r.grp */
+MG_TABLE_HIDDEN MgStatus mgWriteValues (MgTable *t, const MgRankGrp *grp, const U64 *dKmer, const MgSegSrc *segSrc, const MgSubSeg *subSeg, U64 n, bool aside, hipStream_t st);   /* r.grp -> value[] */
 /* the element format of the partition passes (MgPartFmt) for a batch of n, and whether an element fits one packed word: mg_table.hip */
 MgPartFmt mgPartFmtOf (const MgTable *t, U64 n, int hiB);
 bool mgPartFmtFits (const MgTable *t, const MgPartFmt &f);

@@ -1,4 +1,4 @@
-"""GPU: the bucketed add's value writer off the caller's stream (MODGPU_VALUE_ASYNC; csrc/mg_table.hip mgValueWriteKernel, csrc/mg_modsetdev.hip
+"""GPU: the bucketed add's value writer off the caller's stream (MODGPU_VALUE_ASYNC; csrc/mg_rank.hip mgValueWriteKernel, csrc/mg_modsetdev.hip
 mgValueSettle).  The add's rank records go out on the caller's stream, value[] is written behind the merge kernel on a stream of the set's own and
 may still be on its way when the call returns: every reader of value[] and everything that frees or reuses what the writer reads has to wait for
 it, the next add's scan has to go into the other scratch arena.  Every case runs with the writer forced onto that stream (1) and kept on the
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 K, W, BITS = 21, 16, 22
 MG_ERR_CAPACITY = 4
-RANK_UNITS = 8192                     # MG_RANK_UNITS of csrc/mg_table.hip: the waves that share the ordered flag count
+RANK_UNITS = 8192                     # MG_RANK_UNITS of csrc/mg_rank.hip: the waves that share the ordered flag count
 MODES = [1, 0]
 
 
