@@ -567,20 +567,23 @@ void mgSeqReleaseBuffers (void) ;	/* the readers keep their two largest buffers 
 void mgReleaseBuffers (void) ;	/* everything the library caches between calls: the readers' buffers (mgSeqReleaseBuffers), the device buffers and pinned staging of the host-buffer entry points (mgAddSequenceBatch, mgUploadPack: they live on the device the last call ran on and are re-made by themselves when the caller moves to another one), the calling thread's iterator scratch (modRCiterator), the page-locked blocks and device arrays mgQueryFile leaves */
 /* Plain FASTA / FASTQ text parsed ON THE DEVICE (the host only moves the bytes: parallel pread into pinned memory, the text as it
  * is across PCIe, record starts / headers / bases found by small kernels per window): mgAddSequenceFile, mgReferenceFastaRead and
- * mgQueryFile take this path by themselves for plain text and for blocked gzip (BGZF) from end to end -- inflated on the device into
- * the same windows, MODGPU_BGZF_HOST=1: by the reader above -- and use the reader above for ordinary gzip, a file that does not end in a
- * newline, a FASTA file whose last line is a header, FASTQ that breaks a rule (from the first record not handed on).
+ * mgQueryFile take this path by themselves for plain text, for blocked gzip (BGZF) from end to end and for ordinary gzip of at least
+ * MODGPU_GZIP_MIN_KB -- both inflated on the device into the same windows; MODGPU_BGZF_HOST=1 / MODGPU_GZIP_HOST=1: by the reader above -- and
+ * use the reader above for smaller gzip files, a file that does not end in a newline, a FASTA file whose last line is a header, FASTQ that
+ * breaks a rule (from the first record not handed on).  The text of an ordinary gzip file has no known end before its last byte is inflated: such
+ * a FASTA file that ends without a newline or in a header line is handed to the reader above at its last record's '>', the records before it added.
  * This entry returns the parser's records as host arrays (bases 0..3 one per byte, offsets[nSeq + 1]; free () both): 0 = done,
  * -1 = error (mgLastError), -2 = not a file the device parser takes as a whole (nothing is returned). */
 int  mgTextParseFileDevice (const char *filename, char **bases, int64_t **offsets, int64_t *nSeq) ;
 /* test hook: the reader that takes a file up where the device parser hands it over -- from the record that starts at byte startOff of the
- * file's TEXT (a file offset for plain text, the offset in the inflated text for blocked gzip), which is line startLine and record
- * startSeq + 1 of the file; 0 for an offset at or past the text's end, for ordinary gzip, for a pipe */
+ * file's TEXT (a file offset for plain text, the offset in the inflated text for blocked and for ordinary gzip -- the latter has no index: the text
+ * before the offset is inflated on the host and dropped), which is line startLine and record startSeq + 1 of the file; 0 for an offset at or past
+ * the text's end, for a pipe */
 MgSeqReader *mgSeqOpenAt (const char *filename, U64 startOff, U64 startLine, U64 startSeq) ;
 /* of the calling thread's last file call (mgAddSequenceFile, mgAddSequenceFile10x, mgReferenceFastaRead, mgQueryFile, mgRefPaintFile,
  * mgTextParseFileDevice ..): which parser took the file -- 0 the host parser from the start, 1 the device parser over plain text, 2 the
- * device parser over blocked gzip inflated on the device --, windows parsed on the device, text bytes parsed on the device, the text
- * offset handed to the host parser (0: none) */
+ * device parser over blocked gzip inflated on the device, 3 the device parser over ordinary gzip inflated on the device --, windows parsed on the
+ * device, text bytes parsed on the device, the text offset handed to the host parser (0: none) */
 void mgTextFileDiag (U64 out4[4]) ;
 /* the callers' per-file loops: parsing of the next batch overlaps the GPU work on the current one */
 int  mgAddSequenceFile (Modset *ms, const char *filename, FILE *out) ;                        /* modutils.c:33-51 */
@@ -774,7 +777,13 @@ int      mgBgzfInflateFile (const char *inName, const char *outName /* "-": stdo
  *   mgGunzipDiag: the calling thread's last mgGzipInflateFile / mgCompositionFile / mgSeqConvertFile: chunks speculated, confirmed, discarded after a
  * chain break, folded (no candidate), batches, members, capacity retries, kernel launches -- all 0 if the file did not take this path.  diag8 of
  * mgGunzipHost counts the same.
- *   mgCompositionFile and mgSeqConvertFile take this path for an ordinary gzip file of at least MODGPU_GZIP_MIN_KB (MODGPU_GZIP_HOST=1: never). */
+ *   mgCompositionFile and mgSeqConvertFile take this path for an ordinary gzip file of at least MODGPU_GZIP_MIN_KB (MODGPU_GZIP_HOST=1: never); they
+ * walk the text twice and keep the compressed file on the device (8 GiB and a quarter of the free memory at the most).
+ *   mgAddSequenceFile, mgAddSequenceFile10x, mgReferenceFastaRead and mgQueryFile take it from the same size up and walk once: the compressed bytes pass
+ * through a bounded range on the device, every byte uploaded once, whatever the file's size.  mgGzipSrcDiag: of the calling thread's last such call the
+ * compressed bytes uploaded, the range's refills, the most compressed bytes resident at once, and the bound on them -- twice (chunks a batch + 1) *
+ * chunk bytes + one upload piece; a single deflate block longer than that makes the range grow past it. */
+void     mgGzipSrcDiag (U64 out4[4]) ;
 int      mgGzipInflateFile (const char *inName, const char *outName /* "-": stdout */, FILE *err) ;
 int      mgGunzipHost (const U8 *comp, U64 n, U32 chunkBytes, U32 batchChunks, U32 symbolsPerChunk, U8 *out, U64 cap, U64 *outLen, U32 *status, U64 diag8[8]) ;
 void     mgGunzipDiag (U64 out8[8]) ;

@@ -135,7 +135,7 @@ EXPORTS = [
     "mgRep1ResultFree", "mgRepRunFinish1", "mgRepAnalyze1File", "mgRepAnalyze1Hits", "mgRepCount2", "mgRepAnalyze2File", "mgRep1Diag",
     "mgCompositionFile", "mgCompositionText", "mgCompositionFree", "mgCompositionDiag",
     "mgSeqConvertFile", "mgSeqConvertText", "mgSeqConvertDiag",
-    "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile", "mgGzipInflateFile", "mgGunzipHost", "mgGunzipDiag",
+    "mgInflateMembersDevice", "mgInflateDiag", "mgInflateMemberHost", "mgBgzfInflateFile", "mgGzipInflateFile", "mgGunzipHost", "mgGunzipDiag", "mgGzipSrcDiag",
     "mgDeflateBlocksDevice", "mgDeflateBlockHost", "mgDeflateDiag", "mgBgzfDeflateFile", "mgSeqConvertFileBgzf",
     "mgSeqOpen", "mgSeqNextBatch", "mgSeqBatchFree", "mgSeqClose", "mgSeqReleaseBuffers", "mgReleaseBuffers", "mgTextParseFileDevice", "mgSeqOpenAt", "mgTextFileDiag", "mgAddSequenceFile", "mgReferenceFastaRead", "mgQueryFile",
     "mgReportDepths", "mgRefPaint", "mgRefPaintFile", "mgModsetWriteTextDevice", "mgModsetReadText", "mgModsetReadTextPath",
@@ -308,7 +308,7 @@ def lib():
     sig("mgSeqConvertFile", i32, C.c_char_p, C.c_char_p, i32, vp, CONV); sig("mgSeqConvertText", i32, vp, u64, i32, vp, vp, CONV); sig("mgSeqConvertDiag", None, vp)
     sig("mgInflateMembersDevice", i32, vp, u64, C.POINTER(MgGzMember), u32, vp, u64, vp, C.POINTER(u32), vp); sig("mgInflateDiag", None, vp)
     sig("mgInflateMemberHost", i32, vp, u32, vp, u32, u32, C.POINTER(u32), vp); sig("mgBgzfInflateFile", i32, C.c_char_p, C.c_char_p, vp)
-    sig("mgGzipInflateFile", i32, C.c_char_p, C.c_char_p, vp); sig("mgGunzipDiag", None, vp)
+    sig("mgGzipInflateFile", i32, C.c_char_p, C.c_char_p, vp); sig("mgGunzipDiag", None, vp); sig("mgGzipSrcDiag", None, vp)
     sig("mgGunzipHost", i32, vp, u64, u32, u32, u32, vp, u64, C.POINTER(u64), C.POINTER(u32), vp)
     sig("mgDeflateBlocksDevice", i32, vp, u64, C.POINTER(MgGzBlock), u32, vp, u64, C.POINTER(u64), vp); sig("mgDeflateDiag", None, vp)
     sig("mgDeflateBlockHost", i32, vp, u32, vp, C.POINTER(u32), vp); sig("mgBgzfDeflateFile", i32, C.c_char_p, C.c_char_p, vp)
@@ -1083,7 +1083,7 @@ def inflate_diag():
 
 def text_file_diag():
     """mgTextFileDiag: dict(path, windows, text, handed_over) of the calling thread's last file call: path 0 = the host parser from the
-    start, 1 = the device parser over plain text, 2 = over blocked gzip inflated on the device"""
+    start, 1 = the device parser over plain text, 2 = over blocked gzip inflated on the device, 3 = over ordinary gzip inflated on the device"""
     v = (C.c_uint64 * 4)()
     lib().mgTextFileDiag(v)
     return dict(zip(("path", "windows", "text", "handed_over"), (int(x) for x in v)))
@@ -1124,6 +1124,14 @@ def gunzip_diag():
     v = (C.c_uint64 * 8)()
     lib().mgGunzipDiag(v)
     return dict(zip(GUNZIP_DIAG, (int(x) for x in v)))
+
+
+def gzip_src_diag():
+    """mgGzipSrcDiag: dict(uploaded, refills, peak, bound) of the calling thread's last file call that walked an ordinary gzip file once (the text
+    parser: path 3): compressed bytes uploaded, the times the resident range took bytes up, the most compressed bytes resident at once, the bound on them"""
+    v = (C.c_uint64 * 4)()
+    lib().mgGzipSrcDiag(v)
+    return dict(zip(("uploaded", "refills", "peak", "bound"), (int(x) for x in v)))
 
 
 def gzip_inflate_file(in_path, out_path):

@@ -140,7 +140,10 @@ extern "C" int mgTextFirstByte (const char *filename)
       if (g < 1) break;
       size_t pay = 0;
       const size_t size = g >= 18 ? bgzfBlockSize (buf.data (), (size_t) g, &pay) : 0;
-      if (!size) { if (!at) first = buf[0]; break; }        /* plain text (or something the host reader judges) */
+      if (!size)                                            /* plain text, ordinary gzip (or something the host reader judges) */
+        { if (!at) first = g >= 3 && buf[0] == 0x1f && buf[1] == 0x8b && buf[2] == 8 ? mgGzipFirstByte (buf.data (), (size_t) g) : buf[0];
+          break;
+        }
       if (size < pay + 8 + 2 || size > (size_t) g) break;
       const U32 crc = bzLe32 (buf.data () + size - 8), uLen = bzLe32 (buf.data () + size - 4);
       if (uLen > BZ_MEMBER) break;

@@ -145,6 +145,7 @@ struct MgGunzipDev {
   MgDevBuf<MgzChunk> ch; MgDevBuf<uint16_t> sym; MgDevBuf<U8> win, text;
   U8 *dCarry = 0; MgzSummary *dSum = 0, *hSum = 0;
   bool hipFailed = false;
+  MgGunzipRangeFn range = 0; void *rangeCtx = 0;         /* one walk: who keeps the part of the file that is on the device */
 };
 
 static uint32_t gzDevPeek (void *v, uint64_t off, uint8_t *buf, uint32_t n)
@@ -158,6 +159,22 @@ static uint32_t gzDevPeek (void *v, uint64_t off, uint8_t *buf, uint32_t n)
     }
   return got;
 }
+/* one run of plan P over comp[.. n) -- the whole file, or a resident range of it by a pointer biased by the range's first offset: every kernel reads at
+   P->start's byte or behind it, and below n */
+static bool gzDevRun (MgGunzipDev *g, const MgzPlan *P, const U8 *comp, U64 n, size_t nSym)
+{
+  hipStream_t st = g->stream;
+  U64 lo, batchEnd;
+  mgzChunkRange (P->start, P->chunkBytes, P->nChunks - 1, n, &lo, &batchEnd);
+  const U32 tiles = (U32) (((U64) P->cap + GZ_RES_TILE - 1) / GZ_RES_TILE);
+  if (hipMemcpyAsync (g->win.p, g->dCarry, MGZ_WINDOW, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+  hipLaunchKernelGGL (mgGunzipFindKernel, dim3 (P->nChunks), dim3 (64), 0, st, comp, n, P->start, P->chunkBytes, P->nChunks, g->ch.p);
+  hipLaunchKernelGGL (mgGunzipDecodeKernel, dim3 (P->nChunks), dim3 (64), 0, st, comp, n, g->ch.p, P->nChunks, batchEnd, g->sym.p, P->cap, P->wlen);
+  hipLaunchKernelGGL (mgGunzipChainKernel, dim3 (1), dim3 (GZ_CHAIN_THREADS), 0, st, g->ch.p, P->nChunks, g->sym.p, P->cap, g->win.p, P->start, P->wlen, (U64) nSym, g->dSum);
+  hipLaunchKernelGGL (mgGunzipResolveKernel, dim3 (P->nChunks, tiles), dim3 (GZ_RES_THREADS), 0, st, g->ch.p, P->nChunks, g->sym.p, P->cap, g->win.p, g->text.p, g->dSum);
+  return hipGetLastError () == hipSuccess
+         && hipMemcpyAsync (g->hSum, g->dSum, sizeof (MgzSummary), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize (st) == hipSuccess;
+}
 static int gzDevBatch (void *v, const MgzPlan *P, MgzSummary *S)
 {
   MgGunzipDev *g = (MgGunzipDev *) v;
@@ -166,18 +183,23 @@ static int gzDevBatch (void *v, const MgzPlan *P, MgzSummary *S)
   const size_t nSym = (size_t) P->nChunks * P->cap;
   if (g->ch.reserve (P->nChunks, P->nChunks, what) || g->sym.reserve (nSym, nSym, what) || g->text.reserve (nSym, nSym, what)
       || g->win.reserve (((size_t) P->nChunks + 1) * MGZ_WINDOW, ((size_t) P->nChunks + 1) * MGZ_WINDOW, what)) { g->hipFailed = true; return -1; }
-  U64 lo, batchEnd;
-  mgzChunkRange (P->start, P->chunkBytes, P->nChunks - 1, g->n, &lo, &batchEnd);
-  const U32 tiles = (U32) (((U64) P->cap + GZ_RES_TILE - 1) / GZ_RES_TILE);
-  bool ok = hipMemcpyAsync (g->win.p, g->dCarry, MGZ_WINDOW, hipMemcpyDeviceToDevice, st) == hipSuccess;
-  if (ok)
-    { hipLaunchKernelGGL (mgGunzipFindKernel, dim3 (P->nChunks), dim3 (64), 0, st, g->dComp, g->n, P->start, P->chunkBytes, P->nChunks, g->ch.p);
-      hipLaunchKernelGGL (mgGunzipDecodeKernel, dim3 (P->nChunks), dim3 (64), 0, st, g->dComp, g->n, g->ch.p, P->nChunks, batchEnd, g->sym.p, P->cap, P->wlen);
-      hipLaunchKernelGGL (mgGunzipChainKernel, dim3 (1), dim3 (GZ_CHAIN_THREADS), 0, st, g->ch.p, P->nChunks, g->sym.p, P->cap, g->win.p, P->start, P->wlen, (U64) nSym, g->dSum);
-      hipLaunchKernelGGL (mgGunzipResolveKernel, dim3 (P->nChunks, tiles), dim3 (GZ_RES_THREADS), 0, st, g->ch.p, P->nChunks, g->sym.p, P->cap, g->win.p, g->text.p, g->dSum);
-      ok = hipGetLastError () == hipSuccess
-           && hipMemcpyAsync (g->hSum, g->dSum, sizeof (MgzSummary), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize (st) == hipSuccess;
-    }
+  bool ok;
+  if (!g->range) ok = gzDevRun (g, P, g->dComp, g->n, nSym);
+  else
+    /* One walk.  The batch's chunks and one more (the last chunk decodes on to a block boundary) are asked for; the range's owner says what is there.
+       A decode that runs out of resident bytes before the file's end says nothing about the stream: behind confirmed chunks it ends the chain like a
+       broken one (the next batch starts at that chunk, with more bytes resident); in chunk 0 -- a stored block of 65 535 bytes, a long dynamic block
+       against a range of a few KiB -- the range grows and the batch is run again.  Only at the file's true end is it the stream's error */
+    for (U64 span = ((U64) P->nChunks + 1) * P->chunkBytes ; ; span *= 2)
+      { const U64 lo = P->start >> 3, hi = g->n - lo < span ? g->n : lo + span;
+        const U8 *comp = 0; U64 n = 0;
+        if (g->range (g->rangeCtx, lo, hi, (void *) st, &comp, &n)) { g->hipFailed = true; return -1; }
+        if (n < hi || n > g->n) { mgSetError ("gzip on the device: bytes %llu .. %llu asked for, the range ends at %llu", (unsigned long long) lo, (unsigned long long) hi, (unsigned long long) n); g->hipFailed = true; return -1; }
+        if (!(ok = gzDevRun (g, P, comp, n, nSym))) break;
+        MgzSummary *h = g->hSum;
+        if (n == g->n || h->reason != MGZ_ERROR || h->status != MGI_INPUT) break;
+        if (h->confirmed) { h->reason = MGZ_BROKE; break; }
+      }
   if (ok)
     { *S = *g->hSum;
       if (S->carrySlot > P->nChunks) { mgSetError ("gzip on the device: the chain's summary is not of this batch"); return -1; }
@@ -211,6 +233,7 @@ extern "C" void mgGunzipDevClose (MgGunzipDev *g)
   delete g;
 }
 extern "C" void mgGunzipDevRewind (MgGunzipDev *g) { gzDevRestart (g); }
+extern "C" void mgGunzipDevRange (MgGunzipDev *g, MgGunzipRangeFn fn, void *ctx) { g->range = fn; g->rangeCtx = ctx; }
 
 /* the stream's next text: batches on `stream` until one has text or the stream ends.  *dText holds *n bytes until the next call.  0; -1 with
    mgLastError: the stream is wrong (*status and the compressed byte *errOff say where), or the device failed (*status 0) */

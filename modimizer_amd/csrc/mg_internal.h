@@ -231,7 +231,7 @@ MG_HIDDEN int mgBgzfSrcOpen (const char *name, int fd, U64 fileSize, MgBgzfSrc *
 MG_HIDDEN void mgBgzfSrcClose (MgBgzfSrc *s);
 MG_HIDDEN void mgBgzfSrcRewind (MgBgzfSrc *s);
 MG_HIDDEN U64 mgBgzfSrcTextBytes (const MgBgzfSrc *s);
-MG_HIDDEN int mgTextFirstByte (const char *filename);      /* the first byte of the file's text, through blocked gzip if that is what the file starts with; -1: none */
+MG_HIDDEN int mgTextFirstByte (const char *filename);      /* the first byte of the file's text, through blocked or ordinary gzip if that is what the file starts with; -1: none */
 MG_HIDDEN void mgBgzfSrcOneWalk (MgBgzfSrc *s);      /* before the first fill: the file is walked once, so its compressed bytes do not stay on the device (no Rewind after it) */
 /* the text's first byte and its last min (cap, text) bytes, from the first and the last non-empty members inflated on the host; 0, -2 = one of them does not inflate */
 MG_HIDDEN int mgBgzfSrcEdges (MgBgzfSrc *s, unsigned char *first, unsigned char *tail, size_t cap, size_t *tailN);
@@ -244,13 +244,25 @@ MG_HIDDEN int mgGunzipDevOpen (const U8 *dComp, U64 n, int fd, U32 chunkBytes, U
 MG_HIDDEN void mgGunzipDevClose (MgGunzipDev *g);
 MG_HIDDEN void mgGunzipDevRewind (MgGunzipDev *g);
 MG_HIDDEN int mgGunzipDevNext (MgGunzipDev *g, void *stream, const U8 **dText, size_t *n, int *done, U32 *status, U64 *errOff);
+/* One walk: the stream's compressed bytes are not all on the device (Open with dComp 0, then this before the first Next).  Before it runs a batch the
+   stream says which file bytes [from, to) the batch reads; fn has them on the device by work on `stream` and returns *comp with *comp + o the file's
+   byte o for the offsets o it holds from `from` on, and *end >= to where they end.  A decode that runs out of bytes below the file's end ends the
+   batch's chain there, or makes the stream ask again for twice as much if it was the batch's first chunk.  fn: 0, -1 with the error set */
+typedef int (*MgGunzipRangeFn) (void *ctx, U64 from, U64 to, void *stream, const U8 **comp, U64 *end);
+MG_HIDDEN void mgGunzipDevRange (MgGunzipDev *g, MgGunzipRangeFn fn, void *ctx);
 MG_HIDDEN void mgGunzipDiagReset (void);
 /* An ordinary gzip file as a source of text on the device (mg_gzipsrc.hip), with the contract of MgBgzfSrc.  Open: -2 = not a file for this path (not
-   gzip, a 'BC' first member, smaller than MODGPU_GZIP_MIN_KB, MODGPU_GZIP_HOST=1 -- `any`: the last two are not asked -- or more than the device holds) */
+   gzip, a 'BC' first member, smaller than MODGPU_GZIP_MIN_KB, MODGPU_GZIP_HOST=1 -- MG_GZIP_ANY: the last two are not asked -- or more than the device
+   holds).  MG_GZIP_ONE_WALK: the caller walks the text once, so the compressed file passes through a bounded range on the device and does not stay
+   (mgGzipSrcDiag); a file of any size is taken, and Rewind is an error (-1) */
 typedef struct MgGzipSrc MgGzipSrc;
-MG_HIDDEN int mgGzipSrcOpen (const char *name, int fd, U64 fileSize, int any, MgGzipSrc **out);
+#define MG_GZIP_ANY 1
+#define MG_GZIP_ONE_WALK 2
+MG_HIDDEN int mgGzipSrcOpen (const char *name, int fd, U64 fileSize, int flags, MgGzipSrc **out);
 MG_HIDDEN void mgGzipSrcClose (MgGzipSrc *s);
-MG_HIDDEN void mgGzipSrcRewind (MgGzipSrc *s);
+MG_HIDDEN int mgGzipSrcRewind (MgGzipSrc *s);
+MG_HIDDEN int mgGzipFirstByte (const unsigned char *head, size_t n);      /* the first byte of the text of the gzip file that begins head[0 .. n), by zlib on the host; -1: the head does not hold it */
+MG_HIDDEN int mgGzipSrcFirstByte (const MgGzipSrc *s);      /* the text's first byte, from the file's head inflated on the host; -1: the head does not say */
 MG_HIDDEN U64 mgGzipSrcSizeHint (const MgGzipSrc *s);
 MG_HIDDEN int mgGzipSrcFill (MgGzipSrc *s, unsigned char *dDst, size_t cap, U64 off, U64 limit, void *stream, size_t *n, int *more, U32 *first, U32 *last);
 /* mg_deflate.hip for mg_bgzfsink.hip: mgDeflateBlocksDevice on `stream` with device scratch that outlives the call (it only grows; Free drops it),

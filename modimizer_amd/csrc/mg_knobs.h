@@ -54,7 +54,7 @@ typedef struct {
   long gzipChunkKb;        /* MODGPU_GZIP_CHUNK_KB: compressed KiB per chunk of the device's gzip inflate (4 at least; default 64) */
   long gzipBatch;          /* MODGPU_GZIP_BATCH: chunks per batch (default 4096, less where device memory is short) */
   long gzipRatio;          /* MODGPU_GZIP_RATIO: symbols a chunk may write, in multiples of its compressed bytes: the guess of guess-and-retry (unset: from the file's ISIZE) */
-  long gzipMinKb;          /* MODGPU_GZIP_MIN_KB: the smallest ordinary gzip file (compressed KiB) mgCompositionFile / mgSeqConvertFile inflate on the device (default 16384; 0: every one) */
+  long gzipMinKb;          /* MODGPU_GZIP_MIN_KB: the smallest ordinary gzip file (compressed KiB) that is inflated on the device -- by mgCompositionFile / mgSeqConvertFile and by the text parser's callers (mgAddSequenceFile, mgAddSequenceFile10x, mgReferenceFastaRead, mgQueryFile ..) -- (default 16384; 0: every one) */
   long bgzfBlock;          /* MODGPU_BGZF_BLOCK: text bytes per member of the device's BGZF writer (mg_bgzfsink.hip), 1 .. 65280 (default and bgzip's: 65280) */
   long queryHostChain;     /* MODGPU_QUERY_HOST_CHAIN: 1 = modmap's chaining on the host */
   long iterHostBelow;      /* MODGPU_ITER_HOST_BELOW: modRCiterator's crossover in bases */

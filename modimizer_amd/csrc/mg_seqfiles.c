@@ -1,6 +1,7 @@
 /* mg_seqfiles.c — the callers' file loops: a FASTA / FASTQ file into a set, a Reference, a query, a painted report.
- * Plain text and blocked gzip are parsed on the device (mg_textgpu.hip) and handed on batch by batch; what that parser leaves --
- * ordinary gzip, a last line without its newline (-2), FASTQ that breaks a rule (-3) -- goes through the host parser's batch loop
+ * Plain text, blocked gzip and ordinary gzip from MODGPU_GZIP_MIN_KB up are parsed on the device (mg_textgpu.hip) and handed on batch by batch; what
+ * that parser leaves -- smaller gzip files, a last line without its newline (-2), FASTQ that breaks a rule, a gzip FASTA file whose last record is
+ * unfinished (-3) -- goes through the host parser's batch loop
  * (mg_seqio.c), from the start or from the record the device parser stopped at.
  */
 #include <stdlib.h>
@@ -109,6 +110,11 @@ static int refDeviceBatch (void *v, const U32 *dPacked, U64 total, const U64 *dO
   return rc;
 }
 
+/* the end of a reference file that the device parser handed over at its last record (-3): the host parser's batches, uploaded, go where the device
+   parser's went */
+typedef struct { WalkUpload up; U64 total; } RefTailCtx;
+static int refTailBatch (MgSeqBatch *b, void *v) { RefTailCtx *t = (RefTailCtx *) v; t->total += (U64) b->total; return walkUploadBatch (b, &t->up); }
+
 /* modmap reads the whole reference before it classifies and packs (modmap.c:93-134), and its report
  * lines are per file.  Plain FASTA text is parsed on the device (mg_textgpu.hip), batch by batch -- first-occurrence
  * indices do not depend on where a stream is cut -- everything else by the host parser as one batch holding every record */
@@ -121,6 +127,12 @@ int mgReferenceFastaRead (MgReference *ref, const char *filename, bool isAdd, FI
       { const int rc = mgTextForEachBatchDevice (filename, refDeviceBatch, &c, 0, 0, &nSeq, &totLen, &resumeOff, &resumeLine);
         if (rc == -1) return -1;
         if (rc == 0) { mgReferenceFinish (ref, totLen, isAdd, out); return 0; }
+        if (rc == -3)                                     /* (ordinary gzip whose last record is unfinished: the records before it are in, the host parser says what the reference says about the last) */
+          { RefTailCtx t; t.up.devFn = refDeviceBatch; t.up.ctx = &c; t.total = 0;
+            if (hostParserTakes (-3, filename, resumeOff, resumeLine, nSeq, refTailBatch, &t)) return -1;
+            mgReferenceFinish (ref, totLen + t.total, isAdd, out);
+            return 0;
+          }
       }
   }
   MgSeqReader *r = mgSeqOpen (filename);

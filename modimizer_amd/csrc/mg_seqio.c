@@ -330,6 +330,12 @@ static MgSeqReader *seqOpenAt (const char *filename, size_t startOff, U64 startL
       if (bgzfSeekText (fd, startOff, &r->bgzfOff, &uOff)) { closeInput (r); free (r); bigFlush (); return 0; }
       skip = startOff - uOff;
     }
+  else if (startOff && gz)                                       /* ordinary gzip has no index: the text before startOff is inflated and dropped (one host
+                                                                    inflate up to there, paid by a file that ends unfinished or breaks a FASTQ rule) */
+    { unsigned char probe;
+      if (gzseek (gz, (z_off_t) startOff, SEEK_SET) != (z_off_t) startOff || gzread (gz, &probe, 1) != 1 || gzungetc (probe, gz) < 0)      /* (the text ends at or before startOff) */
+        { closeInput (r); free (r); bigFlush (); return 0; }
+    }
   else if (startOff)
     { if (!r->fileSize || startOff >= r->fileSize || lseek (fd, (off_t) startOff, SEEK_SET) < 0) { closeInput (r); free (r); bigFlush (); return 0; }
       r->consumed = startOff;

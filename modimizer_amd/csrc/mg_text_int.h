@@ -57,6 +57,7 @@ struct TxBufs {
   hipStream_t copy = 0;
   U64 *hCounts = 0;                    /* pinned: what K4 / Kq4 leave for the host; word 6: the id kernels' total */
   MgDevBuf<TxState> dState; MgDevBuf<TqState> dTq; MgDevBuf<U32> dOverflow;
+  MgDevBuf<U64> dOpenLine;             /* FASTA from a source of unknown size: the line number of the last record start so far (mgTextRecordLineKernel) */
   MgDevBuf<U64> dTileEvent, dTileBaseOff, dTileStartOff, dTileOffQ; MgDevBuf<U32> dTileBases, dTileStarts, dTileQual;      /* per tile (dTileOffQ, dTileQual: FASTQ's third counted quantity) */
   TxKeep<unsigned char> dBases; size_t basesCap = 0;      /* the batch accumulator: one byte a base ... */
   TxKeep<U64> dRecOff, dEndQ, dEndP, dRecPos; size_t recCap = 0;      /* ... and per record: its offset; FASTQ: quality bytes and text position at its end; FASTA: the text position of its '>' */
@@ -78,14 +79,17 @@ U64 txBatchBases (U64 asked);
 
 /* ---- where a window's text comes from: ONE loader for the parser and for the window streamer ----
  * A host source (fill) fills the page-locked buffer and the copy to the device is started; a device source (dfill) fills the device buffer itself by
- * work on the copy stream.  Either way h2dDone[i] is recorded behind it.  Two makers for the parser: the plain file (its team of readers) and a
- * blocked-gzip file inflated on the device (mg_bgzfsrc.hip). */
+ * work on the copy stream.  Either way h2dDone[i] is recorded behind it.  Three makers for the parser: the plain file (its team of readers), a
+ * blocked-gzip file inflated on the device (mg_bgzfsrc.hip), and an ordinary gzip file inflated there (mg_gzipsrc.hip), whose text has no known size:
+ * its fill is asked for windows until one says that no text follows. */
 struct TxSrc { MgTextFillFn fill = 0; MgTextDevFillFn dfill = 0; void *src = 0; };
 struct TxGot { size_t n = 0; int more = 0; U32 first = 0, last = 0; };   /* the window's bytes, whether text follows, its first and last byte */
 struct TxPlain { int fd; U64 size; int nThreads; };
 struct TxBgzf { MgBgzfSrc *bz; U64 size; };              /* size: the text's */
+struct TxGzip { MgGzipSrc *gz; };
 TxSrc txSrcPlain (TxPlain *p);
 TxSrc txSrcBgzf (TxBgzf *b);
+TxSrc txSrcGzip (TxGzip *z);
 
 /* ---- the window walk: the alternation of the two buffers and nothing else.  Every step 0, -1 (the error is set) or -2 (HIP) ----
  *   start ();  while (got.n) { awaitCopy (); <kernels over dText ()>; loadNext (); <synchronise st, the rest of the window>; advance (); }
@@ -142,9 +146,12 @@ struct TxSink {
   U64 batchRecs = 0;                                       /* != 0: ... and this many records -- or the default batch's bases whatever the records (long reads: few lines to format, and a batch's chaining costs its LONGEST read's serial walk: fewer, larger batches) */
   bool wantIds;                                            /* id r = idBytes + idOff[r], 0-terminated */
 };
-/* the text of `src` (textSize bytes, FASTQ or FASTA) through the kernels, every batch of complete records to sink.  0 = the whole text; -1 = error;
-   -3 (FASTQ) = the text from byte *resumeOff on (a record start, line *resumeLine) is left to the host parser: a rule of the format is broken somewhere
-   after it, or the text ends in the middle of a record -- the host parser then reports what the reference reports (seqio.c:213-217,326-339) */
-int txParseText (bool fastq, const TxSrc &src, size_t textSize, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine);
+/* the text of `src` (FASTQ or FASTA) through the kernels, every batch of complete records to sink.  textSize: the text's size, which sets the window;
+   sized = false: a guess, the text ends where the source says so, and what the callers of a sized text look at before they start -- the last byte, the
+   last line -- is settled at the end.  0 = the whole text; -1 = error; -3 = the text from byte *resumeOff on (a record start, line *resumeLine) is left
+   to the host parser, the records before it have been handed on: FASTQ, a rule of the format is broken somewhere after it, or the text ends in the
+   middle of a record; FASTA of unknown size, the text's last byte is no newline or its last line is a header, and the record is the last one -- the
+   host parser then reports what the reference reports (seqio.c:213-217,314,326-339) */
+int txParseText (bool fastq, const TxSrc &src, size_t textSize, bool sized, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine);
 extern thread_local U64 gTxDiag[4];                      /* mg_textgpu.hip (mgTextFileDiag) */
 #endif

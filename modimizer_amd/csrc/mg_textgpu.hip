@@ -25,11 +25,12 @@
  * it, line mod 4 says what the byte is; the format's rules are checked on the device and never judged there.
  *
  * Return codes of the parser (txParseFile, mgAddSequenceFileDevice, mgTextForEachBatchDevice): 0 = the whole file; -1 = error
- * (mgLastError); -2 = not a file for this path -- ordinary gzip (and whatever else mgBgzfSrcOpen declines: blocked gzip followed by a
- * foreign member, mg_pgzip.c's 16 MiB members, a truncated block), text whose last byte is not a newline (the reference reports
+ * (mgLastError); -2 = not a file for this path -- ordinary gzip below MODGPU_GZIP_MIN_KB or under MODGPU_GZIP_HOST=1 (and whatever else mgBgzfSrcOpen
+ * and mgGzipSrcOpen decline: blocked gzip followed by a foreign member, mg_pgzip.c's 16 MiB members, a truncated block), text whose last byte is not a newline (the reference reports
  * the unfinished record, seqio.c:213-217), FASTA text whose last line is a header, anything that is not a regular file, no
  * device, MODGPU_TEXT_HOST=1, blocked gzip under MODGPU_BGZF_HOST=1: the caller uses the host parser from the start; -3 = FASTQ text
- * that breaks a rule, or ends inside a record, somewhere after byte *resumeOff: the records before it have been handed on, the host
+ * that breaks a rule, or ends inside a record, somewhere after byte *resumeOff -- or FASTA text out of ordinary gzip whose last record, which
+ * starts at byte *resumeOff, is unfinished: the records before it have been handed on, the host
  * parser continues from there (and says what the reference says).  mgTextParseFileDevice (the test hook) maps -3 to -2 and hands
  * nothing on.  Record ids (seqio.c:303-304) are extracted for the callers that print them (mgReferenceFastaRead, mgQueryFile), not for
  * mgAddSequenceFile (modutils.c:35 ignores them).
@@ -42,6 +43,16 @@
  *   - prevByte comes from the source's `last` (no page-locked copy of the window exists), and the record ids from the id kernels
  *     ("record ids on the device", mg_textids.hip), not from the host team;
  *   - a member that does not inflate in the middle of the file is -1, the message naming the member's file offset.
+ *
+ * An ordinary gzip file of at least MODGPU_GZIP_MIN_KB is inflated on the device as well (mg_gzipsrc.hip over mg_gunzip.hip, one walk: the compressed
+ * bytes pass through a bounded range) and parsed by the same loop through a third maker (txSrcGzip).  What differs from blocked gzip:
+ *   - a deflate stream has no index, so only the text's first byte is known before the walk (the file's head inflated on the host); the size is a guess
+ *     that sets the window, the text ends where the source says so, and FASTQ's verdict at the end works as it is;
+ *   - the two FASTA cases a sized text is declined for up front -- no newline at the end, a header as the last line -- are met at the end, after
+ *     records have been handed on: the records before the last one are handed on too, and the call returns -3 with the last record's '>' and its line
+ *     number (1 + the newlines before it: counted window by window on the device, mgTextRecordLineKernel), where the host parser takes the file up
+ *     (one host inflate up to that offset: mg_seqio.c seqOpenAt) and says what the reference says;
+ *   - a corrupt stream in the middle of the file is -1 ("corrupt gzip stream at file offset N"), with what earlier windows handed on added.
  */
 #include <fcntl.h>
 #include <stdlib.h>
@@ -51,7 +62,7 @@
 #include "mg_text_int.h"
 
 /* of the calling thread's last file call (mgTextFileDiag): which parser took it (0 the host's from the start, 1 this one over plain text, 2 this one over
-   blocked gzip inflated on the device), windows and text bytes parsed here, the text offset handed to the host parser */
+   blocked gzip inflated on the device, 3 this one over ordinary gzip inflated on the device), windows and text bytes parsed here, the text offset handed to the host parser */
 thread_local U64 gTxDiag[4];
 extern "C" void mgTextFileDiag (U64 out4[4]) { memcpy (out4, gTxDiag, sizeof (gTxDiag)); }
 
@@ -59,38 +70,51 @@ extern "C" void mgTextFileDiag (U64 out4[4]) { memcpy (out4, gTxDiag, sizeof (gT
  * (not a file this path takes: the caller uses the host parser).  *nSeqOut / *totLenOut: records and bases of the file. */
 static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff = 0, U64 *resumeLine = 0)
 {
-  memset (gTxDiag, 0, sizeof (gTxDiag)); mgInflateDiagReset ();      /* the censuses are this call's */
+  memset (gTxDiag, 0, sizeof (gTxDiag)); mgInflateDiagReset (); mgGunzipDiagReset ();      /* the censuses are this call's */
   if (mgEnsureDevice ()) return -2;
   if (mgKnobs ()->textHost == 1) return -2;      /* test knob: the host parser */
-  struct Input { int fd = -1; MgBgzfSrc *bz = 0; ~Input () { if (bz) mgBgzfSrcClose (bz); if (fd >= 0) close (fd); } } in;      /* closed on whichever return */
+  struct Input { int fd = -1; MgBgzfSrc *bz = 0; MgGzipSrc *gz = 0; ~Input () { if (bz) mgBgzfSrcClose (bz); if (gz) mgGzipSrcClose (gz); if (fd >= 0) close (fd); } } in;      /* closed on whichever return */
   in.fd = open (filename, O_RDONLY);
   if (in.fd < 0) return -2;
   const int fd = in.fd;
   struct stat sb;
   if (fstat (fd, &sb) || !S_ISREG (sb.st_mode) || sb.st_size < 2) return -2;
   /* what is looked at before anything starts: the text's size, its first byte, its last bytes (4096, or all of it) -- preads of a plain file, the
-     first and the last members of blocked gzip inflated on the host */
+     first and the last members of blocked gzip inflated on the host.  Ordinary gzip has no index: the first byte comes from the file's head inflated on
+     the host, the size is a guess, and the loop settles the text's end when it gets there (txParseText, sized = false) */
   size_t fileSize = (size_t) sb.st_size;
   unsigned char first = 0, magic[2] = { 0, 0 }, tail[4096]; size_t tn = 0;
   if (pread (fd, magic, 2, 0) != 2) return -2;
   if (magic[0] == 0x1f && magic[1] == 0x8b)
-    { if (mgKnobs ()->bgzfHost == 1) return -2;           /* test knob: blocked gzip inflated on the host, as on every other path */
-      if (mgBgzfSrcOpen (filename, fd, (U64) sb.st_size, &in.bz)) return -2;      /* ordinary gzip, a foreign member, a truncated block ..: the host reader's */
-      mgBgzfSrcOneWalk (in.bz);                           /* (the compressed file does not stay on the device: that memory is the modset table's) */
-      fileSize = (size_t) mgBgzfSrcTextBytes (in.bz);
-      if (fileSize < 2 || mgBgzfSrcEdges (in.bz, &first, tail, sizeof (tail), &tn)) return -2;      /* (a member that does not inflate: the host parser reports it) */
+    { /* blocked gzip from end to end (MODGPU_BGZF_HOST=1, a test knob: inflated on the host, as on every other path); else ordinary gzip of a size the
+         device takes (mgGzipSrcOpen: MODGPU_GZIP_MIN_KB, MODGPU_GZIP_HOST=1); else -- a 'BC' member followed by a foreign one, mg_pgzip.c's 16 MiB
+         members, a truncated block, a small file -- the host reader's */
+      if (mgKnobs ()->bgzfHost != 1 && !mgBgzfSrcOpen (filename, fd, (U64) sb.st_size, &in.bz))
+        { mgBgzfSrcOneWalk (in.bz);                       /* (the compressed file does not stay on the device: that memory is the modset table's) */
+          fileSize = (size_t) mgBgzfSrcTextBytes (in.bz);
+          if (fileSize < 2 || mgBgzfSrcEdges (in.bz, &first, tail, sizeof (tail), &tn)) return -2;      /* (a member that does not inflate: the host parser reports it) */
+        }
+      else
+        { if (mgGzipSrcOpen (filename, fd, (U64) sb.st_size, MG_GZIP_ONE_WALK, &in.gz)) return -2;      /* (one walk, for the same reason) */
+          const int f = mgGzipSrcFirstByte (in.gz);
+          if (f != '>' && f != '@') return -2;            /* (nothing has been handed on) */
+          first = (unsigned char) f;
+          fileSize = (size_t) mgGzipSrcSizeHint (in.gz);
+        }
     }
   else
     { tn = fileSize < sizeof (tail) ? fileSize : sizeof (tail);
       first = magic[0];
       if (pread (fd, tail, tn, (off_t) (fileSize - tn)) != (ssize_t) tn) return -2;
     }
-  if ((first != '>' && first != '@') || tail[tn - 1] != '\n') return -2;
-  if (first == '>')                                       /* FASTA text whose LAST line is a header: the reference reports the record as incomplete and does not
+  if (!in.gz)
+    { if ((first != '>' && first != '@') || tail[tn - 1] != '\n') return -2;
+      if (first == '>')                                   /* FASTA text whose LAST line is a header: the reference reports the record as incomplete and does not
                                                              return it (seqio.c:213-217,314) -- left to the host parser, which says so with the line number */
-    { size_t i = tn - 1;                                   /* the final newline */
-      while (i > 0 && tail[i - 1] != '\n') --i;            /* start of the last line (or of the tail: a header longer than that is no record id line we want to judge here) */
-      if (tail[i] == '>' && (i > 0 || tn == fileSize)) return -2;
+        { size_t i = tn - 1;                               /* the final newline */
+          while (i > 0 && tail[i - 1] != '\n') --i;        /* start of the last line (or of the tail: a header longer than that is no record id line we want to judge here) */
+          if (tail[i] == '>' && (i > 0 || tn == fileSize)) return -2;
+        }
     }
 
   int curDev = 0;
@@ -99,10 +123,11 @@ static int txParseFile (const char *filename, const TxSink &sink, U64 *nSeqOut, 
   std::lock_guard<std::mutex> g (t.lock);
   TxPlain plain; plain.fd = fd; plain.size = fileSize; plain.nThreads = txHostThreads ();
   TxBgzf bgzf; bgzf.bz = in.bz; bgzf.size = fileSize;
-  const TxSrc src = in.bz ? txSrcBgzf (&bgzf) : txSrcPlain (&plain);
-  const bool devIds = in.bz || mgKnobs ()->textIdsDevice == 1;      /* a device source has no page-locked window for the host team */
-  gTxDiag[0] = in.bz ? 2 : 1;
-  return txParseText (first == '@', src, fileSize, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
+  TxGzip gzip; gzip.gz = in.gz;
+  const TxSrc src = in.bz ? txSrcBgzf (&bgzf) : in.gz ? txSrcGzip (&gzip) : txSrcPlain (&plain);
+  const bool devIds = in.bz || in.gz || mgKnobs ()->textIdsDevice == 1;      /* a device source has no page-locked window for the host team */
+  gTxDiag[0] = in.bz ? 2 : in.gz ? 3 : 1;
+  return txParseText (first == '@', src, fileSize, !in.gz, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
 }
 
 /* ---- sinks ---- */

@@ -1,4 +1,4 @@
-/* mg_textparse.hip — the device text parser's kernels (FASTA: K1 .. K5, FASTQ: Kq1 .. Kq6, the carry) and the ONE parse loop over the window walk,
+/* mg_textparse.hip — the device text parser's kernels (FASTA: K1 .. K5 and K6 for a text of unknown size, FASTQ: Kq1 .. Kq6, the carry) and the ONE parse loop over the window walk,
  * with what differs between the two formats in FaFormat / FqFormat.  mg_textgpu.hip's file comment says what the kernels do and why. */
 #include <stddef.h>
 #include <string.h>
@@ -196,6 +196,26 @@ void mgTextLineScanKernel (U64 *tileNL, U64 nTiles, TqState *st)
   if (threadIdx.x == 0) st->nlCount = total;
 }
 
+/* K6, FASTA out of a source that does not know its text's size: the line number of the last record start so far -- 1 + the newlines before its '>' --
+   which the hand-over of a text that ends in an unfinished record names.  Behind Kq1 and Kq2 over the same window (tileLine: the newlines before every
+   tile) and K5 (recPos); one workgroup, over the tile that holds the '>'.  A record that started windows ago keeps the number it got then. */
+__global__ __launch_bounds__ (TX_THREADS)
+void mgTextRecordLineKernel (const unsigned char *__restrict__ text, U64 n, U64 textBase, const U64 *__restrict__ recPos, U64 lastRec,
+                             const U64 *__restrict__ tileLine, U64 *__restrict__ openLine)
+{
+  __shared__ U32 sRed[TX_THREADS / 64];
+  const U64 p = recPos[lastRec] - textBase;               /* (the record starts in this window: p < n) */
+  if (p >= n) return;
+  const U64 tile = p / TX_TILE, at = (tile * TX_THREADS + threadIdx.x) * TX_PER;
+  unsigned char b[16]; U32 prev = 0, c = 0;
+  if (at < p)
+    { txLoad (text, n, at, 0, b, &prev);
+      c = txNewlines (b, at, p);                           /* the newlines of the tile before byte p */
+    }
+  const U32 before = mgBlockReduce<TX_THREADS, MgSum> (c, sRed);
+  if (threadIdx.x == 0) *openLine = tileLine[tile] + before + 1;
+}
+
 /* the walk over a thread's 16 bytes, shared by Kq3 (counts) and Kq5 (writes): EMIT = false counts only */
 template <bool EMIT>
 __device__ __forceinline__ void tqWalk (const unsigned char *b, U64 at, U64 n, U32 prev, U64 line, U64 filePos,
@@ -319,28 +339,54 @@ static int txFlush (TxBufs &t, const TxSink &sink, U64 total, U64 nRec, hipStrea
 struct TxFormat {
   U64 accBases = 0, accRecs = 0, accQual = 0;
   bool bad = false;                                        /* FASTQ: a rule was broken in the accumulator's text */
-  U64 resume = 0;                                          /* FASTQ: the text offset behind the last record handed on */
+  U64 resume = 0, resumeLine = 1;                          /* where the host parser would take over: FASTQ, the text offset behind the last record handed on; FASTA (a text of unknown size that ends in an unfinished record), the last record's '>' */
+  bool sized = true;                                       /* the text's size was known before the walk, and so its last byte and its last line */
 };
 #define TX_GRID(nTiles, st) dim3 ((unsigned) (nTiles)), dim3 (TX_THREADS), 0, st      /* a workgroup a tile */
 #define TX_ONE(st) dim3 (1), dim3 (MG_GROUP_THREADS), 0, st                          /* the one workgroup of a tile scan */
 struct FaFormat : TxFormat {
   static constexpr bool fastq = false;
+  U64 recsPrev = 0;                                        /* the accumulator's records before the current window */
   bool init (TxBufs &t)
-  { TxState z; z.lastEvent = 0; z.accBases = 0; z.accRecs = 0; return hipMemcpy (t.dState.p, &z, sizeof (z), hipMemcpyHostToDevice) == hipSuccess; }
-  void count (TxBufs &t, const TxWalk &w, U64 nTiles, hipStream_t st)      /* K1 .. K4 */
-  { hipLaunchKernelGGL (mgTextEventKernel, TX_GRID (nTiles, st), w.dText (), (U64) w.got.n, w.off, w.prevByte, t.dTileEvent.p);
+  { TxState z; z.lastEvent = 0; z.accBases = 0; z.accRecs = 0;
+    TqState q; memset (&q, 0, sizeof (q)); const U64 one = 1;      /* (a text of unknown size: the newlines so far in dTq, as FASTQ keeps them) */
+    return hipMemcpy (t.dState.p, &z, sizeof (z), hipMemcpyHostToDevice) == hipSuccess
+           && (sized || (hipMemcpy (t.dTq.p, &q, sizeof (q), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy (t.dOpenLine.p, &one, 8, hipMemcpyHostToDevice) == hipSuccess));
+  }
+  void count (TxBufs &t, const TxWalk &w, U64 nTiles, hipStream_t st)      /* K1 .. K4; a text of unknown size: Kq1 and Kq2 as well, the line number at every tile's first byte */
+  { if (!sized)
+      { hipLaunchKernelGGL (mgTextNewlineKernel, TX_GRID (nTiles, st), w.dText (), (U64) w.got.n, t.dTileOffQ.p);
+        hipLaunchKernelGGL (mgTextLineScanKernel, TX_ONE (st), t.dTileOffQ.p, nTiles, t.dTq.p);
+      }
+    hipLaunchKernelGGL (mgTextEventKernel, TX_GRID (nTiles, st), w.dText (), (U64) w.got.n, w.off, w.prevByte, t.dTileEvent.p);
     hipLaunchKernelGGL (mgTextStateScanKernel, TX_ONE (st), t.dTileEvent.p, nTiles, t.dState.p);
     hipLaunchKernelGGL (mgTextCountKernel, TX_GRID (nTiles, st), w.dText (), (U64) w.got.n, w.off, w.prevByte, t.dTileEvent.p, t.dTileBases.p, t.dTileStarts.p);
     hipLaunchKernelGGL (mgTextOffsetScanKernel, TX_ONE (st), t.dTileBases.p, t.dTileStarts.p, nTiles, t.dTileBaseOff.p, t.dTileStartOff.p, t.dState.p, t.hCounts);
   }
-  void counts (const U64 *h) { accBases = h[0]; accRecs = h[1]; }
+  void counts (const U64 *h) { recsPrev = accRecs; accBases = h[0]; accRecs = h[1]; }
   void emit (TxBufs &t, const TxWalk &w, U64 nTiles, bool wantIds, hipStream_t st)
   { hipLaunchKernelGGL (mgTextEmitKernel, TX_GRID (nTiles, st), w.dText (), (U64) w.got.n, w.off, w.prevByte, t.dTileEvent.p, t.dTileBaseOff.p, t.dTileStartOff.p,
-                        t.dBases.p, (U64) t.basesCap, t.dRecOff.p, (U64) t.recCap, t.dOverflow.p, wantIds ? t.dRecPos.p : (U64 *) 0);
+                        t.dBases.p, (U64) t.basesCap, t.dRecOff.p, (U64) t.recCap, t.dOverflow.p, wantIds || !sized ? t.dRecPos.p : (U64 *) 0);
+    if (!sized && accRecs > recsPrev)                      /* a record starts in this window: the last of them is the open one now */
+      hipLaunchKernelGGL (mgTextRecordLineKernel, dim3 (1), dim3 (TX_THREADS), 0, st, w.dText (), (U64) w.got.n, w.off, t.dRecPos.p, accRecs - 1, t.dTileOffQ.p, t.dOpenLine.p);
   }
   /* the records that start in this window: the id starts a byte after the '>' */
-  bool headers (TxBufs &t, const TxWalk &, U64 recsBefore, U64, TxHdrs *h) { h->dSrc = t.dRecPos.p + recsBefore; h->add = 1; h->n = (size_t) (accRecs - recsBefore); h->at0 = false; return true; }
-  int verdict (TxBufs &, bool, U64, hipStream_t) { return 0; }
+  bool headers (TxBufs &t, const TxWalk &, U64 recsBefore, TxHdrs *h) { h->dSrc = t.dRecPos.p + recsBefore; h->add = 1; h->n = (size_t) (accRecs - recsBefore); h->at0 = false; return true; }
+  /* 0: go on; 1: the text ends here and its last record is unfinished -- the text's last byte is no newline, or its last line is a header (the two cases a
+     sized text is declined for before the walk, mg_textgpu.hip; seqio.c:213-217,314): the records before the last are handed on, the host parser takes
+     the last one up; -1.  The last line is a header if and only if the text's only newline from the last record's '>' on is its last byte; as before the
+     walk, a header that does not lie within the text's last 4096 bytes is not judged */
+  int verdict (TxBufs &t, const TxWalk &w, U64, hipStream_t st)
+  { if (sized || !w.eof || !accRecs) return 0;
+    TqState q; U64 line = 1, pos = 0;
+    if (hipStreamSynchronize (st) != hipSuccess || hipMemcpy (&q, t.dTq.p, sizeof (q), hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy (&line, t.dOpenLine.p, 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy (&pos, t.dRecPos.p + (accRecs - 1), 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const U64 end = w.off + w.got.n;
+    const bool headerLast = w.got.last == '\n' && q.nlCount - (line - 1) == 1 && (end <= 4096 || end - pos < 4096);
+    if (w.got.last == '\n' && !headerLast) return 0;
+    resume = pos; resumeLine = line;
+    return 1;
+  }
   /* complete records: all of them at the end of the text, otherwise all but the one still open */
   bool cut (TxBufs &t, bool eof, U64 *nRec, U64 *total)
   { *nRec = eof ? accRecs : accRecs - 1; *total = accBases;
@@ -350,6 +396,7 @@ struct FaFormat : TxFormat {
   bool flushed (TxBufs &t, bool eof, U64 total, hipStream_t st)
   { if (eof) return true;
     const U64 counters[2] = { accBases - total, 1 }, zero = 0;
+    if (!sized && hipMemcpyAsync (t.dRecPos.p, t.dRecPos.p + (accRecs - 1), 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;      /* (where the open record's '>' is) */
     accBases = counters[0]; accRecs = 1;
     return hipMemcpyAsync ((char *) t.dState.p + offsetof (TxState, accBases), counters, 16, hipMemcpyHostToDevice, st) == hipSuccess
            && hipMemcpyAsync (t.dRecOff.p, &zero, 8, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize (st) == hipSuccess;
@@ -376,18 +423,19 @@ struct FqFormat : TxFormat {
   }
   /* a header starts at the text's first byte and after the last newline of every record this window completed -- but for the text's last record; the id
      starts a byte after the '@' */
-  bool headers (TxBufs &t, const TxWalk &w, U64 recsBefore, U64 textSize, TxHdrs *h)
+  bool headers (TxBufs &t, const TxWalk &w, U64 recsBefore, TxHdrs *h)
   { h->dSrc = t.dEndP.p + recsBefore + 1; h->add = 2; h->n = (size_t) (accRecs - recsBefore); h->at0 = !w.off;
     if (h->n && w.eof)
       { U64 lastEnd = 0;
         if (hipMemcpy (&lastEnd, t.dEndP.p + accRecs, 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
-        if (lastEnd + 1 >= textSize) --h->n;
+        if (lastEnd + 1 >= w.off + w.got.n) --h->n;      /* (the text ends with this window: a source that inflates does not know where before) */
       }
     return true;
   }
   /* 0: go on; 1: nothing of the accumulator has been added, the host parser starts at its first record; -1 */
-  int verdict (TxBufs &t, bool eof, U64 recsBefore, hipStream_t st)
-  { if (!bad && accRecs > recsBefore)                  /* the records this window completed: sequence and quality lines of one length? */
+  int verdict (TxBufs &t, const TxWalk &w, U64 recsBefore, hipStream_t st)
+  { const bool eof = w.eof;
+    if (!bad && accRecs > recsBefore)                  /* the records this window completed: sequence and quality lines of one length? */
       { hipLaunchKernelGGL (mgTextFastqCheckKernel, dim3 ((unsigned) ((accRecs - recsBefore + 255) / 256)), dim3 (256), 0, st, t.dRecOff.p, t.dEndQ.p, recsBefore + 1, accRecs, t.dTq.p);
         TqState now;
         if (hipMemcpy (&now, t.dTq.p, sizeof (now), hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -412,7 +460,7 @@ struct FqFormat : TxFormat {
 /* ---- the one parse loop.  Per window: the count kernels, the next window's load beside them, the counts, room for exactly what this window adds,
  * the emit kernel, the ids, the format's verdict, and a batch handed on where enough has come together ---- */
 template <class F>
-static int txParseLoop (const TxSrc &src, size_t textSize, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
+static int txParseLoop (const TxSrc &src, size_t textSize, bool sized, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
 {
   const size_t window = txWindowBytes (textSize);
   const U64 batch = txBatchBases (sink.batchBases), bigBatch = batch > txBatchBases (0) ? batch : txBatchBases (0);
@@ -421,7 +469,7 @@ static int txParseLoop (const TxSrc &src, size_t textSize, bool devIds, TxBufs &
   hipStream_t st = 0;
   int rc = -1;
   U64 nSeq = 0, totLen = 0;
-  F f;
+  F f; f.sized = sized;
   do {
     TxClock ck; ck.t0 = mgNowS ();
     if (txReserve (t, window, 1 << 20, 4096)) { mgSetError ("%s", noRoom); break; }      /* the accumulators grow to what the windows' counts ask for */
@@ -449,18 +497,18 @@ static int txParseLoop (const TxSrc &src, size_t textSize, bool devIds, TxBufs &
         if (hipGetLastError () != hipSuccess) break;
         const bool wantIds = sink.wantIds && !f.bad;
         TxHdrs h;
-        if ((wantIds && !f.headers (t, wk, recsBefore, (U64) textSize, &h)) || txHeadersOut (t, wantIds && !devIds, h, st)) break;
+        if ((wantIds && !f.headers (t, wk, recsBefore, &h)) || txHeadersOut (t, wantIds && !devIds, h, st)) break;
         if (wantIds)
           { ck.lap (ck.flush);
             if (txWindowIds (t, ids, devIds, wk, h, nThreads, st)) break;
             ck.lap (ck.ids);
           }
         U32 ov = 0; if (hipMemcpy (&ov, t.dOverflow.p, 4, hipMemcpyDeviceToHost) != hipSuccess || ov) { mgSetError ("device text parser: accumulator overflow"); break; }
-        const int v = f.verdict (t, eof, recsBefore, st);
-        if (v) { if (v > 0) end = -3; break; }
+        const int v = f.verdict (t, wk, recsBefore, st);
+        if (v < 0 || (v && F::fastq)) { if (v > 0) end = -3; break; }      /* FASTQ: nothing of the accumulator is handed on */
         if (eof || f.accBases >= bigBatch || (f.accBases >= batch && f.accRecs >= sink.batchRecs))
           { U64 nRec = 0, total = 0;
-            if (!f.cut (t, eof, &nRec, &total)) break;
+            if (!f.cut (t, eof && !v, &nRec, &total)) break;      /* (FASTA that ends in an unfinished record: all but that one, as in mid-text) */
             if (nRec)
               { ck.lap (ck.flush);
                 if (txFlush (t, sink, total, nRec, st, &ids)) break;
@@ -471,6 +519,7 @@ static int txParseLoop (const TxSrc &src, size_t textSize, bool devIds, TxBufs &
                 if (!f.flushed (t, eof, total, st)) break;
               }
           }
+        if (v) { end = -3; break; }
         wk.advance ();
         if (!wk.got.n) end = 0;
       }
@@ -487,15 +536,13 @@ static int txParseLoop (const TxSrc &src, size_t textSize, bool devIds, TxBufs &
   } while (0);
   if (nSeqOut) *nSeqOut = nSeq;
   if (totLenOut) *totLenOut = totLen;
-  if (F::fastq)
-    { if (resumeOff) *resumeOff = f.resume;
-      if (resumeLine) *resumeLine = 4 * nSeq + 1;
-      if (rc == -3) gTxDiag[3] = f.resume;
-    }
+  if (resumeOff) *resumeOff = f.resume;
+  if (resumeLine) *resumeLine = F::fastq ? 4 * nSeq + 1 : f.resumeLine;
+  if (rc == -3) gTxDiag[3] = f.resume;
   return rc;
 }
-int txParseText (bool fastq, const TxSrc &src, size_t textSize, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
+int txParseText (bool fastq, const TxSrc &src, size_t textSize, bool sized, bool devIds, TxBufs &t, const TxSink &sink, U64 *nSeqOut, U64 *totLenOut, U64 *resumeOff, U64 *resumeLine)
 {
-  return fastq ? txParseLoop<FqFormat> (src, textSize, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine)
-               : txParseLoop<FaFormat> (src, textSize, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
+  return fastq ? txParseLoop<FqFormat> (src, textSize, sized, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine)
+               : txParseLoop<FaFormat> (src, textSize, sized, devIds, t, sink, nSeqOut, totLenOut, resumeOff, resumeLine);
 }

@@ -44,7 +44,7 @@ struct CpSource {
   }
   int reopen ()
   { if (bz) { mgBgzfSrcRewind (bz); return 0; }
-    if (gz) { mgGzipSrcRewind (gz); return 0; }
+    if (gz) return mgGzipSrcRewind (gz);
     if (!name || fd >= 0) return 0;
     if (fz) fclose (fz);
     fz = mgFzOpen (name, "r");

@@ -15,7 +15,7 @@ void TxBufs::release ()
   if (copy) (void) hipStreamDestroy (copy);
   if (hCounts) (void) hipHostFree (hCounts);
   copy = 0; hCounts = 0;
-  dState.drop (); dTq.drop (); dOverflow.drop ();
+  dState.drop (); dTq.drop (); dOverflow.drop (); dOpenLine.drop ();
   dTileEvent.drop (); dTileBaseOff.drop (); dTileStartOff.drop (); dTileOffQ.drop (); dTileBases.drop (); dTileStarts.drop (); dTileQual.drop ();
   dBases.drop (); dRecOff.drop (); dEndQ.drop (); dEndP.drop (); dRecPos.drop (); dPacked.drop ();
   hHdr.drop (); dIdLen.drop (); dIdLenT.drop (); dIdPlace.drop (); dIdBytes.drop (); hIdBytes.drop (); hIdPlace.drop ();
@@ -44,7 +44,7 @@ int txReserve (TxBufs &t, size_t window, U64 basesNeed, U64 recsNeed)
         ok = hipHostMalloc ((void **) &t.hPin[i], window + 64, hipHostMallocDefault) == hipSuccess
              && hipEventCreateWithFlags (&t.h2dDone[i], hipEventDisableTiming) == hipSuccess && hipMalloc ((void **) &t.dText[i], window + 64) == hipSuccess;
       ok = ok && hipHostMalloc ((void **) &t.hCounts, 64, hipHostMallocDefault) == hipSuccess && hipStreamCreateWithFlags (&t.copy, hipStreamNonBlocking) == hipSuccess
-           && !t.dState.reserve (1, 1, what) && !t.dTq.reserve (1, 1, what) && !t.dOverflow.reserve (1, 1, what)
+           && !t.dState.reserve (1, 1, what) && !t.dTq.reserve (1, 1, what) && !t.dOverflow.reserve (1, 1, what) && !t.dOpenLine.reserve (1, 1, what)
            && !t.dTileEvent.reserve (tiles, tiles, what) && !t.dTileBaseOff.reserve (tiles, tiles, what) && !t.dTileStartOff.reserve (tiles, tiles, what)
            && !t.dTileOffQ.reserve (tiles, tiles, what) && !t.dTileBases.reserve (tiles, tiles, what) && !t.dTileStarts.reserve (tiles, tiles, what)
            && !t.dTileQual.reserve (tiles, tiles, what);
@@ -130,6 +130,9 @@ TxSrc txSrcPlain (TxPlain *p) { TxSrc s; s.fill = txPlainFill; s.src = p; return
 static int txBgzfFill (void *v, unsigned char *dDst, size_t cap, U64 off, void *stream, size_t *n, int *more, U32 *first, U32 *last)
 { const TxBgzf *b = (const TxBgzf *) v; return mgBgzfSrcFill (b->bz, dDst, cap, off, b->size, stream, n, more, first, last); }
 TxSrc txSrcBgzf (TxBgzf *b) { TxSrc s; s.dfill = txBgzfFill; s.src = b; return s; }
+static int txGzipFill (void *v, unsigned char *dDst, size_t cap, U64 off, void *stream, size_t *n, int *more, U32 *first, U32 *last)
+{ const TxGzip *z = (const TxGzip *) v; return mgGzipSrcFill (z->gz, dDst, cap, off, ~(U64) 0, stream, n, more, first, last); }      /* (no limit: the stream says where its text ends) */
+TxSrc txSrcGzip (TxGzip *z) { TxSrc s; s.dfill = txGzipFill; s.src = z; return s; }
 
 /* ---- the window walk (mg_text_int.h) ---- */
 /* the window at `at` into buffer i and on its way */
